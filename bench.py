@@ -6,6 +6,7 @@ resident 1M x 1024 gallery (BASELINE.json metric), on N GPUs of one node.
     python bench.py --gpus 8 --steps 20 --warmup 5          (starts its own 8 ranks: self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR    (+ the last timed step's results as DIR/*.npy)
 
 One "step" on every rank: embed `--queries` synthetic images (micro-batches of
 `--embed-batch`, already resident in HBM), all-gather the embeddings (N > 1), exact top-10 of
@@ -69,7 +70,38 @@ def parse():
     ap.add_argument("--search-only", action="store_true", help="skip the embed stage (dev aid; not the metric)")
     ap.add_argument("--selftest-launch", action="store_true",
                     help="ranks only rendezvous (gloo) and print a line: exercises the self-launch path without a GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, emb, out):
+    """The last timed step's results as a caller receives them: the query embeddings [Q, D] (fp32) and the top-k of every
+    query -- fp64 ranking scores, fp32 reported scores, gallery ids (as fp64, exact below 2**53).  Above DUMP_LIMIT_BYTES in
+    all, a fixed (seed 0) sorted sample of query rows is written instead; `query_rows.npy` always names the rows written."""
+    import numpy as np
+    s64, s32, ids = out
+    arrays = {"embeddings": emb.float(), "scores_f64": s64.double(), "ids": ids.double()}
+    if s32 is not None:
+        arrays["scores"] = s32.float()
+    nq = emb.shape[0]
+    row_bytes = sum(a[0].numel() * a.element_size() for a in arrays.values()) + 8
+    rows = np.arange(nq)
+    if nq * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    os.makedirs(path, exist_ok=True)
+    sel = torch.as_tensor(rows, device=emb.device)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a.index_select(0, sel).cpu().numpy())
+    np.save(os.path.join(path, "query_rows.npy"), rows.astype(np.float64))
 
 
 def synthetic_images(batch, size, seed, device):
@@ -575,9 +607,11 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step(True)
+        last = step(True)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, emb, last)       # before the calibration passes below reuse `emb`
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
