@@ -406,6 +406,19 @@ struct RingEntry {     // a lane's pair of accumulator tiles that holds a passin
 constexpr int RING_SLOTS = 64;       // per wave: 3 KiB, 24 KiB per workgroup (LDS: 131 + 3 + 24 = 158 of 160 KiB)
 constexpr int SPILL_SLOTS = 2048;    // per wave, global (96 KiB): what the ring overflowed into, kept until the workgroup's end
 constexpr int SPILL_PER_TILE = 1024; // the most one gallery tile can park: every (lane, tile pair) of the wave
+// Bound of the spill area.  A tested tile pair (a "site") moves at most one full ring (RING_SLOTS entries) to it, so:
+//   at the loop's top, after its drain check:           <= SPILL_SLOTS - SPILL_PER_TILE      (1024)
+//   one iteration's 16 sites (FUSE: query tiles 2,3 of the previous gallery tile and 0,1 of this one; else epilogue(gt, 0)):
+//                                                       <= SPILL_PER_TILE                    (1024)
+//   before the cosine filter's final epilogue(gt, 2), after its drain check:
+//                                                       <= SPILL_SLOTS - SPILL_PER_TILE / 2  (1536)
+//   its 8 sites (query tiles 2,3 of the last gallery tile): <= SPILL_PER_TILE / 2            (512)
+// Without the second check a walk of 4, 6, 8, ... gallery tiles that parks every entry reached 448, 1472 | drain | 960, 1984
+// entries and 2496 after the final epilogue: 448 entries into the next wave's area (past the allocation in the last block).
+static_assert(SPILL_PER_TILE == 16 * RING_SLOTS, "an iteration tests 16 sites, each of which can move a full ring");
+static_assert((SPILL_SLOTS - SPILL_PER_TILE) + SPILL_PER_TILE <= SPILL_SLOTS &&
+                  (SPILL_SLOTS - SPILL_PER_TILE / 2) + 8 * RING_SLOTS <= SPILL_SLOTS,
+              "the two drain checks keep every wave inside its spill area");
 
 __device__ inline float vmax3(float a, float b, float c) {
     float d;
@@ -534,7 +547,8 @@ __global__ __launch_bounds__(512, 2) void k_gemm16(GemmArgs A) {
         }
     };
     // Everything parked so far goes out: at the END of the workgroup's life (about 500 entries per wave on the bench
-    // workload: the K loop itself only parks), or between two gallery tiles should the spill area be more than half full.
+    // workload: the K loop itself only parks), or between two gallery tiles and before the final epilogue should the spill
+    // area be too full for what follows (the bound next to SPILL_SLOTS).
     // The spill area is this wave's own and was written by this wave: its stores are complete after vmcnt(0), and it is
     // read past the vector L1.
     RingEntry *gspill = reinterpret_cast<RingEntry *>(A.spill) + ((int64_t)blockIdx.x * 8 + wave) * SPILL_SLOTS;
@@ -954,7 +968,11 @@ __global__ __launch_bounds__(512, 2) void k_gemm16(GemmArgs A) {
         gt = gt_nx;
         rsrc_a = rsrc_a_nx;
     }
-    if constexpr (FUSE) epilogue(gt, 2);               // the last gallery tile of this workgroup: its query tiles 2,3 are still untested
+    if constexpr (FUSE) {
+        // the last gallery tile of this workgroup: its query tiles 2,3 are still untested (8 sites: up to half a tile's spill)
+        if (__builtin_expect(scnt > SPILL_SLOTS - SPILL_PER_TILE / 2, 0)) drain();
+        epilogue(gt, 2);
+    }
 #ifdef MIRX_EXP_CYCLES
     if (lane == 0 && (blockIdx.x % 61) == 0 && cy_n > 1000 && (wave == 0 || wave == 4))
         printf("wg %d wave %d segments (loop top/prev end -> H1(s0) start | H1(s0) | H2(s0) | H1(s1) to barrier | barrier wait | rest): first K-tile %.0f %.0f %.0f %.0f %.0f %.0f ; other K-tiles %.0f %.0f %.0f %.0f %.0f %.0f\n",

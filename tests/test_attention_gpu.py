@@ -158,3 +158,83 @@ def test_attention_split2h_terms_output_carries_the_fp32_output(b, n, heads, dh)
     if cp > c:
         assert torch.isnan(back[:, c:]).all()        # the launch writes features [0, c): padding belongs to the buffer's owner
     assert float((back[:, :c] - out.view(b * n, c).double()).abs().max()) <= bv * 2.0 ** -21
+
+
+# ---- guard bands: what lies next to the operands -------------------------------------------------------------------
+# Every test above hands the kernels a tensor of its own, whose neighbouring bytes happen to be finite.  The two-term kernels
+# (k_attention_h2 for head_dim 64, k_attention_h2g for 32 / 72 / 96) read K / V through a buffer descriptor that spans one
+# image's n token rows, with the tile's offset as the load's scalar offset, and rely on the descriptor's range check to
+# turn the tail tile's rows >= n into zeros; the fp32 and three-term kernels clamp the key instead.  Here qkv is the head
+# of a buffer whose next two 32-token tiles are NaN: a tail-tile row read from beyond the last image reaches the P V
+# product as 0 x NaN.  The outputs, too, are the head of a buffer whose tail holds a sentinel that must come back
+# bit-unchanged.
+_BAND_TILES = 2 * 32                  # token rows of guard band: more than one tile of keys past the last image
+_SENTINEL = 12345.0
+_SENTINEL16 = 0x5A5A                  # fp16 bits of the terms output's guard band (and of its padding features)
+
+
+def _banded(numel, band, fill, dtype, dev):
+    buf = torch.empty(numel + band, dtype=dtype, device=dev)
+    if dtype == torch.float16:
+        buf.view(torch.int16).fill_(fill)
+    else:
+        buf.fill_(fill)
+    return buf, buf[:numel]
+
+
+@pytest.mark.parametrize("kind", ["f32", "split3", "split2h", "split2h_terms"])
+@pytest.mark.parametrize("dh", [64, 72, 32, 96])
+@pytest.mark.parametrize("b,heads", [(1, 1), (3, 12)])
+@pytest.mark.parametrize("n", [1, 5, 33, 63, 257, 1370])
+def test_attention_reads_and_writes_stay_inside_the_operands(n, b, heads, dh, kind):
+    """n = 33, 63, 257, 1370 end in a tail tile after the first one (the only tiles whose rows >= n are out of range at a
+    non-zero tile offset); n = 1, 5 are tail tiles at offset 0.  The output must be finite, within the tolerance of the
+    tests above of a float64 softmax(q k^T / sqrt(d)) v, and the bytes after it untouched."""
+    from mirx import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    tok = 3 * heads * dh
+    qbuf, flat = _banded(b * n * tok, _BAND_TILES * tok, float("nan"), torch.float32, dev)
+    qkv = flat.view(b, n, 3, heads, dh)
+    g = torch.Generator(device=dev).manual_seed(31 * n + 7 * heads + dh + b)
+    qkv.copy_(torch.randn((b, n, 3, heads, dh), generator=g, device=dev) * 1.5)
+    assert torch.isnan(qbuf[b * n * tok:]).all()
+    ref = _ref(qkv)
+    c = heads * dh
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    bqk, bv = float(qkv[:, :, :2].abs().max()), float(qkv[:, :, 2].abs().max())
+    tol = 3e-6 * max(1.0, float(ref.abs().max()))
+    if kind == "split2h_terms":
+        cp = (c + 31) // 32 * 32
+        obuf, flat_o = _banded(b * n * 2 * cp, _BAND_TILES * 2 * cp, _SENTINEL16, torch.float16, dev)
+        scale = 2.0 ** math.floor(math.log2(32768.0 / bv))
+        _lib.check(lib.mirx_attention_qkv_f32_split2h_terms(ctypes.c_void_p(qkv.data_ptr()), b, n, heads, dh, dh ** -0.5, bqk,
+                                                            bv, scale, ctypes.c_void_p(flat_o.data_ptr()), st), kind)
+        torch.cuda.synchronize()
+        tt = flat_o.view(b * n, cp // 32, 2, 32)
+        out = (tt[:, :, 0].double() + tt[:, :, 1].double()).reshape(b * n, cp)[:, :c].view(b, n, c) / scale
+        tol += bv * 2.0 ** -21                       # two fp16 terms of the fp32 result
+        pad = tt.view(torch.int16).transpose(1, 2).reshape(b * n, 2, cp)[:, :, c:]     # both terms' features c .. cp
+        assert (pad == _SENTINEL16).all(), "padding features were written"
+        tail = obuf[b * n * 2 * cp:].view(torch.int16)
+        assert (tail == _SENTINEL16).all(), "the terms output was written past its end"
+    else:
+        obuf, flat_o = _banded(b * n * c, _BAND_TILES * c, _SENTINEL, torch.float32, dev)
+        o = ctypes.c_void_p(flat_o.data_ptr())
+        q = ctypes.c_void_p(qkv.data_ptr())
+        if kind == "f32":
+            rc = lib.mirx_attention_qkv_f32(q, b, n, heads, dh, float(dh) ** -0.5, o, st)
+        elif kind == "split3":
+            rc = lib.mirx_attention_qkv_f32_split3(q, b, n, heads, dh, float(dh) ** -0.5, o, st)
+        else:
+            rc = lib.mirx_attention_qkv_f32_split2h(q, b, n, heads, dh, dh ** -0.5, bqk, bv, o, st)
+        _lib.check(rc, kind)
+        torch.cuda.synchronize()
+        out = flat_o.view(b, n, c).double()
+        tail = obuf[b * n * c:]
+        assert (tail.view(torch.int32) == torch.tensor([_SENTINEL], dtype=torch.float32).view(torch.int32).item()).all(), \
+            "the output was written past its end"
+    assert torch.isnan(qbuf[b * n * tok:]).all(), "the input's guard band was written"
+    assert torch.isfinite(out).all(), f"{kind}: non-finite output (a key / value row beyond the operand reached the result)"
+    err = float((out - ref).abs().max())
+    assert err < tol, (kind, err, tol)

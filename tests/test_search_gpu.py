@@ -2,6 +2,9 @@
 
 Bar: ids identical; fp64 ranking scores bit-identical to oracle/search_ref.c (same lane-tree
 order); reported fp32 values equal to the rounded oracle value."""
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -247,6 +250,141 @@ def test_a_whole_accumulator_tile_of_passing_scores_takes_the_spill_path():
     assert st["candidates"] == nq * run, st
     assert st["incomplete"] == 0 and st["tier1_answered"] + st["exact_answered"] == nq, st
     o_s, o_i = OS.topk(q.numpy(), g.numpy(), 10)
+    np.testing.assert_array_equal(i.cpu().numpy(), o_i)
+    np.testing.assert_array_equal(s.cpu().numpy(), o_s)
+
+
+# ---- the spill area's bound under a wave that parks every entry ---------------------------------------------------------
+_CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "image-retrieval---thesis-2026_amd", "csrc")
+
+
+def _constexpr(fname, name):
+    """The value of `constexpr int[64_t] NAME = <int>;` in csrc/FNAME: the test follows the library's capacities."""
+    with open(os.path.join(_CSRC, fname)) as f:
+        m = re.search(r"constexpr\s+(?:int|int64_t)\s+%s\s*=\s*(\d+)\s*;" % name, f.read())
+    assert m, (fname, name)
+    return int(m.group(1))
+
+
+def _region_slots(regions):                               # k_gemm.hip: region_slots()
+    return min(64, max(8, 2048 // max(regions, 1)))
+
+
+def _plan_unit(u, nqt, nph, group=4):                     # k_gemm.hip: Plan::unit() -> (query tile, phase)
+    full, per = nqt // group, group * nph
+    if u < full * per:
+        return (u // per) * group + (u % per) % group, (u % per) // group
+    l, gsz = u - full * per, nqt - group * full
+    return full * group + l % gsz, l // gsz
+
+
+def _spill_peak(tiles, ring, spill, per_tile, final_drain):
+    """Most entries parked in a wave's spill area by k_gemm16's cosine filter when every lane of every site holds a passing
+    score: the loop's top drains above spill - per_tile; an iteration tests 16 sites (query tiles 2,3 of the previous gallery
+    tile, 0,1 of this one), the final epilogue 8 more; a site that finds the ring full moves the ring to the spill area."""
+    rcnt = scnt = peak = 0
+
+    def sites(k):
+        nonlocal rcnt, scnt, peak
+        for _ in range(k):
+            if rcnt + 64 > ring:
+                scnt, rcnt = scnt + rcnt, 0
+                peak = max(peak, scnt)
+            rcnt += 64
+
+    for t in range(tiles):
+        if scnt > spill - per_tile:
+            scnt = rcnt = 0
+        sites((8 if t else 0) + 8)                        # nothing of the tile "before the first" passes
+    if final_drain and scnt > spill - per_tile // 2:
+        scnt = rcnt = 0
+    sites(8)
+    return peak
+
+
+@pytest.mark.parametrize("tiles", [2, 3, 4, 5, 8])
+def test_every_entry_of_a_wave_passing_stays_inside_its_spill_area(tiles):
+    """k_gemm16 (cosine filter, 256-query tiles) parks the lanes that hold a passing score in a 64-entry ring per wave and
+    moves a full ring to the wave's 2048-slot global spill area.  Here EVERY (lane, tile pair) entry of every wave of the
+    phase-0 workgroups holds exactly one passing score on each of their `tiles` gallery tiles -- the most the spill area can
+    receive -- while each query's passes stay below the candidate regions' and the overflow list's capacities, so that a lost
+    or misplaced candidate is not covered by the overflow fallback.  Walks of 4 and 8 tiles reach the final epilogue with
+    1984 entries parked, 2496 after it without the drain in front of it; 3, 5 and 8 also drain at the loop top, 2 never.
+
+    Construction: query q has class ((q % 16) // 4, (q // 16) % 2), gallery row r class (r % 4, (r // 4) % 2); in the
+    16x16x32 accumulator layout an entry holds rows 16 mi + 4 (lane >> 4) + 0..3 and queries 16 n0 + (lane & 15),
+    16 (n0 + 1) + (lane & 15): exactly one (row, query) pair of the same class.  Same class scores ~0.8, others ~0."""
+    from mirx import _lib as L
+    from mirx.index import FlatIndex
+    cap, ovf_cap = _constexpr("mirx_common.h", "CAND_CAP"), _constexpr("mirx_common.h", "CAND_OVF")
+    min_rows = _constexpr("mirx_api.hip", "TIER1_MIN_ROWS")
+    ring, spill = _constexpr("k_gemm.hip", "RING_SLOTS"), _constexpr("k_gemm.hip", "SPILL_SLOTS")
+    per_tile = _constexpr("k_gemm.hip", "SPILL_PER_TILE")
+    bm, bn, d, tau, k = 256, 256, 128, 0.5, 10
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    grid_cap = cus // 8 * 8
+    # the most query tiles whose plan still gives a tier-1 gallery of `tiles` tiles per workgroup
+    for nqt in (8, 4, 2, 1):
+        nph = grid_cap // nqt
+        if nph * tiles * bm >= min_rows:
+            break
+    nq, ngt = nqt * bn, nph * tiles                       # make_plan(): nph <= ngt, every phase walks exactly `tiles` tiles
+    n = ngt * bm
+    assert nq > 128 and n >= min_rows and nph > 1
+    grid = (nqt * nph + 7) // 8 * 8
+    last = grid - 1                                       # the grid's last block owns the end of the spill allocation
+    u_last = (last & 7) * (grid >> 3) + (last >> 3)
+    assert u_last >= nqt * nph or _plan_unit(u_last, nqt, nph)[1] != 0
+
+    gen = torch.Generator().manual_seed(9000 + tiles)
+    qi, ri = torch.arange(nq), torch.arange(n)
+    qcls = (qi % 16) // 4 + 4 * ((qi // 16) % 2)
+    rcls = ri % 4 + 4 * ((ri // 4) % 2)
+    heavy = (ri // bm) % nph == 0                         # the gallery tiles of phase 0
+    noise = lambda m: torch.nn.functional.normalize(torch.randn(m, d - 16, generator=gen), dim=1)
+    eye = torch.eye(d)
+    q = torch.nn.functional.normalize(torch.cat([eye[qcls, :16], 0.1 * noise(nq)], 1), dim=1)
+    g = torch.cat([0.8 * eye[torch.where(heavy, rcls, 8 + ri % 8), :16], 0.6 * noise(n)], 1)   # dims 8-15: no query's
+    g = torch.nn.functional.normalize(g, dim=1)
+
+    # host self-check (float64): every entry of the heavy workgroups holds exactly one passing score, with margins to tau
+    # far beyond the bf16 filter's error; nothing else passes
+    eps = 2.0 ** -8 + 2.0 ** -18 + d * 2.0 ** -23
+    q64, g64 = q.double(), g.double()
+    hrows = torch.nonzero(heavy).flatten()
+    sh = g64[hrows] @ q64.t()                             # [heavy rows, nq]
+    match = rcls[hrows][:, None] == qcls[None, :]
+    assert float(sh[match].min()) > tau + 20 * eps and float(sh[~match].max()) < tau - 20 * eps
+    lane = torch.arange(64)
+    rows = (torch.arange(2).view(2, 1, 1, 1, 1, 1, 1) * 128 + torch.arange(8).view(1, 1, 8, 1, 1, 1, 1) * 16
+            + 4 * (lane >> 4).view(1, 1, 1, 1, 64, 1, 1) + torch.arange(4).view(1, 1, 1, 1, 1, 4, 1))     # wm, ., mi, ., lane, r, .
+    cols = (torch.arange(4).view(1, 4, 1, 1, 1, 1, 1) * 64 + torch.arange(0, 4, 2).view(1, 1, 1, 2, 1, 1, 1) * 16
+            + torch.arange(2).view(1, 1, 1, 1, 1, 1, 2) * 16 + (lane & 15).view(1, 1, 1, 1, 64, 1, 1))      # ., wn, ., n0, lane, ., j
+    for t in range(tiles):
+        for qt in range(nqt):
+            ent = sh[t * bm:(t + 1) * bm, qt * bn:(qt + 1) * bn][rows, cols] > tau    # [wm, wn, mi, n0/2, lane, r, j]
+            assert (ent.sum(dim=(-2, -1)) == 1).all(), (t, qt)
+    lrows = torch.nonzero(~heavy).flatten()
+    light_max = max(float((g64[lrows[c0:c0 + 8192]] @ q64.t()).max()) for c0 in range(0, len(lrows), 8192))
+    assert light_max < tau - 20 * eps
+    # ...so every entry parks, and the old rule (no drain in front of the final epilogue) overran the area on even walks >= 4
+    assert _spill_peak(tiles, ring, spill, per_tile, final_drain=True) <= spill
+    assert (_spill_peak(tiles, ring, spill, per_tile, final_drain=False) > spill) == (tiles % 2 == 0 and tiles >= 4)
+    # ...and each query's passes fit: region (query, phase 0, wave row wm) holds `slots`, the rest goes to the overflow list
+    slots = _region_slots(nph * 2)
+    per_wm = torch.stack([(match & ((hrows % bm) // 128 == wm)[:, None]).sum(0) for wm in range(2)])   # [2, nq]
+    assert int((per_wm - slots).clamp(min=0).sum(0).max()) < ovf_cap and int(per_wm.sum(0).max()) <= cap
+    assert (per_wm.sum(0) == 32 * tiles).all() and 32 * tiles >= k
+
+    ix = FlatIndex(d, "COSINE", 0)
+    ix.add(g)
+    ix.set_option(L.OPT_FORCE_TAU, int(np.float32(tau).view(np.uint32)))
+    s, i = ix.search(q, k, return_f64=True)
+    st = ix.last_stats()
+    assert st["candidates"] == nq * 32 * tiles, st
+    assert st["overflowed"] == 0 and st["incomplete"] == 0 and st["tier1_answered"] == nq, st
+    # every light row scores below every passing score: the top-k lies among the heavy rows
+    o_s, o_i = OS.topk(q.numpy(), g[hrows].numpy(), k, ids=hrows.numpy())
     np.testing.assert_array_equal(i.cpu().numpy(), o_i)
     np.testing.assert_array_equal(s.cpu().numpy(), o_s)
 
