@@ -112,6 +112,10 @@ SYMBOLS = {
     "mirx_dwconv7x7_nhwc": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     "mirx_stem_conv7_bn_relu_pool_split3": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp]),
     "mirx_stem_conv7_bn_relu_pool": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp]),
+    "mirx_conv_terms": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _int, ctypes.c_float,
+                               ctypes.c_float, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_nchw_to_terms": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
+    "mirx_gap_nhwc_l2norm": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp]),
 }
 
 _lib = None

@@ -256,4 +256,13 @@ hipError_t launch_select_tau(const float *groupmax, int ngroups, int64_t nq, int
                              int rank_j, float *tau, hipStream_t st);
 hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st);
 
+// ---- k_conv_t2.hip: ResNet-50's convolutions on channels-last terms rows (mirx_conv_terms) and their glue ------------------
+hipError_t launch_conv_t2(const void *xt, const float *x_scale, const float *x_range, int64_t n, int h, int w, int cin, int ksz,
+                          int stride, const void *wt, const float *oscale, const float *bias, int cout, float w_abs_sum,
+                          float bias_abs_max, const void *rt, const float *r_scale, const float *r_range, int relu, void *yt,
+                          float *y_scale, float *y, float *out_range, hipStream_t st);
+hipError_t launch_nchw_to_terms(const float *x, int64_t xbs, int64_t n, int c, int hw, const float *range, float *scale_row,
+                                void *xt, hipStream_t st);
+hipError_t launch_gap_nhwc(const float *x, int64_t n, int hw, int c, int normalize, float *y, hipStream_t st);
+
 }  // namespace mirx

@@ -882,53 +882,21 @@ def _conv_patch_tokens(conv, x, ln2d=None, nchw_out=False):
 _TENSOR_VERSION = operator.attrgetter("_version")
 
 
-class DenseNet121(_Configurable, nn.Module):
-    """Reference model.py:42-84, MI355X-native inference path."""
-    accepts_uint8 = True        # forward() takes raw 8-bit images and applies ToTensor + Normalize itself (input_mean / input_std)
+class _InferenceCache:
+    """Mixin of the models whose inference path runs on weights derived once from the parameters (folded BatchNorm, pre-split
+    terms): `_cache()` returns the model's `_prepare_inference()` result and rebuilds it when any watched tensor changed.
+    The model names the module whose parameters and buffers are watched (`_watch_root`)."""
 
-    def __init__(self, pretrained=False, embedding_dim=None, num_labels=None, weights=None):
-        super().__init__()
-        if pretrained and weights is None:
-            raise RuntimeError("pretrained=True needs a download in the reference (model.py:53); "
-                               "pass weights=<state dict or path> instead")
-        feats, in_features = _make_features()
-        self.densenet121 = nn.Sequential(feats)
-        # reference model.py:59-60: ReLU appended to the feature stack, avgpool to the wrapper
-        self.densenet121[0].add_module("relu", nn.ReLU(inplace=True))
-        self.densenet121.add_module("avgpool", nn.AdaptiveAvgPool2d((1, 1)))
-        self.fc = nn.Linear(in_features, embedding_dim) if embedding_dim else None
-        out_features = embedding_dim if embedding_dim else in_features
-        self.classification_head = nn.Linear(out_features, num_labels) if num_labels else None
-        self.conv1x1_timer = None          # list -> (start event, stop event, FLOP) per fused conv launch
-        # raw 8-bit input: forward() also takes uint8 [B, 3, H, W] and applies the reference's ToTensor + Normalize
-        # (test.py:1309-1332) with these constants -- inside the stem kernel at 224 x 224, a quarter of the PCIe / HBM bytes
-        self.register_buffer("input_mean", torch.tensor(IMAGENET_MEAN, dtype=torch.float32), persistent=False)
-        self.register_buffer("input_std", torch.tensor(IMAGENET_STD, dtype=torch.float32), persistent=False)
-        self._infer_cache = None           # folded BatchNorm parameters of the inference path
-        self._init_config()
-        if weights is not None:
-            sd = torch.load(weights, map_location="cpu") if isinstance(weights, str) else weights
-            for key in ("state-dict", "state_dict"):      # wrappers test.py:1273-1276 accepts
-                if isinstance(sd, dict) and key in sd:
-                    sd = sd[key]
-            self.load_state_dict(sd, strict=False)
-
-    # -- the plain module graph (training, CPU tensors): same ops as the reference -------------
-    def forward_eager(self, x):
-        x = self.densenet121(x)
-        return torch.flatten(x, 1)
-
-    # -- MI355X inference path -------------------------------------------------------------------
     # The folded / pre-split weights are derived from the parameters and BatchNorm buffers; they are rebuilt whenever
     # any of those changed.  Routes that announce themselves drop the cache at once: load_state_dict (this module's own
     # and, through the pre-hook, a parent's), _apply (device moves, dtype casts), train().  What remains -- an in-place
     # edit of a parameter, a replaced tensor object -- is caught by ONE pass per forward over the watched tensors
-    # (versions and identities: ~0.1 ms for the 604 tensors; it was two passes of 0.22 ms, 18 % of a one-image forward).
+    # (versions and identities: ~0.1 ms for DenseNet's 604 tensors; it was two passes of 0.22 ms, 18 % of a one-image forward).
     def _watch_lists(self):
         w = self.__dict__.get("_mirx_watch")
         if w is None:
             dicts, keys = [], []
-            for m in self.densenet121[0].modules():
+            for m in self._watch_root().modules():
                 for d in (m._parameters, m._buffers):
                     for k in d:
                         if d[k] is not None and k != "num_batches_tracked":       # not read by an eval-mode BatchNorm
@@ -988,6 +956,47 @@ class DenseNet121(_Configurable, nn.Module):
     def _apply(self, fn, *a, **k):
         self._drop_cache()
         return super()._apply(fn, *a, **k)
+
+
+class DenseNet121(_Configurable, _InferenceCache, nn.Module):
+    """Reference model.py:42-84, MI355X-native inference path."""
+    accepts_uint8 = True        # forward() takes raw 8-bit images and applies ToTensor + Normalize itself (input_mean / input_std)
+
+    def __init__(self, pretrained=False, embedding_dim=None, num_labels=None, weights=None):
+        super().__init__()
+        if pretrained and weights is None:
+            raise RuntimeError("pretrained=True needs a download in the reference (model.py:53); "
+                               "pass weights=<state dict or path> instead")
+        feats, in_features = _make_features()
+        self.densenet121 = nn.Sequential(feats)
+        # reference model.py:59-60: ReLU appended to the feature stack, avgpool to the wrapper
+        self.densenet121[0].add_module("relu", nn.ReLU(inplace=True))
+        self.densenet121.add_module("avgpool", nn.AdaptiveAvgPool2d((1, 1)))
+        self.fc = nn.Linear(in_features, embedding_dim) if embedding_dim else None
+        out_features = embedding_dim if embedding_dim else in_features
+        self.classification_head = nn.Linear(out_features, num_labels) if num_labels else None
+        self.conv1x1_timer = None          # list -> (start event, stop event, FLOP) per fused conv launch
+        # raw 8-bit input: forward() also takes uint8 [B, 3, H, W] and applies the reference's ToTensor + Normalize
+        # (test.py:1309-1332) with these constants -- inside the stem kernel at 224 x 224, a quarter of the PCIe / HBM bytes
+        self.register_buffer("input_mean", torch.tensor(IMAGENET_MEAN, dtype=torch.float32), persistent=False)
+        self.register_buffer("input_std", torch.tensor(IMAGENET_STD, dtype=torch.float32), persistent=False)
+        self._infer_cache = None           # folded BatchNorm parameters of the inference path
+        self._init_config()
+        if weights is not None:
+            sd = torch.load(weights, map_location="cpu") if isinstance(weights, str) else weights
+            for key in ("state-dict", "state_dict"):      # wrappers test.py:1273-1276 accepts
+                if isinstance(sd, dict) and key in sd:
+                    sd = sd[key]
+            self.load_state_dict(sd, strict=False)
+
+    # -- the plain module graph (training, CPU tensors): same ops as the reference -------------
+    def forward_eager(self, x):
+        x = self.densenet121(x)
+        return torch.flatten(x, 1)
+
+    # -- MI355X inference path -------------------------------------------------------------------
+    def _watch_root(self):
+        return self.densenet121[0]
 
     def _prepare_inference(self):
         """Fold every eval-mode BatchNorm once: norm1/transition norm -> (scale, shift) for the
@@ -1846,6 +1855,249 @@ class MedSigLIP(_Configurable, nn.Module):
         return _normalize_rows(_linear_auto(p[3], h))
 
 
+# =================================================================================================
+# ResNet-50 (reference model.py:9-39: torchvision resnet50 without its classifier, children [:-1]).  torchvision is not a
+# dependency: the tree below reproduces its names -- resnet50 = Sequential(conv1, bn1, relu, maxpool, layer1..layer4, avgpool)
+# with indices 0-8, Bottleneck blocks {conv1, bn1, conv2, bn2, conv3, bn3, relu, downsample.0/.1}, the stride on conv2
+# (v1.5) -- so reference checkpoints (`resnet50.*`, `fc.*`) load unchanged.  23 508 032 backbone parameters.
+#
+# MI355X path (CUDA input, eval mode, grad off): the stem is DenseNet's (conv 7x7 / 2 + BN + ReLU + max-pool, one kernel,
+# mirx_stem_conv7_bn_relu_pool_split2h_into / _u8_into), turned into channels-last terms rows by one glue pass; every other
+# convolution is mirx_conv_terms (k_conv_t2.hip) with its BatchNorm folded, the block's residual and ReLU in the epilogue;
+# the head is mirx_gap_nhwc_l2norm on the last block's fp32 rows; fc through _linear_auto.  DESIGN 15.
+# =================================================================================================
+RESNET_LAYERS = (3, 4, 6, 3)
+RESNET_WIDTHS = (64, 128, 256, 512)
+
+
+class _Bottleneck(nn.Module):
+    """torchvision Bottleneck (expansion 4, stride on the 3x3 convolution)."""
+    expansion = 4
+
+    def __init__(self, cin, width, stride):
+        super().__init__()
+        cout = width * self.expansion
+        self.conv1 = nn.Conv2d(cin, width, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(width)
+        self.conv3 = nn.Conv2d(width, cout, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(cout)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = (nn.Sequential(nn.Conv2d(cin, cout, 1, stride=stride, bias=False), nn.BatchNorm2d(cout))
+                           if stride != 1 or cin != cout else None)
+        self.stride = stride
+
+    def forward(self, x):
+        idt = x if self.downsample is None else self.downsample(x)
+        y = self.relu(self.bn1(self.conv1(x)))
+        y = self.relu(self.bn2(self.conv2(y)))
+        return self.relu(self.bn3(self.conv3(y)) + idt)
+
+
+def _make_resnet50():
+    mods = [nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True),
+            nn.MaxPool2d(3, stride=2, padding=1)]
+    cin = 64
+    for i, (nb, width) in enumerate(zip(RESNET_LAYERS, RESNET_WIDTHS)):
+        blocks = []
+        for j in range(nb):
+            blocks.append(_Bottleneck(cin, width, 2 if (i > 0 and j == 0) else 1))
+            cin = width * _Bottleneck.expansion
+        mods.append(nn.Sequential(*blocks))
+    mods.append(nn.AdaptiveAvgPool2d((1, 1)))
+    seq = nn.Sequential(*mods)
+    for m in seq.modules():                                # torchvision's initialisation
+        if isinstance(m, nn.Conv2d):
+            nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+    return seq, cin
+
+
+def _conv_terms_weights(conv, bn):
+    """A convolution with its eval BatchNorm folded, as mirx_conv_terms takes it: dict of wt (terms rows of W[o] * ws[o] in K
+    order (ky, kx, c), rows padded to a multiple of 128), oscale = 1 / ws, bias, and the host constants of the output bound
+    (w_abs_sum = max_o sum |W[o, :]|, bias_abs_max = max |bias|), plus the geometry."""
+    scale, shift = _bn_affine(bn)
+    w = conv.weight.detach().float() * scale.view(-1, 1, 1, 1)
+    cout, cin, k, _ = w.shape
+    wk = w.permute(0, 2, 3, 1).reshape(cout, k * k * cin)
+    ws = _pow2_row_scales(wk)
+    wp = wk * ws[:, None]
+    if cout % 128:
+        wp = F.pad(wp, (0, 0, 0, 128 - cout % 128))
+    return {"wt": _terms_of(wp, 1.0), "osc": (1.0 / ws).contiguous(), "bias": shift.contiguous(),
+            "wsum": float(wk.abs().sum(dim=1).max()), "bmax": float(shift.abs().max()),
+            "k": k, "s": conv.stride[0], "cin": cin, "cout": cout}
+
+
+def _out_side(side, k, s):
+    p = (k - 1) // 2
+    return (side + 2 * p - k) // s + 1
+
+
+def conv_terms(cw, x, h, w, res=None, relu=True, terms_out=True, fp32_out=False, out_range=None):
+    """[HIP] one mirx_conv_terms launch.  cw = _conv_terms_weights(..); x = (terms rows fp16 [n * h * w, 2 cin], scale row [n],
+    range row [n]); res = (terms rows, scale row, range row) of the residual or None.  -> (yt, y_scale, y_range, y_fp32, ho, wo)
+    with yt / y_scale None unless terms_out and y_fp32 None unless fp32_out; out_range: the range row to fold max |y| into
+    (zeroed by the caller; a fresh one by default)."""
+    xt, xs, xr = x
+    n = xs.shape[0]
+    ho, wo = _out_side(h, cw["k"], cw["s"]), _out_side(w, cw["k"], cw["s"])
+    dev = xt.device
+    m = n * ho * wo
+    yt = torch.empty((m, 2 * cw["cout"]), dtype=torch.float16, device=dev) if terms_out else None
+    ys = torch.empty((n,), dtype=torch.float32, device=dev) if terms_out else None
+    y = torch.empty((m, cw["cout"]), dtype=torch.float32, device=dev) if fp32_out else None
+    yr = torch.zeros((n,), dtype=torch.float32, device=dev) if out_range is None else out_range
+    rt, rs, rr = res if res is not None else (None, None, None)
+    p = lambda t: None if t is None else _ptr(t)          # noqa: E731
+    _lib.check(_lib.load().mirx_conv_terms(_ptr(xt), _ptr(xs), _ptr(xr), n, h, w, cw["cin"], cw["k"], cw["s"], _ptr(cw["wt"]),
+                                           _ptr(cw["osc"]), _ptr(cw["bias"]), cw["cout"], cw["wsum"], cw["bmax"], p(rt), p(rs),
+                                           p(rr), 1 if relu else 0, p(yt), p(ys), p(y), _ptr(yr), _stream(dev)),
+               "mirx_conv_terms")
+    return yt, ys, yr, y, ho, wo
+
+
+class ResNet50(_Configurable, _InferenceCache, nn.Module):
+    """Reference model.py:9-39 (ResNet50), MI355X-native inference path."""
+    accepts_uint8 = True        # forward() takes raw 8-bit images and applies ToTensor + Normalize itself (input_mean / input_std)
+
+    def __init__(self, pretrained=False, embedding_dim=None, num_labels=None, weights=None):
+        super().__init__()
+        if pretrained and weights is None:
+            raise RuntimeError("pretrained=True needs a download in the reference (model.py:13); "
+                               "pass weights=<state dict or path> instead")
+        self.resnet50, in_features = _make_resnet50()
+        self.fc = nn.Linear(in_features, embedding_dim) if embedding_dim else None
+        out_features = embedding_dim if embedding_dim else in_features
+        self.classification_head = nn.Linear(out_features, num_labels) if num_labels else None
+        self.register_buffer("input_mean", torch.tensor(IMAGENET_MEAN, dtype=torch.float32), persistent=False)
+        self.register_buffer("input_std", torch.tensor(IMAGENET_STD, dtype=torch.float32), persistent=False)
+        self._infer_cache = None
+        self._init_config()
+        if weights is not None:
+            sd = torch.load(weights, map_location="cpu") if isinstance(weights, str) else weights
+            for key in ("state-dict", "state_dict"):
+                if isinstance(sd, dict) and key in sd:
+                    sd = sd[key]
+            self.load_state_dict(sd, strict=False)
+
+    # -- the plain module graph (training, CPU tensors): same ops as the reference -------------
+    def forward_eager(self, x):
+        return torch.flatten(self.resnet50(x), 1)
+
+    def normalize_uint8(self, x):
+        """ToTensor + Normalize of the reference (test.py:1309-1332) on uint8 [B, 3, H, W]: what the stem kernel's table holds."""
+        m = self.input_mean.to(x.device).view(1, 3, 1, 1)
+        s_ = self.input_std.to(x.device).view(1, 3, 1, 1)
+        return (x.float() / 255.0 - m) / s_
+
+    # -- MI355X inference path -------------------------------------------------------------------
+    def _watch_root(self):
+        return self.resnet50
+
+    def _blocks(self):
+        return [blk for layer in self.resnet50[4:8] for blk in layer]
+
+    def _prepare_inference(self):
+        """Fold every eval-mode BatchNorm into its convolution and pre-split the weights, once per weight version."""
+        r = self.resnet50
+        cache = {"stem": _stem_weights_split2h(r[0].weight) + _bn_affine(r[1]), "blocks": []}
+        for blk in self._blocks():
+            e = {"conv1": _conv_terms_weights(blk.conv1, blk.bn1), "conv2": _conv_terms_weights(blk.conv2, blk.bn2),
+                 "conv3": _conv_terms_weights(blk.conv3, blk.bn3)}
+            if blk.downsample is not None:
+                e["down"] = _conv_terms_weights(blk.downsample[0], blk.downsample[1])
+            cache["blocks"].append(e)
+        cache["_cuda"] = r[0].weight.is_cuda
+        self._infer_cache = cache
+        self._mark_built(cache)
+        return cache
+
+    def _features_native(self, x, cache):
+        """-> fp32 rows [B * h/32 * w/32, 2048] of layer4's output (channels last) and the pixels per image."""
+        lib = _lib.load()
+        u8 = x.dtype == torch.uint8
+        x = x.contiguous() if u8 else x.contiguous().float()
+        b, _, h, w = x.shape
+        dev = x.device
+        st = _stream(dev)
+        blocks = cache["blocks"]
+        # range rows: the input images, the stem's output, then per block conv1 / conv2 / downsample / conv3
+        ranges = torch.zeros((2 + 4 * len(blocks), b), dtype=torch.float32, device=dev)
+        xr = ranges[0]
+        if u8:
+            _lib.check(lib.mirx_range_absmax_u8(_ptr(x), h * w, b, _ptr(self.input_mean), _ptr(self.input_std), _ptr(xr), st),
+                       "mirx_range_absmax_u8")
+        else:
+            _lib.check(lib.mirx_range_absmax(_ptr(x), x[0].numel(), b, _ptr(xr), st), "mirx_range_absmax")
+        w2, osc, sc, sh = cache["stem"]
+        hs, wsd = h // 4, w // 4
+        y0 = torch.empty((b, 64, hs, wsd), dtype=torch.float32, device=dev)
+        if u8:
+            _lib.check(lib.mirx_stem_conv7_bn_relu_pool_split2h_u8_into(_ptr(x), _ptr(self.input_mean), _ptr(self.input_std),
+                                                                        _ptr(w2), _ptr(osc), _ptr(sc), _ptr(sh), b, h, w,
+                                                                        _ptr(y0), 64 * hs * wsd, _ptr(xr), _ptr(ranges[1]), st),
+                       "mirx_stem_split2h_u8_into")
+        else:
+            _lib.check(lib.mirx_stem_conv7_bn_relu_pool_split2h_into(_ptr(x), _ptr(w2), _ptr(osc), _ptr(sc), _ptr(sh), b, h, w,
+                                                                     _ptr(y0), 64 * hs * wsd, _ptr(xr), _ptr(ranges[1]), st),
+                       "mirx_stem_split2h_into")
+        t0 = torch.empty((b * hs * wsd, 128), dtype=torch.float16, device=dev)
+        s0 = torch.empty((b,), dtype=torch.float32, device=dev)
+        _lib.check(lib.mirx_nchw_to_terms(_ptr(y0), 64 * hs * wsd, b, 64, hs * wsd, _ptr(ranges[1]), _ptr(s0), _ptr(t0), st),
+                   "mirx_nchw_to_terms")
+        del y0
+        cur, side_h, side_w = (t0, s0, ranges[1]), hs, wsd
+        out = None
+        for i, e in enumerate(blocks):
+            last = i == len(blocks) - 1
+            r = 2 + 4 * i
+            t1, s1, r1, _, h1, w1 = conv_terms(e["conv1"], cur, side_h, side_w, out_range=ranges[r])
+            t2, s2, r2, _, h2, w2 = conv_terms(e["conv2"], (t1, s1, r1), h1, w1, out_range=ranges[r + 1])
+            del t1
+            if "down" in e:
+                td, sd_, rd, _, _, _ = conv_terms(e["down"], cur, side_h, side_w, relu=False, out_range=ranges[r + 2])
+                res = (td, sd_, rd)
+            else:
+                res = cur
+            t3, s3, r3, out, h3, w3 = conv_terms(e["conv3"], (t2, s2, r2), h2, w2, res=res, terms_out=not last,
+                                                 fp32_out=last, out_range=ranges[r + 3])
+            cur, side_h, side_w = (t3, s3, r3), h3, w3
+        self.__dict__["_mirx_last_ranges"] = ranges                 # kept for diagnostics (the bound's bit cost, DESIGN 15)
+        return out, side_h * side_w
+
+    def _embed_native(self, x, normalize, cache):
+        b, _, h, w = x.shape
+        if h % 4 or w % 4 or h < 8 or w < 8:
+            raise ValueError(f"ResNet50 native path: H and W must be multiples of 4 and at least 8 (got {h} x {w}); "
+                             f"resize the input (the reference's transform gives 224 x 224)")
+        if b > 65535:
+            return torch.cat([self._embed_native(x[i:i + 65535], normalize, cache) for i in range(0, b, 65535)])
+        rows, hw = self._features_native(x, cache)
+        out = torch.empty((b, rows.shape[1]), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().mirx_gap_nhwc_l2norm(_ptr(rows), b, hw, rows.shape[1], 1 if normalize else 0, _ptr(out),
+                                                    _stream(x.device)), "mirx_gap_nhwc_l2norm")
+        return out
+
+    def forward(self, x):
+        native = x.is_cuda and not self.training and not torch.is_grad_enabled()
+        if native:
+            with torch.cuda.device(x.device):
+                cache = self._cache()
+                plain_head = self.fc is None and self.classification_head is None
+                x = self._embed_native(x, plain_head, cache)
+                if plain_head:
+                    return x                       # already unit-norm (reference model.py:38)
+        else:
+            x = self.forward_eager(self.normalize_uint8(x) if x.dtype == torch.uint8 else x)
+        if self.fc:
+            x = _linear_auto(self.fc, x)         # [HIP] on the inference path: no library GEMM in a forward
+        if self.classification_head is not None:
+            return {"embedding": F.normalize(x, dim=1), "logits": self.classification_head(x)}
+        return F.normalize(x, dim=1)
+
+
 def build_model(model_type, embedding_dim=None, **kw):
     """Factory in the spirit of milvus_retrieval.py:143-162 (unknown type -> ValueError)."""
     if model_type == "densenet121":
@@ -1856,9 +2108,11 @@ def build_model(model_type, embedding_dim=None, **kw):
         return DinoV2(embedding_dim=embedding_dim, **kw), 518
     if model_type == "medsiglip":
         return MedSigLIP(embed_dim=embedding_dim if embedding_dim is not None else 512, **kw), 448
-    if model_type in ("resnet50", "convnextv2_sra"):
+    if model_type == "resnet50":
+        return ResNet50(embedding_dim=embedding_dim, **kw), 224
+    if model_type == "convnextv2_sra":
         # named in the reference's MODEL_CONFIGS (collection names) and kept there for compatibility, but not on the hot path
-        # SURVEY section 8 scopes (DenseNet-121, ConvNeXtV2, DINOv2, MedSigLIP): no MI355X-native forward exists for them
+        # SURVEY section 8 scopes (DenseNet-121, ConvNeXtV2, DINOv2, MedSigLIP): no MI355X-native forward exists for it
         raise ValueError(f"Unknown model type: {model_type} (outside the accelerated path: build it with the reference's own "
                          f"model.py and feed its embeddings to MilvusRetriever / FlatIndex)")
     raise ValueError(f"Unknown model type: {model_type}")

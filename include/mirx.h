@@ -626,6 +626,45 @@ int mirx_dwconv7x7_nchw_to_nhwc(const float *x, const float *w, const float *bia
 int mirx_dwconv7x7_nhwc(const float *x, const float *w_taps_first, const float *bias, int64_t n, int c, int h, int wd, float *y,
                         void *stream);
 
+/*
+ * ResNet-50 on channels-last TERMS ROWS (layout: mirx_linear_terms above; image b of a map is n_pixels rows of c / 32 lines).
+ * Every terms map travels with two device fp32 rows [n]: its SCALE row (the power of two image b was written with) and its
+ * RANGE row (largest |value| of image b before the split, zeroed by the caller once per forward, folded in by unsigned atomic
+ * max: mirx_common.h).  An image's arithmetic reads only its own rows, so its embedding does not depend on its batch mates and
+ * a non-finite image makes only its own outputs NaN.  Replaces the torchvision Bottleneck convolutions the reference's
+ * ResNet50 runs (model.py:9-39 there, models.resnet50 children [:-1]).
+ *
+ * mirx_conv_terms: y[b, oy, ox, o] = relu?( oscale[o] / x_scale[b] * sum_{ky, kx, c} x[b, s oy + ky - p, s ox + kx - p, c]
+ *                  * W2[o, ky, kx, c] + bias[o] (+ res[b, oy, ox, o]) ),  p = (ksize - 1) / 2, ho = (h + 2 p - ksize) / s + 1
+ *     as an implicit GEMM on two fp16 terms per operand (k_conv_t2.hip); padding taps read zeros.
+ *     xt = terms rows [n, h, w, cin] with x_scale / x_range its scale and range rows; ksize 1 or 3, stride 1 or 2,
+ *     cin and cout multiples of 32, any h and w.
+ *     wt = terms rows of W2[o, :] = W[o, ky, kx, c] * ws[o] in K order (ky, kx, c) (W: conv weight with the eval BatchNorm
+ *     folded in, ws a power of two per output channel putting max |W2[o, :]| in [2^13, 2^14)), rows padded with zeros to
+ *     a multiple of 128; oscale = device fp32 [cout] = 1 / ws; bias = device fp32 [cout] (the folded BatchNorm shift).
+ *     w_abs_sum = max_o sum |W[o, :]| and bias_abs_max = max |bias| (host constants of the layer).
+ *     res_or_null = terms rows [n, ho, wo, cout] (the Bottleneck's identity or downsample branch) with its scale and
+ *     range rows.  relu != 0: ReLU after the residual.
+ *     Outputs (either or both): yt_or_null = terms rows [n, ho, wo, cout] of y_scale[b] * y, where
+ *         y_scale[b] = 2^(14 - floor(log2 bound_b)),  bound_b = x_range[b] * w_abs_sum + bias_abs_max (+ res_range[b])
+ *     (>= every |y| of the image; a function of rows complete before the launch, written into y_scale_or_null for the
+ *     consumer); y_or_null = fp32 rows [n * ho * wo, cout].  out_range_or_null: range row of y.
+ * mirx_nchw_to_terms: xt (terms rows [n, hw, c]) of the NCHW fp32 map x (images x_batch_stride floats apart: the stem's
+ *     output, mirx_stem_conv7_bn_relu_pool_split2h_into / _u8_into) with image b scaled by 2^(14 - floor(log2 range_row[b]))
+ *     (range_row = the stem's output range), written into scale_row[b].  c % 32 == 0.
+ * mirx_gap_nhwc_l2norm: y[b, :] = mean over the hw pixels of x[b, p, :] (fp32 rows [n, hw, c], c % 4 == 0), then, with
+ *     normalize, y[b] / max(||y[b]||_2, 1e-12): AdaptiveAvgPool2d(1) + flatten + F.normalize of the reference's ResNet50
+ *     (model.py:26-38 there); the channels-last form of mirx_bn_relu_gap_l2norm without norm and ReLU.
+ * Buffers 16-byte aligned.
+ */
+int mirx_conv_terms(const void *xt, const float *x_scale, const float *x_range, int64_t n, int h, int w, int cin, int ksize,
+                    int stride, const void *wt, const float *oscale, const float *bias, int cout, float w_abs_sum,
+                    float bias_abs_max, const void *res_or_null, const float *res_scale, const float *res_range, int relu,
+                    void *yt_or_null, float *y_scale_or_null, float *y_or_null, float *out_range_or_null, void *stream);
+int mirx_nchw_to_terms(const float *x, int64_t x_batch_stride, int64_t n, int c, int hw, const float *range_row,
+                       float *scale_row, void *xt, void *stream);
+int mirx_gap_nhwc_l2norm(const float *x, int64_t n, int hw, int c, int normalize, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
