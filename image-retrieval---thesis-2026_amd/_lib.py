@@ -116,6 +116,9 @@ SYMBOLS = {
                                ctypes.c_float, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "mirx_nchw_to_terms": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "mirx_gap_nhwc_l2norm": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp]),
+    "mirx_window_attention_split2h": (_int, [_vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, ctypes.c_float, _vp]),
+    "mirx_swin_postnorm": (_int, [_vp, _vp, _i64, _int, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, _vp]),
+    "mirx_patch_merge_terms": (_int, [_vp, _i64, _int, _int, _int, ctypes.c_float, _vp, _vp]),
 }
 
 _lib = None

@@ -265,4 +265,11 @@ hipError_t launch_nchw_to_terms(const float *x, int64_t xbs, int64_t n, int c, i
                                 void *xt, hipStream_t st);
 hipError_t launch_gap_nhwc(const float *x, int64_t n, int hw, int c, int normalize, float *y, hipStream_t st);
 
+// ---- k_attention_win.hip / k_swin.hip: SwinV2's shifted-window cosine attention and its res-post-norm / merge glue ----------
+hipError_t launch_attention_win(const float *qkv, int64_t n, int side, int window, int shift, int heads, const float *bias_tab,
+                                const float *lscale, float *out, void *out_t, float t_scale, hipStream_t st);
+hipError_t launch_postnorm_rows(const float *x, const float *y, int64_t m, int c, const float *gamma, const float *beta, float eps,
+                                float *out, void *out_t, float scale, hipStream_t st);
+hipError_t launch_patch_merge(const float *x, int64_t n, int h, int w, int c, float scale, void *out_t, hipStream_t st);
+
 }  // namespace mirx

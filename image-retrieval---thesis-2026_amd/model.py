@@ -2098,6 +2098,381 @@ class ResNet50(_Configurable, _InferenceCache, nn.Module):
         return F.normalize(x, dim=1)
 
 
+# =================================================================================================
+# SwinV2-B (reference model.py:418-446: timm 0.9.7 `swinv2_base_window12to24_192to384.ms_in22k_ft_in1k`, num_classes=0, at
+# 384 x 384, + optional fc + F.normalize).  timm is not a dependency: the tree below reproduces its names -- swinv2.patch_embed.
+# {proj, norm}, swinv2.layers.{0..3}.{downsample (PatchMerging at the START of stages 1-3), blocks.j.{attn.{qkv, q_bias, v_bias,
+# logit_scale, cpb_mlp.{0,2}, proj}, norm1, mlp.{fc1, fc2}, norm2}}, swinv2.norm -- so reference checkpoints load unchanged.
+# k_bias, relative_coords_table, relative_position_index and attn_mask are derived from the configuration (non-persistent; a
+# checkpoint that carries them loads and is not read).  86 893 816 backbone parameters.  Res-post-norm blocks:
+#   x = x + norm1(attn(x)),  x = x + norm2(mlp(x)).
+#
+# MI355X path (CUDA fp32 384 x 384 input, eval mode, grad off), per block: qkv Linear (mirx_linear_terms) -> shifted-window
+# cosine attention written as terms rows (mirx_window_attention_split2h: roll / partition / mask by addressing, compact bias
+# table) -> proj -> x += norm1(.) with x also written as terms rows (mirx_swin_postnorm) -> fc1 + GELU as terms -> fc2 ->
+# x += norm2(.).  Stages start with mirx_patch_merge_terms -> reduction -> LayerNorm; the stem is _conv_patch_tokens; the head
+# the final LayerNorm + mirx_gap_nhwc_l2norm.  Every Linear reads two fp16 terms scaled by a host-side bound of its input
+# (the residual stream's bound grows by the LayerNorm bounds of norm1 / norm2 per block).  DESIGN 16.
+# =================================================================================================
+SWIN_IMG = 384
+SWIN_PATCH = 4
+SWIN_DEPTHS = (2, 2, 18, 2)
+SWIN_DIMS = (128, 256, 512, 1024)
+SWIN_HEADS = (4, 8, 16, 32)
+SWIN_WINDOW = 24
+SWIN_PRETRAINED_WINDOWS = (12, 12, 12, 6)
+SWIN_CHUNK = 64                 # images per pass of the native path (bounds the activation memory; results do not depend on it)
+_SWIN_DERIVED = ("k_bias", "relative_coords_table", "relative_position_index")
+
+
+class _SwinAttention(nn.Module):
+    """timm 0.9.7 swin_transformer_v2.WindowAttention: cosine attention with a learned per-head logit scale and a continuous
+    relative-position bias (cpb_mlp over a log-spaced coordinate table)."""
+
+    def __init__(self, dim, heads, window, pretrained_window):
+        super().__init__()
+        self.dim, self.num_heads, self.window = dim, heads, window
+        self.logit_scale = nn.Parameter(torch.log(10 * torch.ones((heads, 1, 1))))
+        self.cpb_mlp = nn.Sequential(nn.Linear(2, 512, bias=True), nn.ReLU(inplace=True), nn.Linear(512, heads, bias=False))
+        r = torch.arange(-(window - 1), window, dtype=torch.float32)
+        table = torch.stack(torch.meshgrid([r, r], indexing="ij")).permute(1, 2, 0).contiguous().unsqueeze(0)
+        table /= (pretrained_window - 1) if pretrained_window > 0 else (window - 1)
+        table *= 8
+        table = torch.sign(table) * torch.log2(torch.abs(table) + 1.0) / math.log2(8)
+        self.register_buffer("relative_coords_table", table, persistent=False)          # [1, 2w-1, 2w-1, 2]
+        c = torch.arange(window)
+        coords = torch.stack(torch.meshgrid([c, c], indexing="ij")).flatten(1)          # [2, w*w]
+        rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0)
+        self.register_buffer("relative_position_index", (rel[..., 0] + window - 1) * (2 * window - 1) + rel[..., 1] + window - 1,
+                             persistent=False)                                            # [w*w, w*w]
+        self.qkv = nn.Linear(dim, dim * 3, bias=False)
+        self.q_bias = nn.Parameter(torch.zeros(dim))
+        self.register_buffer("k_bias", torch.zeros(dim), persistent=False)
+        self.v_bias = nn.Parameter(torch.zeros(dim))
+        self.proj = nn.Linear(dim, dim)
+
+    def _load_from_state_dict(self, state_dict, prefix, *a, **k):
+        for name in _SWIN_DERIVED:                     # derived from the configuration: a checkpoint's copy is not read
+            state_dict.pop(prefix + name, None)
+        return super()._load_from_state_dict(state_dict, prefix, *a, **k)
+
+    def bias_table(self):
+        """16 sigmoid(cpb_mlp(relative_coords_table)) -> [heads, (2 w - 1)^2] (the compact table the kernel gathers from)."""
+        t = self.cpb_mlp(self.relative_coords_table.to(self.cpb_mlp[0].weight.dtype)).view(-1, self.num_heads)
+        return (16 * torch.sigmoid(t)).t()
+
+    def logit_scales(self):
+        return torch.clamp(self.logit_scale, max=math.log(1.0 / 0.01)).exp()
+
+    def forward(self, x, mask=None):
+        """x: windows [B_, N, C] -> [B_, N, C]; mask [nW, N, N] (0 / -100) or None."""
+        b_, n, c = x.shape
+        qkv = F.linear(x, self.qkv.weight, torch.cat((self.q_bias, self.k_bias.to(self.q_bias.dtype), self.v_bias)))
+        q, k, v = qkv.reshape(b_, n, 3, self.num_heads, -1).permute(2, 0, 3, 1, 4).unbind(0)
+        attn = F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-2, -1)
+        attn = attn * self.logit_scales()
+        bias = self.bias_table()[:, self.relative_position_index.view(-1)].view(self.num_heads, n, n)
+        attn = attn + bias.unsqueeze(0)
+        if mask is not None:
+            nw = mask.shape[0]
+            attn = (attn.view(-1, nw, self.num_heads, n, n) + mask.to(attn.dtype).unsqueeze(1).unsqueeze(0)).view(-1, self.num_heads, n, n)
+        x = (attn.softmax(dim=-1) @ v).transpose(1, 2).reshape(b_, n, c)
+        return self.proj(x)
+
+
+class _SwinMlp(nn.Module):
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.act = nn.GELU()
+        self.fc2 = nn.Linear(hidden, dim)
+
+    def forward(self, x):
+        return self.fc2(self.act(self.fc1(x)))
+
+
+class _SwinBlock(nn.Module):
+    """timm 0.9.7 SwinTransformerV2Block (res-post-norm); the window is clamped to the map and the shift dropped when the window
+    covers the map (_calc_window_shift)."""
+
+    def __init__(self, dim, side, heads, window, shift, pretrained_window):
+        super().__init__()
+        self.side = side
+        self.window = min(window, side)
+        self.shift = 0 if side <= self.window else shift
+        self.attn = _SwinAttention(dim, heads, self.window, pretrained_window)
+        self.norm1 = nn.LayerNorm(dim)
+        self.mlp = _SwinMlp(dim, 4 * dim)
+        self.norm2 = nn.LayerNorm(dim)
+        mask = None
+        if self.shift:
+            ws, s = self.window, self.shift
+            img = torch.zeros((1, side, side, 1))
+            cnt = 0
+            for h in (slice(0, -ws), slice(-ws, -s), slice(-s, None)):
+                for w in (slice(0, -ws), slice(-ws, -s), slice(-s, None)):
+                    img[:, h, w, :] = cnt
+                    cnt += 1
+            mw = _window_partition(img, ws).view(-1, ws * ws)
+            mask = mw.unsqueeze(1) - mw.unsqueeze(2)
+            mask = mask.masked_fill(mask != 0, -100.0).masked_fill(mask == 0, 0.0)
+        self.register_buffer("attn_mask", mask, persistent=False)
+
+    def _load_from_state_dict(self, state_dict, prefix, *a, **k):
+        state_dict.pop(prefix + "attn_mask", None)
+        return super()._load_from_state_dict(state_dict, prefix, *a, **k)
+
+    def _attn(self, x):
+        b, h, w, c = x.shape
+        ws, s = self.window, self.shift
+        if s:
+            x = torch.roll(x, shifts=(-s, -s), dims=(1, 2))
+        win = self.attn(_window_partition(x, ws).view(-1, ws * ws, c), mask=self.attn_mask)
+        x = _window_reverse(win.view(-1, ws, ws, c), ws, h, w)
+        if s:
+            x = torch.roll(x, shifts=(s, s), dims=(1, 2))
+        return x
+
+    def forward(self, x):
+        x = x + self.norm1(self._attn(x))
+        return x + self.norm2(self.mlp(x))
+
+
+def _window_partition(x, ws):
+    b, h, w, c = x.shape
+    return x.view(b, h // ws, ws, w // ws, ws, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, ws, ws, c)
+
+
+def _window_reverse(win, ws, h, w):
+    c = win.shape[-1]
+    return win.view(-1, h // ws, w // ws, ws, ws, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, h, w, c)
+
+
+class _SwinPatchMerging(nn.Module):
+    """timm 0.9.7 PatchMerging: 2 x 2 quads concatenated as (0, 0), (1, 0), (0, 1), (1, 1) (row, column), reduction, norm."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = nn.LayerNorm(2 * dim)
+
+    def forward(self, x):
+        b, h, w, c = x.shape
+        x = x.reshape(b, h // 2, 2, w // 2, 2, c).permute(0, 1, 3, 4, 2, 5).flatten(3)
+        return self.norm(self.reduction(x))
+
+
+class _SwinStage(nn.Module):
+    def __init__(self, dim, out_dim, side, depth, heads, window, pretrained_window, downsample):
+        super().__init__()
+        self.downsample = _SwinPatchMerging(dim) if downsample else nn.Identity()
+        side = side // 2 if downsample else side
+        self.side = side
+        self.blocks = nn.ModuleList([_SwinBlock(out_dim, side, heads, window, 0 if i % 2 == 0 else window // 2, pretrained_window)
+                                     for i in range(depth)])
+
+    def forward(self, x):
+        x = self.downsample(x)
+        for blk in self.blocks:
+            x = blk(x)
+        return x
+
+
+class _SwinPatchEmbed(nn.Module):
+    def __init__(self, dim):
+        super().__init__()
+        self.proj = nn.Conv2d(3, dim, kernel_size=SWIN_PATCH, stride=SWIN_PATCH)
+        self.norm = nn.LayerNorm(dim)
+
+    def forward(self, x):
+        return self.norm(self.proj(x).permute(0, 2, 3, 1))
+
+
+class _SwinV2Backbone(nn.Module):
+    """timm SwinTransformerV2 with num_classes=0: forward(x [B, 3, 384, 384]) -> mean over tokens of norm(layers(patch_embed(x)))."""
+
+    def __init__(self):
+        super().__init__()
+        self.img_size = SWIN_IMG
+        self.num_features = SWIN_DIMS[-1]
+        self.patch_embed = _SwinPatchEmbed(SWIN_DIMS[0])
+        side = SWIN_IMG // SWIN_PATCH
+        layers = []
+        for i, (depth, dim, heads) in enumerate(zip(SWIN_DEPTHS, SWIN_DIMS, SWIN_HEADS)):
+            layers.append(_SwinStage(SWIN_DIMS[max(i - 1, 0)], dim, side, depth, heads, SWIN_WINDOW, SWIN_PRETRAINED_WINDOWS[i],
+                                     downsample=i > 0))
+            side = layers[-1].side
+        self.layers = nn.ModuleList(layers)
+        self.norm = nn.LayerNorm(self.num_features)
+        for m in self.modules():                                 # timm's initialisation
+            if isinstance(m, nn.Linear):
+                nn.init.trunc_normal_(m.weight, std=0.02)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        if tuple(x.shape[-2:]) != (self.img_size, self.img_size):
+            raise ValueError(f"SwinV2: input size ({x.shape[-2]}*{x.shape[-1]}) doesn't match model ({self.img_size}*{self.img_size})")
+        x = self.patch_embed(x)
+        for layer in self.layers:
+            x = layer(x)
+        return self.norm(x).mean(dim=(1, 2))
+
+
+class _LinearView:
+    """A Linear's weight with another bias (the qkv Linear with cat(q_bias, 0, v_bias)), duck-typed for _linear_terms."""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight.detach(), bias
+        self.out_features, self.in_features = weight.shape
+
+
+class SwinV2(_Configurable, _InferenceCache, nn.Module):
+    """Reference model.py:418-446 (SwinV2: `swinv2`, `fc`, unit-norm output), MI355X-native inference path."""
+
+    def __init__(self, pretrained=False, embedding_dim=None, weights=None):
+        super().__init__()
+        if pretrained and weights is None:
+            raise RuntimeError("pretrained=True needs a download in the reference (model.py:424-428); "
+                               "pass weights=<state dict or path> instead")
+        self.swinv2 = _SwinV2Backbone()
+        self.fc = nn.Linear(self.swinv2.num_features, embedding_dim) if embedding_dim else None
+        self._infer_cache = None
+        self._init_config()
+        if weights is not None:
+            sd = torch.load(weights, map_location="cpu") if isinstance(weights, str) else weights
+            for key in ("state-dict", "state_dict"):
+                if isinstance(sd, dict) and key in sd:
+                    sd = sd[key]
+            self.load_state_dict(sd, strict=False)
+
+    # -- the plain module graph (training, CPU tensors): same ops as timm ---------------------------------------------------
+    def forward_eager(self, x):
+        return torch.flatten(self.swinv2(x), 1)
+
+    # -- MI355X inference path -------------------------------------------------------------------------------------------------
+    def _watch_root(self):
+        return self.swinv2
+
+    def _prepare_inference(self):
+        """Per block: the qkv view with its concatenated bias, the compact bias table, exp(clamp(logit_scale)) and the host-side
+        bounds of every Linear's input (the residual stream's bound R: a stage starts at its LayerNorm's bound and every block adds
+        the bounds of norm1 and norm2)."""
+        bb = self.swinv2
+        with torch.no_grad():
+            r = _layernorm_bound(bb.patch_embed.norm)
+            cache = {"r0": r, "stages": []}
+            for stage in bb.layers:
+                st = {"r_in": r, "blocks": []}
+                if isinstance(stage.downsample, _SwinPatchMerging):
+                    r = _layernorm_bound(stage.downsample.norm)
+                for blk in stage.blocks:
+                    at = blk.attn
+                    c = at.dim
+                    qkv = _LinearView(at.qkv.weight, torch.cat((at.q_bias, at.k_bias, at.v_bias)).detach().float().contiguous())
+                    wv = at.qkv.weight.detach()[2 * c:].double()
+                    # |attention output| <= max |v_j| <= ||x||_2 ||W_v,j||_2 + |b_j|, ||x||_2 <= sqrt(C) R
+                    ba = math.sqrt(c) * r * float(torch.linalg.vector_norm(wv, dim=1).max()) + float(at.v_bias.detach().abs().max())
+                    r1 = r + _layernorm_bound(blk.norm1)
+                    w1 = blk.mlp.fc1
+                    bh = (math.sqrt(c) * r1 * float(torch.linalg.vector_norm(w1.weight.detach().double(), dim=1).max())
+                          + float(w1.bias.detach().abs().max()))                    # |gelu(v)| <= |v|
+                    r2 = r1 + _layernorm_bound(blk.norm2)
+                    st["blocks"].append({"qkv": qkv, "table": at.bias_table().detach().float().contiguous(),
+                                         "ls": at.logit_scales().detach().float().reshape(-1).contiguous(),
+                                         "r_qkv": r, "b_att": ba, "r_fc1": r1, "b_hid": bh, "r_out": r2})
+                    r = r2
+                cache["stages"].append(st)
+        cache["_cuda"] = bb.patch_embed.proj.weight.is_cuda
+        self._infer_cache = cache
+        self._mark_built(cache)
+        return cache
+
+    def _features_native(self, x, cache):
+        """x [b, 3, 384, 384] fp32 CUDA -> fp32 rows [b * 144, 1024] of the final LayerNorm (channels last)."""
+        bb = self.swinv2
+        lib = _lib.load()
+        dev = x.device
+        st_ = _stream(dev)
+        b = x.shape[0]
+        side = SWIN_IMG // SWIN_PATCH
+        y = _conv_patch_tokens(bb.patch_embed.proj, x)                     # [b * 96 * 96, 128]
+        xs = _terms_scale(cache["r0"])
+        cur, xt = self._postnorm(None, y, bb.patch_embed.norm, xs)
+        for si, (stage, sc) in enumerate(zip(bb.layers, cache["stages"])):
+            if isinstance(stage.downsample, _SwinPatchMerging):
+                ds = stage.downsample
+                c = cur.shape[1]
+                ms = _terms_scale(sc["r_in"])
+                mt = torch.empty((b * (side // 2) ** 2, 4 * c * 2), dtype=torch.float16, device=dev)
+                _lib.check(lib.mirx_patch_merge_terms(_ptr(cur), b, side, side, c, ms, _ptr(mt), st_), "mirx_patch_merge_terms")
+                side //= 2
+                y = _linear_terms(ds.reduction, mt, ms, (mt.shape[0],))
+                del mt
+                cur, xt = self._postnorm(None, y, ds.norm, _terms_scale(sc["blocks"][0]["r_qkv"]))
+            for j, (blk, e) in enumerate(zip(stage.blocks, sc["blocks"])):
+                at = blk.attn
+                m, c = cur.shape
+                last = j == len(stage.blocks) - 1
+                xs = _terms_scale(e["r_qkv"])
+                qkv = _linear_terms(e["qkv"], xt, xs, (m,))
+                sa = _terms_scale(e["b_att"])
+                att = torch.empty((m, 2 * c), dtype=torch.float16, device=dev)
+                _lib.check(lib.mirx_window_attention_split2h(_ptr(qkv), b, side, blk.window, blk.shift, at.num_heads, c // at.num_heads,
+                                                              _ptr(e["table"]), _ptr(e["ls"]), None, _ptr(att), sa, st_),
+                           "mirx_window_attention_split2h")
+                del qkv
+                y = _linear_terms(at.proj, att, sa, (m,))
+                del att
+                s1 = _terms_scale(e["r_fc1"])
+                cur, xt = self._postnorm(cur, y, blk.norm1, s1)
+                ht, hs = _linear_terms(blk.mlp.fc1, xt, s1, (m,), act=1, terms_bound=e["b_hid"])
+                y = _linear_terms(blk.mlp.fc2, ht, hs, (m,))
+                del ht
+                nxt = None if last else _terms_scale(sc["blocks"][j + 1]["r_qkv"])
+                cur, xt = self._postnorm(cur, y, blk.norm2, nxt)
+        return _layernorm(bb.norm, cur), side * side
+
+    @staticmethod
+    def _postnorm(x, y, ln, terms_scale):
+        """[HIP] x + LayerNorm(y) (x None: LayerNorm(y)), in place into x; with terms_scale also as terms rows -> (out, terms)."""
+        m, c = y.shape
+        out = x if x is not None else torch.empty_like(y)
+        t = torch.empty((m, 2 * c), dtype=torch.float16, device=y.device) if terms_scale is not None else None
+        _lib.check(_lib.load().mirx_swin_postnorm(_ptr(x) if x is not None else None, _ptr(y), m, c, _ptr(ln.weight.detach()),
+                                                  _ptr(ln.bias.detach()), float(ln.eps), _ptr(out), _ptr(t) if t is not None else None,
+                                                  terms_scale if terms_scale is not None else 1.0, _stream(y.device)),
+                   "mirx_swin_postnorm")
+        return out, t
+
+    def _embed_native(self, x, normalize, cache):
+        b = x.shape[0]
+        if b > SWIN_CHUNK:
+            return torch.cat([self._embed_native(x[i:i + SWIN_CHUNK], normalize, cache) for i in range(0, b, SWIN_CHUNK)])
+        rows, hw = self._features_native(x.contiguous(), cache)
+        out = torch.empty((b, rows.shape[1]), dtype=torch.float32, device=x.device)
+        _lib.check(_lib.load().mirx_gap_nhwc_l2norm(_ptr(rows), b, hw, rows.shape[1], 1 if normalize else 0, _ptr(out),
+                                                    _stream(x.device)), "mirx_gap_nhwc_l2norm")
+        return out
+
+    def forward(self, x):
+        if tuple(x.shape[-2:]) != (SWIN_IMG, SWIN_IMG) or x.dim() != 4:
+            raise ValueError(f"SwinV2: input size ({x.shape[-2]}*{x.shape[-1]}) doesn't match model ({SWIN_IMG}*{SWIN_IMG}); "
+                             f"the reference's transform gives {SWIN_IMG} x {SWIN_IMG}")
+        native = x.is_cuda and not self.training and not torch.is_grad_enabled() and x.dtype == torch.float32
+        if native:
+            with torch.cuda.device(x.device):
+                cache = self._cache()
+                x = self._embed_native(x, self.fc is None, cache)
+                if self.fc is None:
+                    return x                       # already unit-norm (reference model.py:444)
+                return _normalize_rows(_linear_auto(self.fc, x))        # [HIP] no library GEMM in a forward
+        x = self.forward_eager(x)
+        if self.fc:
+            x = self.fc(x)
+        return F.normalize(x, dim=1)
+
+
 def build_model(model_type, embedding_dim=None, **kw):
     """Factory in the spirit of milvus_retrieval.py:143-162 (unknown type -> ValueError)."""
     if model_type == "densenet121":
@@ -2110,6 +2485,8 @@ def build_model(model_type, embedding_dim=None, **kw):
         return MedSigLIP(embed_dim=embedding_dim if embedding_dim is not None else 512, **kw), 448
     if model_type == "resnet50":
         return ResNet50(embedding_dim=embedding_dim, **kw), 224
+    if model_type == "swinv2":
+        return SwinV2(embedding_dim=embedding_dim, **kw), SWIN_IMG
     if model_type == "convnextv2_sra":
         # named in the reference's MODEL_CONFIGS (collection names) and kept there for compatibility, but not on the hot path
         # SURVEY section 8 scopes (DenseNet-121, ConvNeXtV2, DINOv2, MedSigLIP): no MI355X-native forward exists for it

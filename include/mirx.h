@@ -665,6 +665,37 @@ int mirx_nchw_to_terms(const float *x, int64_t x_batch_stride, int64_t n, int c,
                        float *scale_row, void *xt, void *stream);
 int mirx_gap_nhwc_l2norm(const float *x, int64_t n, int hw, int c, int normalize, float *y, void *stream);
 
+/*
+ * SwinV2 (timm 0.9.7 swinv2_base_window12to24_192to384, the backbone of the reference's SwinV2, model.py:418-446 there) on
+ * fp32 raster rows [n, side, side, c] (c = heads * head_dim).  Replace torch.roll + window_partition + WindowAttention +
+ * window_reverse + roll back (one mirx_window_attention_split2h), `x + norm1(..)` / `x + norm2(..)` (mirx_swin_postnorm) and
+ * PatchMerging's reshape / permute / flatten (mirx_patch_merge_terms) of SwinTransformerV2Block and its stages.
+ *
+ * mirx_window_attention_split2h: qkv = the qkv Linear's output rows [n * side * side, 3 c] (bias cat(q_bias, 0, v_bias) included;
+ *     q, k, v of head h at columns h * 32, c + h * 32, 2 c + h * 32).  For every window of the map shifted by `shift` (token
+ *     (ty, tx) of window (wy, wx) is pixel ((wy window + ty + shift) mod side, (wx window + tx + shift) mod side)):
+ *         out[pixel(t), h * 32 + d] = sum_u softmax_u(cos(q_t, k_u) ls[h] + bias_table[h, rel(t, u)] + mask(t, u)) v_u[d],
+ *     rel(t, u) = (ty - uy + window - 1) (2 window - 1) + (tx - ux + window - 1), mask = -100 where t and u lie in different
+ *     regions of timm's shifted-window mask (slices [0, side - window), [side - window, side - shift), [side - shift, side) per
+ *     axis; no mask for shift 0); cos from F.normalize(.., eps 1e-12) in fp32.  bias_table = device fp32 [heads, (2 window -
+ *     1)^2] (16 sigmoid(cpb_mlp(relative_coords_table)) transposed); logit_scale = device fp32 [heads], exp(min(logit_scale,
+ *     ln 100)).  Both GEMMs on two fp16 terms per operand (k_attention_win.hip); v staged at a power of two from the largest
+ *     |v| of its own (image, window, head).  head_dim 32, window 12 or 24, side a multiple of window, 0 <= shift < window.
+ *     Outputs (either or both): out_or_null fp32 rows [n * side * side, c]; out_terms_or_null terms rows (mirx_linear_terms) of
+ *     out_scale * out.
+ * mirx_swin_postnorm: out = x + LayerNorm(y) over rows of c (x_or_null NULL: out = LayerNorm(y)); out may be x, not y.  gamma,
+ *     beta device [c].  out_terms_or_null: out also written as terms rows of terms_scale * out.  c % 32 == 0, c <= 1024.
+ * mirx_patch_merge_terms: terms rows [n, h / 2, w / 2, 4 c] of scale * x, x = fp32 rows [n, h, w, c]: row (b, i, j) holds the
+ *     pixels (2 i, 2 j), (2 i + 1, 2 j), (2 i, 2 j + 1), (2 i + 1, 2 j + 1) in that order (timm PatchMerging).  c % 8 == 0.
+ * Buffers 16-byte aligned.
+ */
+int mirx_window_attention_split2h(const float *qkv, int64_t n, int side, int window, int shift, int heads, int head_dim,
+                                  const float *bias_table, const float *logit_scale, float *out_or_null, void *out_terms_or_null,
+                                  float out_scale, void *stream);
+int mirx_swin_postnorm(const float *x_or_null, const float *y, int64_t m, int c, const float *gamma, const float *beta, float eps,
+                       float *out, void *out_terms_or_null, float terms_scale, void *stream);
+int mirx_patch_merge_terms(const float *x, int64_t n, int h, int w, int c, float scale, void *out_terms, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
