@@ -119,6 +119,9 @@ SYMBOLS = {
     "mirx_window_attention_split2h": (_int, [_vp, _i64, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp, ctypes.c_float, _vp]),
     "mirx_swin_postnorm": (_int, [_vp, _vp, _i64, _int, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, _vp]),
     "mirx_patch_merge_terms": (_int, [_vp, _i64, _int, _int, _int, ctypes.c_float, _vp, _vp]),
+    "mirx_sra_head_nhwc": (_int, [_vp, _i64, _int, _int, _vp, _int, _vp, _vp, ctypes.c_float, ctypes.c_float, _int, _vp, _vp]),
+    "mirx_pcam_head_nhwc": (_int, [_vp, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, ctypes.c_float, ctypes.c_float, _int, _vp, _vp,
+                                   _vp]),
 }
 
 _lib = None

@@ -272,4 +272,10 @@ hipError_t launch_postnorm_rows(const float *x, const float *y, int64_t m, int c
                                 float *out, void *out_t, float scale, hipStream_t st);
 hipError_t launch_patch_merge(const float *x, int64_t n, int h, int w, int c, float scale, void *out_t, hipStream_t st);
 
+// ---- k_attnpool.hip: the SRA / PCAM attention-pooling heads on channels-last rows, one workgroup per image ------------------
+hipError_t launch_sra_head(const float *x, int64_t n, int hw, int c, const float *w, int K, const float *gamma, const float *beta,
+                           float eps, float lam, int normalize, float *y, hipStream_t st);
+hipError_t launch_pcam_head(const float *x, int64_t n, int hw, int c, const float *w, const float *b, int K, const float *gamma,
+                            const float *beta, float eps, float lam, int normalize, float *feat, float *logits, hipStream_t st);
+
 }  // namespace mirx

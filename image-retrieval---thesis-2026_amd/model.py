@@ -1466,10 +1466,11 @@ class _ConvNeXtV2Backbone(nn.Module):
             return _layernorm(self.stem[1], tok, tokens_per_image=(h // 4) * (w // 4)).view(b, -1, h // 4, w // 4)
         return self.stem(x)
 
-    def _forward_nhwc(self, x):
+    def _forward_rows(self, x):
         """[HIP] The whole backbone with a channels-last residual stream [b * h * w, c] (no NCHW map between the patch embedding
         and the pooled head): stem = patch gather + MFMA Linear + LayerNorm rows; downsample = LayerNorm written straight into
-        2 x 2 patch rows + MFMA Linear (weight in (ky, kx, c) order); blocks = _CnxBlock._forward_nhwc."""
+        2 x 2 patch rows + MFMA Linear (weight in (ky, kx, c) order); blocks = _CnxBlock._forward_nhwc.
+        -> (the final stream [b * h * w, c], h, w): the pre-pool map, channels-last."""
         lib = _lib.load()
         b, _, h, w = x.shape
         dev = x.device
@@ -1495,7 +1496,12 @@ class _ConvNeXtV2Backbone(nn.Module):
                 t = _linear_h2(pl, rows, bound) if _linear_h2_ok(pl, rows, bound) else _linear_s3(pl, rows)
             for blk in stage.blocks:
                 t = blk._forward_nhwc(t, b, h, w)
-        pooled = t.view(b, h * w, t.shape[-1]).mean(dim=1)                                    # global average pool
+        return t, h, w
+
+    def _forward_nhwc(self, x):
+        """[HIP] _forward_rows, then the global average pool and head.norm."""
+        t, h, w = self._forward_rows(x)
+        pooled = t.view(x.shape[0], h * w, t.shape[-1]).mean(dim=1)                           # global average pool
         return _layernorm(self.head.norm, pooled)
 
     def _nhwc_ok(self, x):
@@ -1508,6 +1514,14 @@ class _ConvNeXtV2Backbone(nn.Module):
         if h % 32 or w % 32:                                  # stem / 4, three downsamples / 2
             return False
         return all(blk._nhwc_ok() for stage in self.stages for blk in stage.blocks)
+
+    def forward_features(self, x):
+        """timm's forward_features: the pre-pool map [b, c, h / 32, w / 32] (on the native path a channels-last view of the
+        stream)."""
+        if self._nhwc_ok(x):
+            t, h, w = self._forward_rows(x.contiguous())
+            return t.view(x.shape[0], h, w, t.shape[-1]).permute(0, 3, 1, 2)
+        return self.stages(self._stem(x))
 
     def forward(self, x):
         if self._nhwc_ok(x):
@@ -1543,6 +1557,160 @@ class ConvNeXtV2(_Configurable, nn.Module):
             return l2_normalize_(x)                # HIP F.normalize (model.py:116)
         return F.normalize(x, dim=1)
 
+
+# =================================================================================================
+# ConvNeXtV2 with the reference's pooling heads (model.py:120-278 there): SRA ("Spatial Residual Attention", the thesis'
+# ConvNeXtV2_SRA, trained by train_sra.py) and PCAMPool (probabilistic-CAM pooling, ConvNeXtV2_PCAM).  Both heads share the
+# backbone's head.norm as their `norm_layer` (one module object under two names, as there), so `convnext.*`, `sra.*` and
+# `pcam.*` checkpoints load with strict=True.  On CUDA in eval mode the backbone's channels-last stream goes straight into one
+# HIP head kernel (k_attnpool.hip); everywhere else the heads below are the reference's formulas in torch.
+# =================================================================================================
+ATTNPOOL_MAX_C = 8192             # include/mirx.h: the limits mirx_sra_head_nhwc / mirx_pcam_head_nhwc accept
+ATTNPOOL_MAX_K = 64
+ATTNPOOL_LDS_FLOATS = 16384       # (K + 3) * hw <= this
+
+
+def _attnpool_ok(c, k, hw):
+    return c % 4 == 0 and 4 <= c <= ATTNPOOL_MAX_C and 1 <= k <= ATTNPOOL_MAX_K and hw >= 1 and (k + 3) * hw <= ATTNPOOL_LDS_FLOATS
+
+
+def _load_local_weights(model, weights):
+    """ConvNeXtV2's rules: a state dict or a path to one (optionally under "state-dict" / "state_dict"), loaded strict=False."""
+    sd = torch.load(weights, map_location="cpu") if isinstance(weights, str) else weights
+    for key in ("state-dict", "state_dict"):
+        if isinstance(sd, dict) and key in sd:
+            sd = sd[key]
+    model.load_state_dict(sd, strict=False)
+
+
+class SRA(nn.Module):
+    """Reference model.py:120-164: GAP + LayerNorm plus lam x the LayerNormed mean over K softmax-attention pools."""
+
+    def __init__(self, input_dim, num_heads=8, lam=0.1, norm_layer=None):
+        super().__init__()
+        self.num_heads = num_heads
+        self.lam = lam
+        self.norm_layer = norm_layer
+        self.conv_att = nn.Conv2d(input_dim, num_heads, kernel_size=1, bias=False)
+        self.softmax = nn.Softmax(dim=2)
+        nn.init.normal_(self.conv_att.weight, mean=0.0, std=1e-4)
+
+    def forward(self, x):
+        b, c, h, w = x.shape
+        gap = x.mean(dim=(2, 3), keepdim=True)
+        if self.norm_layer is not None:
+            gap = self.norm_layer(gap)
+        gap = torch.flatten(gap, 1)
+        att = self.softmax(self.conv_att(x).reshape(b, self.num_heads, h * w))          # [b, K, hw]
+        pooled = torch.bmm(att, x.reshape(b, c, h * w).permute(0, 2, 1)).mean(dim=1).reshape(b, c, 1, 1)
+        if self.norm_layer is not None:
+            pooled = self.norm_layer(pooled)
+        return gap + self.lam * torch.flatten(pooled, 1)
+
+
+class PCAMPool(nn.Module):
+    """Reference model.py:199-257: probabilistic-CAM pooling -> (embedding, class_logits, pcam_probs)."""
+
+    def __init__(self, input_dim, num_classes, lam=0.1, norm_layer=None, embedding_dim=None):
+        super().__init__()
+        self.num_classes = num_classes
+        self.lam = lam
+        self.norm_layer = norm_layer
+        self.classifier = nn.Conv2d(input_dim, num_classes, kernel_size=1)
+        self.fc = nn.Linear(input_dim, embedding_dim) if embedding_dim else None
+
+    def forward(self, x):
+        b, c, h, w = x.shape
+        gap = x.mean(dim=(2, 3), keepdim=True)
+        if self.norm_layer is not None:
+            gap = self.norm_layer(gap)
+        gap = torch.flatten(gap, 1)
+        z = self.norm_layer(x) if self.norm_layer is not None else x
+        probs = torch.sigmoid(self.classifier(z))                                         # [b, K, h, w]
+        q = probs.reshape(b, self.num_classes, h * w)
+        q = q / (q.sum(dim=2, keepdim=True) + 1e-8)
+        pooled = torch.bmm(q, z.reshape(b, c, h * w).permute(0, 2, 1))                    # [b, K, c]
+        logits = torch.einsum("bkc,kc->bk", pooled, self.classifier.weight.reshape(self.num_classes, c))
+        if self.classifier.bias is not None:
+            logits = logits + self.classifier.bias
+        feat = gap + self.lam * (F.softmax(logits, dim=1).unsqueeze(2) * pooled).sum(dim=1)
+        if self.fc is not None:
+            feat = self.fc(feat)
+        return F.normalize(feat, dim=1), logits, probs
+
+
+def _native_head_ok(model, x, k):
+    """The backbone's native path takes x, the model is in eval mode, and the head kernel's limits hold for the final map."""
+    bb = model.convnext
+    if model.training or not bb._nhwc_ok(x):
+        return False
+    return _attnpool_ok(bb.num_features, k, (x.shape[2] // 32) * (x.shape[3] // 32))
+
+
+def _head_rows(model, x):
+    """[HIP] The backbone's final channels-last stream and the head norm's arguments."""
+    t, h, w = model.convnext._forward_rows(x.contiguous())
+    ln = model.convnext.head.norm
+    return t, h * w, t.shape[-1], _ptr(ln.weight.detach()), _ptr(ln.bias.detach()), float(ln.eps)
+
+
+class ConvNeXtV2_SRA(_Configurable, nn.Module):
+    """Reference model.py:167-196: `convnext` backbone + `sra` head (norm_layer = convnext.head.norm), unit-norm [B, 1024]."""
+
+    def __init__(self, pretrained=False, num_heads=8, lam=0.1, weights=None):
+        super().__init__()
+        if pretrained and weights is None:
+            raise RuntimeError("pretrained=True needs a download in the reference (model.py:176-180); "
+                               "pass weights=<state dict or path> instead")
+        self.convnext = _ConvNeXtV2Backbone()
+        self.sra = SRA(self.convnext.num_features, num_heads=num_heads, lam=lam, norm_layer=self.convnext.head.norm)
+        if weights is not None:
+            _load_local_weights(self, weights)
+
+    def forward(self, x):
+        if _native_head_ok(self, x, self.sra.num_heads):
+            t, hw, c, g, bt, eps = _head_rows(self, x)
+            wa = self.sra.conv_att.weight.detach().reshape(self.sra.num_heads, c)
+            y = torch.empty((x.shape[0], c), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().mirx_sra_head_nhwc(_ptr(t), x.shape[0], hw, c, _ptr(wa), self.sra.num_heads, g, bt, eps,
+                                                          float(self.sra.lam), 1, _ptr(y), _stream(x.device)), "mirx_sra_head_nhwc")
+            return y
+        return F.normalize(self.sra(self.convnext.forward_features(x)), dim=1)
+
+
+class ConvNeXtV2_PCAM(_Configurable, nn.Module):
+    """Reference model.py:260-278: `convnext` backbone + `pcam` head; eval -> unit-norm [B, embedding_dim or 1024], training ->
+    {"embedding", "class_logits", "pcam_maps"}."""
+
+    def __init__(self, pretrained=False, num_classes=3, lam=0.1, embedding_dim=None, weights=None):
+        super().__init__()
+        if pretrained and weights is None:
+            raise RuntimeError("pretrained=True needs a download in the reference (model.py:263-267); "
+                               "pass weights=<state dict or path> instead")
+        self.convnext = _ConvNeXtV2Backbone()
+        self.pcam = PCAMPool(self.convnext.num_features, num_classes=num_classes, lam=lam, norm_layer=self.convnext.head.norm,
+                             embedding_dim=embedding_dim)
+        if weights is not None:
+            _load_local_weights(self, weights)
+
+    def forward(self, x):
+        pc = self.pcam
+        if pc.classifier.bias is not None and _native_head_ok(self, x, pc.num_classes):
+            t, hw, c, g, bt, eps = _head_rows(self, x)
+            wc = pc.classifier.weight.detach().reshape(pc.num_classes, c)
+            feat = torch.empty((x.shape[0], c), dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().mirx_pcam_head_nhwc(_ptr(t), x.shape[0], hw, c, _ptr(wc), _ptr(pc.classifier.bias.detach()),
+                                                           pc.num_classes, g, bt, eps, float(pc.lam), int(pc.fc is None),
+                                                           _ptr(feat), None, _stream(x.device)), "mirx_pcam_head_nhwc")
+            if pc.fc is None:
+                return feat
+            return _normalize_rows(_linear_auto(pc.fc, feat))
+        embedding, class_logits, probs = pc(self.convnext.forward_features(x))
+        if self.training:
+            return {"embedding": embedding, "class_logits": class_logits, "pcam_maps": probs}
+        return embedding
 
 # =================================================================================================
 # DINOv2 ViT-B/14 (reference model.py:448-494 and nih_multilabel_retrieval.py:170-221 around timm
@@ -2488,8 +2656,8 @@ def build_model(model_type, embedding_dim=None, **kw):
     if model_type == "swinv2":
         return SwinV2(embedding_dim=embedding_dim, **kw), SWIN_IMG
     if model_type == "convnextv2_sra":
-        # named in the reference's MODEL_CONFIGS (collection names) and kept there for compatibility, but not on the hot path
-        # SURVEY section 8 scopes (DenseNet-121, ConvNeXtV2, DINOv2, MedSigLIP): no MI355X-native forward exists for it
-        raise ValueError(f"Unknown model type: {model_type} (outside the accelerated path: build it with the reference's own "
-                         f"model.py and feed its embeddings to MilvusRetriever / FlatIndex)")
+        # named in the reference's MODEL_CONFIGS (collection names), but its factory (milvus_retrieval.py:143-162) has no such
+        # branch either: the reference builds the class directly (test.py:1172, ingest_embeddings.py:46), and so does a user here
+        raise ValueError(f"Unknown model type: {model_type} (construct mirx.model.ConvNeXtV2_SRA(num_heads=.., lam=..) directly, "
+                         f"as the reference does)")
     raise ValueError(f"Unknown model type: {model_type}")

@@ -696,6 +696,34 @@ int mirx_swin_postnorm(const float *x_or_null, const float *y, int64_t m, int c,
                        float *out, void *out_terms_or_null, float terms_scale, void *stream);
 int mirx_patch_merge_terms(const float *x, int64_t n, int h, int w, int c, float scale, void *out_terms, void *stream);
 
+/*
+ * Attention-pooling heads of the reference's ConvNeXtV2_SRA / ConvNeXtV2_PCAM (model.py:120-278 there: SRA.forward and
+ * PCAMPool.forward after convnext.forward_features) on the backbone's final channels-last residual stream x = fp32 rows
+ * [n, hw, c] (image b's pixel p at row b * hw + p).  LN(v) = LayerNorm over c with device affine gamma, beta [c] and eps (the
+ * shared convnext.head.norm).  One workgroup per image with one fixed reduction order, so an image's output bits depend only on
+ * its own rows and the weights; non-finite rows reach only their own image's output.  fp32 arithmetic throughout.
+ *
+ * mirx_sra_head_nhwc: w_att device [K, c] (conv_att, no bias).
+ *     g = LN(mean_p x[p]);  a[k, p] = softmax_p(w_att[k] . x[p]) (max-subtracted);  s = LN(sum_p ((1 / K) sum_k a[k, p]) x[p]);
+ *     y[b] = g + lam s, divided by max(||.||_2, 1e-12) when normalize != 0 (F.normalize).
+ * mirx_pcam_head_nhwc: w_cls device [K, c], b_cls device [K] (classifier).
+ *     g = LN(mean_p x[p]);  z[p] = LN(x[p]);  q[k, p] = sigmoid(w_cls[k] . z[p] + b_cls[k]) / (sum_p sigmoid(..) + 1e-8);
+ *     P[k] = sum_p q[k, p] z[p];  logit[k] = P[k] . w_cls[k] + b_cls[k];  feat[b] = g + lam sum_k softmax_k(logit)[k] P[k],
+ *     normalised as above when normalize != 0 (the reference normalises after its optional fc: pass 0 when an fc follows).
+ *     class_logits_or_null: device [n, K] <- logit.
+ * Limits (MIRX_EINVAL with a message, nothing launched, outside them): c % 4 == 0, 4 <= c <= 8192; 1 <= K <= 64; hw >= 1 and
+ * (K + 3) * hw <= 16384 (the per-pixel weights live in 64 KiB of LDS: K = 8 allows hw <= 1489, K = 64 allows hw <= 244);
+ * n < 2^31; x, w, gamma, beta and the output 16-byte aligned.
+ */
+#define MIRX_ATTNPOOL_MAX_C 8192
+#define MIRX_ATTNPOOL_MAX_K 64
+#define MIRX_ATTNPOOL_LDS_FLOATS 16384
+int mirx_sra_head_nhwc(const float *x, int64_t n, int hw, int c, const float *w_att, int K, const float *gamma, const float *beta,
+                       float eps, float lam, int normalize, float *y, void *stream);
+int mirx_pcam_head_nhwc(const float *x, int64_t n, int hw, int c, const float *w_cls, const float *b_cls, int K, const float *gamma,
+                        const float *beta, float eps, float lam, int normalize, float *feat, float *class_logits_or_null,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
