@@ -19,6 +19,7 @@ OPT_FORCE_TAU = 3
 OPT_PROFILE = 4
 TUNE_CONV1X1_SMALL_MAX_WG = 1      # mirx_set_tuning keys
 TUNE_CONV3X3_SMALL_MAX_WG = 2
+TUNE_CONV1X1_RING = 3
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
 

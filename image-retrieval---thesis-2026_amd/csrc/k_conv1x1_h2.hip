@@ -18,7 +18,8 @@
 //
 // Contract otherwise as mirx_conv1x1_bn_relu_split3: y = act_out(W * act_in(x) + bias), NCHW, tile 128 output
 // channels x 128 (small launches) or 2 x 128 pixels, 16-channel stages, double-buffered LDS (32 / 48 KiB), weights by LDS
-// DMA, activations register-prefetched.  w2 = [cout / 128][cin / 16][2 terms][128 out][16 in] fp16.
+// DMA, activations register-prefetched (the tiled arm); large launches whose 16-byte chunks stay inside a channel plane take
+// the ring arm below (activations by LDS DMA too).  w2 = [cout / 128][cin / 16][2 terms][128 out][16 in] fp16.
 #include <atomic>
 
 #include "mirx_kernels.h"
@@ -96,17 +97,17 @@ __device__ __forceinline__ void pair_exchange(const u32x4 &p, const u32x4 &q, u3
 // (An eight-wave arm -- ONE workgroup per CU, waves 0-3 and 4-7 each on two pixel tiles against one staged copy of the weights,
 // half the L2 -> LDS weight stream per pixel -- was built in round 3, parity-green and SLOWER (89.8 / 90.1 vs 88.5 / 88.5 ms
 // per forward): eight waves meeting at one barrier lose more than the shared operand saves.  Removed in round 4)
+#define C1H2_PARAMS                                                                                                      \
+    const float *__restrict__ x, int64_t xbs, int cin, const float *__restrict__ scale, const float *__restrict__ shift, \
+        const uint16_t *__restrict__ w2, const float *__restrict__ oscale, const float *__restrict__ bias, int64_t n,     \
+        int hw, int cout, float *__restrict__ y, int64_t ybs, const float *__restrict__ in_amax, float in_ks, float in_kb, \
+        unsigned *__restrict__ out_amax, float y_ks, float y_kb, float *__restrict__ y_inv_out, int64_t xps, int64_t yps
+#define C1H2_ARGS x, xbs, cin, scale, shift, w2, oscale, bias, n, hw, cout, y, ybs, in_amax, in_ks, in_kb, out_amax, y_ks, y_kb, \
+                  y_inv_out, xps, yps
+
+// The tiled arm: activations register-staged, split into terms by the staging thread and written to LDS as terms.
 template <bool PROLOGUE, bool RELU_OUT, bool YTERMS, int NPT, bool TABLED>
-__global__ __launch_bounds__(256, NPT == 2 ? 2 : 3) void k_conv1x1_h2(const float *__restrict__ x, int64_t xbs, int cin,
-                                                       const float *__restrict__ scale,
-                                                       const float *__restrict__ shift,
-                                                       const uint16_t *__restrict__ w2,
-                                                       const float *__restrict__ oscale,
-                                                       const float *__restrict__ bias, int64_t n, int hw, int cout,
-                                                       float *__restrict__ y, int64_t ybs,
-                                                       const float *__restrict__ in_amax, float in_ks, float in_kb,
-                                                       unsigned *__restrict__ out_amax, float y_ks, float y_kb,
-                                                       float *__restrict__ y_inv_out, int64_t xps, int64_t yps) {
+__device__ __forceinline__ void conv1x1_tiled(C1H2_PARAMS) {
     extern __shared__ __attribute__((aligned(16))) char sm[];
     constexpr int KIMG = 8;                        // images a workgroup's pixels may span with a table row each (else: multiply)
     __shared__ float sBias[CM], sOsc[KIMG][CM];
@@ -511,6 +512,324 @@ __global__ __launch_bounds__(256, NPT == 2 ? 2 : 3) void k_conv1x1_h2(const floa
     }
 }
 
+// ---- the ring arm (large launches; the launcher picks it where its conditions hold) -----------------------------------
+// Tile 128 output channels x 256 pixels, 16-channel stages as the tiled arm, but nothing of a stage passes through
+// registers on its way into LDS: the stage's 8 KiB of weight terms AND its 16 KiB of raw fp32 activations go global -> LDS
+// by 16-byte LDS DMA (6 wave-instructions per stage instead of 2 + 16 loads and 4 LDS term stores) into a ring of three
+// slots, two stages in flight, one barrier per stage behind a COUNTED wait among DMA pieces only.  BN + ReLU + x_scale +
+// the fp16 split happen on the consumer side: wave w owns all 128 output channels x pixels 64 w .. 64 w + 63 (acc[4][2],
+// the same 128 accumulator registers), so every activation value is read from LDS and converted by exactly ONE lane --
+// the lane whose B fragment holds it -- and the weight terms are the only operand the waves share.
+// Bit-identical to the tiled arm: the same fp32 operations on every value (fma, max, x 2^s, split2h_pair), the same fragments
+// (channel 8 kg + j -> K slot j of lane half kg, the same column -> pixel map) and the same three MFMAs per product block,
+// stage kt ascending, for every accumulator.
+// Conditions (launcher): 16-byte chunks never straddle an image or a channel plane (hw, xps, xbs multiples of 4, x 16-byte
+// aligned), byte offsets fit 31 bits, cin <= 1024 with a prologue (the BN table lives in LDS for the whole launch).
+constexpr int RSLOTS = 3;                          // ring slots: stages kt (read), kt + 1 (landing), kt + 2 (issued)
+constexpr int RNP = 2 * CP;                        // pixels per workgroup
+constexpr int RSLOT_W = 2 * PLANE_A;               // a slot: weight terms (as the tiled arm's A region) ...
+constexpr int RSLOT = RSLOT_W + KC * RNP * 4;      // ... then raw activations [16 channels][256 pixels] fp32: 24 KiB
+constexpr int RING_BN = RSLOTS * RSLOT;            // BN scale[cin], shift[cin] behind the ring (prologue only)
+constexpr int RING_BN_MAX_CIN = 1024;              // 72 + 8 KiB: two workgroups per CU in 160 KiB
+constexpr int RING_PIECES = 6;                     // DMA wave-instructions per wave and stage: 2 weight + 4 activation
+
+template <bool PROLOGUE, bool RELU_OUT, bool YTERMS, bool TABLED>
+__device__ __forceinline__ void conv1x1_ring(C1H2_PARAMS) {
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    constexpr int KIMG = 8;                        // images a workgroup's pixels may span with a table row each
+    constexpr bool YFOLD = YTERMS && TABLED;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int tid = threadIdx.x;
+    const int64_t total = n * (int64_t)hw;
+    const int64_t p0 = (int64_t)blockIdx.x * RNP;
+    const int co0 = blockIdx.y * CM;
+    const int nk = cin / KC;
+    auto image_bound = [&](int64_t img) { return fmaf(in_ks, in_amax ? in_amax[img] : 0.f, in_kb); };
+    const unsigned img_first = (unsigned)p0 / (unsigned)hw;                 // p0 < total: the grid has no empty workgroup
+    const unsigned p_last = (unsigned)(p0 + RNP - 1 < total ? p0 + RNP - 1 : total - 1);
+
+    // weights: the tiled arm's DMA pieces (piece p, lane l -> term p / 4, row 32 (p & 3) + l / 2, swizzled slot)
+    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)(w2 + ((int64_t)blockIdx.y * nk) * (2 * CM * KC)), 0, nk * (2 * CM * KC * 2), 0x00020000);
+    const int w_voff = (lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) << 4);
+    // activations: one piece = one channel's 256 pixels, lane l -> pixels 4 l .. 4 l + 3 (one 16-byte chunk of one image's
+    // plane); the resource starts at the workgroup's first image, so the offsets stay small.  A dead chunk (past the batch)
+    // re-reads the first chunk: its columns are never stored.
+    const __amdgpu_buffer_rsrc_t xrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void *)(x + (int64_t)img_first * xbs), 0, 0x7fffffff, 0x00020000);
+    int x_voff = 0;
+    {
+        const unsigned pp = (unsigned)p0 + 4u * lane;
+        if (pp < (unsigned)total) {
+            const unsigned pimg = pp / (unsigned)hw;
+            x_voff = (int)(((int64_t)(pimg - img_first) * xbs + (pp - pimg * (unsigned)hw)) * 4);
+        }
+    }
+    const int xps4 = (int)xps * 4;
+    auto dma = [&](int kt, int slot) {
+        char *sb = sm + slot * RSLOT;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int piece = wave + 4 * i;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrsrc, LDS_PTR(sb + piece * 1024), 16, w_voff,
+                                                     kt * (2 * CM * KC * 2) + piece * 1024, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int c = 4 * wave + i;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrsrc, LDS_PTR(sb + RSLOT_W + c * (RNP * 4)), 16, x_voff,
+                                                     (kt * KC + c) * xps4, 0, 0);
+        }
+    };
+
+    // the BN table: read into registers first, written to LDS behind the first two stages' DMA
+    float *bn = reinterpret_cast<float *>(sm + RING_BN);
+    constexpr int BNR = PROLOGUE ? 2 * RING_BN_MAX_CIN / 256 : 1;
+    float bnv[BNR];
+    if (PROLOGUE) {
+#pragma unroll
+        for (int i = 0; i < BNR; ++i) {
+            const int e = tid + 256 * i;
+            bnv[i] = e < cin ? scale[e] : (e < 2 * cin ? shift[e - cin] : 0.f);
+        }
+    }
+    // the epilogue's constants (its tables are built in a free ring slot after the K loop)
+    float t_bias = 0.f, t_osc = 0.f;
+    if (tid < CM) {
+        t_bias = bias ? bias[co0 + tid] : 0.f;
+        t_osc = oscale[co0 + tid];
+    }
+    const unsigned nimg = p_last / (unsigned)hw - img_first + 1;
+    __builtin_amdgcn_sched_barrier(0);
+    dma(0, 0);
+    if (nk > 1) dma(1, 1);
+    __builtin_amdgcn_sched_barrier(0);
+    if (PROLOGUE) {
+#pragma unroll
+        for (int i = 0; i < BNR; ++i) {
+            const int e = tid + 256 * i;
+            if (e < 2 * cin) bn[e] = bnv[i];
+        }
+    }
+    float ib[KIMG];                                                   // bounds of the images the tile spans (TABLED)
+#pragma unroll
+    for (int k = 0; k < KIMG; ++k) ib[k] = TABLED && (unsigned)k < nimg ? image_bound(img_first + k) : 0.f;
+
+    // per B column (ni): this lane's pixel (the tiled arm's column -> pixel map), its image and that image's scales
+    const int ep_px = YTERMS ? 16 * (lane & 1) + ((lane & 31) >> 1) : (lane & 31);
+    float x_scale[2], ep_xinv[2], ep_ys[2];
+    int ep_k[2];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        unsigned pp = (unsigned)(p0 + 64 * wave + 32 * ni + ep_px);
+        if (pp >= (unsigned)total) pp = (unsigned)total - 1u;
+        const unsigned pimg = pp / (unsigned)hw;
+        const float xb = image_bound(pimg);
+        float yi_;
+        range_scales(xb, x_scale[ni], ep_xinv[ni]);
+        ep_k[ni] = TABLED ? (int)(pimg - img_first) : 0;
+        if (TABLED) ep_xinv[ni] = 1.f;                                  // folded into the table row
+        ep_ys[ni] = 1.f;
+        if (YTERMS) range_scales(fmaf(y_ks, xb, y_kb), ep_ys[ni], yi_);
+    }
+
+    // fragment addressing: A as the tiled arm, rows 32 mi + (lane & 31); B: raw value of channel 8 kg + j, column ni at
+    // fb + j * (RNP * 4) + ni * 128
+    const int kg = lane >> 5;
+    int fa[4];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int ra_ = mi * 32 + (lane & 31);
+        fa[mi] = ra_ * 32 + ((kg ^ ((ra_ >> 3) & 1)) << 4);
+    }
+    const int fb = RSLOT_W + 8 * kg * (RNP * 4) + (64 * wave + ep_px) * 4;
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+
+    int slot = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        // stage kt landed: this wave's pieces of it are retired when at most the pieces of stage kt + 1 are outstanding
+        // (DMA pieces only: nothing else is issued to the vector memory pipe inside the loop); the barrier then makes
+        // every wave's pieces visible, and tells that every wave has finished reading slot (kt + 2) % 3 (stage kt - 1)
+        if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RING_PIECES) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (kt + 2 < nk) dma(kt + 2, slot == 0 ? 2 : slot - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const char *sb = sm + slot * RSLOT;
+        f16x8 a[4][2], b[2][2];
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int p = 0; p < 2; ++p) a[mi][p] = *reinterpret_cast<const f16x8 *>(sb + fa[mi] + p * PLANE_A);
+        float sc[8], sh[8];
+        if (PROLOGUE) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                sc[j] = bn[kt * KC + 8 * kg + j];
+                sh[j] = bn[cin + kt * KC + 8 * kg + j];
+            }
+        }
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            u32x4 ph, pl;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                f32x2 v;
+                v[0] = *reinterpret_cast<const float *>(sb + fb + (2 * j) * (RNP * 4) + ni * 128);
+                v[1] = *reinterpret_cast<const float *>(sb + fb + (2 * j + 1) * (RNP * 4) + ni * 128);
+                if (PROLOGUE) {
+                    v[0] = fmaxf(fmaf(v[0], sc[2 * j], sh[2 * j]), 0.f);
+                    v[1] = fmaxf(fmaf(v[1], sc[2 * j + 1], sh[2 * j + 1]), 0.f);
+                }
+                unsigned th, tl;
+                split2h_pair(v[0] * x_scale[ni], v[1] * x_scale[ni], th, tl);
+                ph[j] = th;
+                pl[j] = tl;
+            }
+            b[ni][0] = __builtin_bit_cast(f16x8, ph);
+            b[ni][1] = __builtin_bit_cast(f16x8, pl);
+        }
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                f32x16 c = acc[mi][ni];
+                // smallest terms first
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi][1], b[ni][0], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi][0], b[ni][1], c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi][0], b[ni][0], c, 0, 0, 0);
+                acc[mi][ni] = c;
+            }
+        }
+        slot = slot == RSLOTS - 1 ? 0 : slot + 1;
+    }
+
+    // the epilogue's tables go to slot nk % 3: read last by stage nk - 3, before the barrier of stage nk - 1 that every wave
+    // has passed, and no DMA targets it any more (the last wait of the loop was vmcnt(0))
+    float *sBias = reinterpret_cast<float *>(sm + (nk % RSLOTS) * RSLOT);
+    float(*sOsc)[CM] = reinterpret_cast<float(*)[CM]>(sBias + CM);
+    float(*sBiasY)[CM] = reinterpret_cast<float(*)[CM]>(sBias + CM + KIMG * CM);
+    if (tid < CM) {
+        sBias[tid] = t_bias;
+        sOsc[0][tid] = t_osc;
+        if (TABLED) {
+#pragma unroll
+            for (int k = 0; k < KIMG; ++k) {
+                if ((unsigned)k < nimg) {
+                    float xs_, xi_;
+                    range_scales(ib[k], xs_, xi_);
+                    float ys_ = 1.f, yi_;
+                    if (YFOLD) range_scales(fmaf(y_ks, ib[k], y_kb), ys_, yi_);
+                    sOsc[k][tid] = t_osc * xi_ * ys_;                     // powers of two: exact
+                    if (YFOLD) sBiasY[k][tid] = t_bias * ys_;
+                }
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+
+    // epilogue: register r of tile (mi, ni) = channel co0 + 32 mi + (r&3) + 8 (r>>2) + 4 (lane>>5), pixel p0 + 64 wave +
+    // 32 ni + (this lane's column pixel) -- the tiled arm's epilogue with (wm, mi) -> mi and (ni >> 1, wn) -> wave
+    if (YTERMS) {
+        uint16_t *yt = reinterpret_cast<uint16_t *>(y);
+        auto nb = [](unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, true); };   // quad_perm [1,0,3,2]
+        const bool even = !(lane & 1);
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const unsigned pp = (unsigned)(p0 + 64 * wave + 32 * ni + ep_px);
+            const bool live = pp < (unsigned)total;
+            const unsigned ubimg = (live ? pp : 0u) / (unsigned)hw;
+            const int64_t bimg = ubimg;
+            const unsigned off = pp - ubimg * (unsigned)hw;
+            if (live && off == 0 && lane < 32) {                               // one writer per image: the lane of its pixel 0
+                float ys_, y_inv;
+                range_scales(fmaf(y_ks, image_bound(bimg), y_kb), ys_, y_inv);
+                y_inv_out[bimg] = y_inv;
+            }
+            const unsigned q_own = live ? ubimg * 16u * (unsigned)hw + off : 0xffffffffu;
+            const unsigned q_nb = nb(q_own);
+            const unsigned qa = even ? q_own : q_nb, qb = even ? q_nb : q_own;
+            [[maybe_unused]] const float x_inv = ep_xinv[ni], y_scale = ep_ys[ni];
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const int g = 2 * mi + (lane >> 5);
+                u32x4 h0, h1, l0, l1;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    f32x2 v;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const int r = 2 * j + e;
+                        const int ch = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                        float t = fmaf(acc[mi][ni][r], TABLED ? sOsc[ep_k[ni]][ch] : sOsc[0][ch] * x_inv,
+                                       YFOLD ? sBiasY[ep_k[ni]][ch] : sBias[ch]);
+                        t = __int_as_float(max(__float_as_int(t), 0));
+                        v[e] = YFOLD ? t : t * y_scale;
+                    }
+                    unsigned hh, ll;
+                    split2h_pair(v[0], v[1], hh, ll);
+                    if (j < 4) { h0[j] = hh; l0[j] = ll; }
+                    else { h1[j - 4] = hh; l1[j - 4] = ll; }
+                }
+                u32x4 ah, al, bh, bl;
+                pair_exchange(h0, h1, ah, bh);
+                pair_exchange(l0, l1, al, bl);
+                const int64_t gofs = (int64_t)(2 * g) * hw;
+                const int half = (lane & 1) * 8;
+                if (qa != 0xffffffffu) {
+                    uint16_t *dst = yt + ((int64_t)qa + gofs) * 16 + half;
+                    *reinterpret_cast<u32x4 *>(dst) = ah;
+                    *reinterpret_cast<u32x4 *>(dst + (int64_t)hw * 16) = al;
+                }
+                if (qb != 0xffffffffu) {
+                    uint16_t *dst = yt + ((int64_t)qb + gofs) * 16 + half;
+                    *reinterpret_cast<u32x4 *>(dst) = bh;
+                    *reinterpret_cast<u32x4 *>(dst + (int64_t)hw * 16) = bl;
+                }
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        unsigned pp = (unsigned)(p0 + 64 * wave + 32 * ni + (lane & 31));
+        const bool live = pp < (unsigned)total;
+        if (!live) pp = (unsigned)total - 1u;                 // carries nothing: a valid image index and vmax = 0
+        const unsigned ubimg = pp / (unsigned)hw;
+        const int64_t bimg = ubimg, off = pp - ubimg * (unsigned)hw;
+        const float x_inv = ep_xinv[ni];
+        float vmax = 0.f;
+        float *yo = y + bimg * ybs + off;
+        if (live) {
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int ch = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    float v = fmaf(acc[mi][ni][r], TABLED ? sOsc[ep_k[ni]][ch] : sOsc[0][ch] * x_inv, sBias[ch]);
+                    if (RELU_OUT) v = v < 0.f ? 0.f : v;          // keeps a NaN (fmaxf would turn it into 0)
+                    vmax = range_max(vmax, v);
+                    yo[(int64_t)(co0 + ch) * yps] = v;
+                }
+        }
+        if (out_amax) range_publish_lanes(out_amax, (int)bimg, vmax, lane);
+    }
+}
+
+// RING: the ring arm (NPT is 2 there); otherwise the tiled arm with NPT pixel tiles per workgroup
+template <bool PROLOGUE, bool RELU_OUT, bool YTERMS, int NPT, bool TABLED, bool RING>
+__global__ __launch_bounds__(256, NPT == 2 ? 2 : 3) void k_conv1x1_h2(C1H2_PARAMS) {
+    if constexpr (RING) conv1x1_ring<PROLOGUE, RELU_OUT, YTERMS, TABLED>(C1H2_ARGS);
+    else conv1x1_tiled<PROLOGUE, RELU_OUT, YTERMS, NPT, TABLED>(C1H2_ARGS);
+}
+
 }  // namespace
 
 #ifdef MIRX_C1H2_STAMPS
@@ -524,6 +843,11 @@ extern "C" int mirx_debug_c1_stamps(unsigned long long *out) {
 static std::atomic<int> g_small_max_wg{128};
 void set_conv1x1_small_max_wg(int v) { g_small_max_wg.store(v < 0 ? 0 : v); }
 static int conv1x1_small_max_wg() { return g_small_max_wg.load(std::memory_order_relaxed); }
+// large launches take the ring arm where it applies (mirx_set_tuning MIRX_TUNE_CONV1X1_RING; 0 keeps them on the tiled arm --
+// the two arms agree bit for bit, so this is speed only)
+static std::atomic<int> g_ring{1};
+void set_conv1x1_ring(int v) { g_ring.store(v ? 1 : 0); }
+static bool conv1x1_ring_enabled() { return g_ring.load(std::memory_order_relaxed) != 0; }
 
 hipError_t launch_conv1x1_h2(const float *x, int64_t xbs, int cin, const float *scale, const float *shift,
                              const uint16_t *w2, const float *oscale, const float *bias, int64_t n, int hw, int cout,
@@ -547,29 +871,34 @@ hipError_t launch_conv1x1_h2(const float *x, int64_t xbs, int cin, const float *
         return launch_conv1x1_h2_small(x, xbs, cin, scale, shift, w2, oscale, bias, n, hw, cout, relu_out, y, ybs, in_amax,
                                        in_ks, in_kb, out_amax, y_ks, y_kb, y_inv_out, xps, yps, st);
     const int npt = px >= (int64_t)2 * CP * MIRX_C1H2_MIN_WG ? MIRX_C1H2_NPT : 1;
+    // the ring arm where its 16-byte chunks stay inside one image's channel plane and its offsets fit (conv1x1_ring)
+    const bool ring = npt == 2 && conv1x1_ring_enabled() && hw % 4 == 0 && xps % 4 == 0 && xbs % 4 == 0 &&
+                      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (!scale || cin <= RING_BN_MAX_CIN) &&
+                      ((int64_t)((RNP - 1) / hw + 2) * xbs + (int64_t)cin * xps) * 4 < ((int64_t)1 << 31);
     const dim3 grid((unsigned)((px + CP * npt - 1) / (CP * npt)), (unsigned)(cout / CM));
-    const size_t lds = 2 * (size_t)(2 * PLANE_A + npt * 2 * PLANE_B);
+    const size_t lds = ring ? (size_t)RING_BN + (scale ? (size_t)cin * 8 : 0) : 2 * (size_t)(2 * PLANE_A + npt * 2 * PLANE_B);
     unsigned *oa = reinterpret_cast<unsigned *>(out_amax);
     // the oscale table has 8 rows: a workgroup's CP * npt pixels span at most (CP * npt - 1) / hw + 2 images
     const bool tabled = (CP * npt - 1) / hw + 2 <= 8;
-#define MIRX_H2K(P, R, T, N)                                                                               \
+#define MIRX_H2K(P, R, T, N, RG)                                                                           \
     {                                                                                                      \
-        if (tabled) MIRX_H2KT(P, R, T, N, true) else MIRX_H2KT(P, R, T, N, false)                          \
+        if (tabled) MIRX_H2KT(P, R, T, N, true, RG) else MIRX_H2KT(P, R, T, N, false, RG)                  \
     }
-#define MIRX_H2KT(P, R, T, N, TB)                                                                          \
+#define MIRX_H2KT(P, R, T, N, TB, RG)                                                                      \
     {                                                                                                      \
         static unsigned long long attr_devs = 0;      /* per instantiation: the attribute call costs a host microsecond per launch */ \
         if (first_use_on_device(attr_devs)) {                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1x1_h2<P, R, T, N, TB>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (2 * PLANE_A + N * 2 * PLANE_B)); \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1x1_h2<P, R, T, N, TB, RG>), \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize,                 \
+                                               RG ? RING_BN + 8 * RING_BN_MAX_CIN : 2 * (2 * PLANE_A + N * 2 * PLANE_B)); \
             if (e != hipSuccess) return e;                                                                 \
         }                                                                                                  \
-        hipLaunchKernelGGL((k_conv1x1_h2<P, R, T, N, TB>), grid, dim3(256), lds, st, x, xbs, cin, scale, shift, w2, oscale, bias, \
-                           n, hw, cout, y, ybs, in_amax, in_ks, in_kb, oa, y_ks, y_kb, y_inv_out, xps, yps); \
+        hipLaunchKernelGGL((k_conv1x1_h2<P, R, T, N, TB, RG>), grid, dim3(256), lds, st, x, xbs, cin, scale, shift, w2, oscale, \
+                           bias, n, hw, cout, y, ybs, in_amax, in_ks, in_kb, oa, y_ks, y_kb, y_inv_out, xps, yps); \
     }
 #define MIRX_H2C(P, R, T)                                                                                  \
     {                                                                                                      \
-        if (npt == 2) MIRX_H2K(P, R, T, 2) else MIRX_H2K(P, R, T, 1)                                        \
+        if (ring) MIRX_H2K(P, R, T, 2, true) else if (npt == 2) MIRX_H2K(P, R, T, 2, false) else MIRX_H2K(P, R, T, 1, false) \
     }
     if (yterms) {
         MIRX_H2C(true, true, true)

@@ -491,6 +491,10 @@ int mirx_set_tuning(int key, int64_t value) {
             MIRX_CHECK(value >= 0 && value <= (1 << 20), "set_tuning: conv3x3 small-launch limit out of range");
             set_conv3x3_small_max_wg((int)value);
             return MIRX_OK;
+        case MIRX_TUNE_CONV1X1_RING:
+            MIRX_CHECK(value == 0 || value == 1, "set_tuning: conv1x1 ring switch must be 0 or 1");
+            set_conv1x1_ring((int)value);
+            return MIRX_OK;
         default:
             return fail(MIRX_EINVAL, "set_tuning: unknown key");
     }

@@ -91,6 +91,7 @@ hipError_t launch_conv1x1_h2(const float *x, int64_t xbs, int cin, const float *
                              hipStream_t st);
 
 void set_conv1x1_small_max_wg(int v);      // mirx_set_tuning(MIRX_TUNE_CONV1X1_SMALL_MAX_WG)
+void set_conv1x1_ring(int v);             // mirx_set_tuning(MIRX_TUNE_CONV1X1_RING)
 // k_conv1x1_h2s.hip: the same contract for small launches (one wave per 32 x 32 tile, no LDS); bit-identical results
 hipError_t launch_conv1x1_h2_small(const float *x, int64_t xbs, int cin, const float *scale, const float *shift,
                                    const uint16_t *w2, const float *oscale, const float *bias, int64_t n, int hw, int cout,

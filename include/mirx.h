@@ -89,9 +89,12 @@ int mirx_version(void);
  *                                   B = 1); 0 = never.  Default 128.
  *   MIRX_TUNE_CONV3X3_SMALL_MAX_WG  the same for the dense layer's 3x3 convolution: fewer strip workgroups than this ->
  *                                   one wave per 32 output pixels; 0 = never.  Default 96.
+ *   MIRX_TUNE_CONV1X1_RING          1: a large 1x1 convolution runs on the LDS-DMA ring arm of its kernel where that arm
+ *                                   applies; 0: always on the register-staged tiled arm.  Default 1.
  */
 #define MIRX_TUNE_CONV1X1_SMALL_MAX_WG 1
 #define MIRX_TUNE_CONV3X3_SMALL_MAX_WG 2
+#define MIRX_TUNE_CONV1X1_RING 3
 int mirx_set_tuning(int key, int64_t value);
 
 /*
