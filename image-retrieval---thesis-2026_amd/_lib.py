@@ -123,6 +123,12 @@ SYMBOLS = {
     "mirx_sra_head_nhwc": (_int, [_vp, _i64, _int, _int, _vp, _int, _vp, _vp, ctypes.c_float, ctypes.c_float, _int, _vp, _vp]),
     "mirx_pcam_head_nhwc": (_int, [_vp, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, ctypes.c_float, ctypes.c_float, _int, _vp, _vp,
                                    _vp]),
+    "mirx_hamming_words": (_int, [_int]),
+    "mirx_hamming_pack": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp]),
+    "mirx_hamming_workspace_bytes": (_i64, [_i64, _i64, _int, _int]),
+    "mirx_hamming_topk": (_int, [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mirx_ath_workspace_floats": (_i64, [_i64, _int]),
+    "mirx_ath_forward": (_int, [_vp, _i64, _int, _vp, _int, _int, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -727,6 +727,70 @@ int mirx_pcam_head_nhwc(const float *x, int64_t n, int hw, int c, const float *w
                         const float *beta, float eps, float lam, int normalize, float *feat, float *class_logits_or_null,
                         void *stream);
 
+/*
+ * Binary-code retrieval of the reference's ATH path (test_ath.py / train_ath.py there: pairwise_distance on 0/1 codes + argsort).
+ *
+ * mirx_hamming_words: the words per packed row for `bits` (ceil(bits / 32) rounded up to a power of two: 1, 2, 4, ..., 32).
+ * mirx_hamming_pack: src = device [rows, bits] contiguous, dtype MIRX_BITS_F32 (float32) or MIRX_BITS_U8 (uint8 / bool bytes) ->
+ *     dst = device uint32 [rows, mirx_hamming_words(bits)], bit j of a row in bit j % 32 of word j / 32, padding bits 0.  Any value
+ *     other than 0 or 1 (NaN included) stores 1 into the device int *bad_flag (which the caller zeroes first and reads after).
+ * mirx_hamming_topk: exact top-k by Hamming distance of packed queries [nq, words] against packed rows [n, words]:
+ *     ranking = (distance ascending, row ascending); exclude_or_null = device int64 [nq], that row never appears for that query.
+ *     out_dist = device int32 [nq, k] distances, out_ids = device int64 [nq, k] rows; when fewer than k rows remain (an excluded row
+ *     and k = n) the tail holds -1 in both.  The result is a function of the query, the rows, k and the exclusion alone (the same
+ *     bits on every run and in every batch).  workspace = device, >= mirx_hamming_workspace_bytes(nq, n, bits, k) bytes, 16-byte
+ *     aligned; its size is bounded by nq, n, k and bits, whatever the distances are.  Limits (MIRX_EINVAL, nothing launched):
+ *     1 <= bits <= 1024, 1 <= k <= 1024, k <= n < 2^31, 0 <= nq <= 2^24; packed buffers 16-byte aligned.
+ */
+#define MIRX_HAMMING_MAX_BITS 1024
+#define MIRX_HAMMING_MAX_K 1024
+#define MIRX_HAMMING_MAX_Q (1 << 24)
+#define MIRX_BITS_F32 0
+#define MIRX_BITS_U8 1
+int mirx_hamming_words(int bits);
+int mirx_hamming_pack(const void *src, int dtype, int64_t rows, int bits, uint32_t *dst, int *bad_flag, void *stream);
+int64_t mirx_hamming_workspace_bytes(int64_t nq, int64_t n, int bits, int k);
+int mirx_hamming_topk(const uint32_t *q_packed, int64_t nq, const uint32_t *g_packed, int64_t n, int bits, int k,
+                      const int64_t *exclude_or_null, void *workspace, int64_t workspace_bytes, int *out_dist, int64_t *out_ids,
+                      void *stream);
+
+/*
+ * The forward of the reference's ATHNet (ath_model.py there) in fp32: x = device fp32 [n, 3, size, size] (NCHW) ->
+ * hash_out [n, hash_size], logits_out [n, num_classes].  params = device fp32, the eval-mode BatchNorms folded into their
+ * convolutions (w' = w g / sqrt(var + eps), b' = beta - mean g / sqrt(var + eps)), at the offsets below (conv weights [out, in, 3, 3]):
+ *     W11/B11 net1.0.net.0+1   W12/B12 net1.0.net.3+4   W1D/B1D net1.0.downsample   WSA sa.conv [1, 2, 3, 3]
+ *     W21..B2D net2.0 (16 -> 8)   W31..B3D dense (8 -> 1)
+ *     HEADS: hashlayer.weight [hash_size, f], hashlayer.bias, typelayer.weight [num_classes, f], typelayer.bias; f = (size / 8)^2.
+ * Each output is a fixed-order fp32 sum over its own image (k_ath.hip), so an image's bits do not depend on its batch mates.
+ * workspace = device fp32, >= mirx_ath_workspace_floats(n, size).  Limits (MIRX_EINVAL, nothing launched): size % 8 == 0,
+ * 8 <= size <= 1024, n <= 65536, hash_size, num_classes >= 1; x, params, workspace 16-byte aligned.
+ */
+#define MIRX_ATH_MAX_SIZE 1024
+#define MIRX_ATH_MAX_BATCH 65536
+#define MIRX_ATH_P_W11 0
+#define MIRX_ATH_P_B11 432
+#define MIRX_ATH_P_W12 448
+#define MIRX_ATH_P_B12 2752
+#define MIRX_ATH_P_W1D 2768
+#define MIRX_ATH_P_B1D 3200
+#define MIRX_ATH_P_WSA 3216
+#define MIRX_ATH_P_W21 3234
+#define MIRX_ATH_P_B21 4386
+#define MIRX_ATH_P_W22 4394
+#define MIRX_ATH_P_B22 4970
+#define MIRX_ATH_P_W2D 4978
+#define MIRX_ATH_P_B2D 6130
+#define MIRX_ATH_P_W31 6138
+#define MIRX_ATH_P_B31 6210
+#define MIRX_ATH_P_W32 6211
+#define MIRX_ATH_P_B32 6220
+#define MIRX_ATH_P_W3D 6221
+#define MIRX_ATH_P_B3D 6293
+#define MIRX_ATH_P_HEADS 6296
+int64_t mirx_ath_workspace_floats(int64_t n, int size);
+int mirx_ath_forward(const float *x, int64_t n, int size, const float *params, int hash_size, int num_classes, float *workspace,
+                     int64_t workspace_floats, float *hash_out, float *logits_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
