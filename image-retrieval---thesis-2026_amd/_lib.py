@@ -20,6 +20,8 @@ OPT_PROFILE = 4
 TUNE_CONV1X1_SMALL_MAX_WG = 1      # mirx_set_tuning keys
 TUNE_CONV3X3_SMALL_MAX_WG = 2
 TUNE_CONV1X1_RING = 3
+SIMCAM_MAPS_BOTH = 0               # mirx_simcam `maps`
+SIMCAM_MAPS_RETRIEVED = 1
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
 
@@ -129,6 +131,10 @@ SYMBOLS = {
     "mirx_hamming_topk": (_int, [_vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _i64, _vp, _vp, _vp]),
     "mirx_ath_workspace_floats": (_i64, [_i64, _int]),
     "mirx_ath_forward": (_int, [_vp, _i64, _int, _vp, _int, _int, _vp, _i64, _vp, _vp, _vp]),
+    "mirx_simcam_workspace_floats": (_i64, [_i64, _i64]),
+    "mirx_simcam": (_int, [_vp, _vp, _i64, _i64, _int, _int, _i64, ctypes.c_float, _int, ctypes.POINTER(ctypes.c_double), _int, _int,
+                           _vp, _i64, _vp, _vp]),
+    "mirx_bn_relu_rows": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -30,6 +30,7 @@ import ctypes
 import dataclasses
 import math
 import operator
+import weakref
 from collections import OrderedDict
 
 import torch
@@ -958,6 +959,25 @@ class _InferenceCache:
         return super()._apply(fn, *a, **k)
 
 
+class _OwnerRef:
+    """A weak reference from a submodule to the model that owns it, kept in the submodule's __dict__ (outside the module tree
+    and the state dict).  Pickling and deep copies drop it (a weakref can be neither pickled nor copied to the new model); the
+    owner's __setstate__ puts one back that points at the new model."""
+    __slots__ = ("_ref",)
+
+    def __init__(self, owner=None):
+        self._ref = weakref.ref(owner) if owner is not None else None
+
+    def __call__(self):
+        return self._ref() if self._ref is not None else None
+
+    def __reduce__(self):
+        return (_OwnerRef, ())
+
+    def __deepcopy__(self, memo):
+        return _OwnerRef()
+
+
 class DenseNet121(_Configurable, _InferenceCache, nn.Module):
     """Reference model.py:42-84, MI355X-native inference path."""
     accepts_uint8 = True        # forward() takes raw 8-bit images and applies ToTensor + Normalize itself (input_mean / input_std)
@@ -972,6 +992,9 @@ class DenseNet121(_Configurable, _InferenceCache, nn.Module):
         # reference model.py:59-60: ReLU appended to the feature stack, avgpool to the wrapper
         self.densenet121[0].add_module("relu", nn.ReLU(inplace=True))
         self.densenet121.add_module("avgpool", nn.AdaptiveAvgPool2d((1, 1)))
+        # SimCAM_Densenet121 is handed only the feature stack (or a Sequential of this model's children): it finds the model through
+        # this weak reference, kept in __dict__ so it stays out of the module tree and the state dict
+        self.densenet121[0].__dict__["_mirx_owner"] = _OwnerRef(self)
         self.fc = nn.Linear(in_features, embedding_dim) if embedding_dim else None
         out_features = embedding_dim if embedding_dim else in_features
         self.classification_head = nn.Linear(out_features, num_labels) if num_labels else None
@@ -988,6 +1011,13 @@ class DenseNet121(_Configurable, _InferenceCache, nn.Module):
                 if isinstance(sd, dict) and key in sd:
                     sd = sd[key]
             self.load_state_dict(sd, strict=False)
+
+    def __setstate__(self, state):
+        # unpickled or deep-copied: the feature stack's owner reference points at this model again
+        super().__setstate__(state)
+        feats = self.__dict__.get("_modules", {}).get("densenet121")
+        if feats is not None and len(feats) > 0:
+            feats[0].__dict__["_mirx_owner"] = _OwnerRef(self)
 
     # -- the plain module graph (training, CPU tensors): same ops as the reference -------------
     def forward_eager(self, x):
@@ -1194,6 +1224,17 @@ class DenseNet121(_Configurable, _InferenceCache, nn.Module):
         buf = buf.view(b, buf.shape[1], side, side)                 # the 7 x 7 planes are packed
         self.__dict__["_mirx_last_ranges"] = ranges            # kept for diagnostics (tools/h2_state_probe.py)
         return buf
+
+    def _relu_rows(self, x, cache):
+        """[HIP] the map of densenet121[0].relu (norm5 + ReLU) as channels-last rows [B, h * w, 1024] -> (rows, h, w): the
+        feature map SimCAM_Densenet121 decomposes.  _features_fused, then norm5 + ReLU + NCHW -> rows in one pass."""
+        fmap = self._features_fused(x, cache).contiguous()
+        b, c, h, w = fmap.shape
+        sc, sh = cache["norm5"]
+        rows = torch.empty((b, h * w, c), dtype=torch.float32, device=fmap.device)
+        _lib.check(_lib.load().mirx_bn_relu_rows(_ptr(fmap), b, c, h * w, _ptr(sc), _ptr(sh), _ptr(rows), _stream(fmap.device)),
+                   "mirx_bn_relu_rows")
+        return rows, h, w
 
     def _head_fused(self, fmap, normalize, cache=None):
         lib = _lib.load()
@@ -2184,6 +2225,11 @@ class ResNet50(_Configurable, _InferenceCache, nn.Module):
 
     def _features_native(self, x, cache):
         """-> fp32 rows [B * h/32 * w/32, 2048] of layer4's output (channels last) and the pixels per image."""
+        out, side_h, side_w = self._features_native_sides(x, cache)
+        return out, side_h * side_w
+
+    def _features_native_sides(self, x, cache):
+        """-> fp32 rows [B * h/32 * w/32, 2048] of layer4's output (channels last) and its height and width."""
         lib = _lib.load()
         u8 = x.dtype == torch.uint8
         x = x.contiguous() if u8 else x.contiguous().float()
@@ -2233,11 +2279,20 @@ class ResNet50(_Configurable, _InferenceCache, nn.Module):
                                                  fp32_out=last, out_range=ranges[r + 3])
             cur, side_h, side_w = (t3, s3, r3), h3, w3
         self.__dict__["_mirx_last_ranges"] = ranges                 # kept for diagnostics (the bound's bit cost, DESIGN 15)
-        return out, side_h * side_w
+        return out, side_h, side_w
+
+    @staticmethod
+    def _native_size_ok(x):
+        return x.shape[-1] % 4 == 0 and x.shape[-2] % 4 == 0 and x.shape[-1] >= 8 and x.shape[-2] >= 8
+
+    def _layer4_rows(self, x, cache):
+        """[HIP] the output of resnet50[7][-1] as fp32 channels-last rows [B, h * w, 2048] -> (rows, h, w): SimCAM's tap."""
+        rows, h, w = self._features_native_sides(x, cache)
+        return rows.view(x.shape[0], h * w, rows.shape[-1]), h, w
 
     def _embed_native(self, x, normalize, cache):
         b, _, h, w = x.shape
-        if h % 4 or w % 4 or h < 8 or w < 8:
+        if not self._native_size_ok(x):
             raise ValueError(f"ResNet50 native path: H and W must be multiples of 4 and at least 8 (got {h} x {w}); "
                              f"resize the input (the reference's transform gives 224 x 224)")
         if b > 65535:

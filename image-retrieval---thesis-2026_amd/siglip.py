@@ -284,11 +284,18 @@ class SiglipVisionTower(nn.Module):
         self.head = _PoolingHead(hidden_size, intermediate_size, num_attention_heads)
 
     def forward(self, pixel_values=None, output_attentions=False, return_dict=True, **_):
-        x = self.embeddings(pixel_values)
-        x, atts = self.encoder(x, None, output_attentions)
-        x = _m._layernorm(self.post_layernorm, x)
+        x, atts = self._hidden(pixel_values, output_attentions)
         pooled = self.head(x, _m._layernorm_bound(self.post_layernorm))
         return TowerOutput(last_hidden_state=x, pooler_output=pooled, attentions=atts)
+
+    def _hidden(self, pixel_values, output_attentions=False):
+        x = self.embeddings(pixel_values)
+        x, atts = self.encoder(x, None, output_attentions)
+        return _m._layernorm(self.post_layernorm, x), atts
+
+    def last_hidden_state(self, pixel_values):
+        """forward(pixel_values).last_hidden_state without the pooling head: the post-LayerNorm tokens [B, N, D]."""
+        return self._hidden(pixel_values)[0]
 
 
 class SiglipTextTower(nn.Module):

@@ -170,3 +170,7 @@ class SBSMBatch:
                 gain = (m_dist - o_dist).clamp(min=0)                                       # [Q * B, N]
             sal = (gain.float() @ self._inv_t.t()) / self._count                            # [., HW]
         return sal.reshape(-1, h, w)
+
+
+# SimCAM similarity saliency (explanations.py:664-976), native on the retrieval backbones: simcam.py
+from .simcam import SimCAM, SimCAM_Densenet121, SimCAM_MedSigLIP  # noqa: E402,F401

@@ -791,6 +791,34 @@ int64_t mirx_ath_workspace_floats(int64_t n, int size);
 int mirx_ath_forward(const float *x, int64_t n, int size, const float *params, int hash_size, int num_classes, float *workspace,
                      int64_t workspace_floats, float *hash_out, float *logits_out, void *stream);
 
+/* ---- SimCAM similarity saliency (k_simcam.hip) -------------------------------------------------------------------------
+ * The reference's explanations.py SimCAM / SimCAM_MedSigLIP / SimCAM_Densenet121 on channels-last fp32 token rows.
+ * q: [h * w, c] query rows; r: P retrieved row blocks, block p at r + p * pair_stride, each [h * w, c] (row-major, any c).
+ * Per pair D_p = q r_p^T in f32 (a fixed-order reduction on the f32 matrix pipe), s_p = max(D_p) + eps (NaN kept),
+ *   map 0 (query)     decom_1[i] = sum_j relu(D_p[i, j] / s_p)
+ *   map 1 (retrieved) decom_2[j] = sum_i relu(D_p[i, j] / s_p), or with point != NULL (double[2], point[0] along H) the
+ *                     reference's Point_Specific: the bilinear blend of the rows relu(D_p[i*, :] / s_p) at the point on the
+ *                     replicate-padded query grid, clamped at 0,
+ * each bilinearly upsampled to H x W (align_corners=False) into out: maps = MIRX_SIMCAM_MAPS_BOTH -> [P, 2, H, W] (map 0, map 1),
+ * MIRX_SIMCAM_MAPS_RETRIEVED -> [P, H, W] (map 1).  s_p == 0 or a NaN in D_p gives NaN maps for pair p only.  Every output of
+ * pair p is a fixed-order function of q and r_p: bit-identical whatever P is.
+ * workspace = device fp32, >= mirx_simcam_workspace_floats(P, h * w).  Limits (MIRX_EINVAL, nothing launched): 1 <= h * w <= 1024,
+ * 1 <= c <= 16384, 0 <= P <= 65535, pair_stride >= h * w * c, 1 <= H, W <= 8192, eps finite >= 0, point inside [0, H) x [0, W).
+ *
+ * mirx_bn_relu_rows: out[b, i, ch] = relu(x[b, ch, i] * scale[ch] + shift[ch]) -- an NCHW map [b, c, hw] as channels-last rows.
+ */
+#define MIRX_SIMCAM_MAX_HW 1024
+#define MIRX_SIMCAM_MAX_C 16384
+#define MIRX_SIMCAM_MAX_PAIRS 65535
+#define MIRX_SIMCAM_MAX_SIZE 8192
+#define MIRX_SIMCAM_MAPS_BOTH 0
+#define MIRX_SIMCAM_MAPS_RETRIEVED 1
+int64_t mirx_simcam_workspace_floats(int64_t pairs, int64_t hw);
+int mirx_simcam(const float *q, const float *r, int64_t pairs, int64_t pair_stride, int h, int w, int64_t c, float eps, int maps,
+                const double *point, int H, int W, float *workspace, int64_t workspace_floats, float *out, void *stream);
+int mirx_bn_relu_rows(const float *x, int64_t b, int64_t c, int64_t hw, const float *scale, const float *shift, float *out,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
