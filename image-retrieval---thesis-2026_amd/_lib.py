@@ -22,6 +22,7 @@ TUNE_CONV3X3_SMALL_MAX_WG = 2
 TUNE_CONV1X1_RING = 3
 SIMCAM_MAPS_BOTH = 0               # mirx_simcam `maps`
 SIMCAM_MAPS_RETRIEVED = 1
+ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
 
@@ -135,6 +136,10 @@ SYMBOLS = {
     "mirx_simcam": (_int, [_vp, _vp, _i64, _i64, _int, _int, _i64, ctypes.c_float, _int, ctypes.POINTER(ctypes.c_double), _int, _int,
                            _vp, _i64, _vp, _vp]),
     "mirx_bn_relu_rows": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "mirx_rollout_workspace_floats": (_i64, [_int, _i64, _i64]),
+    "mirx_rollout_layer": (_int, [_vp, _i64, _int, _int, _int, ctypes.c_float, _int, _int, _int, _int, _vp, _i64, _vp]),
+    "mirx_rollout_rows": (_int, [_vp, _i64, _int, _int, _vp]),
+    "mirx_rollout_finish": (_int, [_vp, _i64, _int, _i64, _int, _int, _vp, _vp, _i64, _int, _int, _vp, _vp]),
 }
 
 _lib = None

@@ -121,7 +121,9 @@ class _EncoderLayer(nn.Module):
         x = x + self.self_attn.out_proj(ctx)
         return x + self.mlp(self.layer_norm2(x)), att
 
-    def _forward_mirx(self, x, key_mask):
+    def _forward_mirx(self, x, key_mask, tap=None):
+        """tap: None, or a callable handed the packed qkv [b, n, 3c] (fp32, on the layer's stream) once it exists; it may
+        launch work that reads it (on another stream: after waiting on this one, with qkv.record_stream) and must not write it."""
         sa, mlp = self.self_attn, self.mlp
         b, n, c = x.shape
         x = x.contiguous()
@@ -138,6 +140,8 @@ class _EncoderLayer(nn.Module):
         else:
             h1 = _m._layernorm(self.layer_norm1, x)
             qkv = _m._linear_h2(pk, h1, b1) if _m._linear_h2_ok(pk, h1, b1) else _m._linear_s3(pk, h1)      # [b, n, 3c]
+        if tap is not None:
+            tap(qkv)
         bqk = max(_m._linear_out_bound(self.layer_norm1, sa.q_proj), _m._linear_out_bound(self.layer_norm1, sa.k_proj))
         bv = _m._linear_out_bound(self.layer_norm1, sa.v_proj)
         flash = key_mask is None and n >= 32 and sa.head_dim in (32, 64, 72, 96) and b <= 65535
@@ -292,6 +296,20 @@ class SiglipVisionTower(nn.Module):
         x = self.embeddings(pixel_values)
         x, atts = self.encoder(x, None, output_attentions)
         return _m._layernorm(self.post_layernorm, x), atts
+
+    def _native_encoder_ok(self, x):
+        """Every encoder layer takes _EncoderLayer._forward_mirx for the CUDA batch x (as forward() decides it, per layer)."""
+        at = self.encoder.layers[0].self_attn if len(self.encoder.layers) else None
+        return (at is not None and _fast(x) and at.head_dim in (16, 32, 64, 72) and at.embed_dim % 16 == 0
+                and all(p.device == x.device and p.dtype == torch.float32 for p in self.parameters()))
+
+    def _hidden_tapped(self, pixel_values, tap):
+        """The native encoder with tap(layer index, qkv [b, n, 3c]) after each layer's packed q / k / v projection ->
+        the post-LayerNorm tokens [B, N, D], the same bits as _hidden(pixel_values)[0].  Needs _native_encoder_ok."""
+        x = self.embeddings(pixel_values)
+        for i, layer in enumerate(self.encoder.layers):
+            x = layer._forward_mirx(x, None, tap=lambda qkv, i=i: tap(i, qkv))
+        return _m._layernorm(self.post_layernorm, x)
 
     def last_hidden_state(self, pixel_values):
         """forward(pixel_values).last_hidden_state without the pooling head: the post-LayerNorm tokens [B, N, D]."""

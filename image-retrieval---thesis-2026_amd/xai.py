@@ -174,3 +174,5 @@ class SBSMBatch:
 
 # SimCAM similarity saliency (explanations.py:664-976), native on the retrieval backbones: simcam.py
 from .simcam import SimCAM, SimCAM_Densenet121, SimCAM_MedSigLIP  # noqa: E402,F401
+# attention rollout (explanations.py:979-1147), native on MedSigLIP: rollout.py
+from .rollout import AttentionRolloutMedSigLIP  # noqa: E402,F401

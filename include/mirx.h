@@ -819,6 +819,42 @@ int mirx_simcam(const float *q, const float *r, int64_t pairs, int64_t pair_stri
 int mirx_bn_relu_rows(const float *x, int64_t b, int64_t c, int64_t hw, const float *scale, const float *shift, float *out,
                       void *stream);
 
+/* ---- Attention rollout (k_rollout.hip) ---------------------------------------------------------------------------------
+ * The reference's explanations.py AttentionRolloutMedSigLIP, from the packed qkv [b, n, 3c] (q | k | v, c = heads * head_dim,
+ * head h at columns h * head_dim) of each encoder layer.
+ * mirx_rollout_layer: A_l[b] = normalise(discard(fuse_h softmax((q_h k_h^T) * scale)) + I) into workspace slot `layer`:
+ *   scores in f32 on the matrix pipe (fixed-order reductions), the exact softmax per row, the heads fused in ascending order
+ *   (fusion: MIRX_ROLLOUT_FUSE_MEAN sum / heads, _MAX, _MIN; NaN kept; up to 4 splits of consecutive heads, a function of
+ *   the head count alone, combined in split order), then the row stage of mirx_rollout_rows.
+ * mirx_rollout_rows: in place on a [rows, n] fp32 matrix, per row: k > 0 -> thr = the k-th smallest value, a = a * (a > thr)
+ *   (ties at thr dropped); then a[row % n] += 1 and a = a / (sum(a) + 1e-8).  k = 0: no discard.
+ * mirx_rollout_finish: v = 1/n, v <- v^T A_l for l = layers - 1 .. 0 (fixed order), v *= clamp(patches[b, j] . query, 0) when
+ *   patches ([b, n, e]) and query ([e]) are given (both or neither), then the h x w map (n = h * w) bilinearly upsampled
+ *   (align_corners=False) into out [b, H, W].  It reads the `layers` slots mirx_rollout_layer filled.
+ * Every output of image b is a fixed-order function of image b's inputs alone: bit-identical whatever b is.  A NaN in image b's
+ * qkv makes its map NaN.  workspace = device fp32, >= mirx_rollout_workspace_floats(layers, b, n) ((layers + 4) b n^2 + 17 b n).
+ * Limits (MIRX_EINVAL, nothing launched): 1 <= layers <= 256, 0 <= b <= 65535, 1 <= n <= 1024, 1 <= heads <= 256,
+ * head_dim % 4 == 0 in [4, 128], 0 <= k <= n, scale finite, qkv 16-byte aligned, 0 <= rows <= 2^26, 1 <= H, W <= 8192,
+ * 1 <= e <= 65536.
+ */
+#define MIRX_ROLLOUT_MAX_N 1024
+#define MIRX_ROLLOUT_MAX_HEAD_DIM 128
+#define MIRX_ROLLOUT_MAX_HEADS 256
+#define MIRX_ROLLOUT_MAX_LAYERS 256
+#define MIRX_ROLLOUT_MAX_IMAGES 65535
+#define MIRX_ROLLOUT_MAX_ROWS (1LL << 26)
+#define MIRX_ROLLOUT_MAX_SIZE 8192
+#define MIRX_ROLLOUT_MAX_EMBED 65536
+#define MIRX_ROLLOUT_FUSE_MEAN 0
+#define MIRX_ROLLOUT_FUSE_MAX 1
+#define MIRX_ROLLOUT_FUSE_MIN 2
+int64_t mirx_rollout_workspace_floats(int layers, int64_t b, int64_t n);
+int mirx_rollout_layer(const float *qkv, int64_t b, int n, int heads, int head_dim, float scale, int fusion, int k, int layer, int layers,
+                       float *workspace, int64_t workspace_floats, void *stream);
+int mirx_rollout_rows(float *a, int64_t rows, int n, int k, void *stream);
+int mirx_rollout_finish(float *workspace, int64_t workspace_floats, int layers, int64_t b, int h, int w, const float *patches,
+                        const float *query, int64_t e, int H, int W, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
