@@ -140,6 +140,15 @@ SYMBOLS = {
     "mirx_rollout_layer": (_int, [_vp, _i64, _int, _int, _int, ctypes.c_float, _int, _int, _int, _int, _vp, _i64, _vp]),
     "mirx_rollout_rows": (_int, [_vp, _i64, _int, _int, _vp]),
     "mirx_rollout_finish": (_int, [_vp, _i64, _int, _i64, _int, _int, _vp, _vp, _i64, _int, _int, _vp, _vp]),
+    "mirx_gradcam_workspace_floats": (_i64, [_i64, _int, _int, _int]),
+    "mirx_gradcam_pool": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mirx_gradcam_tokens": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "mirx_gradcam_finish": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _int, _int, _vp, _vp]),
+    "mirx_gradcam_gemv": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _int, _int, _i64, _i64, _vp]),
+    "mirx_gradcam_layernorm": (_int, [_vp, _i64, _int, _vp, _vp, ctypes.c_float, _int, _vp, _vp, _vp]),
+    "mirx_gradcam_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    "mirx_gradcam_gelu": (_int, [_vp, _vp, _i64, _int, _vp, _vp]),
+    "mirx_gradcam_cosine_bwd": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -311,6 +311,14 @@ class SiglipVisionTower(nn.Module):
             x = layer._forward_mirx(x, None, tap=lambda qkv, i=i: tap(i, qkv))
         return _m._layernorm(self.post_layernorm, x)
 
+    def _last_layer_tokens(self, pixel_values):
+        """The native encoder's last layer output [B, N, D], before post_layernorm (the target of the reference's Grad-CAM):
+        the same layers as _hidden, nothing after them.  Needs _native_encoder_ok."""
+        x = self.embeddings(pixel_values)
+        for layer in self.encoder.layers:
+            x = layer._forward_mirx(x, None)
+        return x
+
     def last_hidden_state(self, pixel_values):
         """forward(pixel_values).last_hidden_state without the pooling head: the post-LayerNorm tokens [B, N, D]."""
         return self._hidden(pixel_values)[0]

@@ -176,3 +176,5 @@ class SBSMBatch:
 from .simcam import SimCAM, SimCAM_Densenet121, SimCAM_MedSigLIP  # noqa: E402,F401
 # attention rollout (explanations.py:979-1147), native on MedSigLIP: rollout.py
 from .rollout import AttentionRolloutMedSigLIP  # noqa: E402,F401
+# Grad-CAM retrieval saliency (medsiglip_saliency.py:137-269), native on MedSigLIP: siglip_gradcam.py
+from .siglip_gradcam import _compute_single_gradcam, compute_gradcam_saliency  # noqa: E402,F401

@@ -855,6 +855,52 @@ int mirx_rollout_rows(float *a, int64_t rows, int n, int k, void *stream);
 int mirx_rollout_finish(float *workspace, int64_t workspace_floats, int layers, int64_t b, int h, int w, const float *patches,
                         const float *query, int64_t e, int H, int W, float *out, void *stream);
 
+/* ---- Grad-CAM retrieval saliency (k_gradcam.hip) ------------------------------------------------------------------------
+ * The reference's medsiglip_saliency.py _compute_single_gradcam for a SigLIP tower, from the last encoder layer's tokens
+ * x [b, n, d] (before post_layernorm, LayerNorm gamma / beta / eps), heads of width d / heads; see DESIGN 21.
+ * mirx_gradcam_pool: y = LN(x); S[t, h] = y_t . u[h] + c[h] (u [heads, d], c [heads]: the probe query folded into the keys);
+ *   P = softmax over t per head (exact, NaN kept); ybar [b, heads, d] = sum_t P[t, h] y_t.  Stats and P stay in the workspace.
+ * mirx_gradcam_tokens: dP[t, h] = y_t . w[b, h] + e[b, h] (w [b, heads, d], e [b, heads]: the gradient at the value
+ *   projection), dS = P (dP - sum_t P dP), g_y = sum_h dS u_h + P w_h, the LayerNorm backward g_x, summed over blocks of
+ *   MIRX_GRADCAM_TOKENS_PER_BLOCK tokens into the workspace.  Needs the workspace mirx_gradcam_pool filled.
+ * mirx_gradcam_finish: wbar = (1/n) sum_t g_x[t] (block partials in order), cam_t = relu(x_t . wbar), the sqrt(n)^2 grid
+ *   bilinearly upsampled (align_corners=False, ATen's source index) into out [b, H, W], then per image numpy's float32 rule:
+ *   max - min > 1e-8 -> (v - min) / (max - min), else 0.  A NaN anywhere in an image's map therefore gives it an all-zero map.
+ * mirx_gradcam_gemv: out[i * os + j] = sum_t A[(j % rmod) * lda + (j / mg) * acol + t] * x[i * xs + (j / mg) * xg + t]
+ *   (+ bias[j]) (+ res[i * rs + j]), t < k, j < m, i < b (plain GEMV: mg = rmod = m); a wave per output.
+ * mirx_gradcam_layernorm: rows of len, out = LN(v) (relu != 0: then ReLU, NaN kept), stats [b, 2] = (mean, 1 / std).
+ * mirx_gradcam_layernorm_bwd: out = LN backward of g (times (after > 0) when after is given) (+ res), from v and stats.
+ * mirx_gradcam_gelu: mode 0 out = tanh-GELU(h); mode 1 out = g * tanh-GELU'(h), as ATen writes both.
+ * mirx_gradcam_cosine_bwd: out [b, e] = d/dp sum_r cosine_similarity(normalize(p), q_r) for q [bq, e].
+ * Every output of image b is a fixed-order function of image b's inputs alone (no atomics): bit-identical whatever b is and
+ * however the images are chunked.  workspace = device fp32, >= mirx_gradcam_workspace_floats(b, n, d, heads).
+ * Limits (MIRX_EINVAL, nothing launched): 0 <= b <= 65535, 1 <= n <= 1024 (a square for finish), 1 <= heads <= 16,
+ * 1 <= d <= 8192 with d % heads == 0, eps finite >= 0, buffers 4-byte aligned, 1 <= H, W <= 8192, 1 <= len, e <= 8192,
+ * 1 <= bq <= 65535, gemv m, k, mg, rmod >= 1 and strides >= 0.
+ */
+#define MIRX_GRADCAM_MAX_N 1024
+#define MIRX_GRADCAM_MAX_HEADS 16
+#define MIRX_GRADCAM_MAX_WIDTH 8192
+#define MIRX_GRADCAM_MAX_IMAGES 65535
+#define MIRX_GRADCAM_MAX_SIZE 8192
+#define MIRX_GRADCAM_MAX_EMBED 8192
+#define MIRX_GRADCAM_TOKENS_PER_BLOCK 4
+int64_t mirx_gradcam_workspace_floats(int64_t b, int n, int d, int heads);
+int mirx_gradcam_pool(const float *x, int64_t b, int n, int d, int heads, const float *gamma, const float *beta, float eps, const float *u,
+                      const float *c, float *workspace, int64_t workspace_floats, float *ybar, void *stream);
+int mirx_gradcam_tokens(const float *x, int64_t b, int n, int d, int heads, const float *gamma, const float *beta, const float *u,
+                        const float *w, const float *e, float *workspace, int64_t workspace_floats, void *stream);
+int mirx_gradcam_finish(const float *x, int64_t b, int n, int d, int heads, float *workspace, int64_t workspace_floats, int H, int W,
+                        float *out, void *stream);
+int mirx_gradcam_gemv(const float *A, int64_t lda, const float *x, int64_t xs, const float *bias, const float *res, int64_t rs, float *out,
+                      int64_t os, int64_t b, int m, int k, int mg, int rmod, int64_t acol, int64_t xg, void *stream);
+int mirx_gradcam_layernorm(const float *v, int64_t b, int len, const float *gamma, const float *beta, float eps, int relu, float *out,
+                           float *stats, void *stream);
+int mirx_gradcam_layernorm_bwd(const float *g, const float *after, const float *v, const float *stats, const float *gamma, int64_t b,
+                               int len, const float *res, float *out, void *stream);
+int mirx_gradcam_gelu(const float *h, const float *g, int64_t count, int mode, float *out, void *stream);
+int mirx_gradcam_cosine_bwd(const float *p, int64_t b, int e, const float *q, int64_t bq, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
