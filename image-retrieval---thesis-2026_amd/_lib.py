@@ -149,6 +149,8 @@ SYMBOLS = {
     "mirx_gradcam_layernorm_bwd": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp]),
     "mirx_gradcam_gelu": (_int, [_vp, _vp, _i64, _int, _vp, _vp]),
     "mirx_gradcam_cosine_bwd": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),
+    "mirx_lesion_rerank": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _int, _int, ctypes.c_double, _vp, _vp,
+                                  _vp, _vp]),
 }
 
 _lib = None

@@ -901,6 +901,39 @@ int mirx_gradcam_layernorm_bwd(const float *g, const float *after, const float *
 int mirx_gradcam_gelu(const float *h, const float *g, int64_t count, int mode, float *out, void *stream);
 int mirx_gradcam_cosine_bwd(const float *p, int64_t b, int e, const float *q, int64_t bq, float *out, void *stream);
 
+/* ---- ChestMIR lesion-aware re-ranking (k_rerank.hip) -------------------------------------------------------------------
+ * The reference's ChestMIR/chestmir_eval.py rerank_with_specific_lesion / rerank_with_adaptive_lesion for every stage of a
+ * dataset in one launch (grid: query x stage); see DESIGN 22.
+ * base_ids: device [n, n] int64, row q = the full base ranking of query q (mirx_index_rank_all with the query excluded: q
+ *   itself last).  Base score of (q, id): base_sim_or_null[q * n + id] (device fp64 [n, n]) when given, otherwise the fp64 dot
+ *   of rows q and id of gvec_or_null (device fp32 [n, d]).
+ * Region store, a CSR over images: row_ptr [n + 1] int64, region_lesion [n_regions] int32 (index into the caller's lesion
+ *   name list), region_vec [n_regions, dr] fp32, the regions of an image in stored order.
+ * q_lesion [n_stages, n] int32 and q_region [n_stages, n] int64: per (stage, query) the lesion to match and the region index
+ *   of the query vector (-1, or anything outside the store: no vector).
+ * For each (stage s, query q): every one of the first topk ids c of the base row gets region = max over c's regions of that
+ *   lesion of <q vector, region> (fp64; -1.0 without such a region) and combined = global_weight * base + (1 - global_weight)
+ *   * region; out_matched[s, q] = number of candidates with region >= 0.  Without a query vector or with out_matched == 0 the
+ *   base row is copied and out_reranked[s, q] = 0; otherwise the first topk ids are sorted on (combined desc, base desc, base
+ *   position asc), the rest of the base row follows unchanged, and out_reranked[s, q] = 1.
+ * out_ids: device [n_stages, n, n] int64, so that stage s is the ranks argument of mirx_rank_metrics at out_ids + s * n * n
+ *   with row_stride n (or all stages at once with nq = n_stages * n).
+ * All sums run in a fixed order (k_rerank.hip): a result does not depend on n_stages, on the other stages or on other queries.
+ * Limits (MIRX_EINVAL, nothing launched): 2 <= n <= 65536, 1 <= dr <= 4096, 1 <= topk <= min(1024, n - 1),
+ * 0 <= n_stages <= 65535, 0 <= global_weight <= 1, 0 <= n_regions < 2^31, 1 <= d <= 65536 when base_sim is null, 8-byte
+ * aligned int64 / fp64 buffers, 4-byte aligned int32 / fp32 buffers.  The region store may be null when n_regions == 0.
+ */
+#define MIRX_RERANK_MAX_N 65536
+#define MIRX_RERANK_MAX_DR 4096
+#define MIRX_RERANK_MAX_D 65536
+#define MIRX_RERANK_MAX_TOPK 1024
+#define MIRX_RERANK_MAX_STAGES 65535
+#define MIRX_RERANK_MAX_REGIONS 2147483647
+int mirx_lesion_rerank(const int64_t *base_ids, int64_t n, const double *base_sim_or_null, const float *gvec_or_null, int d,
+                       const int64_t *row_ptr, const int32_t *region_lesion, const float *region_vec, int64_t n_regions, int dr,
+                       const int32_t *q_lesion, const int64_t *q_region, int n_stages, int topk, double global_weight, int64_t *out_ids,
+                       int32_t *out_matched, int32_t *out_reranked, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
