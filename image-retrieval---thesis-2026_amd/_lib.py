@@ -22,6 +22,8 @@ TUNE_CONV3X3_SMALL_MAX_WG = 2
 TUNE_CONV1X1_RING = 3
 SIMCAM_MAPS_BOTH = 0               # mirx_simcam `maps`
 SIMCAM_MAPS_RETRIEVED = 1
+SIMATT_GROUP = 0                   # mirx_simatt `mode`
+SIMATT_PAIRS = 1
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
@@ -151,6 +153,8 @@ SYMBOLS = {
     "mirx_gradcam_cosine_bwd": (_int, [_vp, _i64, _int, _vp, _i64, _vp, _vp]),
     "mirx_lesion_rerank": (_int, [_vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _int, _int, ctypes.c_double, _vp, _vp,
                                   _vp, _vp]),
+    "mirx_simatt_workspace_floats": (_i64, [_i64, _i64, _i64, _int]),
+    "mirx_simatt": (_int, [_vp, _i64, _int, _int, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

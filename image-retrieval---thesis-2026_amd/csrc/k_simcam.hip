@@ -214,14 +214,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_simcam_maps(MapsArgs a) {
     const int64_t n = (int64_t)(y_hi - y_lo) * a.W;
     for (int64_t e = tid; e < n; e += SC_THREADS) {
         const int y = y_lo + (int)(e / a.W), x = (int)(e % a.W);
-        const float fy = fmaxf(sh * ((float)y + 0.5f) - 0.5f, 0.f);
-        const float fx = fmaxf(sw * ((float)x + 0.5f) - 0.5f, 0.f);
-        const int y0 = (int)fy, x0 = (int)fx;
-        const int y1 = y0 + (y0 < a.h - 1 ? 1 : 0), x1 = x0 + (x0 < a.w - 1 ? 1 : 0);
-        const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-        const float v = hy * (hx * smap[y0 * a.w + x0] + lx * smap[y0 * a.w + x1]) +
-                        ly * (hx * smap[y1 * a.w + x0] + lx * smap[y1 * a.w + x1]);
-        out[(int64_t)y * a.W + x] = v;
+        out[(int64_t)y * a.W + x] = bilinear_half_pixel(smap, a.h, a.w, sh, sw, y, x);
     }
 }
 

@@ -982,15 +982,16 @@ class DenseNet121(_Configurable, _InferenceCache, nn.Module):
     """Reference model.py:42-84, MI355X-native inference path."""
     accepts_uint8 = True        # forward() takes raw 8-bit images and applies ToTensor + Normalize itself (input_mean / input_std)
 
-    def __init__(self, pretrained=False, embedding_dim=None, num_labels=None, weights=None):
+    def __init__(self, pretrained=False, embedding_dim=None, num_labels=None, weights=None, _features=None):
         super().__init__()
         if pretrained and weights is None:
             raise RuntimeError("pretrained=True needs a download in the reference (model.py:53); "
                                "pass weights=<state dict or path> instead")
-        feats, in_features = _make_features()
+        feats, in_features = _make_features() if _features is None else (_features, _features.norm5.num_features)
         self.densenet121 = nn.Sequential(feats)
         # reference model.py:59-60: ReLU appended to the feature stack, avgpool to the wrapper
-        self.densenet121[0].add_module("relu", nn.ReLU(inplace=True))
+        if _features is None:
+            self.densenet121[0].add_module("relu", nn.ReLU(inplace=True))
         self.densenet121.add_module("avgpool", nn.AdaptiveAvgPool2d((1, 1)))
         # SimCAM_Densenet121 is handed only the feature stack (or a Sequential of this model's children): it finds the model through
         # this weak reference, kept in __dict__ so it stays out of the module tree and the state dict
@@ -1011,6 +1012,18 @@ class DenseNet121(_Configurable, _InferenceCache, nn.Module):
                 if isinstance(sd, dict) and key in sd:
                     sd = sd[key]
             self.load_state_dict(sd, strict=False)
+
+    @classmethod
+    def _adopt(cls, features):
+        """A headless DenseNet121 around an EXISTING feature stack (the same module objects: no parameter is copied) whose own
+        model has been collected -- the reference's saliency drivers rebind `model` to a Sequential of its children, which drops
+        the wrapper and keeps the stack.  The native feature path (_features_fused, _relu_rows) then runs on that stack again.
+        The stack's owner reference points at the new model; the caller keeps the model alive."""
+        owner = cls(_features=features)
+        dev = features.conv0.weight.device
+        owner.input_mean, owner.input_std = owner.input_mean.to(dev), owner.input_std.to(dev)
+        owner.training = features.training           # the wrapper alone: the stack's own flags are not touched
+        return owner
 
     def __setstate__(self, state):
         # unpickled or deep-copied: the feature stack's owner reference points at this model again

@@ -178,3 +178,5 @@ from .simcam import SimCAM, SimCAM_Densenet121, SimCAM_MedSigLIP  # noqa: E402,F
 from .rollout import AttentionRolloutMedSigLIP  # noqa: E402,F401
 # Grad-CAM retrieval saliency (medsiglip_saliency.py:137-269), native on MedSigLIP: siglip_gradcam.py
 from .siglip_gradcam import _compute_single_gradcam, compute_gradcam_saliency  # noqa: E402,F401
+# SimAtt similarity-attention saliency (explanations.py:605-661), native on DenseNet121's flattened Sequential: simatt.py
+from .simatt import SimAtt, simatt_maps, simatt_pairs  # noqa: E402,F401

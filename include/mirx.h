@@ -934,6 +934,38 @@ int mirx_lesion_rerank(const int64_t *base_ids, int64_t n, const double *base_si
                        const int32_t *q_lesion, const int64_t *q_region, int n_stages, int topk, double global_weight, int64_t *out_ids,
                        int32_t *out_matched, int32_t *out_reranked, void *stream);
 
+/* ---- SimAtt similarity-attention saliency (k_simatt.hip) ---------------------------------------------------------------
+ * The reference's explanations.py SimAtt in closed form for a model whose tail after the target feature map is
+ * average pool -> optional fc.  rows: device fp32 [b, h * w, c], the channels-last rows of that map, image 0 the query.
+ * fc_weight [d, c] / fc_bias [d] (row-major; bias may be null); no fc: fc_weight = fc_bias = null and d = 0 (the embedding is
+ * the pooled vector, width c).  With x_i = fc(mean over positions of rows[i]) and xn_i = x_i / max(|x_i|, 1e-12):
+ *   wt[e]   = product over the non-query images j of |xn_0[e] - xn_j[e]|, the FIRST factor replaced by 1 - itself when
+ *             positive = 1
+ *   g_i[ch] = sum_e W[e, ch] * sign(x_i[e]) * wt[e] / (h * w)        (W = identity without fc, sign(0) = 0)
+ *   map_i   = relu(sum_ch g_i[ch] * rows[i, :, ch]) as an h x w grid, bilinearly upsampled (align_corners=False) to H x W
+ * mode MIRX_SIMATT_GROUP: one wt over the images 1 .. b - 1; out [b, H, W].
+ * mode MIRX_SIMATT_PAIRS: retrieval k = image k + 1 alone against the query (wt_k has the single factor of image k + 1, flipped
+ *   when positive = 1); out [b - 1, 2, H, W]: the query's map under pair k, then retrieval k's.
+ * Two launches whatever b is, no host synchronisation.  Every sum runs in an order fixed by h * w, c and d: x_i depends on image
+ * i only and a pairs-mode map on the query and its retrieval only, bit-identical whatever b is.  relu keeps NaN; a NaN in image j
+ * makes every map NaN in group mode and pair j - 1's two maps (every pair's when j = 0) in pairs mode.
+ * Cost: pairs mode is linear in b.  In group mode every map's workgroup rebuilds the b norms and wt itself (two launches, no
+ * hand-off between workgroups), b * b * d operations in all: nothing at the handful of images the explainer is called with, an
+ * estimated several seconds of one launch at b = 65535 with d = 16384 (not measured).  Use pairs mode for large batches.
+ * workspace = device fp32, >= mirx_simatt_workspace_floats(b, c, d, mode).  Limits (MIRX_EINVAL, nothing launched):
+ * 1 <= h * w <= 1024, 1 <= c <= 16384, 1 <= d <= 16384 (or 0: no fc), 2 <= b <= 65535, 1 <= H, W <= 8192, positive 0 or 1.
+ */
+#define MIRX_SIMATT_MAX_HW 1024
+#define MIRX_SIMATT_MAX_C 16384
+#define MIRX_SIMATT_MAX_D 16384
+#define MIRX_SIMATT_MAX_B 65535
+#define MIRX_SIMATT_MAX_SIZE 8192
+#define MIRX_SIMATT_GROUP 0
+#define MIRX_SIMATT_PAIRS 1
+int64_t mirx_simatt_workspace_floats(int64_t b, int64_t c, int64_t d, int mode);
+int mirx_simatt(const float *rows, int64_t b, int h, int w, int64_t c, const float *fc_weight, const float *fc_bias, int64_t d,
+                int mode, int positive, int H, int W, float *workspace, int64_t workspace_floats, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
