@@ -12,6 +12,7 @@
 //
 // Every output is a fixed-order sum over its own image's inputs (taps in (ci, ky, kx) order, the two branches of a ResBlock added
 // last), so an image's bits do not depend on its batch mates, and a non-finite image reaches only its own outputs.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
@@ -19,8 +20,6 @@ namespace mirx {
 namespace {
 
 constexpr int ATH_THREADS = 256;
-
-__device__ inline float relu_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }      // NaN passes, as torch's relu
 
 template <int CIN, int COUT, int STRIDE>
 __device__ inline void conv_acc(const float *__restrict__ xb, int h, int w, int oy, int ox, const float *__restrict__ wt,

@@ -19,14 +19,12 @@
 // K is staged de-interleaved by channel parity (the A operand of step s is channel 2s + half), rows
 // pitched at 4 mod 8 floats (36 for head_dim 64 and 72) so the ds_read_b128 of 16 different keys hit 16
 // different bank groups.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int KT = 32;                 // keys per tile
 

@@ -7,32 +7,12 @@
 // accumulators are multiplied back by 1 / (qs ks) before the softmax and 1 / (1024 vs) at the end.
 // Layout, key permutation and LDS swizzles are k_attention_s3's; an LDS buffer is 16 KiB instead of 24.
 // k_attention_h2: head_dim 64 (ViT-B / DINOv2); k_attention_h2g<DH>: 32 / 72 / 96.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-// 2^x as the bare v_exp_f32.  exp2f() wraps the instruction in a compare, two selects, an add and a multiply so that results below
-// 2^-126 come out as denormals; a softmax weight that small changes neither the running sum (>= 1) nor its bf16 terms, and the
-// wrapper was 4 of every 6 VALU instructions of the softmax.
-__device__ inline float exp2_raw(float x) { return __builtin_amdgcn_exp2f(x); }
-
-// max of a value over the two 32-lane halves of the wave, in every lane: v_permlane32_swap (gfx950) hands each half the other's
-// value inside the vector unit -- the ds_bpermute of __shfl_xor(.., 32) was an LDS round trip on the critical path of every tile
-__device__ inline float max_over_halves(float v) {
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2_;
-    const unsigned b = __float_as_uint(v);
-    const u32x2_ r = __builtin_amdgcn_permlane32_swap(b, b, false, false);    // r[0] = the low half's value, r[1] = the high half's
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8;   // (fp16 here)
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 bf16x2;
 
 // Diagnostic builds (results wrong, timing only; -DMIRX_DIAG): bits of MIRX_ATT_EXP in k_attention_h2 -- 1 no softmax arithmetic,
 // 2 no tile staging after the first tile, 4 no P V MFMAs, 8 no Q K MFMAs, 16 no workgroup barrier in the K loop
@@ -44,30 +24,6 @@ constexpr int KT = 32;                 // keys per tile
 constexpr int K_PLANE = KT * DH * 2;   // bytes of one term of the K tile (4 KiB)
 constexpr int V_PLANE = DH * KT * 2;   // bytes of one term of the V^T tile (4 KiB)
 constexpr int BUF = 2 * K_PLANE + 2 * V_PLANE;   // 16 KiB
-
-__device__ inline void split2(float a, float b, unsigned &h, unsigned &l) {
-    split2h_pair(a, b, h, l);
-}
-
-// 8 fp32 values -> two fp16x8 fragments
-__device__ inline void split8(const float (&v)[8], bf16x8 &h, bf16x8 &l) {
-    u32x4 ph, pl;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        unsigned th, tl;
-        split2(v[2 * p], v[2 * p + 1], th, tl);
-        ph[p] = th; pl[p] = tl;
-    }
-    h = __builtin_bit_cast(bf16x8, ph);
-    l = __builtin_bit_cast(bf16x8, pl);
-}
-
-#define MIRX_MFMA3(C, AH, AL, BH, BL)                                               \
-    {                                                                               \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, C, 0, 0, 0);             \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, C, 0, 0, 0);             \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, C, 0, 0, 0);             \
-    }
 
 // XCD-aware order: workgroups are dealt to the 8 XCDs round-robin in linear order (x fastest), so the query tiles of one
 // (image, head) -- which all stream the same K and V -- would sit behind eight different L2s.  Re-dealt, XCD x takes the
@@ -89,19 +45,6 @@ __device__ inline void attention_block(int &qt, int &head, int64_t &img) {
 #endif
 }
 
-// Four consecutive channels `ch ..` (ch % 4 == 0) of token row `row` written as "terms rows" (k_linear_t2.hip: per 32 features one
-// 128-byte line, fp16 high terms | fp16 low terms of scale * value): the input format of the DMA-fed Linear that follows.
-__device__ inline void store_terms4(char *out_t, int64_t row, int c, int ch, const f32x4 &v, float scale) {
-    unsigned h0, l0, h1, l1;
-    split2h_pair(v[0] * scale, v[1] * scale, h0, l0);
-    split2h_pair(v[2] * scale, v[3] * scale, h1, l1);
-    typedef __attribute__((ext_vector_type(2))) unsigned u32x2_;
-    const u32x2_ hi = {h0, h1}, lo = {l0, l1};
-    char *dst = out_t + row * ((int64_t)((c + 31) / 32 * 32) * 4) + (ch >> 5) * 128 + (ch & 31) * 2;
-    *reinterpret_cast<u32x2_ *>(dst) = hi;
-    *reinterpret_cast<u32x2_ *>(dst + 64) = lo;
-}
-
 __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict__ qkv, int n, int heads,
                                                          float q_mul, float k_mul, float v_mul, float s_inv, float o_inv,
                                                          float *__restrict__ out, char *__restrict__ out_t, float t_scale) {
@@ -117,7 +60,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict
     const int q_ld = q_idx < n ? q_idx : n - 1;
 
     // this lane's query: channels 16 ks + 8 half + i, pre-multiplied by scale * log2(e), three terms each
-    bf16x8 qh[4], ql[4];
+    f16x8 qh[4], ql[4];
     {
         const float *qp = base + q_ld * tok + 8 * half;
 #pragma unroll
@@ -125,7 +68,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict
             const f32x4 a = *reinterpret_cast<const f32x4 *>(qp + 16 * ks), b = *reinterpret_cast<const f32x4 *>(qp + 16 * ks + 4);
             const float v[8] = {a[0] * q_mul, a[1] * q_mul, a[2] * q_mul, a[3] * q_mul,
                                 b[0] * q_mul, b[1] * q_mul, b[2] * q_mul, b[3] * q_mul};
-            split8(v, qh[ks], ql[ks]);
+            split2h_x8(v, qh[ks], ql[ks]);
         }
     }
 
@@ -167,7 +110,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             unsigned th, tl;
-            split2(rk[p >> 1][2 * (p & 1)] * k_mul, rk[p >> 1][2 * (p & 1) + 1] * k_mul, th, tl);
+            split2h_pair(rk[p >> 1][2 * (p & 1)] * k_mul, rk[p >> 1][2 * (p & 1) + 1] * k_mul, th, tl);
             ph[p] = th; pl[p] = tl;
         }
         *reinterpret_cast<u32x4 *>(sb + k_lds) = ph;
@@ -175,7 +118,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             unsigned th, tl;
-            split2(rv[0][j] * v_mul, rv[1][j] * v_mul, th, tl);            // keys 2m, 2m + 1 of channel 4 vc + j
+            split2h_pair(rv[0][j] * v_mul, rv[1][j] * v_mul, th, tl);            // keys 2m, 2m + 1 of channel 4 vc + j
             *reinterpret_cast<unsigned *>(sb + v_lds[j]) = th;
             *reinterpret_cast<unsigned *>(sb + v_lds[j] + V_PLANE) = tl;
         }
@@ -216,8 +159,8 @@ __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict
         for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
-            const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(sb + fk[ks]);
-            const bf16x8 al = *reinterpret_cast<const bf16x8 *>(sb + fk[ks] + K_PLANE);
+            const f16x8 ah = *reinterpret_cast<const f16x8 *>(sb + fk[ks]);
+            const f16x8 al = *reinterpret_cast<const f16x8 *>(sb + fk[ks] + K_PLANE);
             if (MIRX_ATT_EXP & 8) { sacc[ks] += (float)ah[0] + (float)al[1] + (float)qh[ks][2]; continue; }
             MIRX_MFMA3(sacc, ah, al, qh[ks], ql[ks])
         }
@@ -262,12 +205,12 @@ __global__ __launch_bounds__(256, 3) void k_attention_h2(const float *__restrict
         for (int s = 0; s < 2; ++s) {
             const float pv[8] = {sacc[8 * s] * 1024.f, sacc[8 * s + 1] * 1024.f, sacc[8 * s + 2] * 1024.f, sacc[8 * s + 3] * 1024.f,
                                  sacc[8 * s + 4] * 1024.f, sacc[8 * s + 5] * 1024.f, sacc[8 * s + 6] * 1024.f, sacc[8 * s + 7] * 1024.f};
-            bf16x8 bh, bl;
-            split8(pv, bh, bl);
+            f16x8 bh, bl;
+            split2h_x8(pv, bh, bl);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(sb + fv[t][s]);
-                const bf16x8 al = *reinterpret_cast<const bf16x8 *>(sb + fv[t][s] + V_PLANE);
+                const f16x8 ah = *reinterpret_cast<const f16x8 *>(sb + fv[t][s]);
+                const f16x8 al = *reinterpret_cast<const f16x8 *>(sb + fv[t][s] + V_PLANE);
                 if (MIRX_ATT_EXP & 4) { o[t][s] += (float)ah[0] + (float)al[1] + (float)bh[2] + (float)bl[3]; continue; }
                 MIRX_MFMA3(o[t], ah, al, bh, bl)
             }
@@ -314,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_h2g(const float *__restric
     const int q_idx = qt * 128 + wave * 32 + nq;
     const int q_ld = q_idx < n ? q_idx : n - 1;
 
-    bf16x8 qh[KS], ql[KS];
+    f16x8 qh[KS], ql[KS];
     {
         const float *qp = base + q_ld * tok;
 #pragma unroll
@@ -326,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_h2g(const float *__restric
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { v[j] = a[j] * q_mul; v[4 + j] = b[j] * q_mul; }
             }
-            split8(v, qh[ks], ql[ks]);
+            split2h_x8(v, qh[ks], ql[ks]);
         }
     }
 
@@ -390,7 +333,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_h2g(const float *__restric
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 unsigned th, tl;
-                split2(rk[i][p >> 1][2 * (p & 1)] * km, rk[i][p >> 1][2 * (p & 1) + 1] * km, th, tl);
+                split2h_pair(rk[i][p >> 1][2 * (p & 1)] * km, rk[i][p >> 1][2 * (p & 1) + 1] * km, th, tl);
                 ph[p] = th; pl[p] = tl;
             }
             if (live) {
@@ -409,7 +352,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_h2g(const float *__restric
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned th, tl;
-                split2(rv[i][0][j] * v_mul, rv[i][1][j] * v_mul, th, tl);
+                split2h_pair(rv[i][0][j] * v_mul, rv[i][1][j] * v_mul, th, tl);
                 const int d = 4 * vc + j;
                 char *dst = sb + 2 * KPL + d * 64 + (((vpos >> 3) ^ ((d >> 2) & 3)) << 4) + (vpos & 7) * 2;
                 if (live) {
@@ -456,8 +399,8 @@ __global__ __launch_bounds__(256, 2) void k_attention_h2g(const float *__restric
         for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(sb + fk[ks]);
-            const bf16x8 al = *reinterpret_cast<const bf16x8 *>(sb + fk[ks] + KPL);
+            const f16x8 ah = *reinterpret_cast<const f16x8 *>(sb + fk[ks]);
+            const f16x8 al = *reinterpret_cast<const f16x8 *>(sb + fk[ks] + KPL);
             MIRX_MFMA3(sacc, ah, al, qh[ks], ql[ks])
         }
         // (the scores stay unscaled: s_inv, a power of two, goes into the exponent's multiply-add below -- the same bits)
@@ -500,12 +443,12 @@ __global__ __launch_bounds__(256, 2) void k_attention_h2g(const float *__restric
             float pv[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) pv[j] = sacc[8 * s + j] * 1024.f;
-            bf16x8 bh, bl;
-            split8(pv, bh, bl);
+            f16x8 bh, bl;
+            split2h_x8(pv, bh, bl);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(sb + fv[t][s]);
-                const bf16x8 al = *reinterpret_cast<const bf16x8 *>(sb + fv[t][s] + VPL);
+                const f16x8 ah = *reinterpret_cast<const f16x8 *>(sb + fv[t][s]);
+                const f16x8 al = *reinterpret_cast<const f16x8 *>(sb + fv[t][s] + VPL);
                 MIRX_MFMA3(o[t], ah, al, bh, bl)
             }
         }
@@ -535,8 +478,8 @@ hipError_t launch_h2g(const float *qkv, int64_t batch, int n, int heads, float q
                       float o_inv, float *out, char *out_t, float t_scale, hipStream_t st) {
     constexpr int KS = (DH + 15) / 16;
     const size_t lds = (size_t)2 * 2 * (KT * KS * 32 + DH * 64);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_h2g<DH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_attention_h2g<DH>, lds, &attr_devs);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((n + 127) / 128), (unsigned)heads, (unsigned)batch);
     hipLaunchKernelGGL(k_attention_h2g<DH>, grid, dim3(256), lds, st, qkv, n, heads, q_mul, k_mul, v_mul, s_inv, o_inv, out, out_t, t_scale);

@@ -14,50 +14,18 @@
 // LDS rows: K planes [32 keys][64 ch] bf16 (128 B rows, 16-byte chunk c at c ^ ((key >> 1) & 7)); V^T planes
 // [64 d][32 positions] bf16 (64 B rows, chunk c at c ^ ((d >> 2) & 3)): the chunk index changes every 256 bytes.
 // k_attention_s3: head_dim 64 (ViT-B / DINOv2); k_attention_s3g<DH>: 32 / 72 / 96.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
 constexpr int DH = 64;                 // head dimension
 constexpr int KT = 32;                 // keys per tile
 constexpr int K_PLANE = KT * DH * 2;   // bytes of one term of the K tile (4 KiB)
 constexpr int V_PLANE = DH * KT * 2;   // bytes of one term of the V^T tile (4 KiB)
 constexpr int BUF = 3 * K_PLANE + 3 * V_PLANE;   // 24 KiB
-
-__device__ inline void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    const f32x2 v = {a, b};
-    const bf16x2 vh = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(vh, f32x2);
-    const bf16x2 vm = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(vm, f32x2);
-    const bf16x2 vl = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, vh);
-    m = __builtin_bit_cast(unsigned, vm);
-    l = __builtin_bit_cast(unsigned, vl);
-}
-
-// 8 fp32 values -> three bf16x8 fragments
-__device__ inline void split8(const float (&v)[8], bf16x8 &h, bf16x8 &m, bf16x8 &l) {
-    u32x4 ph, pm, pl;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        unsigned th, tm, tl;
-        split2(v[2 * p], v[2 * p + 1], th, tm, tl);
-        ph[p] = th; pm[p] = tm; pl[p] = tl;
-    }
-    h = __builtin_bit_cast(bf16x8, ph);
-    m = __builtin_bit_cast(bf16x8, pm);
-    l = __builtin_bit_cast(bf16x8, pl);
-}
 
 #define MIRX_MFMA6(C, AH, AM, AL, BH, BM, BL)                                       \
     {                                                                               \
@@ -90,7 +58,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_s3(const float *__restrict
             const f32x4 a = *reinterpret_cast<const f32x4 *>(qp + 16 * ks), b = *reinterpret_cast<const f32x4 *>(qp + 16 * ks + 4);
             const float v[8] = {a[0] * scale_log2e, a[1] * scale_log2e, a[2] * scale_log2e, a[3] * scale_log2e,
                                 b[0] * scale_log2e, b[1] * scale_log2e, b[2] * scale_log2e, b[3] * scale_log2e};
-            split8(v, qh[ks], qm[ks], ql[ks]);
+            split3b_x8(v, qh[ks], qm[ks], ql[ks]);
         }
     }
 
@@ -128,7 +96,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_s3(const float *__restrict
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             unsigned th, tm, tl;
-            split2(rk[p >> 1][2 * (p & 1)], rk[p >> 1][2 * (p & 1) + 1], th, tm, tl);
+            split3b_pair(rk[p >> 1][2 * (p & 1)], rk[p >> 1][2 * (p & 1) + 1], th, tm, tl);
             ph[p] = th; pm[p] = tm; pl[p] = tl;
         }
         *reinterpret_cast<u32x4 *>(sb + k_lds) = ph;
@@ -137,7 +105,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_s3(const float *__restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             unsigned th, tm, tl;
-            split2(rv[0][j], rv[1][j], th, tm, tl);                        // keys 2m, 2m + 1 of channel 4 vc + j
+            split3b_pair(rv[0][j], rv[1][j], th, tm, tl);                        // keys 2m, 2m + 1 of channel 4 vc + j
             *reinterpret_cast<unsigned *>(sb + v_lds[j]) = th;
             *reinterpret_cast<unsigned *>(sb + v_lds[j] + V_PLANE) = tm;
             *reinterpret_cast<unsigned *>(sb + v_lds[j] + 2 * V_PLANE) = tl;
@@ -216,7 +184,7 @@ __global__ __launch_bounds__(256, 3) void k_attention_s3(const float *__restrict
             const float pv[8] = {sacc[8 * s], sacc[8 * s + 1], sacc[8 * s + 2], sacc[8 * s + 3],
                                  sacc[8 * s + 4], sacc[8 * s + 5], sacc[8 * s + 6], sacc[8 * s + 7]};
             bf16x8 bh, bm, bl;
-            split8(pv, bh, bm, bl);
+            split3b_x8(pv, bh, bm, bl);
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(sb + fv[t][s]);
@@ -279,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_s3g(const float *__restric
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { v[j] = a[j] * scale_log2e; v[4 + j] = b[j] * scale_log2e; }
             }
-            split8(v, qh[ks], qm[ks], ql[ks]);
+            split3b_x8(v, qh[ks], qm[ks], ql[ks]);
         }
     }
 
@@ -335,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_s3g(const float *__restric
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 unsigned th, tm, tl;
-                split2(real ? rk[i][p >> 1][2 * (p & 1)] : 0.f, real ? rk[i][p >> 1][2 * (p & 1) + 1] : 0.f, th, tm, tl);
+                split3b_pair(real ? rk[i][p >> 1][2 * (p & 1)] : 0.f, real ? rk[i][p >> 1][2 * (p & 1) + 1] : 0.f, th, tm, tl);
                 ph[p] = th; pm[p] = tm; pl[p] = tl;
             }
             if (live) {
@@ -355,7 +323,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_s3g(const float *__restric
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 unsigned th, tm, tl;
-                split2(rv[i][0][j], rv[i][1][j], th, tm, tl);
+                split3b_pair(rv[i][0][j], rv[i][1][j], th, tm, tl);
                 const int d = 4 * vc + j;
                 char *dst = sb + 3 * KPL + d * 64 + (((vpos >> 3) ^ ((d >> 2) & 3)) << 4) + (vpos & 7) * 2;
                 if (live) {
@@ -438,7 +406,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_s3g(const float *__restric
             const float pv[8] = {sacc[8 * s], sacc[8 * s + 1], sacc[8 * s + 2], sacc[8 * s + 3],
                                  sacc[8 * s + 4], sacc[8 * s + 5], sacc[8 * s + 6], sacc[8 * s + 7]};
             bf16x8 bh, bm, bl;
-            split8(pv, bh, bm, bl);
+            split3b_x8(pv, bh, bm, bl);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(sb + fv[t][s]);
@@ -471,8 +439,8 @@ template <int DH>
 hipError_t launch_s3g(const float *qkv, int64_t batch, int n, int heads, float scale, float *out, hipStream_t st) {
     constexpr int KS = (DH + 15) / 16;
     const size_t lds = (size_t)2 * 3 * (KT * KS * 32 + DH * 64);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_attention_s3g<DH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_attention_s3g<DH>, lds, &attr_devs);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((n + 127) / 128), (unsigned)heads, (unsigned)batch);
     hipLaunchKernelGGL(k_attention_s3g<DH>, grid, dim3(256), lds, st, qkv, n, heads, scale * 1.4426950408889634f, out);

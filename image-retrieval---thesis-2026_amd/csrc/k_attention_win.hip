@@ -17,17 +17,12 @@
 //   window's V rows (read again from L2 by the tile loop), so an image's bits never depend on its batch mates and a non-finite
 //   value turns only its own window's output into NaN;
 //   probabilities as p * 1024.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr int DH = 32;                  // head dimension (SwinV2-B: 128 / 4, 256 / 8, 512 / 16, 1024 / 32)
 constexpr int KT = 32;                  // keys per tile
@@ -38,44 +33,6 @@ constexpr int TBUF = 2 * (KPL + VPL);   // 8 KiB per buffer
 constexpr float LOG2E = 1.4426950408889634f;
 constexpr float Q_STAGE = 64.f, K_STAGE = 16384.f;
 constexpr float MASK_L2 = -100.f * LOG2E;
-
-__device__ inline float exp2_raw(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ inline float max_over_halves(float v) {
-    const unsigned b = __float_as_uint(v);
-    const u32x2 r = __builtin_amdgcn_permlane32_swap(b, b, false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
-__device__ inline void split8(const float (&v)[8], f16x8 &h, f16x8 &l) {
-    u32x4 ph, pl;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        unsigned th, tl;
-        split2h_pair(v[2 * p], v[2 * p + 1], th, tl);
-        ph[p] = th; pl[p] = tl;
-    }
-    h = __builtin_bit_cast(f16x8, ph);
-    l = __builtin_bit_cast(f16x8, pl);
-}
-
-#define MIRX_MFMA3(C, AH, AL, BH, BL)                                               \
-    {                                                                               \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, C, 0, 0, 0);             \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, C, 0, 0, 0);             \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, C, 0, 0, 0);             \
-    }
-
-// four consecutive channels `ch ..` of row `row` as terms rows (k_linear_t2.hip layout) of scale * value
-__device__ inline void store_terms4(char *out_t, int64_t row, int c, int ch, const f32x4 &v, float scale) {
-    unsigned h0, l0, h1, l1;
-    split2h_pair(v[0] * scale, v[1] * scale, h0, l0);
-    split2h_pair(v[2] * scale, v[3] * scale, h1, l1);
-    const u32x2 hi = {h0, h1}, lo = {l0, l1};
-    char *dst = out_t + row * ((int64_t)((c + 31) / 32 * 32) * 4) + (ch >> 5) * 128 + (ch & 31) * 2;
-    *reinterpret_cast<u32x2 *>(dst) = hi;
-    *reinterpret_cast<u32x2 *>(dst + 64) = lo;
-}
 
 // region of timm's shifted-window mask along one axis: slices [0, side - ws), [side - ws, side - shift), [side - shift, side)
 __device__ inline int region1(int y, int side, int ws, int shift) { return y < side - ws ? 0 : (y < side - shift ? 1 : 2); }
@@ -168,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_win(const float *__restric
         for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[ks][j] *= qm;
-            split8(v[ks], qh[ks], ql[ks]);
+            split2h_x8(v[ks], qh[ks], ql[ks]);
         }
     }
 
@@ -304,7 +261,7 @@ __global__ __launch_bounds__(256, 2) void k_attention_win(const float *__restric
 #pragma unroll
             for (int j = 0; j < 8; ++j) pv[j] = sacc[8 * s + j] * 1024.f;
             f16x8 bh, bl;
-            split8(pv, bh, bl);
+            split2h_x8(pv, bh, bl);
             const f16x8 ah = *reinterpret_cast<const f16x8 *>(sb + fv[s]);
             const f16x8 al = *reinterpret_cast<const f16x8 *>(sb + fv[s] + VPL);
             MIRX_MFMA3(o, ah, al, bh, bl)

@@ -13,27 +13,14 @@
 //
 // Every sum has one fixed order per image (lane partials in index order, butterflies, the 4 wave partials as (0 + 1) + (2 + 3)), so
 // an image's output bits depend on nothing but its own rows and the weights.  fp32 throughout: the head is ~2 K hw c FLOP per image.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 constexpr int AP_THREADS = 256;
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // sum over the workgroup; every thread gets the same value.  red = 4 floats of LDS, free on entry (guarded by the barriers)
 __device__ inline float block_sum(float v, float *red) {
@@ -122,7 +109,7 @@ __global__ __launch_bounds__(AP_THREADS) void k_attnpool(const float *__restrict
         if (!PCAM) {
             float m = -INFINITY;
             for (int p = lane; p < hw; p += 64) m = fmaxf(m, dk[p]);
-            m = wave_max(m);
+            m = wave_fmax(m);
             float s = 0.f;
             for (int p = lane; p < hw; p += 64) {
                 const float e = expf(dk[p] - m);
@@ -149,7 +136,7 @@ __global__ __launch_bounds__(AP_THREADS) void k_attnpool(const float *__restrict
     __syncthreads();
     if (PCAM && wv == 0) {                        // softmax over the K <= 64 class logits, lane = class
         const float l = lane < K ? s_kv[lane] : -INFINITY;
-        const float m = wave_max(l);
+        const float m = wave_fmax(l);
         const float e = lane < K ? expf(l - m) : 0.f;
         const float s = wave_sum(e);
         if (logits_out && lane < K) logits_out[(int64_t)blockIdx.x * K + lane] = l;

@@ -15,13 +15,12 @@
 // ds_read_b32 per lane with consecutive lanes on consecutive words (conflict-free).
 #include <cstdlib>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int CM = 128;   // output channels per workgroup
 

@@ -4,7 +4,7 @@
 // Half the matrix-pipe time and 4 instead of 6 LDS bytes per element; the layer then runs against its HBM stream.
 //
 // fp16 has 5 exponent bits, so the kernel needs the RANGE of its input.  DenseNet activations have no a-priori bound,
-// so the range travels with the data, PER IMAGE (mirx_common.h): every kernel that writes into a dense block's buffer
+// so the range travels with the data, PER IMAGE (mirx_device.h): every kernel that writes into a dense block's buffer
 // also folds the largest |value| it wrote for image b into the buffer's range row[b] (unsigned atomic max -- the bit
 // patterns of non-negative floats order like the floats).  This kernel reads row[b] of its input buffer, and
 //     bound_b = in_ks * row[b] + in_kb      (in_ks = max |BN scale|, in_kb = max |BN shift| of the prologue; 1, 0 without)
@@ -22,18 +22,12 @@
 // the ring arm below (activations by LDS DMA too).  w2 = [cout / 128][cin / 16][2 terms][128 out][16 in] fp16.
 #include <atomic>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 // Diagnostic build -DMIRX_C1H2_STAMPS: s_memtime at the phase boundaries of every stage, wave 0 of each workgroup, into
 // g_c1_stamps (read back by tools/bench_conv1x1.py --stamps through mirx_debug_c1_stamps); never in the shipped library.
@@ -867,7 +861,8 @@ hipError_t launch_conv1x1_h2(const float *x, int64_t xbs, int cin, const float *
     if (yterms && px >= ((int64_t)1 << 27)) return hipErrorInvalidValue;     // ... and the 32-byte records of y (16 per pixel) too
     // small launches (the reference's own batch sizes): one wave per 32 x 32 tile, no LDS (k_conv1x1_h2s.hip) -- when this
     // kernel's 128 x 128 tiles would leave most CUs without a workgroup
-    if (px * (cout / CM) < (int64_t)CP * conv1x1_small_max_wg() && (cin <= 1024 || !scale))
+    const bool small_bn_ok = !scale || (cin <= 1024 && ((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) == 0);
+    if (px * (cout / CM) < (int64_t)CP * conv1x1_small_max_wg() && small_bn_ok)
         return launch_conv1x1_h2_small(x, xbs, cin, scale, shift, w2, oscale, bias, n, hw, cout, relu_out, y, ybs, in_amax,
                                        in_ks, in_kb, out_amax, y_ks, y_kb, y_inv_out, xps, yps, st);
     const int npt = px >= (int64_t)2 * CP * MIRX_C1H2_MIN_WG ? MIRX_C1H2_NPT : 1;
@@ -886,13 +881,9 @@ hipError_t launch_conv1x1_h2(const float *x, int64_t xbs, int cin, const float *
     }
 #define MIRX_H2KT(P, R, T, N, TB, RG)                                                                      \
     {                                                                                                      \
-        static unsigned long long attr_devs = 0;      /* per instantiation: the attribute call costs a host microsecond per launch */ \
-        if (first_use_on_device(attr_devs)) {                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1x1_h2<P, R, T, N, TB, RG>), \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,                 \
-                                               RG ? RING_BN + 8 * RING_BN_MAX_CIN : 2 * (2 * PLANE_A + N * 2 * PLANE_B)); \
-            if (e != hipSuccess) return e;                                                                 \
-        }                                                                                                  \
+        static std::atomic<unsigned long long> attr_devs{0};      /* per instantiation: the attribute call costs a host microsecond per launch */ \
+        hipError_t e = set_dynamic_lds(k_conv1x1_h2<P, R, T, N, TB, RG>, RG ? RING_BN + 8 * RING_BN_MAX_CIN : 2 * (2 * PLANE_A + N * 2 * PLANE_B), &attr_devs);    \
+        if (e != hipSuccess) return e;                                                                 \
         hipLaunchKernelGGL((k_conv1x1_h2<P, R, T, N, TB, RG>), grid, dim3(256), lds, st, x, xbs, cin, scale, shift, w2, oscale, \
                            bias, n, hw, cout, y, ybs, in_amax, in_ks, in_kb, oa, y_ks, y_kb, y_inv_out, xps, yps); \
     }

@@ -19,16 +19,12 @@
 // positions), the operands are formed by the same instructions (split2h_pair on act(x) * 2^s), and the epilogue applies
 // the same power-of-two scales and the same fmaf.  tests/test_model_gpu.py checks rows of a small batch against the same
 // images inside a 2048-image batch (which takes the big kernel) bit for bit.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int KC = 16;             // channels per stage
 constexpr int CMB = 128;           // output channels per weight block of w2 ([cout / 128][cin / 16][2][128][16])
@@ -89,6 +85,7 @@ __global__ __launch_bounds__(64) void k_conv1x1_h2s(const float *__restrict__ x,
             *reinterpret_cast<f32x4 *>(s_bn + i) = *reinterpret_cast<const f32x4 *>(scale + i);
             *reinterpret_cast<f32x4 *>(s_bn + MAX_CIN + i) = *reinterpret_cast<const f32x4 *>(shift + i);
         }
+        __syncthreads();                                  // every lane reads what the other lanes wrote
     }
     // the range of this pixel's image -> its power-of-two staging scale (read behind the first loads)
     const float xb = fmaf(in_ks, in_amax ? in_amax[pimg] : 0.f, in_kb);
@@ -218,7 +215,10 @@ hipError_t launch_conv1x1_h2_small(const float *x, int64_t xbs, int cin, const f
                                    int relu_out, float *y, int64_t ybs, const float *in_amax, float in_ks, float in_kb,
                                    float *out_amax, float y_ks, float y_kb, float *y_inv_out, int64_t xps, int64_t yps,
                                    hipStream_t st) {
-    if (cin > MAX_CIN && scale) return hipErrorInvalidValue;      // (launch_conv1x1_h2 keeps such a layer on the tiled kernel)
+    // (launch_conv1x1_h2 keeps such layers on the tiled kernel: more channels than s_bn holds, or BN vectors that the 16-byte
+    // loads of the s_bn fill cannot read)
+    if (scale && (cin > MAX_CIN || ((reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15)))
+        return hipErrorInvalidValue;
     const int64_t px = n * (int64_t)hw;
     const int64_t waves1 = ((px + 31) / 32) * (cout / 32);
     // two channel blocks per wave once one block per wave gives every CU several waves anyway

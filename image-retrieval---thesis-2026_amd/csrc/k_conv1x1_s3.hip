@@ -16,18 +16,12 @@
 // coalesced loads, BN + ReLU with wave-uniform scalars, three 16-byte LDS stores).  LDS rows are 32 B
 // (16 bf16); chunk c of row r sits at c ^ ((r >> 3) & 1): conflict-free ds_read_b128 for the hardware's
 // 16-lane groups.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int CM = 128;            // output channels per workgroup
 constexpr int CP = 128;            // pixels per workgroup
@@ -206,8 +200,8 @@ hipError_t launch_conv1x1_s3(const float *x, int64_t xbs, int cin, const float *
     const size_t lds = 2 * (size_t)STAGE;
 #define MIRX_S3(P, R)                                                                                      \
     {                                                                                                      \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv1x1_s3<P, R>),             \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+        static std::atomic<unsigned long long> attr_devs{0};    \
+        hipError_t e = set_dynamic_lds(k_conv1x1_s3<P, R>, lds, &attr_devs);    \
         if (e != hipSuccess) return e;                                                                     \
         hipLaunchKernelGGL((k_conv1x1_s3<P, R>), grid, dim3(256), lds, st, x, xbs, cin, scale, shift, w3, bias, n, hw, \
                            cout, y, ybs);                                                                       \

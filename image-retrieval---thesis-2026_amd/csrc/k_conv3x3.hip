@@ -17,14 +17,12 @@
 // prefetched, 47 KiB, three workgroups per CU).  The output transform first folds j inside the wave
 // (P_i0 = M_i0 + M_i1 + M_i2, P_i1 = M_i1 - M_i2 - M_i3), exchanges the P's through LDS and finishes
 // with Y_0p = P_0p + P_1p + P_2p, Y_1p = P_1p - P_2p - P_3p.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int CIN = 128, COUT = 32;
 constexpr int KC = 8;                         // channels per stage
@@ -178,7 +176,7 @@ __global__ __launch_bounds__(256, 3) void k_conv3x3_wino(const float *__restrict
     }
     __syncthreads();
     // item = (oc, tile): 32 x 28 items, 256 threads; lanes walk tiles -> coalesced float2 stores
-    float vmax = 0.f;                                       // largest |output| (range slots, mirx_common.h)
+    float vmax = 0.f;                                       // largest |output| (range slots, mirx_device.h)
     float *oi = out + img * out_bs;
     for (int it = threadIdx.x; it < COUT * 32; it += 256) {
         const int oc = it >> 5, t = it & 31;
@@ -198,7 +196,7 @@ __global__ __launch_bounds__(256, 3) void k_conv3x3_wino(const float *__restrict
             vmax = range_max(range_max(range_max(range_max(vmax, v0.x), v0.y), v1.x), v1.y);
         }
     }
-    (void)vmax; (void)out_range;        // range publishing lives on the two-fp16-term path only (per image, mirx_common.h)
+    (void)vmax; (void)out_range;        // range publishing lives on the two-fp16-term path only (per image, mirx_device.h)
 }
 
 // The 7x7 maps (last dense block): a map is 4 x 4 tiles (the 8th row / column of outputs is computed and
@@ -327,7 +325,7 @@ __global__ __launch_bounds__(256, 3) void k_conv3x3_wino7(const float *__restric
             if (col1) { o[W + 1] = v11; vmax = range_max(vmax, v11); }
         }
     }
-    (void)vmax; (void)out_range;        // range publishing lives on the two-fp16-term path only (per image, mirx_common.h)
+    (void)vmax; (void)out_range;        // range publishing lives on the two-fp16-term path only (per image, mirx_device.h)
 }
 
 template <int W, int R>
@@ -337,8 +335,8 @@ hipError_t launch_w(const float *x, const float *u, int64_t n, float *out, int64
     const size_t stage = (size_t)(2 * U_STAGE + 2 * KC * ROWS * PITCH) * sizeof(float);
     const size_t xch = (size_t)4 * 2 * COUT * 32 * sizeof(float);
     const size_t lds = stage > xch ? stage : xch;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv3x3_wino<W, R>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_conv3x3_wino<W, R>, lds, &attr_devs);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_conv3x3_wino<W, R>), dim3((W / 2 + R - 1) / R, (unsigned)n), dim3(256), lds, st, x, u, out,
                        out_bs, out_range);
@@ -357,8 +355,8 @@ hipError_t launch_conv3x3_wino(const float *x, const float *u, int64_t n, int si
     if (side == 14) return launch_w<14, 4>(x, u, n, out, out_bs, out_range, st);
     if (side == 7) {
         const size_t lds = (size_t)(2 * U_STAGE + 2 * 2 * KC * 10 * 12) * sizeof(float);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv3x3_wino7),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        static std::atomic<unsigned long long> attr_devs{0};
+        hipError_t e = set_dynamic_lds(k_conv3x3_wino7, lds, &attr_devs);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_conv3x3_wino7, dim3((unsigned)((n + 1) / 2)), dim3(256), lds, st, x, u, out, out_bs, n, out_range);
         return hipGetLastError();

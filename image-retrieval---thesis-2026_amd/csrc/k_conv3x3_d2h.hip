@@ -7,7 +7,7 @@
 // k_conv3x3_d2p reads the bottleneck ALREADY SPLIT into its fp16 terms by the 1x1 conv that produced it (scaled per image
 // by 2^t, 2^-t in in_inv[image]), reads weights that were scaled per OUTPUT channel by the caller (largest |w| of the channel
 // in [2^13, 2^14): mirx.model._conv3x3_weights_split2h), multiplies the accumulator by oscale[oc] * 2^-t and folds the largest
-// |output| of image b into out_range[b] (ranges are per image: mirx_common.h).
+// |output| of image b into out_range[b] (ranges are per image: mirx_device.h).
 //
 // One workgroup (4 waves) = a strip of R rows x W columns = 224 (196 for the 14 x 14 map) output pixels of one image
 // = 7 column blocks of 32 pixels (waves 0..2 take two, wave 3 one) x all 32 output channels.
@@ -19,19 +19,12 @@
 //     issued right after the stage barrier) and every wave reads its A fragments from there.
 // (The round-2 variant with an fp32 bottleneck split inside this kernel, k_conv3x3_d2h, and the 16x16x32 re-tiling
 // k_conv3x3_d2q were A/B arms that lost to this kernel; they live in the history of this file)
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int CIN = 128, COUT = 32;
 constexpr int KC = 16;                        // channels per stage = one MFMA K
@@ -294,12 +287,9 @@ hipError_t launch_d2p(const uint16_t *yt, const uint16_t *w2, const float *oscal
     constexpr int NP = (IPW * (R + 2) * (W + 2) + 31) / 32;
     const size_t lds = (size_t)2 * 2 * NP * 1024 + 2 * 9 * 2 * 32 * 16 * 2;
     static_assert((size_t)2 * 2 * NP * 1024 + 2 * 9 * 2 * 32 * 16 * 2 <= 160 * 1024, "LDS of one CU");
-    static unsigned long long attr_devs = 0;          // per instantiation
-    if (first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv3x3_d2p<W, R, IPW, NW>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> attr_devs{0};          // per instantiation
+    hipError_t e = set_dynamic_lds(k_conv3x3_d2p<W, R, IPW, NW>, lds, &attr_devs);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_conv3x3_d2p<W, R, IPW, NW>), dim3((W + R - 1) / R, (unsigned)((n + IPW - 1) / IPW)), dim3(64 * NW), lds,
                        st, yt, w2, oscale, out, out_bs, in_inv, reinterpret_cast<unsigned *>(out_range), out_ps, n, pool_sc, pool_sh,
                        pool_out, pool_bs);

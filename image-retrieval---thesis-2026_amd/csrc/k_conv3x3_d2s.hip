@@ -17,15 +17,12 @@
 // same multiply.  tests/test_model_gpu.py runs both on one input and compares bits.
 #include <atomic>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr int CIN = 128, COUT = 32, KC = 16, NST = CIN / KC;
 constexpr int DEPTH = 6;                        // (stage, tap) steps of loads in flight

@@ -21,33 +21,16 @@
 //   * W: pre-split and pre-ordered by the caller ([8 stages][9 taps][3 terms][32 oc][16 c] bf16,
 //     mirx.model._conv3x3_weights_split3); a lane reads its 16-byte A fragments straight from global memory (221 KiB
 //     per layer, L2-resident): taps 0..3 at the end of the previous stage, taps 4..8 two taps ahead of their use.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
 constexpr int CIN = 128, COUT = 32;
 constexpr int KC = 16;                        // channels per stage = one MFMA K
 constexpr int NST = CIN / KC;                 // 8 stages
-
-__device__ inline void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    const f32x2 v = {a, b};
-    const bf16x2 vh = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(vh, f32x2);
-    const bf16x2 vm = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(vm, f32x2);
-    const bf16x2 vl = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, vh);
-    m = __builtin_bit_cast(unsigned, vm);
-    l = __builtin_bit_cast(unsigned, vl);
-}
 
 // W = map side (56 / 28 / 14); R = output rows per strip (4 / 8 / 14)
 template <int W, int R>
@@ -102,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_d3(const float *__restrict__
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 unsigned th, tm, tl;
-                split2(inside[i] ? rin[i][2 * p] : 0.f, inside[i] ? rin[i][2 * p + 1] : 0.f, th, tm, tl);
+                split3b_pair(inside[i] ? rin[i][2 * p] : 0.f, inside[i] ? rin[i][2 * p + 1] : 0.f, th, tm, tl);
                 ph[p] = th; pm[p] = tm; pl[p] = tl;
             }
             if (l_off[i] >= 0) {
@@ -230,8 +213,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_d3(const float *__restrict__
 template <int W, int R>
 hipError_t launch_d3(const float *x, const uint16_t *w3, int64_t n, float *out, int64_t out_bs, hipStream_t st) {
     const size_t lds = (size_t)2 * 3 * (R + 2) * (W + 2) * 32;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv3x3_d3<W, R>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_conv3x3_d3<W, R>, lds, &attr_devs);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_conv3x3_d3<W, R>), dim3((W + R - 1) / R, (unsigned)n), dim3(256), lds, st, x, w3, out, out_bs);
     return hipGetLastError();

@@ -25,19 +25,12 @@
 // cycles of MFMA.  Net: 28x28 maps 0.325 vs 0.364 ms, 14x14 0.094 vs 0.102 ms, 56x56 1.42 vs 1.375 ms against the
 // fp32-MFMA kernel; the model uses this kernel on the 28 / 14 maps only.  A wave tile of two column blocks (U
 // fragments reused for 64 tiles) is what would lift the bound.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int CIN = 128, COUT = 32;
 constexpr int KC = 16;                        // channels per stage = one MFMA K
@@ -271,8 +264,8 @@ hipError_t launch_ws3(const float *x, const uint16_t *u3, int64_t n, float *out,
     const size_t stage = (size_t)(2 * KC * ROWS * PITCH) * sizeof(float);
     const size_t xch = (size_t)4 * 2 * COUT * 32 * sizeof(float);
     const size_t lds = stage > xch ? stage : xch;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv3x3_wino_s3<W, R>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_conv3x3_wino_s3<W, R>, lds, &attr_devs);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_conv3x3_wino_s3<W, R>), dim3((W / 2 + R - 1) / R, (unsigned)n), dim3(256), lds, st, x, u3, out,
                        out_bs);

@@ -25,19 +25,13 @@
 //   y_scale[b] = 2^(14 - floor(log2 bound_b)),  bound_b = x_range[b] * w_abs_sum + bias_abs_max (+ res_range[b])
 // (>= every |y| of image b: max_o sum |W[o, :]| * max |x| + max |bias| + max |res|), a function of ranges complete before the
 // launch; the workgroup that holds image b's first pixel stores it for the consumer.  The epilogue folds max |y| of every image
-// into out_range (unsigned atomic max on the float bits, mirx_common.h), which the next layer's bound starts from.
+// into out_range (unsigned atomic max on the float bits, mirx_device.h), which the next layer's bound starts from.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int CT_TM = 128;                 // pixels per workgroup
 constexpr int CT_LINE = 128;               // bytes of one row of one stage: 32 channels x (hi | lo)
@@ -331,12 +325,9 @@ hipError_t launch_conv_t2(const void *xt, const float *x_scale, const float *x_r
     const dim3 grid((unsigned)(per_xcd * 8));
 #define MIRX_CT2(TN, R)                                                                                                \
     {                                                                                                                  \
-        static unsigned long long attr_devs = 0;                                                                       \
-        if (first_use_on_device(attr_devs)) {                                                                          \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv_t2<TN, R>),                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, ConvTile<TN>::LDS);         \
-            if (e != hipSuccess) return e;                                                                             \
-        }                                                                                                              \
+        static std::atomic<unsigned long long> attr_devs{0};                                                                       \
+        hipError_t e = set_dynamic_lds(k_conv_t2<TN, R>, ConvTile<TN>::LDS, &attr_devs);    \
+        if (e != hipSuccess) return e;                                                                             \
         hipLaunchKernelGGL((k_conv_t2<TN, R>), grid, dim3(256), ConvTile<TN>::LDS, st,                                 \
                            reinterpret_cast<const char *>(xt), x_scale, x_range, n, h, w, cin, ho, wo, ksz, stride, pad, \
                            reinterpret_cast<const char *>(wt), oscale, bias, cout, w_abs_sum, bias_abs_max,            \

@@ -10,6 +10,7 @@
 // puts the 32 channels of a pixel in one 128-byte segment.
 #include <cstdio>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {

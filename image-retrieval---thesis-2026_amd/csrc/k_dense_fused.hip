@@ -36,21 +36,14 @@
 //     copy: the padded image would not fit).  The 18 KiB of weights per stage go global -> registers -> LDS, double-buffered
 //     in the space the 1x1 phase staged in; stages 0 and 1 are requested before the 1x1 epilogue runs.  The 32 x 196 outputs
 //     leave through LDS as 16-byte stores of whole channel rows (16 four-byte stores per lane took 8 000 cycles to issue).
-// Ranges are per image (mirx_common.h): the unit's images read their own row entries and fold their own output maxima in.
+// Ranges are per image (mirx_device.h): the unit's images read their own row entries and fold their own output maxima in.
 // Channel planes must be packed (plane stride = side^2: the stage offsets are instruction immediates).
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 
 constexpr int CM = 128;                        // bottleneck channels
 constexpr int KC = 16;                         // channels per stage = one MFMA K
@@ -719,12 +712,9 @@ hipError_t launch_dense_fused(float *buf, int64_t bs, int cin, const float *scal
     unsigned *rr = reinterpret_cast<unsigned *>(range_row);
 #define MIRX_DF_LAUNCH(WW)                                                                                        \
     {                                                                                                             \
-        static unsigned long long attr_devs = 0;                                                                             \
-        if (first_use_on_device(attr_devs)) {                                                                                          \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_dense_fused<WW>),                  \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);            \
-            if (e != hipSuccess) return e;                                                                        \
-        }                                                                                                         \
+        static std::atomic<unsigned long long> attr_devs{0};                                                                             \
+        hipError_t e = set_dynamic_lds(k_dense_fused<WW>, LDS_BYTES, &attr_devs);    \
+        if (e != hipSuccess) return e;                                                                        \
         const int64_t units = (n + (196 / (WW * WW)) - 1) / (196 / (WW * WW));                                    \
         const unsigned grid = (unsigned)(units < n_cu ? units : n_cu);      /* one persistent workgroup per CU */ \
         hipLaunchKernelGGL((k_dense_fused<WW>), dim3(grid), dim3(512), LDS_BYTES, st, buf, bs, cin, scale, shift, w2, oscale, \

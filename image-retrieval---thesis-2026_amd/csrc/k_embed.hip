@@ -16,13 +16,12 @@
 //   * weights re-laid [k][32];
 //   * the 32 x 255 conv tile after BN + ReLU, from which the pool phase writes only the pooled map.
 // Every LDS address inside the K loop is one per-lane base plus an immediate.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int PTH = 8, PTW = 7;              // pooled tile
 constexpr int CTH = 2 * PTH + 1;             // 17 conv rows
@@ -173,8 +172,8 @@ hipError_t launch_stem(const float *x, const float *w, const float *scale, const
     const int ph = h / 4, pw = wd / 4;
     const int tiles = ((ph + PTH - 1) / PTH) * ((pw + PTW - 1) / PTW);
     const size_t lds = (size_t)(S_IN + S_W) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_stem),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_stem, lds, &attr_devs);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_stem, dim3((unsigned)tiles, (unsigned)n, 64 / OCB), dim3(256), lds, st, x, w, scale, shift,
                        h, wd, y);

@@ -7,6 +7,7 @@
 //   fill_diagonal_(-inf)                            test.py:1081   -> exclude ids
 //   output.topk(maxk, 1, True, True)                test.py:44
 //   torch.argsort(dists, dim=0, descending=True)    test.py:1090,179  -> launch_rank_rows
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 #include <math.h>
@@ -227,12 +228,6 @@ __device__ inline void bitonic_sort_lds(Hit *a, int m) {
     __syncthreads();
 }
 
-__device__ inline int pow2_ceil(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 __device__ inline float reported_value(double rank_score, int metric) {
     if (rank_score == -INFINITY) return -INFINITY;
     return metric == MIRX_METRIC_IP ? (float)rank_score : (float)(-sqrt(fmax(-rank_score, 0.0)));
@@ -412,8 +407,7 @@ hipError_t launch_scores_t(const float *q32p, const int32_t *qlist, int nq, cons
         const dim3 grid((unsigned)((nq + qt - 1) / qt), (unsigned)((n + SCORE_ROWS - 1) / SCORE_ROWS));
 #define MIRX_LDS_LAUNCH(CPL)                                                                              \
     {                                                                                                     \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_scores_f64_lds<METRIC, CPL>), \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);         \
+        hipError_t e = set_dynamic_lds(k_scores_f64_lds<METRIC, CPL>, lds);    \
         if (e != hipSuccess) return e;                                                                    \
         hipLaunchKernelGGL((k_scores_f64_lds<METRIC, CPL>), grid, dim3(512), lds, st, q32p, qlist, nq, qt, g32, n, \
                            dimp, out, ld);                                                                \
@@ -501,8 +495,7 @@ hipError_t launch_topk_merge(const double *in_scores, const int64_t *in_ids, int
     while (m < nshard * k) m <<= 1;
     const size_t lds = (size_t)m * sizeof(Hit);
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_topk_merge),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = set_dynamic_lds(k_topk_merge, lds);
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)nq), dim3(256), lds, st, in_scores, in_ids, nshard,

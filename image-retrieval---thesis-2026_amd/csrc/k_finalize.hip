@@ -7,6 +7,7 @@
 // overflow, re-scoring exactly the rows with s~ >= kth(s~) - 2*eps in fp64 and sorting them
 // (score desc, id asc) gives the oracle's answer.  Queries failing the guard go to the exact
 // scan; nothing is ever answered approximately.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 #include <math.h>
@@ -40,12 +41,6 @@ __device__ inline void bitonic_lds(T *a, int m, Before before) {
         }
     }
     __syncthreads();
-}
-
-__device__ inline int pow2_ceil(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
 }
 
 // tau[q] = rank_j-th largest sampled group maximum of query q; +inf for padding queries.
@@ -229,8 +224,8 @@ hipError_t launch_select_tau(const float *groupmax, int ngroups, int64_t nq, int
     int m = 1;
     while (m < ngroups) m <<= 1;
     if (m > 16384) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_select_tau),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * (int)sizeof(float));
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_select_tau, 16384 * (int)sizeof(float), &attr_devs);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_select_tau, dim3((unsigned)nq_pad), dim3(256), (size_t)m * sizeof(float), st,
                        groupmax, ngroups, nq, rank_j, tau);

@@ -28,14 +28,12 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int BM = 256;
 constexpr int BK = 64;
@@ -59,7 +57,6 @@ constexpr int A_TILE_BYTES = BM * ROW_BYTES;  // 32 KiB
         __syncthreads();                                     \
     } while (0)
 #endif
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 // Stage ROWS tile rows of a K-contiguous bf16 matrix into LDS through a buffer descriptor.
 // Wave w issues pieces w, w+8, ...; piece = 64 lanes x 16 B = 8 tile rows.  `voff` is the
@@ -279,14 +276,14 @@ __global__ __launch_bounds__(512, 2) void k_gemm(GemmArgs A) {
 #define MIRX_LDA(KK, CUR, MI) (*reinterpret_cast<const bf16x8 *>(smem + a_addr[KK] + (CUR) * A_TILE_BYTES + (MI) * 32 * ROW_BYTES))
 #define MIRX_LDB(KK, CUR, NI) (*reinterpret_cast<const bf16x8 *>(smem + b_addr[KK] + (CUR) * B_TILE_BYTES + (NI) * 32 * ROW_BYTES))
 #endif
-#define MIRX_MFMA2(MI, FB_CUR)                                                                    \
+#define MIRX_MFMA2_32X32(MI, FB_CUR)                                                                    \
     acc[MI][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[MI], FB_CUR[0], acc[MI][0], 0, 0, 0); \
     acc[MI][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[MI], FB_CUR[1], acc[MI][1], 0, 0, 0);
     // one k-slice: MFMAs with (fa, FB_CUR); refresh fa[] and fill FB_NXT from buffer NCUR, slice NKK.
     // sched_group_barrier pins "2 MFMAs, then the reads that refresh what they consumed".
 #define MIRX_SLICE(FB_CUR, FB_NXT, NCUR, NKK)                                     \
     {                                                                             \
-        MIRX_MFMA2(0, FB_CUR)                                                     \
+        MIRX_MFMA2_32X32(0, FB_CUR)                                                     \
         fa[0] = MIRX_LDA(NKK, NCUR, 0);                                           \
         FB_NXT[0] = MIRX_LDB(NKK, NCUR, 0);                                       \
         if constexpr (M_REP == 1) FB_NXT[1] = MIRX_LDB(NKK, NCUR, 1);             \
@@ -294,18 +291,18 @@ __global__ __launch_bounds__(512, 2) void k_gemm(GemmArgs A) {
         if constexpr (M_REP == 1) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0); \
         else __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                   \
         if constexpr (M_REP > 1) {                                                \
-            MIRX_MFMA2(1, FB_CUR)                                                 \
+            MIRX_MFMA2_32X32(1, FB_CUR)                                                 \
             fa[1] = MIRX_LDA(NKK, NCUR, 1);                                       \
             FB_NXT[1] = MIRX_LDB(NKK, NCUR, 1);                                   \
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                    \
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);                    \
         }                                                                         \
         if constexpr (M_REP > 2) {                                                \
-            MIRX_MFMA2(2, FB_CUR)                                                 \
+            MIRX_MFMA2_32X32(2, FB_CUR)                                                 \
             fa[2] = MIRX_LDA(NKK, NCUR, 2);                                       \
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                    \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                    \
-            MIRX_MFMA2(3, FB_CUR)                                                 \
+            MIRX_MFMA2_32X32(3, FB_CUR)                                                 \
             fa[3] = MIRX_LDA(NKK, NCUR, 3);                                       \
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                    \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                    \
@@ -382,7 +379,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm(GemmArgs A) {
     }
 #undef MIRX_KTILE
 #undef MIRX_SLICE
-#undef MIRX_MFMA2
+#undef MIRX_MFMA2_32X32
 #undef MIRX_LDA
 #undef MIRX_LDB
 }
@@ -396,7 +393,6 @@ __global__ __launch_bounds__(512, 2) void k_gemm(GemmArgs A) {
 //   B fragment: lane -> query     (lane & 15), same K chunk
 //   accumulator register r of tile (mi, ni): gallery row 16 mi + 4 (lane >> 4) + r, query 16 ni + (lane & 15)
 // ================================================================================================
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 struct RingEntry {     // a lane's pair of accumulator tiles that holds a passing score, parked in LDS by k_gemm16's K loop
     f32x4 a0, a1;      // tiles (mi, n0) and (mi, n0 + 1): rows 16 mi + 4 (lane >> 4) + r, queries 16 n + (lane & 15)
@@ -716,7 +712,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm16(GemmArgs A) {
     if constexpr ((Z) && FUSE && (N0) == 0) MIRX_CHECK2(gt_prev, MI, 2)                                \
     acc[MI][N0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[MI], fb[N0], (Z) ? zero4 : acc[MI][N0], 0, 0, 0); \
     acc[MI][N0 + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[MI], fb[N0 + 1], (Z) ? zero4 : acc[MI][N0 + 1], 0, 0, 0);
-#define MIRX_MFMA2(MI, N0) MIRX_MFMA2Z(MI, N0, 0)
+#define MIRX_MFMA2_16X16(MI, N0) MIRX_MFMA2Z(MI, N0, 0)
     // L = 1 (last K-tile of a gallery tile, its last H2): query tiles 0,1 of row tile MI are final -- test them here
 #define MIRX_MFMA2L(MI, L)                                                                             \
     if constexpr ((L) && FUSE) MIRX_CHECK2(gt, MI, 0)                                                  \
@@ -867,18 +863,18 @@ __global__ __launch_bounds__(512, 2) void k_gemm16(GemmArgs A) {
     MIRX_H2(0, 1, Z)                                                                               \
     MIRX_SEG(Z, 2)                                                                                 \
     MIRX_H1_HEAD(0, 1, 0)                                                                          \
-    MIRX_MFMA2(1, 0) MIRX_MFMA2(2, 0) MIRX_MFMA2(3, 0) MIRX_MFMA2(4, 0)                            \
+    MIRX_MFMA2_16X16(1, 0) MIRX_MFMA2_16X16(2, 0) MIRX_MFMA2_16X16(3, 0) MIRX_MFMA2_16X16(4, 0)                            \
     __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);                                             \
     MIRX_SEG(Z, 3)                                                                                 \
     MIRX_KBARRIER(); /* last reads of `cur` returned; the other buffer's DMA (mine) landed */      \
     MIRX_SEG(Z, 4)                                                                                 \
     MIRX_DMA_AT_BARRIER(KT)                                                                        \
     MIRX_SLOT_A(0, 0)                                                                              \
-    MIRX_MFMA2(5, 0)                                                                               \
+    MIRX_MFMA2_16X16(5, 0)                                                                               \
     MIRX_SLOT_A(1, 0)                                                                              \
-    MIRX_MFMA2(6, 0)                                                                               \
+    MIRX_MFMA2_16X16(6, 0)                                                                               \
     MIRX_SLOT_A(0, 1)                                                                              \
-    MIRX_MFMA2(7, 0)                                                                               \
+    MIRX_MFMA2_16X16(7, 0)                                                                               \
     MIRX_SLOT_A(1, 1)                                                                              \
     MIRX_H2_DMA(1, 0, L)                                                                           \
     if constexpr ((L) && FUSE) MIRX_FLUSH_HITS(gt, 0)                                              \
@@ -1003,7 +999,7 @@ __global__ __launch_bounds__(512, 2) void k_gemm16(GemmArgs A) {
 #undef MIRX_DMA_AT_BARRIER
 #undef MIRX_H2_ROWL
 #undef MIRX_MFMA2L
-#undef MIRX_MFMA2
+#undef MIRX_MFMA2_16X16
 #undef MIRX_MFMA2Z
 #undef MIRX_CHECK2
 #undef MIRX_SITE_TEST
@@ -1045,13 +1041,13 @@ hipError_t launch_bn(const GemmArgs &a0, hipStream_t st) {
     if constexpr (BN == 256) {
         if (use_mfma16()) {
             if (a.gbias) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm16<MODE, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                static std::atomic<unsigned long long> attr_devs{0};
+                e = set_dynamic_lds(k_gemm16<MODE, true>, lds, &attr_devs);
                 if (e != hipSuccess) return e;
                 hipLaunchKernelGGL((k_gemm16<MODE, true>), dim3((unsigned)plan.grid), dim3(512), lds, st, a);
             } else {
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm16<MODE, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                static std::atomic<unsigned long long> attr_devs{0};
+                e = set_dynamic_lds(k_gemm16<MODE, false>, lds, &attr_devs);
                 if (e != hipSuccess) return e;
                 hipLaunchKernelGGL((k_gemm16<MODE, false>), dim3((unsigned)plan.grid), dim3(512), lds, st, a);
             }
@@ -1059,13 +1055,13 @@ hipError_t launch_bn(const GemmArgs &a0, hipStream_t st) {
         }
     }
     if (a.gbias) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm<BN, MODE, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        static std::atomic<unsigned long long> attr_devs{0};
+        e = set_dynamic_lds(k_gemm<BN, MODE, true>, lds, &attr_devs);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_gemm<BN, MODE, true>), dim3((unsigned)plan.grid), dim3(512), lds, st, a);
     } else {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm<BN, MODE, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        static std::atomic<unsigned long long> attr_devs{0};
+        e = set_dynamic_lds(k_gemm<BN, MODE, false>, lds, &attr_devs);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_gemm<BN, MODE, false>), dim3((unsigned)plan.grid), dim3(512), lds, st, a);
     }

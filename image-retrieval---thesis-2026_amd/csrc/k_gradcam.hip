@@ -21,6 +21,7 @@
 // n, d and heads only): bit-identical whatever b is and however the images are chunked.
 #include <cmath>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
@@ -32,16 +33,6 @@ constexpr int GC_MAXH = MIRX_GRADCAM_MAX_HEADS;     // 16: one accumulator per h
 constexpr int GC_TB = MIRX_GRADCAM_TOKENS_PER_BLOCK;
 constexpr int GC_MAP_ROWS = 16;                    // output rows per upsample workgroup
 constexpr int GC_MM = 2 * ((MIRX_GRADCAM_MAX_SIZE + GC_MAP_ROWS - 1) / GC_MAP_ROWS);
-
-__device__ inline float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
-__device__ inline float nanmin(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ inline float relu_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);    // a + b == b + a: every lane ends with the same bits
-    return v;
-}
 
 // fixed-shape tree over the GC_THREADS values of a workgroup (LDS scratch of GC_THREADS floats); every thread gets the result
 __device__ inline float block_sum(float v, float *sh) {

@@ -21,6 +21,7 @@
 //
 // Workspace: Q * (bits + 1) + Q * 2 (S + 1) + 4 Q ints and Q * kp keys (kp = next power of two >= k), S = ceil(N / L): bounded by Q,
 // N, k and bits, never by how the distances are spread (a gallery at distance 0 from every query costs what any other does).
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {

@@ -14,19 +14,12 @@
 // Contract: |x * x_scale| <= 65504 for every element (mirx.model uses it where a bound is provable: the inputs that
 // come out of a LayerNorm).  Everything else (tiling, DMA'd weight stages, paired x loads, XCD-contiguous tile order,
 // epilogues) is k_linear_s3's.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 bf16x8;   /* fp16 in this experiment */
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 bf16x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 // A stage is published by a barrier only after THIS wave's LDS DMA has landed: the compiler's own s_waitcnt
 // before s_barrier covers the registers it knows about, not the asynchronous buffer_load ... lds writes.
 #define STAGE_BARRIER()                                      \
@@ -159,13 +152,13 @@ __global__ __launch_bounds__(256, 3) void k_linear_h2(const float *__restrict__ 
 
     auto mfma_stage = [&](int cur) {
         const char *sb = sm + cur * STAGE;
-        bf16x8 a[2][2], b[2][2];
+        f16x8 a[2][2], b[2][2];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                a[t][p] = *reinterpret_cast<const bf16x8 *>(sb + fx[t] + p * PLANE);
-                b[t][p] = *reinterpret_cast<const bf16x8 *>(sb + fw[t] + p * PLANE);
+                a[t][p] = *reinterpret_cast<const f16x8 *>(sb + fx[t] + p * PLANE);
+                b[t][p] = *reinterpret_cast<const f16x8 *>(sb + fw[t] + p * PLANE);
             }
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -332,16 +325,16 @@ hipError_t launch_linear_h2(const float *x, int64_t m, int k, const uint16_t *w2
     const size_t lds = 2 * (size_t)STAGE;
 #define MIRX_H2(A, R, C, G)                                                                                \
     {                                                                                                      \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_linear_h2<A, R, C, G>),        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+        static std::atomic<unsigned long long> attr_devs{0};    \
+        hipError_t e = set_dynamic_lds(k_linear_h2<A, R, C, G>, lds, &attr_devs);    \
         if (e != hipSuccess) return e;                                                                     \
         hipLaunchKernelGGL((k_linear_h2<A, R, C, G>), grid, dim3(256), lds, st, x, m, k, w2, bias, n, res, gamma, y, ntn, \
                            total, per_xcd, tokens_per_image, x_scale, out_scale, xb_dev);                  \
     }
     if (sq_out) {                                     // ConvNeXt fc1 + GELU with the GRN partial sums (row-major)
         if (act != 1 || res || gamma || xb_dev || tokens_per_image < TM) return hipErrorInvalidValue;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_linear_h2<1, false, false, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        static std::atomic<unsigned long long> attr_devs{0};
+        hipError_t e = set_dynamic_lds(k_linear_h2<1, false, false, false, true>, lds, &attr_devs);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_linear_h2<1, false, false, false, true>), grid, dim3(256), lds, st, x, m, k, w2, bias, n, res, gamma, y,
                            ntn, total, per_xcd, tokens_per_image, x_scale, out_scale, xb_dev, sq_out);

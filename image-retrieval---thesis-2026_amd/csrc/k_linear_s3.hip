@@ -17,19 +17,12 @@
 // a token row is fetched while it is still in the vector L1.  The output tile index runs
 // with n fastest and is laid out per XCD (workgroup id % 8 = XCD on gfx950), so the n-tiles that share a token
 // tile are resident on the SAME L2 at the same time: x is read from HBM once per token tile.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 // A stage is published by a barrier only after THIS wave's LDS DMA has landed: the compiler's own s_waitcnt
 // before s_barrier covers the registers it knows about, not the asynchronous buffer_load ... lds writes.
 #define STAGE_BARRIER()                                      \
@@ -260,8 +253,8 @@ hipError_t launch_linear_s3(const float *x, int64_t m, int k, const uint16_t *w3
     const size_t lds = 2 * (size_t)STAGE;
 #define MIRX_L3(A, R, C, G)                                                                                \
     {                                                                                                      \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_linear_s3<A, R, C, G>),        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+        static std::atomic<unsigned long long> attr_devs{0};    \
+        hipError_t e = set_dynamic_lds(k_linear_s3<A, R, C, G>, lds, &attr_devs);    \
         if (e != hipSuccess) return e;                                                                     \
         hipLaunchKernelGGL((k_linear_s3<A, R, C, G>), grid, dim3(256), lds, st, x, m, k, w3, bias, n, res, gamma, y, \
                            ntn, total, per_xcd, tokens_per_image);                                         \

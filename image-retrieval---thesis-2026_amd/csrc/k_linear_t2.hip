@@ -25,16 +25,12 @@
 // LDS image of a stage (the distance GEMM's, k_gemm.hip): operand tile rows of 128 B; 16-byte chunk c of row r sits at
 // r * 128 + ((c ^ ((r >> 1) & 7)) << 4) -- the XOR is applied to the DMA's SOURCE address, the LDS side of a DMA piece is
 // lane-linear -- chunks 0-3 = hi, 4-7 = lo; a 16x16x32 fragment read (16 rows x 4 chunks of one term) is conflict-free.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int TM = 256;                  // tokens per workgroup
 constexpr int TN = 256;                  // outputs per workgroup
@@ -600,12 +596,9 @@ hipError_t launch_linear_t2(const void *xt, int64_t m, int k, const void *wt, co
     float *ws = reinterpret_cast<float *>(workspace);
 #define MIRX_T2(A, R, T)                                                                                               \
     {                                                                                                                  \
-        static unsigned long long attr_devs = 0;                                                                                  \
-        if (first_use_on_device(attr_devs)) {                                                                                               \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_linear_t2<A, R, T>),                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                 \
-            if (e != hipSuccess) return e;                                                                             \
-        }                                                                                                              \
+        static std::atomic<unsigned long long> attr_devs{0};                                                                                  \
+        hipError_t e = set_dynamic_lds(k_linear_t2<A, R, T>, LDS_BYTES, &attr_devs);    \
+        if (e != hipSuccess) return e;                                                                             \
         hipLaunchKernelGGL((k_linear_t2<A, R, T>), grid, dim3(512), LDS_BYTES, st, reinterpret_cast<const char *>(xt), m, kp, \
                            reinterpret_cast<const char *>(wt), bias, n, res, gamma, out_scale, y,                      \
                            reinterpret_cast<char *>(yt), y_scale, np, ntn, plain, per_xcd, parts, ws);                 \

@@ -12,6 +12,7 @@
 // Relevance is label equality (int64) or Jaccard(multi-hot bit masks) > threshold, evaluated as
 // inter / (union + 1e-8) > thr in fp64 like test.py:958-961; an optional per-query id is never relevant
 // (self-exclusion).  Sums are fp64, per-lane partials combined by a fixed butterfly: deterministic.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {

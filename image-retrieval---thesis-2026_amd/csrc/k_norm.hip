@@ -15,20 +15,12 @@
 //                      lanes over keys, online softmax per lane, butterfly combine.  fp32 VALU (exact products).  Used where
 //                      the MFMA flash kernels do not fit: the SigLIP text tower (64 tokens, key-padding mask) and the
 //                      SigLIP attention-pooling head (1 probe query over 1024 keys).
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- LayerNorm over rows ----------------------------------------------------------------------------------------
 // grid: ceil(m / 4) workgroups of 4 waves; wave w normalises row 4 * blockIdx.x + w.  c % 4 == 0.
@@ -285,8 +277,7 @@ hipError_t launch_layernorm_rows(const float *x, int64_t m, int c, const float *
     if (tokens_per_image > 0) {
         if (c > 512) return hipErrorInvalidValue;
         const size_t lds = (size_t)c * 65 * sizeof(float);
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_layernorm_rows_nchw),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = set_dynamic_lds(k_layernorm_rows_nchw, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_layernorm_rows_nchw, dim3((unsigned)((m + 63) / 64)), dim3(256), lds, st, x, m, c,
                            tokens_per_image, gamma, beta, eps, y);

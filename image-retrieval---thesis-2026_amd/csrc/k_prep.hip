@@ -5,6 +5,7 @@
 //   F.normalize(x, dim=1)                       model.py:83,116,493,634; milvus_retrieval.py:63
 //   norm5 -> relu -> AdaptiveAvgPool2d(1) -> flatten -> normalize      model.py:59-60,73-74,83
 // All kernels: one 64-lane wave per row, 16-byte loads, wave-shuffle reductions.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 #include <algorithm>

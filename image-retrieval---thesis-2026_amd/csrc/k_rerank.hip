@@ -16,6 +16,7 @@
 // shape or on any other query.  No atomics; nothing is accumulated across workgroups.
 #include <cmath>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
@@ -25,17 +26,11 @@ namespace {
 constexpr int RR_THREADS = 256;
 constexpr int RR_WAVES = RR_THREADS / 64;
 
-__device__ inline double rr_wave_sum(double p) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p = p + __shfl_xor(p, off, 64);
-    return p;
-}
-
 // fp64 dot of two float vectors of length d by one wave (every lane returns the sum)
 __device__ inline double rr_dot(const float *a, const float *b, int d, int lane) {
     double p = 0.0;
     for (int t = lane; t < d; t += 64) p = p + (double)a[t] * (double)b[t];
-    return rr_wave_sum(p);
+    return wave_butterfly_sum(p);
 }
 
 struct RerankArgs {

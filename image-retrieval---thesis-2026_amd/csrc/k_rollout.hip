@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
@@ -48,27 +49,6 @@ constexpr int RO_HEAD_SPLIT = MIRX_RO_SPLIT;
 #else
 constexpr int RO_HEAD_SPLIT = 4;
 #endif
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
-__device__ inline float nanmin(float a, float b) { return (a < b || a != a) ? a : b; }
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);    // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = nanmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ inline int wave_isum(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // order-preserving key of an fp32 bit pattern (negative values below positive ones, -0 just below +0)
 __device__ inline uint32_t fkey(float f) {
@@ -239,7 +219,7 @@ __global__ __launch_bounds__(RO_THREADS) void k_rollout_layer(LayerArgs a) {
 #pragma unroll
             for (int t = 0; t < RO_VALS; ++t)
                 if (lane + 64 * t < n) m = nanmax(m, sr[lane + 64 * t]);
-            m = wave_max(m);
+            m = wave_nanmax(m);
             float ev[RO_VALS], s = 0.f;
 #pragma unroll
             for (int t = 0; t < RO_VALS; ++t) {

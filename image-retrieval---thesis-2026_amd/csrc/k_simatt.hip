@@ -21,6 +21,7 @@
 // j as a factor: all maps in group mode, pair j - 1's two maps in pairs mode.
 #include <cmath>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
@@ -37,16 +38,8 @@ constexpr int SA_WT = MIRX_SIMATT_MAX_D / SA_MTHREADS;   // wt components a thre
 constexpr float SA_NORM_EPS = 1e-12f;                    // F.normalize's eps
 static_assert(MIRX_SIMATT_MAX_C <= MIRX_SIMATT_MAX_D, "without fc the embedding is the pooled vector: D = C");
 
-// clamp(min=0) as torch: NaN passes
-__device__ inline float relu_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
 // torch.sign (abs' backward): 0 at 0
 __device__ inline float sign0(float v) { return (float)(v > 0.f) - (float)(v < 0.f); }
-// s[l] + s[l ^ off], off = 32 .. 1: every lane ends with the same sum
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
 
 struct EmbedArgs {
     const float *rows;       // [B, hw, c]

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
@@ -30,13 +31,6 @@ constexpr int SC_THREADS = 256;          // 4 waves, a 32 x 32 quarter of the ti
 constexpr int SC_LDS_STRIDE = SC_KT + 1; // operand rows in LDS, padded
 constexpr int SC_D_STRIDE = SC_TILE + 1; // the D tile in LDS, padded
 constexpr int SC_MAP_ROWS = 16;          // output rows per maps workgroup
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// max that keeps NaN (amax propagates it; fmaxf drops it)
-__device__ inline float nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
-// clamp(min=0) as torch: NaN passes
-__device__ inline float relu_nan(float v) { return (v > 0.f || v != v) ? v : 0.f; }
 
 struct PairsArgs {
     const float *q;          // [hw, c]

@@ -4,22 +4,16 @@
 // of three bf16 terms and six MFMAs: 66 MFMAs of 32 cycles per wave instead of 132.
 //
 // fp16 needs the range of the input: `in_range[b]` = the largest |pixel| of image b (mirx_range_absmax, one pass over
-// the images; ranges are per image, mirx_common.h); the patch is multiplied by 2^s (bound * 2^s in [2^14, 2^15)) while it is
+// the images; ranges are per image, mirx_device.h); the patch is multiplied by 2^s (bound * 2^s in [2^14, 2^15)) while it is
 // staged, the weights arrive scaled per output channel (mirx.model._stem_weights_split2h) and the accumulator is
 // multiplied by oscale[oc] / 2^s before norm0.  Tiling, patch layout and pooling are k_stem_s3's; it writes image b at
 // y + b * y_bs (the channel prefix of dense block 1's buffer) and folds the largest pooled value into `out_range[b]`.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
 
 constexpr int PTH = 8, PTW = 7;              // pooled tile
 constexpr int CTH = 2 * PTH + 1;             // 17 conv rows
@@ -40,9 +34,10 @@ constexpr int W_BYTES = NOB * NSTEP * 2 * OCB * 16 * 2;      // all weights of t
 constexpr int W_OFF = S_IN * 4;                              // behind the patch (the conv tile reuses both after the K loop)
 constexpr int PAR_OFF = (W_OFF + W_BYTES > S_ALL * 4 ? W_OFF + W_BYTES : S_ALL * 4);   // epilogue constants behind everything
 constexpr int LDS_BYTES = PAR_OFF + 4 * NOB * OCB * 4;
-#define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
-__device__ inline void split2(float a, float b, unsigned &h, unsigned &l) {
+// split2h_pair's values in the compiler's own form (convert back, packed subtract) rather than v_fma_mix_f32: a different
+// instruction sequence, and this kernel's schedule was tuned around it -- kept as it is.
+__device__ inline void split2h_pair_cvt(float a, float b, unsigned &h, unsigned &l) {
     const f32x2 v = {a, b};
     const f16x2 vh = __builtin_convertvector(v, f16x2);
     const f32x2 r1 = v - __builtin_convertvector(vh, f32x2);
@@ -283,12 +278,9 @@ static hipError_t launch_stem_h2_t(const TIN *x, const uint16_t *w2, const float
     const int ph = h / 4, pw = wd / 4;
     const int tiles = ((ph + PTH - 1) / PTH) * ((pw + PTW - 1) / PTW);
     const size_t lds = LDS_BYTES;
-    static unsigned long long attr_devs = 0;           // per instantiation
-    if (first_use_on_device(attr_devs)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_stem_h2<TIN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    static std::atomic<unsigned long long> attr_devs{0};           // per instantiation
+    hipError_t e = set_dynamic_lds(k_stem_h2<TIN>, lds, &attr_devs);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_stem_h2<TIN>, dim3((unsigned)tiles, (unsigned)n, 1), dim3(256), lds, st, x, w2, oscale, scale, shift,
                        h, wd, y, y_bs, in_range, reinterpret_cast<unsigned *>(out_range), mean, stdv);
     return hipGetLastError();
@@ -312,7 +304,6 @@ hipError_t launch_stem_h2_u8(const uint8_t *x, const float *mean, const float *s
 // ---- largest |value| of every image (`per` contiguous fp32 each) into its range: grid (chunks, images) -----------------
 namespace {
 __global__ __launch_bounds__(256) void k_range_absmax(const float *__restrict__ x, int64_t per, unsigned *__restrict__ row) {
-    typedef __attribute__((ext_vector_type(4))) float f32x4;
     const float *xi = x + (int64_t)blockIdx.y * per;
     float m = 0.f;
     if ((reinterpret_cast<uintptr_t>(xi) & 15) == 0) {

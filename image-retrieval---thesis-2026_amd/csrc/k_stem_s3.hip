@@ -14,17 +14,12 @@
 //     lane and step, no LDS.
 // 132 MFMAs of 32 cycles per wave instead of 168 of 64: 2.5x less matrix time; LDS drops to the patch / conv tile
 // (33 KiB).
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 
 constexpr int PTH = 8, PTW = 7;              // pooled tile
 constexpr int CTH = 2 * PTH + 1;             // 17 conv rows
@@ -40,18 +35,6 @@ constexpr int CONV_PITCH = 260;              // 255 pixels + pad, 260 = 4 (mod 3
 constexpr int S_IN = 2 * PLANE;
 constexpr int S_CONV = OCB * CONV_PITCH;
 constexpr int S_ALL = S_IN > S_CONV ? S_IN : S_CONV;
-
-__device__ inline void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-    const f32x2 v = {a, b};
-    const bf16x2 vh = __builtin_convertvector(v, bf16x2);
-    const f32x2 r1 = v - __builtin_convertvector(vh, f32x2);
-    const bf16x2 vm = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(vm, f32x2);
-    const bf16x2 vl = __builtin_convertvector(r2, bf16x2);
-    h = __builtin_bit_cast(unsigned, vh);
-    m = __builtin_bit_cast(unsigned, vm);
-    l = __builtin_bit_cast(unsigned, vl);
-}
 
 __global__ __launch_bounds__(256, 3) void k_stem_s3(const float *__restrict__ x, const uint16_t *__restrict__ w3,
                                                     const float *__restrict__ scale, const float *__restrict__ shift,
@@ -126,10 +109,10 @@ __global__ __launch_bounds__(256, 3) void k_stem_s3(const float *__restrict__ x,
             const float *po = pe + PLANE;                // odd plane:  kx = 1, 3, 5, (7: zero weight)
             u32x4 bh, bm, bl;
             unsigned th, tm, tl;
-            split2(pe[0], pe[1], th, tm, tl); bh[0] = th; bm[0] = tm; bl[0] = tl;
-            split2(pe[2], pe[3], th, tm, tl); bh[1] = th; bm[1] = tm; bl[1] = tl;
-            split2(po[0], po[1], th, tm, tl); bh[2] = th; bm[2] = tm; bl[2] = tl;
-            split2(po[2], po[3], th, tm, tl); bh[3] = th; bm[3] = tm; bl[3] = tl;
+            split3b_pair(pe[0], pe[1], th, tm, tl); bh[0] = th; bm[0] = tm; bl[0] = tl;
+            split3b_pair(pe[2], pe[3], th, tm, tl); bh[1] = th; bm[1] = tm; bl[1] = tl;
+            split3b_pair(po[0], po[1], th, tm, tl); bh[2] = th; bm[2] = tm; bl[2] = tl;
+            split3b_pair(po[2], po[3], th, tm, tl); bh[3] = th; bm[3] = tm; bl[3] = tl;
             const bf16x8 xh = __builtin_bit_cast(bf16x8, bh), xm = __builtin_bit_cast(bf16x8, bm),
                          xl = __builtin_bit_cast(bf16x8, bl);
             f32x16 c = acc[t];
@@ -181,7 +164,7 @@ __global__ __launch_bounds__(256, 3) void k_stem_s3(const float *__restrict__ x,
             vmax = range_max(vmax, m);
         }
     }
-    (void)vmax; (void)out_range;        // range publishing lives on the two-fp16-term path only (per image, mirx_common.h)
+    (void)vmax; (void)out_range;        // range publishing lives on the two-fp16-term path only (per image, mirx_device.h)
 }
 
 }  // namespace
@@ -193,8 +176,8 @@ hipError_t launch_stem_s3(const float *x, const uint16_t *w3, const float *scale
     const int ph = h / 4, pw = wd / 4;
     const int tiles = ((ph + PTH - 1) / PTH) * ((pw + PTW - 1) / PTW);
     const size_t lds = (size_t)S_ALL * sizeof(float);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_stem_s3),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    static std::atomic<unsigned long long> attr_devs{0};
+    hipError_t e = set_dynamic_lds(k_stem_s3, lds, &attr_devs);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_stem_s3, dim3((unsigned)tiles, (unsigned)n, 64 / OCB), dim3(256), lds, st, x, w3, scale, shift, h,
                        wd, y, y_bs, reinterpret_cast<unsigned *>(out_range));

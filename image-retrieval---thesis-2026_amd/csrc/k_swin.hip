@@ -7,22 +7,15 @@
 //                      of scale * out (k_linear_t2.hip layout) for the Linear that reads the residual stream next (qkv, fc1).
 //   k_patch_merge      the 2 x 2 quads of [n, h, w, c] fp32 rows gathered into terms rows [n, h / 2, w / 2, 4 c] of scale * x in
 //                      timm's order -- quad (0, 0), (1, 0), (0, 1), (1, 1) as (row, column) offsets -- for the reduction Linear.
+#include "mirx_device.h"
 #include "mirx_kernels.h"
 
 namespace mirx {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// 4 values at feature 4 i of a terms row (line i >> 3: 64 bytes of high terms, then 64 of low terms)
+// store_terms4's layout addressed inside one terms row by quad: 4 values at feature 4 i (line i >> 3: 64 bytes of high terms, then
+// 64 of low terms).  Kept beside store_terms4: the quad-index form compiles to a different instruction order.
 __device__ inline void put_terms4(char *trow, int i, const f32x4 &o, float scale) {
     unsigned h0, l0, h1, l1;
     split2h_pair(o[0] * scale, o[1] * scale, h0, l0);

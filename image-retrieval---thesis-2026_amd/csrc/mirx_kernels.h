@@ -279,19 +279,4 @@ hipError_t launch_sra_head(const float *x, int64_t n, int hw, int c, const float
 hipError_t launch_pcam_head(const float *x, int64_t n, int hw, int c, const float *w, const float *b, int K, const float *gamma,
                             const float *beta, float eps, float lam, int normalize, float *feat, float *logits, hipStream_t st);
 
-#ifdef __HIPCC__
-// ---- k_simcam.hip / k_simatt.hip: the saliency maps' upsample ------------------------------------------------------------------
-// Output pixel (y, x) of an h x w map `m` (row-major) resized by F.interpolate(mode="bilinear", align_corners=False): ATen's
-// upsample_bilinear2d source index max(scale * (dst + 0.5) - 0.5, 0) with scale sh = h / H, sw = w / W, the upper neighbour
-// clamped to the last row / column.
-__device__ inline float bilinear_half_pixel(const float *m, int h, int w, float sh, float sw, int y, int x) {
-    const float fy = fmaxf(sh * ((float)y + 0.5f) - 0.5f, 0.f);
-    const float fx = fmaxf(sw * ((float)x + 0.5f) - 0.5f, 0.f);
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    return hy * (hx * m[y0 * w + x0] + lx * m[y0 * w + x1]) + ly * (hx * m[y1 * w + x0] + lx * m[y1 * w + x1]);
-}
-#endif  // __HIPCC__
-
 }  // namespace mirx

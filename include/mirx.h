@@ -633,7 +633,7 @@ int mirx_dwconv7x7_nhwc(const float *x, const float *w_taps_first, const float *
  * ResNet-50 on channels-last TERMS ROWS (layout: mirx_linear_terms above; image b of a map is n_pixels rows of c / 32 lines).
  * Every terms map travels with two device fp32 rows [n]: its SCALE row (the power of two image b was written with) and its
  * RANGE row (largest |value| of image b before the split, zeroed by the caller once per forward, folded in by unsigned atomic
- * max: mirx_common.h).  An image's arithmetic reads only its own rows, so its embedding does not depend on its batch mates and
+ * max: mirx_device.h).  An image's arithmetic reads only its own rows, so its embedding does not depend on its batch mates and
  * a non-finite image makes only its own outputs NaN.  Replaces the torchvision Bottleneck convolutions the reference's
  * ResNet50 runs (model.py:9-39 there, models.resnet50 children [:-1]).
  *

@@ -126,7 +126,7 @@ def test_channels_last_patch_rows_reproduce_the_stride2_convolution():
 
 
 def test_tanh_gelu_sigmoid_form_is_as_accurate_as_the_tanh_form():
-    """csrc/mirx_common.h:gelu_tanh computes v / (1 + 2^(v (K1 + K2 v^2))) -- the identity 1 + tanh(u) = 2 / (1 + e^(-2u)) -- with
+    """csrc/mirx_device.h:gelu_tanh computes v / (1 + 2^(v (K1 + K2 v^2))) -- the identity 1 + tanh(u) = 2 / (1 + e^(-2u)) -- with
     one v_exp_f32 and one v_rcp_f32.  Emulated in float32 with numpy: within 1e-6 (absolute) of the float64 value of the
     reference's activation (transformers "gelu_pytorch_tanh") and at least as accurate relatively as the tanh form itself."""
     import numpy as np

@@ -28,7 +28,7 @@ CASES = [
 ]
 
 
-def _run(lib, _lib, case, ring, small):
+def _run(lib, _lib, case, ring, small, bn_offset=False):
     cin, cout, hw, n, terms, prologue, xpad, ypad = case
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(cin * 7 + hw + n)
@@ -40,6 +40,9 @@ def _run(lib, _lib, case, ring, small):
     sc = torch.rand(cin, generator=g, device=dev) + 0.5
     sh = torch.randn(cin, generator=g, device=dev) * 0.3
     bias = torch.randn(cout, generator=g, device=dev)
+    if bn_offset:                                                      # the same values, 4 bytes into a larger allocation
+        sc, sh = (torch.cat([v.new_zeros(1), v])[1:] for v in (sc, sh))
+        assert sc.data_ptr() % 16 == 4 and sh.data_ptr() % 16 == 4
     from mirx.model import _split2h_weights
     w2, osc = _split2h_weights(w)
     rng_in = buf[:, :cin, :hw].abs().amax(dim=(1, 2)).contiguous()
@@ -88,6 +91,24 @@ def test_ring_arm_is_bit_identical_to_the_tiled_arm_and_the_small_kernel(case):
     # the padding between planes is never written
     if ypad and not terms:
         assert bool((outs[0][0].view(torch.float32)[:, :, hw:] == -7.0).all())
+
+
+@pytest.mark.parametrize("n,terms", [(2, False), (2, True), (3, False)])
+def test_small_launch_falls_back_to_the_tiled_kernel_on_misaligned_bn_vectors(n, terms):
+    """The one-wave kernel fills its BN table with 16-byte loads; `scale` / `shift` that are not 16-byte aligned (views 4 bytes
+    into a larger allocation) keep the layer on the tiled kernel, which reads them element by element: the same bits as the
+    aligned call, which takes the one-wave kernel (7 x 7 map, 512 channels, 2 or 3 images: far below the small-launch limit)."""
+    from mirx import _lib
+    lib = _lib.load()
+    case = (512, 128, 49, n, terms, True, 0, 0)
+    try:
+        (ya, auxa), (yo, auxo) = (_run(lib, _lib, case, False, True, bn_offset=off) for off in (False, True))
+    finally:
+        _lib.check(lib.mirx_set_tuning(_lib.TUNE_CONV1X1_RING, 1), "set_tuning")
+        _lib.check(lib.mirx_set_tuning(_lib.TUNE_CONV1X1_SMALL_MAX_WG, 128), "set_tuning")
+    clean = [b for b in range(n) if b != 1]                            # image 1 is poisoned (NaN from either kernel)
+    assert torch.equal(ya[clean], yo[clean])
+    assert torch.equal(auxa[clean], auxo[clean])
 
 
 def test_ring_switch_validates_its_argument():

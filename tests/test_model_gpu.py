@@ -654,6 +654,57 @@ def test_concurrent_forwards_on_two_streams_equal_the_sequential_result(model_an
             assert torch.equal(out, seq), rep
 
 
+_CONCURRENT_FIRST_USE = r"""
+import sys, threading
+import torch
+sys.path.insert(0, sys.argv[1])
+from mirx.model import DenseNet121
+torch.manual_seed(0)
+m = DenseNet121().eval().cuda()
+g = torch.Generator(device="cuda").manual_seed(11)
+x = torch.randn(4, 2, 3, 224, 224, generator=g, device="cuda")
+with torch.no_grad():
+    m._cache()                       # the folded weights, built once here: the threads below start at the forward's launchers
+torch.cuda.synchronize()
+outs, errs, gate = [None] * 4, [], threading.Barrier(4)
+def work(j):
+    try:
+        st = torch.cuda.Stream()
+        with torch.no_grad(), torch.cuda.stream(st):
+            gate.wait()
+            outs[j] = m(x[j])
+        st.synchronize()
+    except Exception as e:           # a launch error surfaces as an exception of the forward
+        errs.append(repr(e))
+threads = [threading.Thread(target=work, args=(j,)) for j in range(4)]
+for t in threads: t.start()
+for t in threads: t.join()
+torch.cuda.synchronize()
+assert not errs, errs
+with torch.no_grad():
+    for j in range(4):
+        ref = m(x[j])
+        assert torch.isfinite(ref).all()
+        assert torch.equal(outs[j], ref), j
+print("CONCURRENT_FIRST_USE_OK")
+"""
+
+
+@pytest.mark.gpu
+def test_concurrent_first_use_of_the_launchers_from_four_threads():
+    """Every launcher raises its kernel's dynamic-LDS limit on its first launch per device and records that in an atomic
+    per-call-site mask.  In a fresh process (untouched masks) four host threads make their first DenseNet121 forward (2 images
+    at 224 x 224, a stream each) at the same moment, released by a barrier: no launch error, and each embedding bit-identical
+    to the same images embedded afterwards from one thread."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _CONCURRENT_FIRST_USE, root], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    assert "CONCURRENT_FIRST_USE_OK" in r.stdout
+
+
 @pytest.mark.gpu
 def test_padded_channel_planes_agree(model_and_sd):
     """Padded channel planes (KernelConfig.plane_stride: measured, no gain, kept as an option of the kernels' ABI) against the

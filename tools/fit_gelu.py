@@ -1,6 +1,6 @@
-"""Measures, in float32 arithmetic emulated with numpy, the error of csrc/mirx_common.h:gelu_tanh (the sigmoid form) against
+"""Measures, in float32 arithmetic emulated with numpy, the error of csrc/mirx_device.h:gelu_tanh (the sigmoid form) against
 float64, next to what 0.5 v (1 + tanh u) gives with a correctly rounded tanh; and fits / measures the branch-free erf that was
-tried for gelu_erf and not kept (it was not faster than ocml's erff: mirx_common.h).
+tried for gelu_erf and not kept (it was not faster than ocml's erff: mirx_device.h).
   python tools/fit_gelu.py          (CPU, numpy + scipy)"""
 import numpy as np
 from scipy.special import erf, erfc
