@@ -17,6 +17,11 @@ OPT_TIERS = 1
 OPT_SAMPLE_RANK = 2
 OPT_FORCE_TAU = 3
 OPT_PROFILE = 4
+OPT_RANK_SORT = 5                  # which sort rank_all runs
+RANK_SORT_AUTO = 0                 # bitonic up to 65536 rows, radix above
+RANK_SORT_BITONIC = 1
+RANK_SORT_RADIX = 2
+MAX_SEARCH_K = 1024                # mirx_index_search's k limit; FlatIndex.search goes to rank_top above it
 TUNE_CONV1X1_SMALL_MAX_WG = 1      # mirx_set_tuning keys
 TUNE_CONV3X3_SMALL_MAX_WG = 2
 TUNE_CONV1X1_RING = 3
@@ -63,6 +68,9 @@ SYMBOLS = {
     "mirx_index_last_stats": (_int, [_vp, _vp, ctypes.POINTER(SearchStats)]),
     "mirx_index_last_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "mirx_index_rank_all": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mirx_index_rank_top": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_rank_key": (ctypes.c_uint64, [ctypes.c_double]),
+    "mirx_rank_sort_tile": (_int, []),
     "mirx_topk_merge": (_int, [_vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "mirx_rank_metrics": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _int, _int, ctypes.c_double, _int,
                                  ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp, _vp, _vp, _vp]),

@@ -40,7 +40,7 @@ try:
 except Exception:  # pragma: no cover
     torch = None
 
-RERANK_MAX_N = 65536             # include/mirx.h MIRX_RERANK_MAX_N (the rank_all limit)
+RERANK_MAX_N = 65536             # include/mirx.h MIRX_RERANK_MAX_N (the re-rank kernel's own limit)
 RERANK_MAX_DR = 4096             # MIRX_RERANK_MAX_DR
 RERANK_MAX_TOPK = 1024           # MIRX_RERANK_MAX_TOPK
 DEVICE_SHARE = 0.8               # of the free device memory: base ranking, base scores and every re-ranked stage of a call

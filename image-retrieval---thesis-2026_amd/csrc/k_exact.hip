@@ -228,11 +228,6 @@ __device__ inline void bitonic_sort_lds(Hit *a, int m) {
     __syncthreads();
 }
 
-__device__ inline float reported_value(double rank_score, int metric) {
-    if (rank_score == -INFINITY) return -INFINITY;
-    return metric == MIRX_METRIC_IP ? (float)rank_score : (float)(-sqrt(fmax(-rank_score, 0.0)));
-}
-
 // ---- streaming top-k of one score row ---------------------------------------------------------
 constexpr int TK_TOTAL = 2048;   // LDS records: kp sorted + (TK_TOTAL - kp) pending, kp <= 1024
 

@@ -70,13 +70,19 @@ struct mirx_index {
     int sample_rank = 8;
     uint32_t force_tau_bits = 0x7fc00000u;
     int profile = 0;
+    int rank_sort = MIRX_RANK_SORT_AUTO;
+    // the radix ranking starts from the rows in (id, row) order: the identity while ids ascend with the row (always, for auto ids),
+    // else a permutation built on first use and dropped by every add
+    bool ids_ascend = true;
+    int64_t last_id = INT64_MIN;
+    bool idperm_valid = false;
     std::vector<hipEvent_t> ev_pool;      // lazily created, reused
     struct Span { int stage; hipEvent_t a, b; };
     std::vector<Span> spans;              // of the last search
     size_t ev_used = 0;
     // workspace
     DevBuf q32p, q16, qnorm, tau, cnt, cand, ovf_cnt, ovf, groupmax, fail_list, retry_list, tau2, q16r, taur,
-        scores, stage, rankwork, spill;
+        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm;
     int *fail_count = nullptr;            // device
     mirx_search_stats *stats_dev = nullptr;
     int *fail_count_host = nullptr;       // pinned
@@ -474,6 +480,69 @@ int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t
     return MIRX_OK;
 }
 
+// ---- the radix ranking (k_ranksort.hip) ---------------------------------------------------------------------------------
+constexpr int64_t RANK_BITONIC_MAX_ROWS = 65536;     // the bitonic network's reach (launch_rank_rows)
+constexpr size_t RANK_WS_BYTES = (size_t)1 << 29;    // workspace budget of a ranking batch, either sort
+
+// ix->idperm = the rows in (id, row) order: one segment sorted by id ^ sign bit, stably, from the identity.
+int build_id_permutation(mirx_index *ix, hipStream_t st) {
+    const int64_t n = ix->size;
+    MIRX_HIP(ix->rkeys.ensure((size_t)2 * n * sizeof(uint64_t)));
+    MIRX_HIP(ix->rpay.ensure((size_t)2 * n * sizeof(int32_t)));
+    MIRX_HIP(ix->rhist.ensure((size_t)256 * rank_sort_tiles(n) * sizeof(unsigned)));
+    MIRX_HIP(ix->idperm.ensure((size_t)n * sizeof(int32_t)));
+    uint64_t *ka = ix->rkeys.as<uint64_t>();
+    int32_t *pa = ix->rpay.as<int32_t>();
+    MIRX_HIP(launch_rank_sort_build_ids(ix->ids, n, ka, pa, st));
+    MIRX_HIP(launch_rank_sort(ka, pa, ka + n, pa + n, ix->rhist.as<unsigned>(), n, 1, st));
+    MIRX_HIP(hipMemcpyAsync(ix->idperm.p, pa, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    ix->idperm_valid = true;
+    return MIRX_OK;
+}
+
+// Ranks 0 .. kout-1 of every query by the radix sort.  Per query of a batch: n fp64 scores, two key and two payload buffers =
+// 32 bytes per row, batches sized to RANK_WS_BYTES (16 queries at 2^20 rows); a gallery whose single query does not fit is
+// bounded by the allocation alone.
+int rank_radix(mirx_index *ix, const float *q, int64_t nq, int64_t kout, const int64_t *exclude, bool drop_excluded,
+               int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st) {
+    const int64_t n = ix->size;
+    if (!ix->ids_ascend && !ix->idperm_valid) {
+        int rc = build_id_permutation(ix, st);
+        if (rc) return rc;
+    }
+    const int32_t *perm = ix->ids_ascend ? nullptr : ix->idperm.as<int32_t>();
+    const int64_t ld = round_up(n, 64);
+    int64_t per = (int64_t)RANK_WS_BYTES / (ld * 32);
+    per = std::max<int64_t>(1, std::min<int64_t>(per, std::min<int64_t>(1024, nq)));
+    if (ix->scores.ensure((size_t)per * ld * sizeof(double)) != hipSuccess ||
+        ix->rkeys.ensure((size_t)2 * per * n * sizeof(uint64_t)) != hipSuccess ||
+        ix->rpay.ensure((size_t)2 * per * n * sizeof(int32_t)) != hipSuccess ||
+        ix->rhist.ensure((size_t)per * 256 * rank_sort_tiles(n) * sizeof(unsigned)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIRX_ENOMEM, "rank: the sort workspace (32 bytes per gallery row) does not fit the device");
+    }
+    MIRX_HIP(ix->q32p.ensure((size_t)per * ix->dimp * sizeof(float)));
+    MIRX_HIP(ix->q16.ensure((size_t)per * ix->dimp * sizeof(uint16_t)));
+    MIRX_HIP(ix->qnorm.ensure((size_t)per * sizeof(float)));
+    uint64_t *ka = ix->rkeys.as<uint64_t>(), *kb = ka + per * n;
+    int32_t *pa = ix->rpay.as<int32_t>(), *pb = pa + per * n;
+    for (int64_t b = 0; b < nq; b += per) {
+        const int cnt = (int)std::min<int64_t>(per, nq - b);
+        const int64_t *exb = exclude ? exclude + b : nullptr;
+        MIRX_HIP(launch_prep_queries(q + b * ix->dim, cnt, cnt, ix->dim, ix->dimp, ix->q32p.as<float>(),
+                                     ix->q16.as<uint16_t>(), ix->qnorm.as<float>(), st));
+        MIRX_HIP(launch_scores_f64(ix->q32p.as<float>(), nullptr, cnt, ix->g32, n, ix->dimp, ix->metric,
+                                   ix->scores.as<double>(), ld, st));
+        MIRX_HIP(launch_rank_sort_build(ix->scores.as<double>(), ld, n, ix->ids, perm, exb, drop_excluded ? 1 : 0, cnt, ka, pa,
+                                        st));
+        MIRX_HIP(launch_rank_sort(ka, pa, kb, pb, ix->rhist.as<unsigned>(), n, cnt, st));
+        MIRX_HIP(launch_rank_sort_write(pa, n, kout, ix->scores.as<double>(), ld, ix->ids, exb, drop_excluded ? 1 : 0,
+                                        ix->metric, cnt, out_ids + b * kout, out_val ? out_val + b * kout : nullptr,
+                                        out_f64 ? out_f64 + b * kout : nullptr, st));
+    }
+    return MIRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -545,7 +614,7 @@ void mirx_index_destroy(mirx_index *ix) {
     if (ix->pend_ev) (void)hipEventDestroy(ix->pend_ev);
     for (DevBuf *b : {&ix->q32p, &ix->q16, &ix->qnorm, &ix->tau, &ix->cnt, &ix->cand, &ix->ovf_cnt, &ix->ovf, &ix->groupmax,
                       &ix->fail_list, &ix->retry_list, &ix->tau2, &ix->q16r, &ix->taur, &ix->scores, &ix->stage,
-                      &ix->rankwork, &ix->spill})
+                      &ix->rankwork, &ix->spill, &ix->rkeys, &ix->rpay, &ix->rhist, &ix->idperm})
         b->release();
     delete ix;
 }
@@ -575,6 +644,11 @@ int mirx_index_set_option(mirx_index *ix, int option, int64_t value) {
             return MIRX_OK;
         case MIRX_OPT_PROFILE:
             ix->profile = value ? 1 : 0;
+            return MIRX_OK;
+        case MIRX_OPT_RANK_SORT:
+            MIRX_CHECK(value == MIRX_RANK_SORT_AUTO || value == MIRX_RANK_SORT_BITONIC || value == MIRX_RANK_SORT_RADIX,
+                       "set_option: rank sort must be 0 (auto), 1 (bitonic) or 2 (radix)");
+            ix->rank_sort = (int)value;
             return MIRX_OK;
         default:
             return fail(MIRX_EINVAL, "set_option: unknown option");
@@ -606,14 +680,31 @@ int mirx_index_add(mirx_index *ix, const float *rows, int64_t n, const int64_t *
                                ix->gbias + at, ix->gnorm_max_bits, ix->metric, nullptr));
         MIRX_HIP(hipStreamSynchronize(nullptr));
     }
+    std::vector<int64_t> host_ids;
+    const int64_t *idh = ids_or_null;                      // the new ids on the host: do they go on ascending with the row?
     if (ids_or_null) {
         MIRX_HIP(hipMemcpy(ix->ids + ix->size, ids_or_null, (size_t)n * sizeof(int64_t),
                            ids_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        if (ids_dev && ix->ids_ascend) {
+            host_ids.resize((size_t)n);
+            MIRX_HIP(hipMemcpy(host_ids.data(), ids_or_null, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+            idh = host_ids.data();
+        }
     } else {
-        std::vector<int64_t> auto_ids((size_t)n);
-        for (int64_t i = 0; i < n; ++i) auto_ids[(size_t)i] = ix->size + i;
-        MIRX_HIP(hipMemcpy(ix->ids + ix->size, auto_ids.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+        host_ids.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) host_ids[(size_t)i] = ix->size + i;
+        MIRX_HIP(hipMemcpy(ix->ids + ix->size, host_ids.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+        idh = host_ids.data();
     }
+    if (ix->ids_ascend) {
+        int64_t last = ix->last_id;
+        for (int64_t i = 0; i < n && ix->ids_ascend; ++i) {
+            ix->ids_ascend = idh[i] >= last;
+            last = idh[i];
+        }
+        ix->last_id = last;
+    }
+    ix->idperm_valid = false;
     ix->size += n;
     return MIRX_OK;
 }
@@ -685,15 +776,21 @@ int mirx_index_last_timings(mirx_index *ix, float *out_ms) {
 int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null,
                         int64_t *out_ids, float *out_scores_or_null, void *stream) {
     MIRX_CHECK(ix && q && out_ids && nq >= 0, "rank_all: bad argument");
-    MIRX_CHECK(ix->size <= 65536, "rank_all: gallery larger than 65536 rows");
+    const bool radix = ix->rank_sort == MIRX_RANK_SORT_RADIX ||
+                       (ix->rank_sort == MIRX_RANK_SORT_AUTO && ix->size > RANK_BITONIC_MAX_ROWS);
+    MIRX_CHECK(radix || ix->size <= RANK_BITONIC_MAX_ROWS,
+               "rank_all: the bitonic sort (MIRX_OPT_RANK_SORT = 1) takes at most 65536 rows");
     if (nq == 0 || ix->size == 0) return MIRX_OK;
     DeviceGuard dg(ix->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (radix)
+        return rank_radix(ix, q, nq, ix->size, exclude_ids_or_null, /*drop_excluded=*/false, out_ids, out_scores_or_null,
+                          nullptr, st);
     const int64_t n = ix->size;
     int64_t np2 = 1;
     while (np2 < n) np2 <<= 1;
     const int64_t ld = round_up(n, 64);
-    int64_t per = std::max<int64_t>(4, std::min<int64_t>(1024, (int64_t)((size_t)1 << 29) / (np2 * 16))) / 4 * 4;
+    int64_t per = std::max<int64_t>(4, std::min<int64_t>(1024, (int64_t)RANK_WS_BYTES / (np2 * 16))) / 4 * 4;
     per = std::min<int64_t>(per, round_up(nq, 4));
     MIRX_HIP(ix->scores.ensure((size_t)per * ld * sizeof(double)));
     MIRX_HIP(ix->rankwork.ensure((size_t)per * np2 * sizeof(Hit)));
@@ -713,6 +810,25 @@ int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq, const int64_
     }
     return MIRX_OK;
 }
+
+int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
+                        float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream) {
+    MIRX_CHECK(k >= 1, "rank_top: k must be at least 1");
+    MIRX_CHECK(nq >= 0, "rank_top: nq < 0");
+    MIRX_CHECK(out_ids, "rank_top: out_ids is null");
+    MIRX_CHECK(out_scores_or_null || out_rank_scores_or_null, "rank_top: both score outputs are null");
+    MIRX_CHECK(ix, "rank_top: null index");
+    MIRX_CHECK(q || nq == 0, "rank_top: null queries");
+    MIRX_CHECK(k <= ix->size, "rank_top: k is larger than the index");
+    if (nq == 0) return MIRX_OK;
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "rank_top: cannot select the index device");
+    return rank_radix(ix, q, nq, k, exclude_ids_or_null, /*drop_excluded=*/true, out_ids, out_scores_or_null,
+                      out_rank_scores_or_null, reinterpret_cast<hipStream_t>(stream));
+}
+
+uint64_t mirx_rank_key(double score) { return rank_key(score); }
+int mirx_rank_sort_tile(void) { return RANK_TILE; }
 
 int mirx_topk_merge(const double *in_scores, const int64_t *in_ids, int nshard, int64_t nq, int k,
                     int metric, double *out_rank_scores, float *out_scores, int64_t *out_ids, void *stream) {

@@ -64,6 +64,22 @@ __host__ __device__ inline bool hit_before(double sa, int64_t ia, double sb, int
     return sa > sb || (sa == sb && ia < ib);
 }
 
+// The radix ranking's sort key (k_ranksort.hip): an unsigned 64-bit image of an fp64 ranking score that ASCENDS as the score
+// descends, so an ascending sort ranks best first: rank_key(a) < rank_key(b) iff a > b for every pair that is not NaN.  The
+// usual bit trick (flip all bits of a negative value, the sign bit of the others) gives an ascending image; its complement is
+// the key.  hit_before compares with ==, for which -0.0 and +0.0 tie, so -0.0 takes +0.0's key.  -inf has the largest key of
+// any number (0xFFF0000000000000); a NaN lands outside the numbers (before +inf or after -inf, by its sign bit).
+__host__ __device__ inline uint64_t rank_key(double s) {
+    uint64_t u;
+    __builtin_memcpy(&u, &s, 8);
+    if ((u << 1) == 0) u = 0;                              // -0.0 -> +0.0
+    return (u >> 63) ? u : ~u ^ 0x8000000000000000ull;     // = ~(u ^ (negative ? all ones : the sign bit))
+}
+// The key that sorts after every score's: rows that a top-k ranking leaves out (k_ranksort.hip).
+constexpr uint64_t RANK_KEY_LAST = ~0ull;
+// Elements one workgroup of the radix ranking's scatter orders at a time (mirx_rank_sort_tile, tests reach its boundaries).
+constexpr int RANK_TILE = 4096;
+
 // CUs of the CURRENT device, cached per device (a process that drives several GPUs sizes every persistent grid for the one it
 // launches on).  Host threads launch concurrently: the cache is atomic, and two threads that both miss store the same value.
 inline int current_device_cus() {

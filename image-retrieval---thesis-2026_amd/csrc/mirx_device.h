@@ -123,6 +123,13 @@ __device__ inline double lane_tree_score(const float *__restrict__ q, const floa
     acc = wave_butterfly_sum(acc);
     return METRIC == 0 ? acc : -acc;
 }
+
+// What the search boundary reports for an fp64 ranking score: metric 0 the dot product, metric 1 -sqrt of the squared distance.
+__device__ inline float reported_value(double rank_score, int metric) {
+    if (rank_score == -INFINITY) return -INFINITY;
+    return metric == MIRX_METRIC_IP ? (float)rank_score : (float)(-sqrt(fmax(-rank_score, 0.0)));
+}
+
 // tanh-form GELU (transformers "gelu_pytorch_tanh", the SigLIP MLP activation): 0.5 v (1 + tanh(u)), u = sqrt(2/pi) (v + 0.044715 v^3).
 // 1 + tanh(u) = 2 / (1 + e^(-2u)) exactly, so the value is v / (1 + 2^(v (K1 + K2 v^2))) with K1 = -2 sqrt(2/pi) log2(e), K2 =
 // 0.044715 K1: one v_exp_f32 and one v_rcp_f32 instead of tanhf's ~25 instructions (the Linear epilogues are VALU-bound on their

@@ -78,6 +78,25 @@ hipError_t launch_topk_merge(const double *in_scores, const int64_t *in_ids, int
                              int64_t nq, int k, int metric, double *out_f64, float *out_val,
                              int64_t *out_ids, hipStream_t st);
 
+// ---- k_ranksort.hip: segmented stable LSD radix sort of (64-bit key, int32 row) pairs, the ranking past 65536 rows ----------
+int64_t rank_sort_tiles(int64_t n);              // RANK_TILE-element tiles of an n-element segment
+// keys[i*n + j], pay[i*n + j] of query i: position j holds row r = perm ? perm[j] : j (perm = the rows in (id, row) order, null
+// when that is the identity) with rank_key(scores[i*ld + r]); rows whose id is exclude[i] get the key of -inf, or with
+// drop_excluded the key after every score's.
+hipError_t launch_rank_sort_build(const double *scores, int64_t ld, int64_t n, const int64_t *ids, const int32_t *perm,
+                                  const int64_t *exclude, int drop_excluded, int nq, uint64_t *keys, int32_t *pay, hipStream_t st);
+// one segment that sorts into (id, row) order: key = id ^ sign bit, payload = row
+hipError_t launch_rank_sort_build_ids(const int64_t *ids, int64_t n, uint64_t *keys, int32_t *pay, hipStream_t st);
+// nseg segments of n pairs, ascending by key, equal keys in their input order; in / out = keys_a, pay_a; keys_b, pay_b = scratch of
+// the same size; hist = nseg * 256 * rank_sort_tiles(n) words.  No workgroup waits for another: three launches per 8-bit digit.
+hipError_t launch_rank_sort(uint64_t *keys_a, int32_t *pay_a, uint64_t *keys_b, int32_t *pay_b, unsigned *hist, int64_t n,
+                            int nseg, hipStream_t st);
+// ranks 0 .. kout-1 of every query from the sorted payload: ids, fp32 reported values and / or fp64 scores ([nq, kout] each).  The
+// excluded id reads -inf; with drop_excluded its slot reads id -1 (those rows are last, see launch_rank_sort_build).
+hipError_t launch_rank_sort_write(const int32_t *pay, int64_t n, int64_t kout, const double *scores, int64_t ld,
+                                  const int64_t *ids, const int64_t *exclude, int drop_excluded, int metric, int nq,
+                                  int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st);
+
 // ---- k_conv1x1_s3.hip --------------------------------------------------------------------
 hipError_t launch_conv1x1_s3(const float *x, int64_t xbs, int cin, const float *scale, const float *shift,
                              const uint16_t *w3, const float *bias, int64_t n, int hw, int cout, int relu_out,

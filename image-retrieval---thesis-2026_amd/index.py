@@ -108,7 +108,9 @@ class FlatIndex:
         """-> (scores [nq,k] float32 reported values, ids [nq,k] int64) on the index device.
 
         With return_f64=True the first tensor holds the fp64 ranking scores instead
-        (dot product, or NEGATIVE SQUARED distance for the L2 metric)."""
+        (dot product, or NEGATIVE SQUARED distance for the L2 metric).  k above 1024 goes to rank_top."""
+        if int(k) > _lib.MAX_SEARCH_K:
+            return self.rank_top(q, k, exclude_ids=exclude_ids, return_f64=return_f64)
         q, ex = self._prep_queries(q, exclude_ids)
         nq = q.shape[0]
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
@@ -151,8 +153,27 @@ class FlatIndex:
         _, _, sc, s64, ids = handle
         return (s64 if return_f64 else sc), ids
 
+    def rank_top(self, q, k, exclude_ids=None, return_f64=False):
+        """The first k entries, 1 <= k <= ntotal, of the full ranking, with search()'s outputs and conventions: -> (scores [nq,k],
+        ids [nq,k]); the excluded id is left out and slots past the eligible rows read (-inf, -1).  Sorts the whole gallery per
+        query (a radix sort, 32 bytes of workspace per row and query): for k <= 1024 search() is the faster call."""
+        q, ex = self._prep_queries(q, exclude_ids)
+        nq, k = q.shape[0], int(k)
+        ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=self.device)
+        sc = torch.empty((nq, max(k, 0)), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+        scp = ctypes.c_void_p(sc.data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self._lib.mirx_index_rank_top(
+                self._h, ctypes.c_void_p(q.data_ptr()), nq, k,
+                ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
+                None if return_f64 else scp, scp if return_f64 else None,
+                ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
+        _lib.check(rc, "mirx_index_rank_top")
+        return sc, ids
+
     def rank_all(self, q, exclude_ids=None, with_scores=False):
-        """Full ranking [nq, ntotal] (row = query, excluded id last)."""
+        """Full ranking [nq, ntotal] (row = query, excluded id last): score descending, equal scores by ascending id.  Any
+        gallery size the [nq, ntotal] outputs and the sort's workspace fit (a radix sort above 65536 rows)."""
         q, ex = self._prep_queries(q, exclude_ids)
         nq, n = q.shape[0], len(self)
         ids = torch.empty((nq, n), dtype=torch.int64, device=self.device)

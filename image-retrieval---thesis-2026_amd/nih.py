@@ -225,7 +225,8 @@ def search_collection(collection, query_vector, top_k, nprobe=10):
 def query_gallery(collection, query_rows, top_k=0, nprobe=10, batch_size=4096):
     """The loop of query_nih_zilliz.py:49-71 as batched searches: -> the list of result items that script writes as
     JSON (query_image_path, query_image_name, query_label_names, query_label_vector, results).  top_k <= 0 retrieves
-    the full gallery ranking."""
+    the full gallery ranking (the script's top_k = num_entities), whatever the gallery's size: above 1024 results the
+    collection ranks with FlatIndex.rank_top.  Lower batch_size for a large gallery: a batch returns batch_size * top_k hits."""
     k = top_k if top_k and top_k > 0 else collection.num_entities
     fields = ["image_path", "image_name", "label_text", "label_vector_json"]
     out = []

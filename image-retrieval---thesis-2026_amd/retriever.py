@@ -129,8 +129,7 @@ class Collection:
             return [[] for _ in range(q.shape[0])]
         limit = min(int(limit), self.num_entities)
         if limit > 1024:
-            ids, sc = self._ensure().rank_all(q, exclude_ids=exclude_ids, with_scores=True)
-            ids, sc = ids[:, :limit], sc[:, :limit]
+            sc, ids = self._ensure().rank_top(q, limit, exclude_ids=exclude_ids)
         else:
             sc, ids = self._ensure().search(q, limit, exclude_ids=exclude_ids)
         ids, sc = ids.cpu().numpy(), sc.cpu().numpy()

@@ -55,6 +55,12 @@ extern "C" {
 #define MIRX_OPT_SAMPLE_RANK 2   /* j: threshold = j-th largest sampled group maximum (default 8)  */
 #define MIRX_OPT_FORCE_TAU 3     /* test hook: float bits of a fixed threshold; 0x7fc00000 = off  */
 #define MIRX_OPT_PROFILE 4       /* 1: record HIP events around every stage of a search           */
+#define MIRX_OPT_RANK_SORT 5     /* which sort mirx_index_rank_all runs: MIRX_RANK_SORT_*          */
+
+/* values of MIRX_OPT_RANK_SORT.  Both sorts return the same ranking; forcing one lets a test run either on any gallery. */
+#define MIRX_RANK_SORT_AUTO 0     /* bitonic network up to 65536 rows, radix sort above            */
+#define MIRX_RANK_SORT_BITONIC 1  /* always the bitonic network: more than 65536 rows is MIRX_EINVAL */
+#define MIRX_RANK_SORT_RADIX 2    /* always the segmented radix sort (any size >= 1)               */
 
 /* stages timed when MIRX_OPT_PROFILE is on (mirx_index_last_timings) */
 #define MIRX_STAGE_PREP 0        /* query conversion                                  */
@@ -175,11 +181,34 @@ int mirx_index_last_timings(mirx_index *ix, float *out_ms);
  * torch.argsort(dists, dim=0, descending=True) (test.py:1090,179) and the
  * top_k = num_entities search of query_nih_zilliz.py:53-63.  out_ids: device [nq, size]
  * int64 (excluded row last); out_scores_or_null: device [nq, size] fp32 reported values.
- * Gallery size limited to 65536 rows per call in this version.
+ * Order: score descending, equal scores by ascending id (-0.0 and +0.0 are equal); rows with equal ids keep row order.
+ * Up to 65536 rows the sort is a bitonic network, above that a segmented radix sort over 64-bit images of the fp64 scores
+ * (MIRX_OPT_RANK_SORT forces either).  The radix sort works on batches of queries with 32 bytes of workspace per gallery row
+ * and query, at most 512 MiB unless one query needs more; the size is bounded by 2^31 rows and by that allocation
+ * (MIRX_ENOMEM).  NaN scores have no defined place in either sort.
  */
 int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq,
                         const int64_t *exclude_ids_or_null, int64_t *out_ids,
                         float *out_scores_or_null, void *stream);
+
+/*
+ * The first k entries of the same ranking, for 1 <= k <= size, without an [nq, size] array on the caller's side: the search
+ * for k past mirx_index_search's 1024 (Milvus' collection.search allows limit = 16384; query_nih_zilliz.py:53-63 passes
+ * top_k = num_entities).  Arguments and conventions are those of mirx_index_search_begin, not of mirx_index_rank_all: the row
+ * with the excluded id is LEFT OUT, slots past the number of eligible rows read id -1 and -inf, and either score output may be
+ * NULL (not both): out_scores fp32 reported values, out_rank_scores the fp64 ranking scores, [nq, k] each.  Always the radix
+ * sort of the whole gallery (MIRX_OPT_RANK_SORT does not apply); cost and workspace are those of mirx_index_rank_all.
+ */
+int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
+                        float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
+
+/*
+ * For tests.  mirx_rank_key: the radix sort's 64-bit key of an fp64 ranking score -- key(a) < key(b) iff a > b, and
+ * key(-0.0) == key(+0.0).  mirx_rank_sort_tile: elements per workgroup tile of its scatter (the sizes around multiples of it
+ * are the sort's edges).  Neither touches a device.
+ */
+uint64_t mirx_rank_key(double score);
+int mirx_rank_sort_tile(void);
 
 /*
  * Merge per-shard top-k lists (multi-GPU: after the all-gather of SURVEY 8e).
