@@ -29,6 +29,10 @@ SIMCAM_MAPS_BOTH = 0               # mirx_simcam `maps`
 SIMCAM_MAPS_RETRIEVED = 1
 SIMATT_GROUP = 0                   # mirx_simatt `mode`
 SIMATT_PAIRS = 1
+ANOMALY_BAD_SCORE = 1              # bits of the anomaly calls' bad_flag
+ANOMALY_BAD_NORM = 2
+ANOMALY_BAD_ONE_CLASS = 4
+ANOMALY_BAD_EMPTY_CLASS = 8
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
@@ -163,6 +167,12 @@ SYMBOLS = {
                                   _vp, _vp]),
     "mirx_simatt_workspace_floats": (_i64, [_i64, _i64, _i64, _int]),
     "mirx_simatt": (_int, [_vp, _i64, _int, _int, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _i64, _vp, _vp]),
+    "mirx_class_centroids_workspace_bytes": (_i64, [_i64, _int, _int]),
+    "mirx_class_centroids": (_int, [_vp, _i64, _int, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mirx_centroid_min_dist": (_int, [_vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp]),
+    "mirx_binary_rank_metrics_workspace_bytes": (_i64, [_i64, _i64]),
+    "mirx_binary_rank_metrics": (_int, [_vp, _vp, _i64, _i64, _vp, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp]),
 }
 
 _lib = None

@@ -1400,4 +1400,73 @@ int mirx_dwconv7x7_nchw_to_nhwc(const float *x, const float *w, const float *bia
     return MIRX_OK;
 }
 
+// ---- anomaly evaluation (k_anomaly.hip) -----------------------------------------------------------------------------------------
+static const char *anomaly_rows_limits(int64_t n, int d, int k) {
+    if (n < 1 || n > MIRX_ANOMALY_MAX_N) return "anomaly: n must be in [1, 2^30]";
+    if (d < 1 || d > MIRX_ANOMALY_MAX_D) return "anomaly: d must be in [1, 16384]";
+    if (k < 1 || k > MIRX_ANOMALY_MAX_K) return "anomaly: k must be in [1, 64]";
+    return nullptr;
+}
+
+static const char *anomaly_metric_limits(int64_t s, int64_t n) {
+    if (n < 1 || n > MIRX_ANOMALY_MAX_N) return "binary_rank_metrics: n must be in [1, 2^30]";
+    if (s < 1 || s > MIRX_ANOMALY_MAX_SEGMENTS) return "binary_rank_metrics: s must be in [1, 65535]";
+    return nullptr;
+}
+
+static bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int64_t mirx_class_centroids_workspace_bytes(int64_t n, int d, int k) {
+    if (const char *msg = anomaly_rows_limits(n, d, k)) return fail(MIRX_EINVAL, msg);
+    return class_centroids_workspace_bytes(n, d, k);
+}
+
+int mirx_class_centroids(const float *rows, int64_t n, int d, const int64_t *labels, const int64_t *classes, int k, void *workspace,
+                         int64_t workspace_bytes, double *centroids, int64_t *counts, int *bad_flag, void *stream) {
+    if (const char *msg = anomaly_rows_limits(n, d, k)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(rows && labels && classes && workspace && centroids && counts && bad_flag, "class_centroids: null buffer");
+    MIRX_CHECK(aligned_to(rows, 4) && aligned_to(labels, 8) && aligned_to(centroids, 8) && aligned_to(counts, 8) &&
+                   aligned_to(bad_flag, 4) && aligned_to(workspace, 256),
+               "class_centroids: misaligned buffer (workspace: 256 bytes)");
+    MIRX_CHECK(workspace_bytes >= class_centroids_workspace_bytes(n, d, k),
+               "class_centroids: workspace smaller than mirx_class_centroids_workspace_bytes()");
+    MIRX_HIP(launch_class_centroids(rows, n, d, labels, classes, k, workspace, centroids, counts, bad_flag,
+                                    reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_centroid_min_dist(const float *rows, int64_t n, int d, const double *centroids, int k, double *dist, int32_t *nearest,
+                           double *max_out, void *stream) {
+    if (const char *msg = anomaly_rows_limits(n, d, k)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(rows && centroids && dist && nearest && max_out, "centroid_min_dist: null buffer");
+    MIRX_CHECK(aligned_to(rows, 4) && aligned_to(centroids, 8) && aligned_to(dist, 8) && aligned_to(nearest, 4) && aligned_to(max_out, 8),
+               "centroid_min_dist: misaligned buffer");
+    MIRX_HIP(launch_centroid_min_dist(rows, n, d, centroids, k, dist, nearest, max_out, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int64_t mirx_binary_rank_metrics_workspace_bytes(int64_t s, int64_t n) {
+    if (const char *msg = anomaly_metric_limits(s, n)) return fail(MIRX_EINVAL, msg);
+    return binary_rank_metrics_workspace_bytes(s, n);
+}
+
+int mirx_binary_rank_metrics(const double *scores, const uint8_t *positive, int64_t s, int64_t n, const double *norm_or_null,
+                             double recall_level, void *workspace, int64_t workspace_bytes, double *thresholds, int64_t *tps,
+                             int64_t *fps, int64_t *out_t, double *out_auroc, double *out_aupr, double *out_fpr, int *bad_flag,
+                             void *stream) {
+    if (const char *msg = anomaly_metric_limits(s, n)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(recall_level >= 0.0 && recall_level <= 1.0, "binary_rank_metrics: recall_level must be in [0, 1]");
+    MIRX_CHECK(scores && positive && workspace && thresholds && tps && fps && out_t && out_auroc && out_aupr && out_fpr && bad_flag,
+               "binary_rank_metrics: null buffer");
+    MIRX_CHECK(aligned_to(scores, 8) && aligned_to(norm_or_null, 8) && aligned_to(thresholds, 8) && aligned_to(tps, 8) &&
+                   aligned_to(fps, 8) && aligned_to(out_t, 8) && aligned_to(out_auroc, 8) && aligned_to(out_aupr, 8) &&
+                   aligned_to(out_fpr, 8) && aligned_to(bad_flag, 4) && aligned_to(workspace, 256),
+               "binary_rank_metrics: misaligned buffer (workspace: 256 bytes)");
+    MIRX_CHECK(workspace_bytes >= binary_rank_metrics_workspace_bytes(s, n),
+               "binary_rank_metrics: workspace smaller than mirx_binary_rank_metrics_workspace_bytes()");
+    MIRX_HIP(launch_binary_rank_metrics(scores, positive, s, n, norm_or_null, recall_level, workspace, thresholds, tps, fps, out_t,
+                                        out_auroc, out_aupr, out_fpr, bad_flag, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
 }  // extern "C"

@@ -97,6 +97,19 @@ hipError_t launch_rank_sort_write(const int32_t *pay, int64_t n, int64_t kout, c
                                   const int64_t *ids, const int64_t *exclude, int drop_excluded, int metric, int nq,
                                   int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st);
 
+// ---- k_anomaly.hip: class centroids, nearest-centroid distances, segmented binary ranking metrics (include/mirx.h) -----------
+int64_t an_chunk_rows(int64_t n, int d);          // rows per chunk of the centroid sums: a function of n and d alone
+int64_t class_centroids_workspace_bytes(int64_t n, int d, int k);
+hipError_t launch_class_centroids(const float *rows, int64_t n, int d, const int64_t *labels, const int64_t *classes_host, int k,
+                                  void *workspace, double *centroids, int64_t *counts, int *bad, hipStream_t st);
+hipError_t launch_centroid_min_dist(const float *rows, int64_t n, int d, const double *centroids, int k, double *dist,
+                                    int32_t *nearest, double *max_out, hipStream_t st);
+int64_t binary_rank_metrics_workspace_bytes(int64_t nseg, int64_t n);
+hipError_t launch_binary_rank_metrics(const double *scores, const uint8_t *positive, int64_t nseg, int64_t n, const double *norm,
+                                      double level, void *workspace, double *thresholds, int64_t *tps, int64_t *fps, int64_t *out_t,
+                                      double *out_auroc, double *out_aupr, double *out_fpr, int *bad, hipStream_t st);
+
+
 // ---- k_conv1x1_s3.hip --------------------------------------------------------------------
 hipError_t launch_conv1x1_s3(const float *x, int64_t xbs, int cin, const float *scale, const float *shift,
                              const uint16_t *w3, const float *bias, int64_t n, int hw, int cout, int relu_out,

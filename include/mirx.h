@@ -995,6 +995,56 @@ int64_t mirx_simatt_workspace_floats(int64_t b, int64_t c, int64_t d, int mode);
 int mirx_simatt(const float *rows, int64_t b, int h, int w, int64_t c, const float *fc_weight, const float *fc_bias, int64_t d,
                 int mode, int positive, int H, int W, float *workspace, int64_t workspace_floats, float *out, void *stream);
 
+/* ---- Anomaly evaluation (k_anomaly.hip) --------------------------------------------------------------------------------
+ * The reference's anomaly/test_anomaly.py + anomaly/anomaly.py on the device: class centroids of an embedding set,
+ * every row's distance to its nearest centroid, and the binary ranking measures and curve points of score segments.
+ *
+ * mirx_class_centroids: rows = device fp32 [n, d], labels = device int64 [n], classes = HOST int64 [k] (read during the call).
+ *   centroids = device fp64 [k, d]: the mean of the rows whose label is classes[j] (the first such j when classes repeat a value;
+ *   rows whose label is in no class are left out), counts = device int64 [k].  Sums are fp64, added per chunk of consecutive rows
+ *   in row order and then in chunk order; the chunking depends on n and d alone and there is no floating atomic, so the bits are
+ *   the same on every call.  The mean is NOT rounded to fp32.  A class without rows gives a NaN centroid, count 0 and
+ *   MIRX_ANOMALY_BAD_EMPTY_CLASS in *bad_flag.  workspace = device, >= mirx_class_centroids_workspace_bytes(n, d, k), 256-byte
+ *   aligned.
+ * mirx_centroid_min_dist: dist[i] = min over j of sqrt(sum_e (rows[i, e] - centroids[j, e])^2) in fp64 (device fp64 [n]),
+ *   nearest[i] = the lowest j that attains it (device int32 [n]), max_out = device fp64 [1], the largest dist.  A NaN in row i
+ *   or in ANY centroid makes dist[i] NaN (nearest[i] = the first class whose distance is NaN) and max_out NaN: a NaN class is
+ *   never skipped in favour of a finite minimum.  The result does not depend on launch order or batch size.
+ * mirx_binary_rank_metrics: scores = device fp64 [s, n], positive = device uint8 [s, n] (non-zero = positive); norm_or_null =
+ *   device fp64 [s], segment i is ranked on scores / norm[i] (null: on the scores).  Per segment, with the distinct scores in
+ *   descending order: out_t[i] = T, their number, thresholds[i, 0..T) the values ranked on (score / norm[i] when a norm is
+ *   given, -0.0 as +0.0), tps / fps[i, 0..T) the positives / negatives
+ *   at or above each (device fp64 / int64 / int64 [s, n], the tail past T is not written); out_auroc = the trapezoid area under
+ *   (fps, tps) from (0, 0), an int64 sum divided once by 2 P Nneg; out_aupr = sum over t of (tps[t] - tps[t - 1]) / P *
+ *   tps[t] / (tps[t] + fps[t]); out_fpr = fps[c] / Nneg at the record c <= (the first with tps == P) whose |tps / P -
+ *   recall_level| is smallest, the later one on a tie (the reference's fpr_and_fdr_at_recall).  Every output is a function of the
+ *   groups of equal scores: nothing depends on the order of equal scores, and a segment's outputs do not depend on s.
+ *   workspace = device, >= mirx_binary_rank_metrics_workspace_bytes(s, n), 256-byte aligned.
+ * *bad_flag (device int, zeroed by the caller, read after): the OR of MIRX_ANOMALY_BAD_SCORE (a NaN or infinite score),
+ *   _BAD_NORM (a norm that is 0, negative, NaN or infinite), _BAD_ONE_CLASS (a segment without positives or without negatives:
+ *   its three measures are NaN), _BAD_EMPTY_CLASS.  A flagged call still completes.
+ * One stream, no host synchronisation.  Limits (MIRX_EINVAL, nothing launched): 1 <= n <= 2^30, 1 <= s <= 65535, 1 <= k <= 64,
+ * 1 <= d <= 16384, recall_level in [0, 1], 8-byte aligned int64 / fp64 buffers, 4-byte aligned fp32 / int32 buffers.
+ */
+#define MIRX_ANOMALY_MAX_N (1LL << 30)
+#define MIRX_ANOMALY_MAX_SEGMENTS 65535
+#define MIRX_ANOMALY_MAX_K 64
+#define MIRX_ANOMALY_MAX_D 16384
+#define MIRX_ANOMALY_BAD_SCORE 1
+#define MIRX_ANOMALY_BAD_NORM 2
+#define MIRX_ANOMALY_BAD_ONE_CLASS 4
+#define MIRX_ANOMALY_BAD_EMPTY_CLASS 8
+int64_t mirx_class_centroids_workspace_bytes(int64_t n, int d, int k);
+int mirx_class_centroids(const float *rows, int64_t n, int d, const int64_t *labels, const int64_t *classes, int k, void *workspace,
+                         int64_t workspace_bytes, double *centroids, int64_t *counts, int *bad_flag, void *stream);
+int mirx_centroid_min_dist(const float *rows, int64_t n, int d, const double *centroids, int k, double *dist, int32_t *nearest,
+                           double *max_out, void *stream);
+int64_t mirx_binary_rank_metrics_workspace_bytes(int64_t s, int64_t n);
+int mirx_binary_rank_metrics(const double *scores, const uint8_t *positive, int64_t s, int64_t n, const double *norm_or_null,
+                             double recall_level, void *workspace, int64_t workspace_bytes, double *thresholds, int64_t *tps,
+                             int64_t *fps, int64_t *out_t, double *out_auroc, double *out_aupr, double *out_fpr, int *bad_flag,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
