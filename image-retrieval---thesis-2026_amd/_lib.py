@@ -173,6 +173,11 @@ SYMBOLS = {
     "mirx_binary_rank_metrics_workspace_bytes": (_i64, [_i64, _i64]),
     "mirx_binary_rank_metrics": (_int, [_vp, _vp, _i64, _i64, _vp, ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp]),
+    "mirx_insdel_steps_workspace_bytes": (_i64, [_i64, _i64]),
+    "mirx_insdel_steps": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "mirx_blur2d_same": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _vp, _vp]),
+    "mirx_insdel_compose": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "mirx_insdel_curves": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -267,13 +267,15 @@ unsigned grid_for(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 25
 int64_t rank_sort_tiles(int64_t n) { return (n + RANK_TILE - 1) / RANK_TILE; }
 
 // Sorts nseg segments of n (key, payload) pairs ascending by key, stably: in and out in keys_a / pay_a, keys_b / pay_b of the
-// same size are scratch, hist = nseg * 256 * rank_sort_tiles(n) words.
+// same size are scratch, hist = nseg * 256 * rank_sort_tiles(n) words.  key_bits (a multiple of 16): the low bits that can differ
+// between keys -- the digits above them are not sorted on.
 hipError_t launch_rank_sort(uint64_t *keys_a, int32_t *pay_a, uint64_t *keys_b, int32_t *pay_b, unsigned *hist, int64_t n,
-                            int nseg, hipStream_t st) {
+                            int nseg, hipStream_t st, int key_bits) {
     if (nseg <= 0 || n <= 0) return hipSuccess;
+    if (key_bits < 2 * RS_BITS || key_bits > 64 || key_bits % (2 * RS_BITS)) return hipErrorInvalidValue;
     const int ntiles = (int)rank_sort_tiles(n);
     const dim3 grid((unsigned)ntiles, (unsigned)nseg);
-    for (int pass = 0; pass < 64 / RS_BITS; ++pass) {
+    for (int pass = 0; pass < key_bits / RS_BITS; ++pass) {
         const int shift = pass * RS_BITS;
         hipLaunchKernelGGL(k_rs_hist, grid, dim3(RS_THREADS), 0, st, keys_a, n, shift, hist, ntiles);
         hipLaunchKernelGGL(k_rs_scan, dim3((unsigned)nseg), dim3(RS_THREADS), 0, st, hist, (int64_t)RS_BINS * ntiles);
@@ -281,7 +283,7 @@ hipError_t launch_rank_sort(uint64_t *keys_a, int32_t *pay_a, uint64_t *keys_b, 
         std::swap(keys_a, keys_b);
         std::swap(pay_a, pay_b);
     }
-    static_assert((64 / RS_BITS) % 2 == 0, "an even number of passes ends in the buffers it started from");
+    // key_bits % (2 * RS_BITS) == 0: an even number of passes ends in the buffers it started from
     return hipGetLastError();
 }
 

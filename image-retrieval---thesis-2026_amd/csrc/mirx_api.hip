@@ -1469,4 +1469,70 @@ int mirx_binary_rank_metrics(const double *scores, const uint8_t *positive, int6
     return MIRX_OK;
 }
 
+// ---- insertion / deletion curves (k_insdel.hip) ---------------------------------------------------------------------------------
+static const char *insdel_steps_limits(int64_t k, int64_t hw) {
+    if (hw < 1 || hw > MIRX_INSDEL_MAX_HW) return "insdel_steps: hw must be in [1, 2^20]";
+    if (k < 1 || k > MIRX_INSDEL_MAX_K) return "insdel_steps: k must be in [1, 65535]";
+    return nullptr;
+}
+
+int64_t mirx_insdel_steps_workspace_bytes(int64_t k, int64_t hw) {
+    if (const char *msg = insdel_steps_limits(k, hw)) return fail(MIRX_EINVAL, msg);
+    return insdel_steps_workspace_bytes(k, hw);
+}
+
+int mirx_insdel_steps(const float *sal, int64_t k, int64_t hw, int64_t step, void *workspace, int64_t workspace_bytes, int32_t *t,
+                      void *stream) {
+    if (const char *msg = insdel_steps_limits(k, hw)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(step >= 1, "insdel_steps: step must be >= 1");
+    MIRX_CHECK(sal && workspace && t, "insdel_steps: null buffer");
+    MIRX_CHECK(aligned_to(sal, 4) && aligned_to(t, 4) && aligned_to(workspace, 256), "insdel_steps: misaligned buffer (workspace: 256 bytes)");
+    MIRX_CHECK(workspace_bytes >= insdel_steps_workspace_bytes(k, hw),
+               "insdel_steps: workspace smaller than mirx_insdel_steps_workspace_bytes()");
+    MIRX_HIP(launch_insdel_steps(sal, k, hw, step, workspace, t, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_blur2d_same(const float *x, int64_t n, int c, int h, int w, const float *kernel, int klen, float *y, void *stream) {
+    MIRX_CHECK(klen >= 1 && klen <= MIRX_BLUR_MAX_KLEN && (klen & 1), "blur2d_same: klen must be odd and in [1, 63]");
+    MIRX_CHECK(n >= 0 && c >= 1 && h >= 1 && w >= 1 && h <= 16384 && w <= 16384, "blur2d_same: needs n >= 0, c >= 1, 1 <= h, w <= 16384");
+    MIRX_CHECK(n <= INT32_MAX && blur2d_blocks(n * c, h, w) <= INT32_MAX, "blur2d_same: more than 2^31 - 1 workgroups");
+    MIRX_CHECK(x && kernel && y, "blur2d_same: null buffer");
+    MIRX_CHECK(aligned_to(x, 4) && aligned_to(kernel, 4) && aligned_to(y, 4), "blur2d_same: misaligned buffer");
+    MIRX_HIP(launch_blur2d_same(x, n * c, h, w, kernel, klen, y, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_insdel_compose(const int32_t *t, int64_t n_rows, int64_t hw, const float *bank, int64_t n_bank, const int32_t *start,
+                        const int32_t *finish, const int32_t *row, int64_t n_curves, int64_t n_steps, int64_t g0, int64_t n,
+                        float *out, void *stream) {
+    MIRX_CHECK(hw >= 1 && hw <= MIRX_INSDEL_MAX_HW, "insdel_compose: hw must be in [1, 2^20]");
+    MIRX_CHECK(n_rows >= 1 && n_rows <= INT32_MAX && n_bank >= 1 && n_bank <= INT32_MAX && n_curves >= 1 && n_curves <= INT32_MAX,
+               "insdel_compose: n_rows, n_bank and n_curves must be in [1, 2^31)");
+    MIRX_CHECK(n_steps >= 1 && n_steps <= MIRX_INSDEL_MAX_HW, "insdel_compose: n_steps must be in [1, 2^20]");
+    MIRX_CHECK(g0 >= 0 && n >= 0 && n <= INT32_MAX && g0 + n <= n_curves * (n_steps + 1),
+               "insdel_compose: [g0, g0 + n) must lie within the job's n_curves * (n_steps + 1) images");
+    MIRX_CHECK(t && bank && start && finish && row && out, "insdel_compose: null buffer");
+    MIRX_CHECK(aligned_to(t, 4) && aligned_to(bank, 4) && aligned_to(start, 4) && aligned_to(finish, 4) && aligned_to(row, 4) &&
+                   aligned_to(out, 4),
+               "insdel_compose: misaligned buffer");
+    MIRX_HIP(launch_insdel_compose(t, n_rows, hw, bank, n_bank, start, finish, row, n_steps, g0, n, out,
+                                   reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_insdel_curves(const float *q_feat, const float *r_feats, int64_t n_curves, int64_t n_steps, int d, double *scores,
+                       double *auc, int64_t *zero_counter, void *stream) {
+    MIRX_CHECK(d >= 1 && d <= (1 << 20), "insdel_curves: d must be in [1, 2^20]");
+    MIRX_CHECK(n_curves >= 1 && n_steps >= 1 && n_curves <= (1LL << 30) && n_steps <= (1LL << 30) &&
+                   n_curves * (n_steps + 1) <= (1LL << 30),
+               "insdel_curves: needs n_curves, n_steps >= 1 and n_curves * (n_steps + 1) <= 2^30");
+    MIRX_CHECK(q_feat && r_feats && scores && auc && zero_counter, "insdel_curves: null buffer");
+    MIRX_CHECK(aligned_to(q_feat, 4) && aligned_to(r_feats, 4) && aligned_to(scores, 8) && aligned_to(auc, 8) && aligned_to(zero_counter, 8),
+               "insdel_curves: misaligned buffer");
+    MIRX_HIP(launch_insdel_curves(q_feat, r_feats, n_curves, n_steps, d, scores, auc, zero_counter,
+                                  reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
 }  // extern "C"

@@ -89,8 +89,9 @@ hipError_t launch_rank_sort_build(const double *scores, int64_t ld, int64_t n, c
 hipError_t launch_rank_sort_build_ids(const int64_t *ids, int64_t n, uint64_t *keys, int32_t *pay, hipStream_t st);
 // nseg segments of n pairs, ascending by key, equal keys in their input order; in / out = keys_a, pay_a; keys_b, pay_b = scratch of
 // the same size; hist = nseg * 256 * rank_sort_tiles(n) words.  No workgroup waits for another: three launches per 8-bit digit.
+// key_bits (a multiple of 16, <= 64): keys that agree above their low key_bits bits need only those digits sorted.
 hipError_t launch_rank_sort(uint64_t *keys_a, int32_t *pay_a, uint64_t *keys_b, int32_t *pay_b, unsigned *hist, int64_t n,
-                            int nseg, hipStream_t st);
+                            int nseg, hipStream_t st, int key_bits = 64);
 // ranks 0 .. kout-1 of every query from the sorted payload: ids, fp32 reported values and / or fp64 scores ([nq, kout] each).  The
 // excluded id reads -inf; with drop_excluded its slot reads id -1 (those rows are last, see launch_rank_sort_build).
 hipError_t launch_rank_sort_write(const int32_t *pay, int64_t n, int64_t kout, const double *scores, int64_t ld,
@@ -109,6 +110,16 @@ hipError_t launch_binary_rank_metrics(const double *scores, const uint8_t *posit
                                       double level, void *workspace, double *thresholds, int64_t *tps, int64_t *fps, int64_t *out_t,
                                       double *out_auroc, double *out_aupr, double *out_fpr, int *bad, hipStream_t st);
 
+// ---- k_insdel.hip: the insertion / deletion game's step maps, blur substrate, step images and curve scores (include/mirx.h) ----
+int64_t insdel_steps_workspace_bytes(int64_t k, int64_t hw);
+hipError_t launch_insdel_steps(const float *sal, int64_t k, int64_t hw, int64_t step, void *workspace, int32_t *t, hipStream_t st);
+int64_t blur2d_blocks(int64_t planes, int h, int w);      // workgroups of the blur's launch
+hipError_t launch_blur2d_same(const float *x, int64_t planes, int h, int w, const float *kern, int klen, float *y, hipStream_t st);
+hipError_t launch_insdel_compose(const int32_t *t, int64_t n_rows, int64_t hw, const float *bank, int64_t n_bank, const int32_t *start,
+                                 const int32_t *finish, const int32_t *row, int64_t n_steps, int64_t g0, int64_t n, float *out,
+                                 hipStream_t st);
+hipError_t launch_insdel_curves(const float *q, const float *r, int64_t n_curves, int64_t n_steps, int d, double *scores, double *auc,
+                                int64_t *zero_counter, hipStream_t st);
 
 // ---- k_conv1x1_s3.hip --------------------------------------------------------------------
 hipError_t launch_conv1x1_s3(const float *x, int64_t xbs, int cin, const float *scale, const float *shift,

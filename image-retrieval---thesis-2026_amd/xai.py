@@ -180,3 +180,5 @@ from .rollout import AttentionRolloutMedSigLIP  # noqa: E402,F401
 from .siglip_gradcam import _compute_single_gradcam, compute_gradcam_saliency  # noqa: E402,F401
 # SimAtt similarity-attention saliency (explanations.py:605-661), native on DenseNet121's flattened Sequential: simatt.py
 from .simatt import SimAtt, simatt_maps, simatt_pairs  # noqa: E402,F401
+# insertion / deletion curves of one query as one device job (evaluate_saliency.py:33-91), native on CUDA float32 images: insdel.py
+from .insdel import GaussianBlur, InsDel, InsDelResult, insdel_curves  # noqa: E402,F401

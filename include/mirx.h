@@ -1045,6 +1045,47 @@ int mirx_binary_rank_metrics(const double *scores, const uint8_t *positive, int6
                              int64_t *fps, int64_t *out_t, double *out_auroc, double *out_aupr, double *out_fpr, int *bad_flag,
                              void *stream);
 
+/* ---- Insertion / deletion curves (k_insdel.hip) ---------------------------------------------------------------------------
+ * The insertion / deletion game of the reference's drivers (evaluation.py CausalMetric, evaluate_saliency.py InsDel) with every
+ * curve of one query as one device job.  A job has n_curves curves of n_steps + 1 images each; flat image g is step
+ * s = g % (n_steps + 1) of curve j = g / (n_steps + 1).
+ *
+ * mirx_insdel_steps: sal = device fp32 [k, hw] -> t = device int32 [k, hw], t[p] = rank(p) / step, where rank is the position
+ *   of p in np.flip(np.argsort(sal_k, kind="stable")): saliency descending, equal values by DESCENDING flat index, -0.0 equal to
+ *   +0.0, every NaN before +inf.  A segmented stable radix sort (k_ranksort.hip) on a 32-bit key; workspace = device, >=
+ *   mirx_insdel_steps_workspace_bytes(k, hw), 256-byte aligned.  Limits: 1 <= hw <= 2^20, 1 <= step, 1 <= k <= 65535.
+ * mirx_blur2d_same: y[n, c, h, w] = the zero-padded cross-correlation of every plane of x with kernel [klen, klen] (device fp32),
+ *   padding klen / 2 -- F.conv2d(x, gkern(klen, nsig), padding=klen // 2) without the zero off-diagonal channel blocks.  Taps are
+ *   added in (ky, kx) order in fp64 and rounded once: a pixel's bits depend on its plane alone.  The kernel need not be separable.
+ *   x and y must not overlap.  Limits: klen odd, 1 <= klen <= 63; 1 <= h, w <= 16384; 0 <= n * c; at most 2^31 - 1 workgroups
+ *   (n * c * ceil(h / 32) * ceil(w / 32)).
+ * mirx_insdel_compose: images [g0, g0 + n) of the job -> out = device fp32 [n, 3, hw]:
+ *     out[c, p] = t[row[j]][p] < s ? bank[finish[j]][c, p] : bank[start[j]][c, p]
+ *   t = device int32 [n_rows, hw], bank = device fp32 [n_bank, 3, hw], start / finish / row = device int32 [n_curves]; a bank index
+ *   of -1 is the all-zero image.  A select on the 32-bit patterns: no arithmetic, a NaN payload passes through.  16-byte loads and
+ *   stores when hw % 4 == 0 and t, bank and out are 16-byte aligned.  A chunk may span curves.  An index outside [-1, n_bank) or a
+ *   row outside [0, n_rows) gives the all-zero image (nothing is read out of bounds).  Limits: 1 <= hw <= 2^20, n_rows, n_bank,
+ *   n_curves >= 1, 1 <= n_steps <= 2^20, 0 <= g0, 0 <= n, g0 + n <= n_curves * (n_steps + 1).
+ * mirx_insdel_curves: q_feat = device fp32 [1, d], r_feats = device fp32 [n_curves * (n_steps + 1), d].  Per curve: scores =
+ *   device fp64 [n_curves, n_steps + 1], the cosine in fp64 of the fp32 rows with each norm clamped at 1e-8 (F.cosine_similarity);
+ *   negative values are counted in zero_counter (device int64 [n_curves]) and set to 0, values above 1 and NaNs are kept
+ *   (single_run's rule); auc = (sum of scores - scores[0] / 2 - scores[n_steps] / 2) / n_steps, summed in index order (device fp64
+ *   [n_curves]).  Limits: 1 <= d <= 2^20, 1 <= n_curves, 1 <= n_steps, n_curves * (n_steps + 1) <= 2^30.
+ * One stream, no host synchronisation, no floating atomic.  Outside the limits: MIRX_EINVAL with a message, nothing launched.
+ */
+#define MIRX_INSDEL_MAX_HW (1 << 20)
+#define MIRX_INSDEL_MAX_K 65535
+#define MIRX_BLUR_MAX_KLEN 63
+int64_t mirx_insdel_steps_workspace_bytes(int64_t k, int64_t hw);
+int mirx_insdel_steps(const float *sal, int64_t k, int64_t hw, int64_t step, void *workspace, int64_t workspace_bytes, int32_t *t,
+                      void *stream);
+int mirx_blur2d_same(const float *x, int64_t n, int c, int h, int w, const float *kernel, int klen, float *y, void *stream);
+int mirx_insdel_compose(const int32_t *t, int64_t n_rows, int64_t hw, const float *bank, int64_t n_bank, const int32_t *start,
+                        const int32_t *finish, const int32_t *row, int64_t n_curves, int64_t n_steps, int64_t g0, int64_t n,
+                        float *out, void *stream);
+int mirx_insdel_curves(const float *q_feat, const float *r_feats, int64_t n_curves, int64_t n_steps, int d, double *scores,
+                       double *auc, int64_t *zero_counter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
