@@ -178,6 +178,10 @@ SYMBOLS = {
     "mirx_blur2d_same": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _vp, _vp]),
     "mirx_insdel_compose": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "mirx_insdel_curves": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mirx_sbsm_compose": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _vp, _int, _i64, _i64, _vp, _vp]),
+    "mirx_sbsm_gain": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _int, _vp, _vp]),
+    "mirx_sbsm_workspace_bytes": (_i64, [_i64, _int, _int]),
+    "mirx_sbsm_accumulate": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _int, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -1535,4 +1535,64 @@ int mirx_insdel_curves(const float *q_feat, const float *r_feats, int64_t n_curv
     return MIRX_OK;
 }
 
+// ---- SBSM occlusion saliency (k_sbsm.hip) ---------------------------------------------------------------------------------------
+static const char *sbsm_grid_limits(int h, int w, int nr, int nc) {
+    if (h < 1 || w < 1 || (int64_t)h * w > MIRX_SBSM_MAX_HW) return "sbsm: needs h, w >= 1 and h * w <= 2^20";
+    if (nr < 1 || nr > MIRX_SBSM_MAX_WINDOWS || nc < 1 || nc > MIRX_SBSM_MAX_WINDOWS) return "sbsm: nr and nc must be in [1, 4096]";
+    return nullptr;
+}
+
+int mirx_sbsm_compose(const float *x, int64_t b, int c, int h, int w, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc,
+                      int64_t g0, int64_t n, float *out, void *stream) {
+    if (const char *msg = sbsm_grid_limits(h, w, nr, nc)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(c >= 1 && (int64_t)c * h * w <= (1LL << 30), "sbsm_compose: needs c >= 1 and c * h * w <= 2^30");
+    MIRX_CHECK(b >= 1 && b <= INT32_MAX, "sbsm_compose: b must be in [1, 2^31)");
+    MIRX_CHECK(g0 >= 0 && n >= 0 && n <= INT32_MAX && g0 <= (int64_t)nr * nc * b && n <= (int64_t)nr * nc * b - g0,
+               "sbsm_compose: [g0, g0 + n) must lie within the job's nr * nc * b images");
+    MIRX_CHECK(x && row_iv && col_iv && out, "sbsm_compose: null buffer");
+    MIRX_CHECK(aligned_to(x, 4) && aligned_to(row_iv, 4) && aligned_to(col_iv, 4) && aligned_to(out, 4), "sbsm_compose: misaligned buffer");
+    MIRX_HIP(launch_sbsm_compose(x, b, c, h, w, row_iv, col_iv, nc, g0, n, out, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_sbsm_gain(const float *e_q, int64_t q, const float *e_m, int64_t n_masks, int64_t b, const float *e_r_or_null, int d,
+                   double *gain, void *stream) {
+    MIRX_CHECK(d >= 1 && d <= MIRX_SBSM_MAX_D, "sbsm_gain: d must be in [1, 16384]");
+    MIRX_CHECK(q >= 1 && b >= 1 && n_masks >= 1 && q <= (1LL << 30) && b <= (1LL << 30) && n_masks <= (1LL << 30),
+               "sbsm_gain: q, b and n_masks must be in [1, 2^30]");
+    MIRX_CHECK(e_r_or_null || q == b, "sbsm_gain: self-similarity (null e_r) needs q == b");
+    const int64_t rows = e_r_or_null ? q * b : b;
+    MIRX_CHECK(rows <= (1LL << 30) && rows * n_masks <= (1LL << 30) && n_masks * b <= (1LL << 30),
+               "sbsm_gain: needs rows * n_masks <= 2^30 and n_masks * b <= 2^30");
+    MIRX_CHECK(e_q && e_m && gain, "sbsm_gain: null buffer");
+    MIRX_CHECK(aligned_to(e_q, 4) && aligned_to(e_m, 4) && aligned_to(e_r_or_null, 4) && aligned_to(gain, 8), "sbsm_gain: misaligned buffer");
+    MIRX_HIP(launch_sbsm_gain(e_q, e_m, e_r_or_null, rows, n_masks, b, d, gain, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+static const char *sbsm_accumulate_limits(int64_t rows, int nr, int w) {
+    if (nr < 1 || nr > MIRX_SBSM_MAX_WINDOWS || w < 1 || w > MIRX_SBSM_MAX_HW) return "sbsm_accumulate: needs 1 <= nr <= 4096 and 1 <= w <= 2^20";
+    if ((int64_t)nr * w > (1LL << 30)) return "sbsm_accumulate: needs nr * w <= 2^30";
+    if (rows < 1 || rows > (1LL << 30) || rows * nr * (int64_t)w > (1LL << 40)) return "sbsm_accumulate: needs rows >= 1 and rows * nr * w <= 2^40";
+    return nullptr;
+}
+
+int64_t mirx_sbsm_workspace_bytes(int64_t rows, int nr, int w) {
+    if (const char *msg = sbsm_accumulate_limits(rows, nr, w)) return fail(MIRX_EINVAL, msg);
+    return sbsm_workspace_bytes(rows, nr, w);
+}
+
+int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc, int h, int w,
+                         void *workspace, int64_t workspace_bytes, float *sal, void *stream) {
+    if (const char *msg = sbsm_grid_limits(h, w, nr, nc)) return fail(MIRX_EINVAL, msg);
+    if (const char *msg = sbsm_accumulate_limits(rows, nr, w)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(rows * nr * (int64_t)nc <= (1LL << 30), "sbsm_accumulate: needs rows * nr * nc <= 2^30");
+    MIRX_CHECK(gain && row_iv && col_iv && workspace && sal, "sbsm_accumulate: null buffer");
+    MIRX_CHECK(aligned_to(gain, 8) && aligned_to(row_iv, 4) && aligned_to(col_iv, 4) && aligned_to(workspace, 8) && aligned_to(sal, 4),
+               "sbsm_accumulate: misaligned buffer (workspace: 8 bytes)");
+    MIRX_CHECK(workspace_bytes >= sbsm_workspace_bytes(rows, nr, w), "sbsm_accumulate: workspace smaller than mirx_sbsm_workspace_bytes()");
+    MIRX_HIP(launch_sbsm_accumulate(gain, rows, row_iv, nr, col_iv, nc, h, w, workspace, sal, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
 }  // extern "C"

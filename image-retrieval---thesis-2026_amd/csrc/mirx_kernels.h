@@ -121,6 +121,15 @@ hipError_t launch_insdel_compose(const int32_t *t, int64_t n_rows, int64_t hw, c
 hipError_t launch_insdel_curves(const float *q, const float *r, int64_t n_curves, int64_t n_steps, int d, double *scores, double *auc,
                                 int64_t *zero_counter, hipStream_t st);
 
+// ---- k_sbsm.hip: SBSM occlusion saliency on interval-described window sets: masked images, gains, the saliency map (include/mirx.h) ----
+hipError_t launch_sbsm_compose(const float *x, int64_t b, int c, int h, int w, const int32_t *row_iv, const int32_t *col_iv, int nc,
+                               int64_t g0, int64_t n, float *out, hipStream_t st);
+hipError_t launch_sbsm_gain(const float *e_q, const float *e_m, const float *e_r, int64_t rows, int64_t n_masks, int64_t b, int d,
+                            double *gain, hipStream_t st);
+int64_t sbsm_workspace_bytes(int64_t rows, int nr, int w);
+hipError_t launch_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc, int h,
+                                  int w, void *workspace, float *sal, hipStream_t st);
+
 // ---- k_conv1x1_s3.hip --------------------------------------------------------------------
 hipError_t launch_conv1x1_s3(const float *x, int64_t xbs, int cin, const float *scale, const float *shift,
                              const uint16_t *w3, const float *bias, int64_t n, int hw, int cout, int relu_out,

@@ -105,45 +105,91 @@ def sliding_window_masks(input_size, window_size, stride):
 
 class SBSMBatch:
     """Same constructor / generate_masks / load_masks / call as explanations.py:15-152 (`SBSMBatch(model,
-    input_size, gpu_batch)`, `explainer(x_q, x)` or `explainer(x)` for self-similarity) -> saliency [B, H, W].
+    input_size, gpu_batch)`, `explainer(x_q, x)` or `explainer(x)` for self-similarity) -> saliency [B, H, W]
+    ([Q * B, H, W] for pairs).
 
-    MI355X design: the reference materialises all B * N masked images ([B*N, C, H, W], 0.6 MB each at 224x224)
-    and then an [H, W, B, N] tensor `K` that it sums over N.  Here the masked images exist only one
-    `gpu_batch` chunk at a time (built on the device from the uint8 masks), and the saliency is the matrix
-    product  sal[b] = (1 - masks)^T [HW x N] . gain[b] [N] / count  -- K never exists.  Distances are
+    MI355X design: the masks of a sliding-window set are the outer product of row and column
+    intervals, so the explainer keeps two small int32 arrays instead of the reference's uint8 [N, 1, H, W]
+    tensor.  On 4-d CUDA float32 images and 2-d CUDA float32 embeddings the call is native (sbsm.py,
+    csrc/k_sbsm.hip): masked images are composed `gpu_batch` at a time from the n-major list -- the reference's
+    chunks exactly -- the gains are fp64 distances of the fp32 embeddings and the map is the fp64 sum over the
+    covering windows.  Every other input (the CPU, other dtypes, a mask file that is not a window grid) takes
+    the torch path: masked images `gpu_batch // B` whole masks at a time, the saliency as the matrix product
+    sal[b] = (1 - masks)^T [HW x N] . gain[b] [N] / count.  `last_native` says which one ran.  Distances are
     Euclidean on the embedder's outputs like `torch.cdist` / `torch.norm` there."""
 
     def __init__(self, model, input_size, gpu_batch=100):
         self.model = model
         self.input_size = tuple(input_size)
         self.gpu_batch = int(gpu_batch)
-        self.masks = None
+        self.last_native = False
+        self._clear()
 
-    def _set_masks(self, masks, device=None):
-        dev = device if device is not None else next(self.model.parameters()).device
-        self.masks = torch.from_numpy(np.ascontiguousarray(masks)).to(dev)
-        self.N = self.masks.shape[0]
-        inv = (1 - self.masks.reshape(self.N, -1)).float()                  # [N, HW]: 1 inside the window
-        self._inv_t = inv.t().contiguous()                                  # [HW, N]
-        self._count = inv.sum(dim=0)                                        # windows covering each pixel
+    def _clear(self):
+        self._intervals = None          # (row_iv, col_iv) numpy int32 when the masks are a window grid
+        self._masks_np = None           # the mask array itself when they are not
+        self._on = {}                   # device -> (row_iv, col_iv) tensors
+        self._masks_t = self._inv_t = self._count = None        # the torch path's tensors, built on first use
+
+    def _device(self):
+        p = next(iter(self.model.parameters()), None) if hasattr(self.model, "parameters") else None
+        return p.device if p is not None else torch.device("cpu")
+
+    def _set_masks(self, masks):
+        self._clear()
+        self._masks_np = np.ascontiguousarray(masks)
+        self.N = self._masks_np.shape[0]
+
+    def _set_intervals(self, row_iv, col_iv):
+        from . import sbsm
+        sbsm.check_intervals(row_iv, col_iv, self.input_size)
+        self._clear()
+        self._intervals = (np.ascontiguousarray(row_iv), np.ascontiguousarray(col_iv))
+        self.N = row_iv.shape[0] * col_iv.shape[0]
+
+    def _masks_on(self, device):
+        """The uint8 [N, 1, H, W] masks as a tensor on `device` (built once; the native path never asks)."""
+        if self._masks_t is None or self._masks_t.device != torch.device(device):
+            from . import sbsm
+            m = self._masks_np if self._masks_np is not None else sbsm.masks_from_intervals(*self._intervals, self.input_size)
+            self._masks_t = torch.from_numpy(m).to(device)
+            self._inv_t = self._count = None
+        return self._masks_t
+
+    @property
+    def masks(self):
+        if self._intervals is None and self._masks_np is None:
+            return None
+        return self._masks_t if self._masks_t is not None else self._masks_on(self._device())
 
     def generate_masks(self, window_size, stride, savepath="masks.npy"):
-        masks = sliding_window_masks(self.input_size, window_size, stride)
+        from . import sbsm
+        row_iv, col_iv = sbsm.window_intervals(self.input_size, window_size, stride)
         if savepath:
-            np.save(savepath, masks)
-        self._set_masks(masks)
+            np.save(savepath, sliding_window_masks(self.input_size, window_size, stride))
+        if max(row_iv.shape[0], col_iv.shape[0]) <= sbsm.SBSM_MAX_WINDOWS:
+            self._set_intervals(row_iv, col_iv)
+        else:
+            self._set_masks(sliding_window_masks(self.input_size, window_size, stride))
         self.window_size, self.stride = window_size, stride
 
     def load_masks(self, filepath):
-        self._set_masks(np.load(filepath))
+        from . import sbsm
+        masks = np.load(filepath)
+        grid = sbsm.grid_of_masks(masks) if tuple(masks.shape[-2:]) == self.input_size else None
+        if grid is not None:
+            self._set_intervals(*grid)
+        else:
+            self._set_masks(masks)
 
     def _embed_masked(self, x):
         """Embeddings of mask n applied to image b, n-major like the reference's stack: row n * B + b."""
         b, c, h, w = x.shape
         out = []
+        masks = self._masks_on(x.device)
         per = max(1, self.gpu_batch // b)                                   # masks per chunk
         for n0 in range(0, self.N, per):
-            m = self.masks[n0:n0 + per].to(x.dtype)                         # [n, 1, H, W]
+            m = masks[n0:n0 + per].to(x.dtype)                              # [n, 1, H, W]
             chunk = (m[:, None] * x[None]).reshape(-1, c, h, w)             # [n * B, C, H, W]
             out.append(CausalMetric._embed(self.model, chunk))
         return torch.cat(out)
@@ -151,24 +197,80 @@ class SBSMBatch:
     def __call__(self, x_q, x=None):
         return self.forward(x_q, x)
 
+    def _native_inputs(self, x_q, x):
+        from . import sbsm
+        return bool(self._intervals is not None and all(
+            torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.device == x.device
+            and tuple(t.shape[2:]) == self.input_size and t.shape[0] >= 1 and t.shape[1] >= 1 for t in (x_q, x))
+            and x[0, 0].numel() <= sbsm.SBSM_MAX_HW and x[0].numel() <= 1 << 30)                 # the kernels' limits
+
+    @staticmethod
+    def _native_rows(e):
+        from . import sbsm
+        return bool(torch.is_tensor(e) and e.is_cuda and e.dtype == torch.float32 and e.dim() == 2 and e.shape[0] >= 1
+                    and 1 <= e.shape[1] <= sbsm.SBSM_MAX_D)
+
     def forward(self, x_q, x=None):
         self_sim = x is None
         if self_sim:
             x = x_q
-        b = x.shape[0]
-        h, w = self.input_size
         with torch.no_grad():
             e_q = CausalMetric._embed(self.model, x_q)
-            e_m = self._embed_masked(x).reshape(self.N, b, -1)              # [N, B, D]
-            if self_sim:
-                gain = torch.linalg.vector_norm(e_q[None] - e_m, dim=2).t()                 # [B, N]
-            else:
-                e_r = CausalMetric._embed(self.model, x)
-                o_dist = torch.cdist(e_q, e_r).reshape(-1, 1)                               # [Q * B, 1]
-                m_dist = torch.cdist(e_q, e_m.reshape(self.N * b, -1))                      # [Q, N * B]
-                m_dist = m_dist.reshape(-1, self.N, b).permute(0, 2, 1).reshape(-1, self.N)
-                gain = (m_dist - o_dist).clamp(min=0)                                       # [Q * B, N]
-            sal = (gain.float() @ self._inv_t.t()) / self._count                            # [., HW]
+            if self._native_inputs(x_q, x) and self._native_rows(e_q):
+                sal = self._forward_native(x, e_q, self_sim)
+                if sal is not None:
+                    self.last_native = True
+                    return sal
+            self.last_native = False
+            return self._forward_torch(x, e_q, self_sim)
+
+    def _forward_native(self, x, e_q, self_sim):
+        """-> the saliency, or None when the model's outputs are not 2-d CUDA float32 rows (the torch path then serves)."""
+        from . import sbsm
+        b = x.shape[0]
+        dev = x.device
+        e_r = None
+        if not self_sim:
+            e_r = CausalMetric._embed(self.model, x)
+            if not self._native_rows(e_r):
+                return None
+        if dev not in self._on:
+            self._on[dev] = tuple(torch.from_numpy(iv).to(dev) for iv in self._intervals)
+        row_iv, col_iv = self._on[dev]
+        x = x.contiguous()
+        total = self.N * b
+        step = max(1, self.gpu_batch)
+        buf = torch.empty((min(step, total),) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
+        e_m = None
+        for g0 in range(0, total, step):                                    # the reference's chunks [i, i + gpu_batch)
+            n = min(step, total - g0)
+            f = CausalMetric._embed(self.model, sbsm.sbsm_compose(x, row_iv, col_iv, g0, n, out=buf[:n]))
+            if not self._native_rows(f) or f.shape[0] != n:
+                return None
+            if e_m is None:
+                e_m = torch.empty((total, f.shape[1]), dtype=torch.float32, device=f.device)
+            e_m[g0:g0 + n] = f
+        e_q = e_q.contiguous()
+        gain = sbsm.sbsm_gain(e_q, e_m, None if self_sim else e_r.contiguous())
+        return sbsm.sbsm_accumulate(gain, row_iv.to(gain.device), col_iv.to(gain.device), self.input_size)
+
+    def _forward_torch(self, x, e_q, self_sim):
+        b = x.shape[0]
+        h, w = self.input_size
+        e_m = self._embed_masked(x).reshape(self.N, b, -1)                  # [N, B, D]
+        if self._inv_t is None:
+            inv = (1 - self._masks_t.reshape(self.N, -1)).float()           # [N, HW]: 1 inside the window
+            self._inv_t = inv.t().contiguous()                              # [HW, N]
+            self._count = inv.sum(dim=0)                                    # windows covering each pixel
+        if self_sim:
+            gain = torch.linalg.vector_norm(e_q[None] - e_m, dim=2).t()                 # [B, N]
+        else:
+            e_r = CausalMetric._embed(self.model, x)
+            o_dist = torch.cdist(e_q, e_r).reshape(-1, 1)                               # [Q * B, 1]
+            m_dist = torch.cdist(e_q, e_m.reshape(self.N * b, -1))                      # [Q, N * B]
+            m_dist = m_dist.reshape(-1, self.N, b).permute(0, 2, 1).reshape(-1, self.N)
+            gain = (m_dist - o_dist).clamp(min=0)                                       # [Q * B, N]
+        sal = (gain.float() @ self._inv_t.t()) / self._count                            # [., HW]
         return sal.reshape(-1, h, w)
 
 
@@ -182,3 +284,5 @@ from .siglip_gradcam import _compute_single_gradcam, compute_gradcam_saliency  #
 from .simatt import SimAtt, simatt_maps, simatt_pairs  # noqa: E402,F401
 # insertion / deletion curves of one query as one device job (evaluate_saliency.py:33-91), native on CUDA float32 images: insdel.py
 from .insdel import GaussianBlur, InsDel, InsDelResult, insdel_curves  # noqa: E402,F401
+# SBSM occlusion saliency on interval-described window sets (explanations.py:15-152), native on CUDA float32 images: sbsm.py
+from .sbsm import grid_of_masks, sbsm_accumulate, sbsm_compose, sbsm_gain, window_intervals  # noqa: E402,F401

@@ -1086,6 +1086,48 @@ int mirx_insdel_compose(const int32_t *t, int64_t n_rows, int64_t hw, const floa
 int mirx_insdel_curves(const float *q_feat, const float *r_feats, int64_t n_curves, int64_t n_steps, int d, double *scores,
                        double *auc, int64_t *zero_counter, void *stream);
 
+/* ---- SBSM occlusion saliency without materialised masks (k_sbsm.hip) ---------------------------------------------------------
+ * The sliding-window occlusion saliency of the reference's drivers (explanations.py SBSMBatch, `--explainer sbsm`).
+ * A window set is two device int32 arrays of clipped half-open intervals, row_iv [nr, 2] and col_iv [nc, 2]: mask n = i * nc + j
+ * zeroes the pixels row_iv[i] x col_iv[j] and keeps the rest, N = nr * nc masks.  A job applies every mask to each of b images;
+ * its flat image g = n * b + k is mask n on image k (the reference's stack order).  The interval arrays stay on the device and
+ * the entry points never read them: an interval is expected inside the image and non-empty (mirx.sbsm.check_intervals verifies
+ * that on the host), and the kernels only compare coordinates against them, so any content stays in bounds.
+ *
+ * mirx_sbsm_compose: x = device fp32 [b, c, h, w] -> out = device fp32 [n, c, h, w], images [g0, g0 + n) of the job.  Every value
+ *   is the IEEE product x * (inside ? 0.0f : 1.0f): the bits of torch's mask.float() * x, including -0.0 and the NaN of inf * 0.
+ *   16-byte loads and stores when c * h * w % 4 == 0 and x and out are 16-byte aligned, single floats otherwise (h * w odd).
+ *   x and out must not overlap.  n = 0 launches nothing.  Limits: 1 <= h * w <= 2^20, c * h * w <= 2^30, 1 <= b, 1 <= nr, nc <=
+ *   4096, 0 <= g0, 0 <= n < 2^31, g0 + n <= nr * nc * b.
+ * mirx_sbsm_gain: e_q = device fp32 [q, d], e_m = device fp32 [n_masks * b, d] (row n * b + k), e_r = device fp32 [b, d] or null
+ *   -> gain = device fp64 [rows, n_masks].
+ *     e_r null (self-similarity, needs q == b; rows = b):   gain[k, n] = |e_q[k] - e_m[n * b + k]|
+ *     otherwise (pairs; rows = q * b):          gain[p * b + k, n] = max(|e_q[p] - e_m[n * b + k]| - |e_q[p] - e_r[k]|, 0)
+ *   |.| is the Euclidean norm; differences, squares, sums and the root are fp64 (one wave per value: lane-strided fma, then the
+ *   butterfly of the other kernels).  The clamp keeps a NaN, like torch's clamp(min=0).  Limits: 1 <= d <= 16384, 1 <= q, b,
+ *   n_masks, rows * n_masks <= 2^30, n_masks * b <= 2^30.
+ * mirx_sbsm_accumulate: gain = device fp64 [rows, nr * nc] -> sal = device fp32 [rows, h, w]:
+ *     sal[r, y, x] = fp32((sum over i with y in row_iv[i] of sum over j with x in col_iv[j] of gain[r, i * nc + j]) / (cr[y] * cc[x]))
+ *   cr[y] / cc[x] = the number of row / column intervals that hold y / x: the weighted_avg of the reference.  A pixel no window
+ *   covers is 0 / 0 = NaN, as there.  fp64 sums in a fixed order: per (r, i) the columns j ascending into the workspace [rows,
+ *   nr, w], then the rows i ascending; one division, one rounding.  A gain is added where its window covers and not touched where
+ *   it does not (the reference multiplies by 0 there, which spreads a non-finite gain over the whole map).  workspace = device,
+ *   >= mirx_sbsm_workspace_bytes(rows, nr, w), 8-byte aligned.  Limits: 1 <= h * w <= 2^20, 1 <= nr, nc <= 4096, 1 <= rows,
+ *   rows * nr * nc <= 2^30, nr * w <= 2^30, rows * nr * w <= 2^40.
+ * One stream, no host synchronisation, no atomic: repeated calls are bit-identical.  Outside the limits: MIRX_EINVAL with a
+ * message, nothing launched.
+ */
+#define MIRX_SBSM_MAX_HW (1 << 20)
+#define MIRX_SBSM_MAX_WINDOWS 4096 /* nr and nc, each */
+#define MIRX_SBSM_MAX_D 16384
+int mirx_sbsm_compose(const float *x, int64_t b, int c, int h, int w, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc,
+                      int64_t g0, int64_t n, float *out, void *stream);
+int mirx_sbsm_gain(const float *e_q, int64_t q, const float *e_m, int64_t n_masks, int64_t b, const float *e_r_or_null, int d,
+                   double *gain, void *stream);
+int64_t mirx_sbsm_workspace_bytes(int64_t rows, int nr, int w);
+int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc, int h, int w,
+                         void *workspace, int64_t workspace_bytes, float *sal, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
