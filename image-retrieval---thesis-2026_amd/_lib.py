@@ -33,6 +33,14 @@ ANOMALY_BAD_SCORE = 1              # bits of the anomaly calls' bad_flag
 ANOMALY_BAD_NORM = 2
 ANOMALY_BAD_ONE_CLASS = 4
 ANOMALY_BAD_EMPTY_CLASS = 8
+RESAMPLE_MAX_SIDE = 8192           # the caps of mirx_resample_batch (include/mirx.h)
+RESAMPLE_MAX_TAPS = 65
+RESAMPLE_MAX_OUT = 1024
+RESAMPLE_MAX_BATCH = 65536
+RESAMPLE_MAX_LDS = 65536
+RESAMPLE_TILE_W, RESAMPLE_TILE_H = 32, 16
+RESAMPLE_DESC_WORDS = 8
+RESAMPLE_OUT_U8, RESAMPLE_OUT_F32 = 0, 1
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
@@ -182,6 +190,9 @@ SYMBOLS = {
     "mirx_sbsm_gain": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _int, _vp, _vp]),
     "mirx_sbsm_workspace_bytes": (_i64, [_i64, _int, _int]),
     "mirx_sbsm_accumulate": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _int, _vp, _i64, _vp, _vp]),
+    "mirx_resample_taps": (_int, [_int, _int]),
+    "mirx_resample_plan": (_int, [_int, _int, _int, _int, _vp, _i64]),
+    "mirx_resample_batch": (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

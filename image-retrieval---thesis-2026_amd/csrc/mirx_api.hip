@@ -1595,4 +1595,45 @@ int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv
     return MIRX_OK;
 }
 
+// ---- batched Resize + CenterCrop (k_resample.hip) -------------------------------------------------------------------------------
+static const char *resample_axis_limits(int in_size, int out_size) {
+    if (in_size < 1 || in_size > MIRX_RESAMPLE_MAX_SIDE) return "resample: source side outside [1, MIRX_RESAMPLE_MAX_SIDE = 8192]";
+    if (out_size < 1 || out_size > MIRX_RESAMPLE_MAX_RESIZED) return "resample: resized side outside [1, 2^24]";
+    if (resample_taps(in_size, out_size) > MIRX_RESAMPLE_MAX_TAPS) return "resample: tap count over the cap (MIRX_RESAMPLE_MAX_TAPS = 65: scale > 32)";
+    return nullptr;
+}
+
+int mirx_resample_taps(int in_size, int out_size) {
+    if (const char *msg = resample_axis_limits(in_size, out_size)) return fail(MIRX_EINVAL, msg);
+    return resample_taps(in_size, out_size);
+}
+
+int mirx_resample_plan(int in_size, int out_size, int first, int n, int32_t *table, int64_t table_words) {
+    if (const char *msg = resample_axis_limits(in_size, out_size)) return fail(MIRX_EINVAL, msg);
+    MIRX_CHECK(n >= 1 && n <= MIRX_RESAMPLE_MAX_OUT && first >= 0 && first <= out_size - n,
+               "resample_plan: the window [first, first + n) must lie inside the resized axis, n in [1, 1024]");
+    MIRX_CHECK(table && aligned_to(table, 4), "resample_plan: null or misaligned table");
+    MIRX_CHECK(table_words >= 4 + 2 * (int64_t)n + (int64_t)n * resample_taps(in_size, out_size),
+               "resample_plan: table smaller than 4 + 2 n + n * mirx_resample_taps()");
+    resample_plan(in_size, out_size, first, n, table);
+    return MIRX_OK;
+}
+
+int mirx_resample_batch(const void *blob_host, const void *blob_dev, int64_t blob_bytes, int64_t b, int s, int out_kind,
+                        const float *mean3, const float *std3, void *out, void *stream) {
+    MIRX_CHECK(b >= 1 && b <= MIRX_RESAMPLE_MAX_BATCH, "resample: b must be in [1, 65536]");
+    MIRX_CHECK(s >= 1 && s <= MIRX_RESAMPLE_MAX_OUT, "resample: s must be in [1, 1024]");
+    MIRX_CHECK(out_kind == MIRX_RESAMPLE_OUT_U8 || out_kind == MIRX_RESAMPLE_OUT_F32, "resample: unknown output kind");
+    MIRX_CHECK(blob_bytes >= 1 && blob_bytes <= MIRX_RESAMPLE_MAX_BYTES, "resample: buffer size outside [1, 2^40]");
+    MIRX_CHECK(blob_host && blob_dev && out, "resample: null buffer");
+    MIRX_CHECK(out_kind == MIRX_RESAMPLE_OUT_U8 || (mean3 && std3), "resample: the fp32 form needs mean and std");
+    const size_t elem = out_kind == MIRX_RESAMPLE_OUT_F32 ? 4 : 1;
+    MIRX_CHECK(aligned_to(blob_host, 8) && aligned_to(blob_dev, 16) && aligned_to(out, (s & 3) ? elem : 4 * elem),
+               "resample: misaligned buffer (device buffer: 16 bytes; output: 4 elements when s % 4 == 0)");
+    int64_t lds = 0;
+    if (const char *msg = resample_check(blob_host, blob_bytes, b, s, &lds)) return fail(MIRX_EINVAL, msg);
+    MIRX_HIP(launch_resample(blob_dev, b, s, out_kind == MIRX_RESAMPLE_OUT_F32, mean3, std3, out, lds, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
 }  // extern "C"

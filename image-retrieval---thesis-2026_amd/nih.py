@@ -188,13 +188,17 @@ def encode_npy_paths(model, transform, image_paths, device, batch_size, progress
     rows = []
     for s in range(0, len(image_paths), batch_size):
         chunk = image_paths[s:s + batch_size]
-        meta, tensors = [], []
+        meta, images = [], []
         for p in chunk:
             names, hot = parse_nih_labels_from_path(p)
-            tensors.append(transform(load_npy_as_pil(p)))
+            images.append(load_npy_as_pil(p))
             meta.append({"image_path": p, "image_name": Path(p).name, "label_names": names, "multi_hot": hot})
+        if hasattr(transform, "batch"):                      # default_transform: one device-side resize per chunk, the same floats
+            x = transform.batch(images, device)
+        else:
+            x = torch.stack([transform(i) for i in images]).to(device, non_blocking=True)
         with torch.no_grad():
-            emb = model(torch.stack(tensors).to(device, non_blocking=True))["embedding"].detach().cpu().numpy()
+            emb = model(x)["embedding"].detach().cpu().numpy()
         for m, e in zip(meta, emb):
             m["embedding"] = e.astype(np.float32)
             rows.append(m)

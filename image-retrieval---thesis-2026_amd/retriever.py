@@ -260,7 +260,10 @@ def default_transform(img_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize
     # and no float pass over the image on the host
     tf.pixels = pixels
     tf.mean, tf.std = tuple(float(v) for v in mean.ravel()), tuple(float(v) for v in std.ravel())
-    return tf
+    # tf.batch_pixels(images, device) / tf.batch(images, device): the same two results for a list of images, resized on the
+    # device in one launch and bit-equal to the above; tf.last_preprocess counts the images per path (mirx.preprocess)
+    from .preprocess import attach
+    return attach(tf, img_size, resize)
 
 
 class MilvusRetriever:
@@ -295,8 +298,18 @@ class MilvusRetriever:
         if px is not None and getattr(m, "accepts_uint8", False) and self._device().type == "cuda" and not m.training:
             mean, std = getattr(m, "input_mean", None), getattr(m, "input_std", None)
             if mean is not None and tuple(float(v) for v in mean) == tf.mean and tuple(float(v) for v in std) == tf.std:
+                if hasattr(tf, "batch_pixels"):              # resized on the device (mirx.preprocess): the same bytes
+                    return tf.batch_pixels([img], self._device())
                 return torch.from_numpy(px(img)).unsqueeze(0)
+        if hasattr(tf, "batch"):
+            return tf.batch([img], self._device())
         return tf(img).unsqueeze(0)
+
+    @property
+    def last_preprocess(self):
+        """{"device": n, "host": m}: how many images of the last query batch were resized on the device / on the host (None for
+        a transform without the batch attributes)."""
+        return getattr(self.transform, "last_preprocess", None)
 
     def embed(self, images):
         """Batched F.normalize(model(x)) for a [B,3,H,W] tensor (milvus_retrieval.py:60-63)."""
@@ -305,6 +318,18 @@ class MilvusRetriever:
             if isinstance(out, dict):
                 out = out["embedding"]
             return F.normalize(out, p=2, dim=1)
+
+    def _embed_rows(self, images):
+        """embed() with every row normalised as the [1, D] tensor a single search() normalises: torch reduces a [B, D] and a
+        [1, D] tensor in different orders, so F.normalize of a batch can put a row's norm one ulp from the single query's and
+        with it every distance of that query.  One small reduction per row, then F.normalize's own clamp and division: each
+        row equals embed(images[i:i + 1]) bit for bit (the model's rows do not depend on the batch)."""
+        with torch.no_grad():
+            out = self.model(images.to(self._device()))
+            if isinstance(out, dict):
+                out = out["embedding"]
+            norms = torch.cat([out[i:i + 1].norm(2, 1, True) for i in range(out.shape[0])])
+            return out / norms.clamp_min(1e-12).expand_as(out)
 
     def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE"):
         """-> (results, query_embedding).  results: best-first dicts {id, image_path, label,
@@ -334,12 +359,15 @@ class MilvusRetriever:
                 "distance": d, "similarity": sim}
 
     def batch_search(self, query_image_paths, top_k=10, search_params=None):
-        """One batched embed + one batched search (the reference loops search(); results equal)."""
+        """One batched embed + one batched search (the reference loops search(); results equal, to the bit: _embed_rows)."""
         if len(query_image_paths) == 0:
             return []
         from PIL import Image
         imgs = [Image.open(p).convert("RGB") if isinstance(p, str) else p for p in query_image_paths]
-        emb = self.embed(torch.stack([self.transform(i) for i in imgs]))
+        if hasattr(self.transform, "batch"):                 # one device-side resize of the whole batch: the same floats
+            emb = self._embed_rows(self.transform.batch(imgs, self._device()))
+        else:
+            emb = self._embed_rows(torch.stack([self.transform(i) for i in imgs]))
         if self.collection is None:
             self.load_collection()
         all_hits = self.collection.search(data=emb, limit=top_k, output_fields=["image_path", "label"])

@@ -1128,6 +1128,55 @@ int64_t mirx_sbsm_workspace_bytes(int64_t rows, int nr, int w);
 int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc, int h, int w,
                          void *workspace, int64_t workspace_bytes, float *sal, void *stream);
 
+/* ---- Batched Resize + CenterCrop of 8-bit images (k_resample.hip) ---------------------------------------------------------------
+ * The transforms.Resize(int) + CenterCrop of the reference's inference transforms on PIL images, as they come out of Pillow's
+ * BILINEAR for 8-bit images, to the bit: milvus/milvus_retrieval.py:176-198, test.py:1286-1332,
+ * ingest_embeddings.py:112-122, nih_multilabel_retrieval.py:64-66 (mirx.retriever.default_transform restates them on the host;
+ * mirx.preprocess drives these entry points).  Tested for sources that are "RGB" (3 interleaved channels) or "L" (1 channel,
+ * written to all three planes); nothing is claimed for other modes.
+ *
+ * One axis, resized from in_size to out_size pixels: scale = in_size / out_size, fs = max(scale, 1); output i has the taps
+ * [xmin, xmax) = [max(0, (int)(c - fs + 0.5)), min(in_size, (int)(c + fs + 0.5))) around c = (i + 0.5) * scale, weights
+ * max(0, 1 - |(x - c + 0.5) * (1 / fs)|) summed in tap order and divided by the sum (double), coefficients (int)(w * 2^22 + 0.5);
+ * out = clip((2^21 + sum pixel * coeff) >> 22, 0, 255) in 32-bit integers.  Horizontal pass first into 8 bits, then vertical.
+ *
+ * mirx_resample_taps: the coefficient slots per output of such an axis, (int)ceil(fs) * 2 + 1.  Host only, no HIP call.
+ * mirx_resample_plan: fills `table` (HOST int32 [4 + 2 n + n * taps]) for the outputs [first, first + n) of the axis, the crop
+ *   window: {taps, n, in_size, 0}, bounds [n][2] = (first tap, tap count), coefficients [n][taps] (zero past the count).  Host
+ *   only, no HIP call; double arithmetic in the order above, compiled without contraction.
+ * mirx_resample_batch: one launch for b images of any mix of sizes -> out = device [b, 3, s, s], uint8 (MIRX_RESAMPLE_OUT_U8:
+ *   the pixels a model that normalises 8-bit input itself takes) or fp32 (MIRX_RESAMPLE_OUT_F32: (u / 255 - mean[c]) / std[c],
+ *   IEEE fp32, correctly rounded division; mean3 / std3 = HOST float [3], unused for uint8).  Everything the kernel reads is one
+ *   byte buffer, given twice: blob_host (what the caller filled; read here, on the host) and blob_dev (its device copy, which the
+ *   caller has enqueued on `stream` before this call; 16-byte aligned).  Layout: b descriptors of MIRX_RESAMPLE_DESC_WORDS int64
+ *   at offset 0: {source offset, w, h, row pitch in bytes, channels (1 or 3, interleaved), x table offset, y table offset, 0};
+ *   offsets are bytes from the start of the buffer, multiples of 16, behind the descriptors.  Images of one size may share tables.
+ *   Checked BEFORE any HIP call, from blob_host: every image inside the buffer, every table inside the buffer and planned for
+ *   this s and this image's side, every tap range inside [0, w) or [0, h), every coefficient >= 0 and every run's sum <= 2^23
+ *   (so the 32-bit sums cannot overflow), the LDS of the largest tile (x coefficients + the source rows a 16-row tile taps, 32
+ *   columns, 8 bits) <= MIRX_RESAMPLE_MAX_LDS.  Output alignment: 4 elements when s % 4 == 0 (vector stores), 1 otherwise.
+ *   out must not overlap blob_dev.
+ * Caps: source side <= MIRX_RESAMPLE_MAX_SIDE, taps <= MIRX_RESAMPLE_MAX_TAPS (scale <= 32: an 8192-pixel side at resize 256), s
+ * <= MIRX_RESAMPLE_MAX_OUT, b <= MIRX_RESAMPLE_MAX_BATCH.  Anything over a cap, or failing a check: MIRX_EINVAL with a message,
+ * nothing launched.  One stream, no host synchronisation, no atomic.
+ */
+#define MIRX_RESAMPLE_MAX_SIDE 8192
+#define MIRX_RESAMPLE_MAX_TAPS 65
+#define MIRX_RESAMPLE_MAX_OUT 1024
+#define MIRX_RESAMPLE_MAX_BATCH 65536
+#define MIRX_RESAMPLE_MAX_RESIZED (1 << 24)
+#define MIRX_RESAMPLE_MAX_BYTES (1LL << 40)
+#define MIRX_RESAMPLE_MAX_LDS 65536
+#define MIRX_RESAMPLE_TILE_W 32
+#define MIRX_RESAMPLE_TILE_H 16
+#define MIRX_RESAMPLE_DESC_WORDS 8
+#define MIRX_RESAMPLE_OUT_U8 0
+#define MIRX_RESAMPLE_OUT_F32 1
+int mirx_resample_taps(int in_size, int out_size);
+int mirx_resample_plan(int in_size, int out_size, int first, int n, int32_t *table, int64_t table_words);
+int mirx_resample_batch(const void *blob_host, const void *blob_dev, int64_t blob_bytes, int64_t b, int s, int out_kind,
+                        const float *mean3, const float *std3, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
