@@ -13,13 +13,32 @@ def steps_ref(sal, step):
     """sal [K, hw] float32 -> int32 [K, hw]: rank under the stable rule // step."""
     sal = np.asarray(sal, dtype=np.float32)
     k, hw = sal.shape
-    t = np.empty((k, hw), dtype=np.int64)
-    for i in range(k):
-        order = np.flip(np.argsort(sal[i], kind="stable"))
-        rank = np.empty(hw, dtype=np.int64)
-        rank[order] = np.arange(hw)
-        t[i] = rank // int(step)
-    return t.astype(np.int32)
+    order = np.flip(np.argsort(sal, axis=1, kind="stable"), axis=1)      # row by row, as np.flip(np.argsort(sal[i], kind="stable"))
+    rank = np.empty((k, hw), dtype=np.int64)
+    np.put_along_axis(rank, order, np.broadcast_to(np.arange(hw), (k, hw)), axis=1)
+    return (rank // int(step)).astype(np.int32)
+
+
+def saliency_maps(k, hw, seed):
+    """name -> [k, hw] float32 tensor, different rows: random with a few ties, half tied at 0 (with a -0.0), a NaN and infinities,
+    all equal."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    a = torch.rand(k, hw, generator=g)
+    if hw > 2:
+        a[:, hw // 3] = a[:, 0]
+    out["random"] = a
+    b = torch.rand(k, hw, generator=g)
+    b[:, ::2] = 0.0
+    b[:, (hw // 2) // 2 * 2] = -0.0
+    out["half_zero"] = b
+    c = torch.randn(k, hw, generator=g)
+    c[:, hw // 2] = float("nan")
+    if hw > 4:
+        c[:, 1], c[:, 2], c[:, hw - 1] = float("inf"), -float("inf"), -float("nan")
+    out["nan"] = c
+    out["all_equal"] = torch.full((k, hw), 0.5) * torch.arange(1, k + 1)[:, None]
+    return out
 
 
 def tie_free(sal):
@@ -48,9 +67,39 @@ def compose_ref(t, bank, start, finish, row, n_steps, g0, n):
 def blur_f64(x, kernel2d):
     """Zero-padded cross-correlation of every plane of x [n, c, h, w] with kernel2d, in float64 (CPU)."""
     x64 = x.detach().cpu().double()
-    c = x64.shape[1]
     k = kernel2d.detach().cpu().double()
-    return F.conv2d(x64, k.expand(c, 1, *k.shape).contiguous(), padding=k.shape[0] // 2, groups=c)
+    klen, pad = k.shape[0], k.shape[0] // 2
+    h, w = x64.shape[2:]
+    xp = F.pad(x64, (pad, pad, pad, pad))
+    acc = torch.zeros_like(x64)
+    for ky in range(klen):                                  # the definition, tap by tap in (ky, kx) order: klen^2 whole-image
+        for kx in range(klen):                              # updates, many times faster on a CPU than a float64 F.conv2d
+            acc.add_(xp[:, :, ky:ky + h, kx:kx + w], alpha=float(k[ky, kx]))
+    return acc
+
+
+def ulp32_of(v):
+    """The spacing of float32 at |v| for float64 v (numpy): 2^(floor(log2 |v|) - 23), the subnormal spacing 2^-149 below 2^-126.
+    Taken from the float64 value itself, so a value just under a power of two keeps the smaller spacing."""
+    v = np.abs(np.asarray(v, dtype=np.float64))
+    _, e = np.frexp(v)                                                    # |v| = m * 2^e with m in [0.5, 1)
+    return np.ldexp(1.0, np.where(v == 0.0, -149, np.maximum(e - 24, -149)))
+
+
+def blur_pixel_bound(x, kernel2d, exp64):
+    """Per pixel, what "the correctly rounded sum up to klen^2 * 2^-53"  allows between the kernel and blur_f64:
+    0.5 ulp32(f64 value) + 2 * klen^2 * 2^-53 * (|k| * |x|), the last factor the float64 correlation of the absolute values.
+    Either float64 sum of klen^2 exact products is within klen^2 * 2^-53 * sum|k x| of the true value whatever its order
+    (hence the 2); the rounding to float32 adds half a float32 ulp.  No measured number enters.  -> float64 tensor like exp64."""
+    klen = kernel2d.shape[0]
+    mag = blur_f64(x.detach().cpu().abs(), kernel2d.detach().cpu().abs())
+    return 0.5 * torch.from_numpy(ulp32_of(exp64.numpy())) + 2.0 * klen * klen * 2.0 ** -53 * mag
+
+
+def blur_pixel_excess(got, x, kernel2d, exp64):
+    """max over the pixels of |got - f64| / blur_pixel_bound (<= 1 passes), and the flat index of that pixel."""
+    ratio = (got.detach().cpu().double() - exp64).abs() / blur_pixel_bound(x, kernel2d, exp64)
+    return float(ratio.max()), int(ratio.argmax())
 
 
 def image_errors(got, exp64):

@@ -26,6 +26,18 @@ def sliding_window_masks(input_size, window_size, stride):
     return masks.reshape(-1, 1, h, w)
 
 
+def masks_of_intervals(row_iv, col_iv, input_size):
+    """uint8 [nr * nc, 1, H, W] from half-open intervals: mask i * nc + j is 0 on rows row_iv[i] x columns col_iv[j], 1 elsewhere."""
+    h, w = input_size
+    masks = np.ones((len(row_iv) * len(col_iv), h, w), dtype=np.uint8)
+    n = 0
+    for r0, r1 in np.asarray(row_iv):
+        for c0, c1 in np.asarray(col_iv):
+            masks[n, r0:r1, c0:c1] = 0
+            n += 1
+    return masks.reshape(-1, 1, h, w)
+
+
 def cdist(a, b):
     """Euclidean distances [len(a), len(b)] in float64, the direct form."""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)

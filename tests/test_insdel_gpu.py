@@ -7,7 +7,8 @@ Tolerances.
   blur      every error is max|got - f64| / max|f64| per image against a float64 correlation; e_ref is that error of float32
             F.conv2d with the gkern weights on the same input and device; the kernel is allowed 4 * e_ref plus one float32 ulp
             (DESIGN 23's rule).  Each case prints `INSDEL_BLUR <case> e_ref=.. native=.. bound=..` before it asserts
-            (profiles/r16_insdel_accuracy.txt is that output).
+            (profiles/r16_insdel_accuracy.txt is that output).  Per pixel as well: |got - f64| <= 0.5 ulp32(f64) + 2 klen^2
+            2^-53 (|k| * |x|), R.blur_pixel_bound -- the design's "correctly rounded up to klen^2 2^-53", no measured number.
   curves    1e-12 against numpy float64: both take the cosine of the same float32 rows in float64; only the summation order of
             at most 1024 terms differs.
   job       2e-6 on scores and AUC against CausalMetric.evaluate with conv2d substrates: the bound tests/test_xai_gpu.py sets
@@ -31,25 +32,7 @@ def _tile():
 
 
 # ---- steps ------------------------------------------------------------------------------------------------------------------
-def _maps(k, hw, seed):
-    """name -> [k, hw] float32, different rows: random with a few ties, half tied at 0 (with a -0.0), a NaN and infinities, all equal."""
-    g = torch.Generator().manual_seed(seed)
-    out = {}
-    a = torch.rand(k, hw, generator=g)
-    if hw > 2:
-        a[:, hw // 3] = a[:, 0]
-    out["random"] = a
-    b = torch.rand(k, hw, generator=g)
-    b[:, ::2] = 0.0
-    b[:, (hw // 2) // 2 * 2] = -0.0
-    out["half_zero"] = b
-    c = torch.randn(k, hw, generator=g)
-    c[:, hw // 2] = float("nan")
-    if hw > 4:
-        c[:, 1], c[:, 2], c[:, hw - 1] = float("inf"), -float("inf"), -float("nan")
-    out["nan"] = c
-    out["all_equal"] = torch.full((k, hw), 0.5) * torch.arange(1, k + 1)[:, None]
-    return out
+_maps = R.saliency_maps                                   # name -> [k, hw] float32: the four map kinds
 
 
 @pytest.mark.parametrize("k", [1, 3])
@@ -131,11 +114,18 @@ def test_blur_accuracy_and_batch_invariance(h, w, klen):
         print(f"INSDEL_BLUR h={h} w={w} klen={klen} n={n} e_ref={e_ref:.3e} native={max(errs):.3e} bound={bound:.3e}")
         assert max(errs) <= bound, (errs, e_ref)
     assert torch.equal(got3.view(torch.int32), torch.cat(ones).view(torch.int32))        # n = 3 is three n = 1 calls, bit for bit
+    # per pixel: half a float32 ulp of the float64 value plus the two float64 sums' own error (R.blur_pixel_bound)
+    exc, at = R.blur_pixel_excess(got3, x, blur.kernel2d, exp)
+    print(f"INSDEL_BLUR h={h} w={w} klen={klen} gkern per-pixel max|err|/bound={exc:.6f} at {at}")
+    assert exc <= 1.0, (exc, at)
     # a kernel that is neither symmetric nor separable: the correlation, not the convolution, and no rank-1 shortcut
     k2 = torch.randn(klen, klen, generator=g)
     got = blur2d_same(dx[:1], k2)
     exp2 = R.blur_f64(x[:1], k2)
     assert max(R.image_errors(got, exp2)) <= R.ULP32
+    exc, at = R.blur_pixel_excess(got, x[:1], k2, exp2)
+    print(f"INSDEL_BLUR h={h} w={w} klen={klen} random per-pixel max|err|/bound={exc:.6f} at {at}")
+    assert exc <= 1.0, (exc, at)
 
 
 def test_blur_limits():
