@@ -560,27 +560,39 @@ def _linear_s3_ok(mod, x):
             and mod.in_features % 16 == 0)
 
 
-def _linear_w3(mod):
-    """The three-term bf16 image of a Linear's weight, rebuilt when the parameter changes."""
-    w = mod.weight
-    key = (w.data_ptr(), w._version, w.device)
-    cached = getattr(mod, "_mirx_w3", None)
+def _tkey(t):
+    """Cache key of a parameter: a replaced tensor object (load_state_dict(assign=True), `m.weight = nn.Parameter(..)`,
+    `p.data = ..`) starts again at version 0, so the version alone would keep a stale entry alive."""
+    return None if t is None else (id(t), t.data_ptr(), t._version)
+
+
+def _cached_image(mod, slot, tensors, build):
+    """build(): something derived from `tensors` (parameters, or None), kept in `mod.__dict__[slot]` and rebuilt when one
+    of them changed (_tkey).  The entry holds the tensors it was built from: the id of a live object is not handed out again."""
+    key = tuple(_tkey(t) for t in tensors)
+    cached = mod.__dict__.get(slot)
     if cached is None or cached[0] != key:
-        cached = (key, _split3_weights(w.detach()))
-        mod._mirx_w3 = cached
+        cached = (key, build(), tensors)
+        mod.__dict__[slot] = cached
     return cached[1]
 
 
+def _pow2_weight_scale(wf):
+    """The power of two that puts the largest |w| in [2^13, 2^14) (so the low fp16 term stays a normal number)."""
+    amax = float(wf.abs().max())
+    return 2.0 ** math.floor(math.log2(16384.0 / amax)) if amax > 0 and math.isfinite(amax) else 1.0
+
+
+def _linear_w3(mod):
+    """The three-term bf16 image of a Linear's weight, rebuilt when the parameter changes."""
+    return _cached_image(mod, "_mirx_w3", (mod.weight,), lambda: _split3_weights(mod.weight.detach()))
+
+
 def _linear_h2_weights(mod):
-    """(w2, w_scale): the two fp16 terms of W * w_scale, w_scale the power of two that puts the largest |w| in
-    [2^13, 2^14) (so the low term stays a normal fp16 number), laid out [ceil(n / 128)][k / 16][2][128][16]."""
-    w = mod.weight
-    key = (w.data_ptr(), w._version, w.device)
-    cached = getattr(mod, "_mirx_w2", None)
-    if cached is None or cached[0] != key:
-        wf = w.detach().float()
-        amax = float(wf.abs().max())
-        ws = 2.0 ** math.floor(math.log2(16384.0 / amax)) if amax > 0 and math.isfinite(amax) else 1.0
+    """(w2, w_scale): the two fp16 terms of W * w_scale (_pow2_weight_scale), laid out [ceil(n / 128)][k / 16][2][128][16]."""
+    def build():
+        wf = mod.weight.detach().float()
+        ws = _pow2_weight_scale(wf)
         wf = wf * ws
         if wf.shape[0] % 128:
             wf = F.pad(wf, (0, 0, 0, 128 - wf.shape[0] % 128))
@@ -588,9 +600,8 @@ def _linear_h2_weights(mod):
         wl = (wf - wh.float()).to(torch.float16)
         n, k = wf.shape
         t = torch.stack([wh, wl], 0).reshape(2, n // 128, 128, k // 16, 16)
-        cached = (key, t.permute(1, 3, 0, 2, 4).contiguous(), ws)
-        mod._mirx_w2 = cached
-    return cached[1], cached[2]
+        return t.permute(1, 3, 0, 2, 4).contiguous(), ws
+    return _cached_image(mod, "_mirx_w2", (mod.weight,), build)
 
 
 def _terms_of(a, scale):
@@ -607,20 +618,14 @@ def _terms_of(a, scale):
 
 
 def _linear_terms_weights(mod):
-    """(wt, w_scale): terms rows of W * w_scale, rows padded to a multiple of 256 with zeros; w_scale the power of two that
-    puts the largest |w| in [2^13, 2^14) (the low term stays a normal fp16 number)."""
-    w = mod.weight
-    key = _tkey(w)
-    cached = getattr(mod, "_mirx_wt", None)
-    if cached is None or cached[0] != key:
-        wf = w.detach().float()
-        amax = float(wf.abs().max())
-        ws = 2.0 ** math.floor(math.log2(16384.0 / amax)) if amax > 0 and math.isfinite(amax) else 1.0
+    """(wt, w_scale): terms rows of W * w_scale (_pow2_weight_scale), rows padded to a multiple of 256 with zeros."""
+    def build():
+        wf = mod.weight.detach().float()
+        ws = _pow2_weight_scale(wf)
         if wf.shape[0] % 256:
             wf = F.pad(wf, (0, 0, 0, 256 - wf.shape[0] % 256))
-        cached = (key, _terms_of(wf, ws), ws)
-        mod._mirx_wt = cached
-    return cached[1], cached[2]
+        return _terms_of(wf, ws), ws
+    return _cached_image(mod, "_mirx_wt", (mod.weight,), build)
 
 
 def _terms_scale(bound):
@@ -694,24 +699,16 @@ def _linear_terms_ok(mod, rows, lins, bounds):
             and all(l.out_features % 4 == 0 for l in lins) and all(math.isfinite(b) and 0.0 < b < 3.0e4 for b in bounds))
 
 
-def _tkey(t):
-    """Cache key of a parameter: a replaced tensor object (load_state_dict(assign=True), `m.weight = nn.Parameter(..)`,
-    `p.data = ..`) starts again at version 0, so the version alone would keep a stale entry alive."""
-    return None if t is None else (id(t), t.data_ptr(), t._version)
-
-
 def _layernorm_bound(ln):
     """max |LayerNorm(x)_j| over all inputs: |x_j - mean| / std <= sqrt(C - 1), so sqrt(C - 1) max|gamma| + max|beta|."""
     g, b = ln.weight, ln.bias
-    key = (_tkey(g), _tkey(b))
-    cached = getattr(ln, "_mirx_bound", None)
-    if cached is None or cached[0] != key:
+
+    def build():
         c = ln.normalized_shape[-1]
         gm = 1.0 if g is None else float(g.detach().abs().max())
         bm = 0.0 if b is None else float(b.detach().abs().max())
-        cached = (key, math.sqrt(max(c - 1, 1)) * gm + bm)
-        ln._mirx_bound = cached
-    return cached[1]
+        return math.sqrt(max(c - 1, 1)) * gm + bm
+    return _cached_image(ln, "_mirx_bound", (g, b), build)
 
 
 def _linear_out_bound(ln, lin, rows=None):
@@ -744,7 +741,7 @@ def _linear_h2(mod, x, bound, act=0, res=None, gamma=None, out=None):
     """[HIP] y = epi(x W^T + b) through mirx_linear_split2h; `bound` >= max |x| (the caller's proof obligation: fp16
     terms overflow at 65504) -- x is scaled by the power of two that brings `bound` to at most 2^15."""
     w2, ws = _linear_h2_weights(mod)
-    xs = 2.0 ** math.floor(math.log2(32768.0 / bound))
+    xs = _terms_scale(bound)
     x = x.contiguous()
     m = x.numel() // mod.in_features
     if out is None:
@@ -780,6 +777,14 @@ def _linear_s3(mod, x, act=0, res=None, gamma=None, out=None):
     return out
 
 
+def _linear_bounded(mod, x, bound, act=0, res=None, gamma=None, out=None):
+    """[HIP] y = epi(x W^T + b) for an input with max |x| <= bound: two fp16 terms where the bound is a proof they cannot
+    overflow (_linear_h2_ok), three bf16 terms otherwise.  bound=None: nothing is known about x."""
+    if bound is not None and _linear_h2_ok(mod, x, bound):
+        return _linear_h2(mod, x, bound, act, res, gamma, out)
+    return _linear_s3(mod, x, act, res, gamma, out)
+
+
 def _linear_auto(mod, x, act=0):
     """nn.Linear forward that takes the MFMA kernel for CUDA fp32 inference (any [..., k] input, k % 16 == 0) and the
     module's own forward otherwise.  act: 0 none, 1 erf-GELU, 2 tanh-GELU (fused in the kernel's epilogue)."""
@@ -812,6 +817,81 @@ def _layernorm(ln, x, tokens_per_image=0):
     return y
 
 
+def _attention_packed(owner, qkv, heads, head_dim, scale, bqk, bv, terms_scale=None, key_mask=None, small_below=0,
+                      fp32_fallback=False):
+    """[HIP] softmax(q k^T * scale) v on a packed projection qkv [b, n, 3c] (fp32, contiguous; q | k | v, each heads x
+    head_dim) under `owner`'s configuration.  bqk >= max |q|, |k| and bv >= max |v| (inf: no proof); key_mask [b, n]
+    (1 = attend) or None.  -> (the context [b, n, c] fp32, False), or -- with terms_scale, where the two-fp16 flash kernel
+    serves -- (the context * terms_scale as terms rows, fp16 [b * n, ceil32(c) * 2], True).
+    Flash kernels (no mask, at least small_below tokens): two fp16 terms behind the bounds, else three bf16 terms -- or fp32
+    MFMAs when fp32_fallback and the configuration turns attention_three_bf16 off.  Everything else: mirx_attention_small."""
+    b, n, c = qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3
+    cfg, dev, lib = _cfg(owner), qkv.device, _lib.load()
+    flash = key_mask is None and n >= small_below and head_dim in (32, 64, 72, 96) and b <= 65535
+    two_fp16 = flash and cfg.attention_two_fp16 and 0.0 < bqk < 3.0e4
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        if two_fp16 and terms_scale is not None:
+            # (a width that does not fill its last 32-feature group: the kernel leaves the padding to the allocation)
+            ct = (torch.empty if c % 32 == 0 else torch.zeros)((b * n, (c + 31) // 32 * 64), dtype=torch.float16, device=dev)
+            _lib.check(lib.mirx_attention_qkv_f32_split2h_terms(_ptr(qkv), b, n, heads, head_dim, scale, bqk, bv, terms_scale,
+                                                                _ptr(ct), st), "mirx_attention_qkv_f32_split2h_terms")
+            return ct, True
+        ctx = torch.empty((b, n, c), dtype=torch.float32, device=dev)
+        if two_fp16 and 0.0 < bv < 3.0e4:
+            # q, k, v are outputs of a LayerNorm-fed Linear: provable bounds -> two fp16 terms per operand
+            _lib.check(lib.mirx_attention_qkv_f32_split2h(_ptr(qkv), b, n, heads, head_dim, scale, bqk, bv, _ptr(ctx), st),
+                       "mirx_attention_qkv_f32_split2h")
+        elif flash and fp32_fallback and not cfg.attention_three_bf16:
+            _lib.check(lib.mirx_attention_qkv_f32(_ptr(qkv), b, n, heads, head_dim, scale, _ptr(ctx), st), "mirx_attention_qkv_f32")
+        elif flash:
+            _lib.check(lib.mirx_attention_qkv_f32_split3(_ptr(qkv), b, n, heads, head_dim, scale, _ptr(ctx), st),
+                       "mirx_attention_qkv_f32_split3")
+        else:
+            km = None if key_mask is None else key_mask.to(device=dev, dtype=torch.uint8).contiguous()
+            base = qkv.data_ptr()
+            _lib.check(lib.mirx_attention_small(ctypes.c_void_p(base), 3 * c, ctypes.c_void_p(base + 4 * c),
+                                                ctypes.c_void_p(base + 8 * c), 3 * c, _ptr(km) if km is not None else None, b,
+                                                heads, head_dim, n, n, scale, _ptr(ctx), st), "mirx_attention_small")
+    return ctx, False
+
+
+def _prenorm_block(owner, x, norm1, qkv, proj, norm2, fc1, fc2, heads, head_dim, scale, bqk, bv, bh, gelu, gamma1=None,
+                   gamma2=None, key_mask=None, tap=None, small_below=0, fp32_fallback=False):
+    """[HIP] The pre-norm transformer block of DINOv2 and the SigLIP towers, x [b, n, c] fp32:
+        x = x + gamma1 * proj(attention(qkv(norm1(x))));  x = x + gamma2 * fc2(gelu(fc1(norm2(x))))
+    in 4 MFMA Linear launches (bias / GELU / LayerScale + skip in their epilogues), one attention kernel and 2 LayerNorms.
+    qkv: the packed projection (a Linear, or a view duck-typed as one); bqk, bv >= max |q|, |k| and max |v|, bh >= max |fc1(..)|
+    over all inputs (the owner's proofs); gelu: 1 erf, 2 tanh; gamma1 / gamma2: LayerScale vectors or None; tap: None, or a
+    callable handed the packed qkv [b, n, 3c] once it exists; small_below / fp32_fallback: as in _attention_packed."""
+    b, n, c = x.shape
+    x = x.contiguous()
+    # the two Linears fed by a LayerNorm have a provable input bound; the context is a softmax-weighted average of V rows:
+    # bounded like them (bv); |gelu(v)| <= |v| (bh)
+    b1, b2 = _layernorm_bound(norm1), _layernorm_bound(norm2)
+    # big batches: every Linear on the DMA-fed kernel, its input handed over as terms rows by the producer
+    terms = _linear_terms_ok(owner, b * n, (qkv, proj, fc1, fc2), (b1, b2, bv, bh))
+    if terms:
+        h1t, s1 = _layernorm_terms(norm1, x, b1)
+        qkv = _linear_terms(qkv, h1t, s1, (b, n))                                                     # [b, n, 3c]
+    else:
+        qkv = _linear_bounded(qkv, _layernorm(norm1, x), b1)
+    if tap is not None:
+        tap(qkv)
+    sc = _terms_scale(bv) if terms else None
+    ctx, is_terms = _attention_packed(owner, qkv, heads, head_dim, scale, bqk, bv, terms_scale=sc, key_mask=key_mask,
+                                      small_below=small_below, fp32_fallback=fp32_fallback)
+    if terms:
+        ct = ctx if is_terms else _rows_to_terms(ctx, bv)[0]                       # (the same scale: _terms_scale(bv))
+        x = _linear_terms(proj, ct, sc, (b, n), res=x, gamma=gamma1)
+        h2t, s2 = _layernorm_terms(norm2, x, b2)
+        hidt, sh = _linear_terms(fc1, h2t, s2, (b, n), act=gelu, terms_bound=bh)
+        return _linear_terms(fc2, hidt, sh, (b, n), res=x, gamma=gamma2, out=x)
+    x = _linear_bounded(proj, ctx, bv, res=x, gamma=gamma1)
+    hid = _linear_bounded(fc1, _layernorm(norm2, x), b2, act=gelu)
+    return _linear_bounded(fc2, hid, bh, res=x, gamma=gamma2, out=x)
+
+
 class _ConvAsLinear:
     """A Conv2d whose kernel equals its stride (non-overlapping patches) seen as a Linear over patch rows: weight =
     conv.weight.flatten(1) zero-padded to a multiple of 16 input features (duck-typed for _linear_s3 / _linear_h2)."""
@@ -819,20 +899,18 @@ class _ConvAsLinear:
     def __init__(self, conv, channels_last=False):
         self.conv = conv
         self.channels_last = channels_last            # feature order (ky, kx, c): patch rows gathered from an NHWC map
-        self._key = None
 
     def refresh(self):
         w, b = self.conv.weight, self.conv.bias
-        key = (w.data_ptr(), w._version, None if b is None else b._version)
-        if key != self._key:
+
+        def build():
             flat = (w.detach().permute(0, 2, 3, 1) if self.channels_last else w.detach()).flatten(1)
             k = flat.shape[1]
-            self.k = k
-            self.in_features = (k + 15) // 16 * 16
-            self.out_features = flat.shape[0]
-            self.weight = F.pad(flat, (0, self.in_features - k)) if self.in_features != k else flat.contiguous()
+            kp = (k + 15) // 16 * 16
+            self.k, self.in_features, self.out_features = k, kp, flat.shape[0]
+            self.weight = F.pad(flat, (0, kp - k)) if kp != k else flat.contiguous()
             self.bias = None if b is None else b.detach()
-            self._key = key
+        _cached_image(self, "_mirx_view", (w, b), build)                 # (nothing to return: build() sets the view's attributes)
         return self
 
 
@@ -873,11 +951,7 @@ def _conv_patch_tokens(conv, x, ln2d=None, nchw_out=False):
                                                    _ptr(pl.bias) if pl.bias is not None else None, pl.out_features, None, None,
                                                    _ptr(out), st), "mirx_linear_split3_nchw")
             return out
-    if ln2d is not None:
-        bound = _layernorm_bound(ln2d)
-        if _linear_h2_ok(pl, rows, bound):
-            return _linear_h2(pl, rows, bound)
-    return _linear_s3(pl, rows)
+    return _linear_bounded(pl, rows, _layernorm_bound(ln2d) if ln2d is not None else None)
 
 
 _TENSOR_VERSION = operator.attrgetter("_version")
@@ -1425,8 +1499,7 @@ class _CnxBlock(nn.Module):
             b, c, h, w = x.shape
             yn = _layernorm(self.norm, y)
             bn = _layernorm_bound(self.norm)                               # fc1 reads a LayerNorm output
-            hid = (_linear_h2(mlp.fc1, yn, bn, act=1) if _linear_h2_ok(mlp.fc1, yn, bn)
-                   else _linear_s3(mlp.fc1, yn, act=1))                    # [b, h, w, 4c]
+            hid = _linear_bounded(mlp.fc1, yn, bn, act=1)                  # [b, h, w, 4c]
             c4 = hid.shape[-1]
             gx = torch.empty((b, c4), dtype=torch.float32, device=x.device)
             out = torch.empty_like(xc)
@@ -1546,8 +1619,7 @@ class _ConvNeXtV2Backbone(nn.Module):
                     _lib.check(lib.mirx_layernorm_patch2_nhwc(_ptr(t), b, h, w, c, _ptr(ln.weight.detach()), _ptr(ln.bias.detach()),
                                                               float(ln.eps), _ptr(rows), _stream(dev)), "mirx_layernorm_patch2_nhwc")
                 h, w = h // 2, w // 2
-                bound = _layernorm_bound(ln)
-                t = _linear_h2(pl, rows, bound) if _linear_h2_ok(pl, rows, bound) else _linear_s3(pl, rows)
+                t = _linear_bounded(pl, rows, _layernorm_bound(ln))
             for blk in stage.blocks:
                 t = blk._forward_nhwc(t, b, h, w)
         return t, h, w
@@ -1793,16 +1865,11 @@ class _VitAttention(nn.Module):
         dh = c // self.num_heads
         qkv = self.qkv(x)                                                # [b, n, 3, heads, dh] packed
         if x.is_cuda and dh in (32, 64, 72, 96) and qkv.dtype == torch.float32 and not torch.is_grad_enabled():
-            # MI355X inference path: fp32 MFMA flash attention straight on the packed projection,
-            # output already [b, n, heads * dh] (include/mirx.h: mirx_attention_qkv_f32)
-            qkv = qkv.contiguous()
-            a = torch.empty((b, n, c), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                lib = _lib.load()
-                att = lib.mirx_attention_qkv_f32_split3 if _cfg(self).attention_three_bf16 else lib.mirx_attention_qkv_f32
-                _lib.check(att(_ptr(qkv), b, n, self.num_heads, dh, float(dh) ** -0.5, _ptr(a), _stream(x.device)),
-                           "mirx_attention_qkv_f32")
-            return self.proj(a)
+            # MI355X inference path: flash attention straight on the packed projection, output already [b, n, heads * dh]
+            # (the rocBLAS projection gives no bounds: three bf16 terms, or fp32 MFMAs when the configuration says so)
+            inf = float("inf")
+            return self.proj(_attention_packed(self, qkv.contiguous(), self.num_heads, dh, float(dh) ** -0.5, inf, inf,
+                                               fp32_fallback=True)[0])
         qkv = qkv.reshape(b, n, 3, self.num_heads, dh).permute(2, 0, 3, 1, 4)
         a = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2])      # softmax(q k^T / sqrt(d)) v
         return self.proj(a.transpose(1, 2).reshape(b, n, c))
@@ -1833,61 +1900,12 @@ class _VitBlock(nn.Module):
         at = self.attn
         if (x.dim() == 3 and x.shape[-1] // at.num_heads == 64 and _linear_s3_ok(at.qkv, x)
                 and _linear_s3_ok(at.proj, x) and _linear_s3_ok(self.mlp.fc1, x) and _linear_s3_ok(self.mlp.fc2, x)):
-            # MI355X inference path: 4 split-3 MFMA Linear launches (bias / GELU / LayerScale + skip in their
-            # epilogues) + the flash-attention kernel + 2 LayerNorms per block
-            b, n, c = x.shape
-            x = x.contiguous()
-            # the two Linears fed by a LayerNorm have a provable input bound: two fp16 terms (3 MFMAs per product)
-            b1, b2 = _layernorm_bound(self.norm1), _layernorm_bound(self.norm2)
-            # attention output = softmax-weighted average of V rows: bounded like the V part of the qkv projection; |gelu(v)| <= |v|
-            ba, bh = _linear_out_bound(self.norm1, at.qkv, slice(2 * c, 3 * c)), _linear_out_bound(self.norm2, self.mlp.fc1)
-            # big batches: every Linear on the DMA-fed kernel, its input handed over as terms rows by the producer
-            terms = _linear_terms_ok(self, b * n, (at.qkv, at.proj, self.mlp.fc1, self.mlp.fc2), (b1, b2, ba, bh))
-            if terms:
-                h1t, s1 = _layernorm_terms(self.norm1, x, b1)
-                qkv = _linear_terms(at.qkv, h1t, s1, (b, n))
-            else:
-                h1 = _layernorm(self.norm1, x)
-                qkv = _linear_h2(at.qkv, h1, b1) if _linear_h2_ok(at.qkv, h1, b1) else _linear_s3(at.qkv, h1)
-            bqk = _linear_out_bound(self.norm1, at.qkv, slice(0, 2 * c))
-            bv = _linear_out_bound(self.norm1, at.qkv, slice(2 * c, 3 * c))
-            att = None
-            if terms and _cfg(self).attention_two_fp16 and 0.0 < bqk < 3.0e4:
-                # the attention kernel hands its output to the projection as terms rows too (|out| <= ba)
-                att, sa = (torch.empty if c % 32 == 0 else torch.zeros)((b * n, (c + 31) // 32 * 64), dtype=torch.float16, device=x.device), _terms_scale(ba)
-                with torch.cuda.device(x.device):
-                    _lib.check(_lib.load().mirx_attention_qkv_f32_split2h_terms(_ptr(qkv), b, n, at.num_heads, 64, 0.125, bqk, bv, sa,
-                                                                                _ptr(att), _stream(x.device)),
-                               "mirx_attention_qkv_f32_split2h_terms")
-            a = torch.empty((b, n, c), dtype=torch.float32, device=x.device) if att is None else None
-            with torch.cuda.device(x.device):
-                lib = _lib.load()
-                if att is not None:
-                    pass
-                elif _cfg(self).attention_two_fp16 and 0.0 < bqk < 3.0e4 and 0.0 < bv < 3.0e4:
-                    # q, k, v are outputs of a LayerNorm-fed Linear: provable bounds -> two fp16 terms per operand
-                    _lib.check(lib.mirx_attention_qkv_f32_split2h(_ptr(qkv), b, n, at.num_heads, 64, 0.125, bqk, bv, _ptr(a),
-                                                                  _stream(x.device)), "mirx_attention_qkv_f32_split2h")
-                else:
-                    att = lib.mirx_attention_qkv_f32_split3 if _cfg(self).attention_three_bf16 else lib.mirx_attention_qkv_f32
-                    _lib.check(att(_ptr(qkv), b, n, at.num_heads, 64, 0.125, _ptr(a), _stream(x.device)),
-                               "mirx_attention_qkv_f32")
-            if terms:
-                if att is None:
-                    att, sa = _rows_to_terms(a, ba)
-                x = _linear_terms(at.proj, att, sa, (b, n), res=x, gamma=self.ls1.gamma)
-                h2t, s2 = _layernorm_terms(self.norm2, x, b2)
-                hidt, sh = _linear_terms(self.mlp.fc1, h2t, s2, (b, n), act=1, terms_bound=bh)
-                return _linear_terms(self.mlp.fc2, hidt, sh, (b, n), res=x, gamma=self.ls2.gamma, out=x)
-            x = (_linear_h2(at.proj, a, ba, res=x, gamma=self.ls1.gamma) if _linear_h2_ok(at.proj, a, ba)
-                 else _linear_s3(at.proj, a, res=x, gamma=self.ls1.gamma))
-            h2 = _layernorm(self.norm2, x)
-            hid = (_linear_h2(self.mlp.fc1, h2, b2, act=1) if _linear_h2_ok(self.mlp.fc1, h2, b2)
-                   else _linear_s3(self.mlp.fc1, h2, act=1))
-            bh = _linear_out_bound(self.norm2, self.mlp.fc1)                 # |gelu(v)| <= |v|
-            if _linear_h2_ok(self.mlp.fc2, hid, bh):
-                return _linear_h2(self.mlp.fc2, hid, bh, res=x, gamma=self.ls2.gamma, out=x)
-            return _linear_s3(self.mlp.fc2, hid, res=x, gamma=self.ls2.gamma, out=x)
+            c = x.shape[-1]
+            return _prenorm_block(self, x, self.norm1, at.qkv, at.proj, self.norm2, self.mlp.fc1, self.mlp.fc2, at.num_heads, 64, 0.125,
+                                  bqk=_linear_out_bound(self.norm1, at.qkv, slice(0, 2 * c)),
+                                  bv=_linear_out_bound(self.norm1, at.qkv, slice(2 * c, 3 * c)),
+                                  bh=_linear_out_bound(self.norm2, self.mlp.fc1), gelu=1, gamma1=self.ls1.gamma,
+                                  gamma2=self.ls2.gamma, fp32_fallback=True)
         x = x + self.ls1(self.attn(self.norm1(x)))
         return x + self.ls2(self.mlp(self.norm2(x)))
 

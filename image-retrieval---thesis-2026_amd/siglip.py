@@ -51,19 +51,18 @@ class _PackedRows:
     """Several Linear layers that read the same input, seen as ONE Linear (weights stacked along the output axis):
     duck-typed for mirx.model._linear_s3 / _linear_h2 (in_features, out_features, weight, bias)."""
 
-    def __init__(self, parts):
-        self.parts = parts                       # callables -> (weight, bias)
-        self._key = None
-        self.__dict__["_cache"] = {}
+    def __init__(self, parts, rows=slice(None)):
+        self.parts = parts                       # callables -> (weight, bias) parameters; `rows`: the output rows taken of each
+        self.rows = rows
 
     def refresh(self):
         wb = [p() for p in self.parts]
-        key = tuple((w.data_ptr(), w._version, None if b is None else b._version) for w, b in wb)
-        if key != self._key:
-            self.weight = torch.cat([w.detach() for w, _ in wb], 0)
-            self.bias = None if wb[0][1] is None else torch.cat([b.detach() for _, b in wb], 0)
+
+        def build():
+            self.weight = torch.cat([w.detach()[self.rows] for w, _ in wb], 0)
+            self.bias = None if wb[0][1] is None else torch.cat([b.detach()[self.rows] for _, b in wb], 0)
             self.in_features, self.out_features = self.weight.shape[1], self.weight.shape[0]
-            self._key = key
+        _m._cached_image(self, "_mirx_view", [t for pair in wb for t in pair], build)     # (build() sets the view's attributes)
         return self
 
 
@@ -124,70 +123,14 @@ class _EncoderLayer(nn.Module):
     def _forward_mirx(self, x, key_mask, tap=None):
         """tap: None, or a callable handed the packed qkv [b, n, 3c] (fp32, on the layer's stream) once it exists; it may
         launch work that reads it (on another stream: after waiting on this one, with qkv.record_stream) and must not write it."""
-        sa, mlp = self.self_attn, self.mlp
-        b, n, c = x.shape
-        x = x.contiguous()
-        lib = _lib.load()
-        b1, b2 = _m._layernorm_bound(self.layer_norm1), _m._layernorm_bound(self.layer_norm2)
-        pk = sa._packed.refresh()
-        pk.__dict__["_mirx_cfg"] = _m._cfg(sa)                   # the packed view runs under its attention module's configuration
-        bctx, bh = _m._linear_out_bound(self.layer_norm1, sa.v_proj), _m._linear_out_bound(self.layer_norm2, mlp.fc1)
-        # big batches: every Linear on the DMA-fed kernel, its input handed over as terms rows by the producer
-        terms = _m._linear_terms_ok(self, b * n, (pk, sa.out_proj, mlp.fc1, mlp.fc2), (b1, b2, bctx, bh))
-        if terms:
-            h1t, s1 = _m._layernorm_terms(self.layer_norm1, x, b1)
-            qkv = _m._linear_terms(pk, h1t, s1, (b, n))                                                   # [b, n, 3c]
-        else:
-            h1 = _m._layernorm(self.layer_norm1, x)
-            qkv = _m._linear_h2(pk, h1, b1) if _m._linear_h2_ok(pk, h1, b1) else _m._linear_s3(pk, h1)      # [b, n, 3c]
-        if tap is not None:
-            tap(qkv)
-        bqk = max(_m._linear_out_bound(self.layer_norm1, sa.q_proj), _m._linear_out_bound(self.layer_norm1, sa.k_proj))
-        bv = _m._linear_out_bound(self.layer_norm1, sa.v_proj)
-        flash = key_mask is None and n >= 32 and sa.head_dim in (32, 64, 72, 96) and b <= 65535
-        ct = None
-        if terms and flash and _m._cfg(self).attention_two_fp16 and 0.0 < bqk < 3.0e4:
-            # the attention kernel hands its output to the projection as terms rows too (|ctx| <= bctx)
-            ct, sc = (torch.empty if c % 32 == 0 else torch.zeros)((b * n, (c + 31) // 32 * 64), dtype=torch.float16, device=x.device), _m._terms_scale(bctx)
-            with torch.cuda.device(x.device):
-                _lib.check(lib.mirx_attention_qkv_f32_split2h_terms(_m._ptr(qkv), b, n, sa.num_heads, sa.head_dim, float(sa.scale),
-                                                                    bqk, bv, sc, _m._ptr(ct), _m._stream(x.device)),
-                           "mirx_attention_qkv_f32_split2h_terms")
-        ctx = torch.empty((b, n, c), dtype=torch.float32, device=x.device) if ct is None else None
-        with torch.cuda.device(x.device):
-            st = _m._stream(x.device)
-            if ct is not None:
-                pass
-            elif flash and _m._cfg(self).attention_two_fp16 and 0.0 < bqk < 3.0e4 and 0.0 < bv < 3.0e4:
-                # q, k, v come out of a LayerNorm-fed Linear: provable bounds -> two fp16 terms per operand
-                _lib.check(lib.mirx_attention_qkv_f32_split2h(_m._ptr(qkv), b, n, sa.num_heads, sa.head_dim, float(sa.scale),
-                                                              bqk, bv, _m._ptr(ctx), st), "mirx_attention_qkv_f32_split2h")
-            elif flash:
-                _lib.check(lib.mirx_attention_qkv_f32_split3(_m._ptr(qkv), b, n, sa.num_heads, sa.head_dim, float(sa.scale),
-                                                             _m._ptr(ctx), st), "mirx_attention_qkv_f32_split3")
-            else:
-                km = None if key_mask is None else key_mask.to(device=x.device, dtype=torch.uint8).contiguous()
-                base = qkv.data_ptr()
-                _lib.check(lib.mirx_attention_small(ctypes.c_void_p(base), 3 * c, ctypes.c_void_p(base + 4 * c),
-                                                    ctypes.c_void_p(base + 8 * c), 3 * c,
-                                                    _m._ptr(km) if km is not None else None, b, sa.num_heads, sa.head_dim,
-                                                    n, n, float(sa.scale), _m._ptr(ctx), st), "mirx_attention_small")
-        # the context is a softmax-weighted average of V rows: bounded like the V rows of the packed projection; |gelu(v)| <= |v|
-        if terms:
-            if ct is None:
-                ct, sc = _m._rows_to_terms(ctx, bctx)
-            x = _m._linear_terms(sa.out_proj, ct, sc, (b, n), res=x)
-            h2t, s2 = _m._layernorm_terms(self.layer_norm2, x, b2)
-            hidt, sh = _m._linear_terms(mlp.fc1, h2t, s2, (b, n), act=2, terms_bound=bh)
-            return _m._linear_terms(mlp.fc2, hidt, sh, (b, n), res=x, out=x)
-        x = (_m._linear_h2(sa.out_proj, ctx, bv, res=x) if _m._linear_h2_ok(sa.out_proj, ctx, bv)
-             else _m._linear_s3(sa.out_proj, ctx, res=x))
-        h2 = _m._layernorm(self.layer_norm2, x)
-        hid = (_m._linear_h2(mlp.fc1, h2, b2, act=2) if _m._linear_h2_ok(mlp.fc1, h2, b2) else _m._linear_s3(mlp.fc1, h2, act=2))
-        bh = _m._linear_out_bound(self.layer_norm2, mlp.fc1)               # |gelu(v)| <= |v|
-        if _m._linear_h2_ok(mlp.fc2, hid, bh):
-            return _m._linear_h2(mlp.fc2, hid, bh, res=x, out=x)
-        return _m._linear_s3(mlp.fc2, hid, res=x, out=x)
+        sa, mlp, ln1, ln2 = self.self_attn, self.mlp, self.layer_norm1, self.layer_norm2
+        # short or masked sequences (the text tower) go to mirx_attention_small; the flash fallback stays on three bf16 terms
+        # whatever attention_three_bf16 says (fp32_fallback=False: DESIGN.md, open question of the shared block routine)
+        return _m._prenorm_block(self, x, ln1, sa._packed.refresh(), sa.out_proj, ln2, mlp.fc1, mlp.fc2, sa.num_heads,
+                                 sa.head_dim, float(sa.scale),
+                                 bqk=max(_m._linear_out_bound(ln1, sa.q_proj), _m._linear_out_bound(ln1, sa.k_proj)),
+                                 bv=_m._linear_out_bound(ln1, sa.v_proj), bh=_m._linear_out_bound(ln2, mlp.fc1), gelu=2,
+                                 key_mask=key_mask, tap=tap, small_below=32, fp32_fallback=False)
 
 
 class _Encoder(nn.Module):
@@ -234,18 +177,18 @@ class _PoolingHead(nn.Module):
         self.layernorm = nn.LayerNorm(dim, eps=LN_EPS)
         self.mlp = _MLP(dim, hidden)
         c = dim
-        self.__dict__["_kv"] = _PackedRows([lambda: (self.attention.in_proj_weight[c:], self.attention.in_proj_bias[c:])])
+        # the whole in_proj parameters with the k / v rows named apart: a slice taken here would be a new tensor object on
+        # every refresh, and the view's cache keys on the identity of its sources
+        self.__dict__["_kv"] = _PackedRows([lambda: (self.attention.in_proj_weight, self.attention.in_proj_bias)], rows=slice(c, None))
 
     def _probe_query(self):
         """in_proj_q(probe): constant for given weights, computed once per weight version."""
         at, c = self.attention, self.probe.shape[-1]
-        key = (self.probe._version, at.in_proj_weight._version, at.in_proj_bias._version, self.probe.device)
-        cached = self.__dict__.get("_q")
-        if cached is None or cached[0] != key:
+
+        def build():
             with torch.no_grad():
-                cached = (key, F.linear(self.probe[0], at.in_proj_weight[:c], at.in_proj_bias[:c]))
-            self.__dict__["_q"] = cached
-        return cached[1]
+                return F.linear(self.probe[0], at.in_proj_weight[:c], at.in_proj_bias[:c])
+        return _m._cached_image(self, "_q", (self.probe, at.in_proj_weight, at.in_proj_bias), build)
 
     def forward(self, hidden, in_bound=None):
         b, n, c = hidden.shape
@@ -255,8 +198,7 @@ class _PoolingHead(nn.Module):
             lib = _lib.load()
             kvp = self._kv.refresh()
             hidden = hidden.contiguous()
-            kv = (_m._linear_h2(kvp, hidden, in_bound) if in_bound is not None and _m._linear_h2_ok(kvp, hidden, in_bound)
-                  else _m._linear_s3(kvp, hidden))                                             # [b, n, 2c]
+            kv = _m._linear_bounded(kvp, hidden, in_bound)                                      # [b, n, 2c]
             q = self._probe_query().expand(b, c).contiguous()                                   # [b, c]
             ctx = torch.empty((b, 1, c), dtype=torch.float32, device=hidden.device)
             with torch.cuda.device(hidden.device):

@@ -166,3 +166,63 @@ def test_kernel_config_reaches_the_linear_views_that_are_not_modules():
     conv.__dict__["_mirx_as_linear"] = view
     mm.set_kernel_config(conv, off)
     assert mm._cfg(view) is off
+
+
+def _replace_weight_in_place(owner, name="weight"):
+    """Replace owner.<name> by a new nn.Parameter on the SAME storage with one row changed by + 1.0, both parameters at
+    version 0: what `_version` and `data_ptr()` cannot tell apart.  -> the old parameter (kept alive by the caller)."""
+    old = getattr(owner, name)
+    alias = old.data                                       # shares the storage; writing through it bumps no version of `old`
+    alias[0] += 1.0
+    new = torch.nn.Parameter(alias.data)
+    setattr(owner, name, new)
+    assert new is not old and new.data_ptr() == old.data_ptr() and new._version == 0 and old._version == 0
+    return old
+
+
+def _stale_image_case(owner, image):
+    """image() before and after the in-place replacement of owner.weight must differ (an additive change: a scaled weight
+    would give the same two-fp16 image under a rescaled w_scale)."""
+    owner.weight = torch.nn.Parameter(owner.weight.detach().clone())
+    first = image().clone()
+    old = _replace_weight_in_place(owner)
+    second = image()
+    assert old is not owner.weight
+    assert first.shape == second.shape and not torch.equal(first, second)
+
+
+def test_linear_w3_image_follows_a_replaced_weight():
+    import mirx.model as mm
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(32, 24)
+    _stale_image_case(lin, lambda: mm._linear_w3(lin))
+
+
+def test_linear_h2_image_follows_a_replaced_weight():
+    import mirx.model as mm
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(32, 24)
+    _stale_image_case(lin, lambda: mm._linear_h2_weights(lin)[0])
+
+
+def test_linear_terms_image_follows_a_replaced_weight():
+    import mirx.model as mm
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(32, 24)
+    _stale_image_case(lin, lambda: mm._linear_terms_weights(lin)[0])
+
+
+def test_conv_as_linear_view_follows_a_replaced_weight():
+    import mirx.model as mm
+    torch.manual_seed(0)
+    conv = torch.nn.Conv2d(3, 8, 2, 2)                      # 12 features per patch: padded to 16, so the view's weight is a copy
+    view = mm._ConvAsLinear(conv)
+    _stale_image_case(conv, lambda: view.refresh().weight)
+
+
+def test_packed_rows_view_follows_a_replaced_weight():
+    from mirx.siglip import SiglipVisionTower
+    torch.manual_seed(0)
+    v = SiglipVisionTower(hidden_size=64, intermediate_size=128, num_hidden_layers=1, num_attention_heads=2, image_size=28, patch_size=14)
+    sa = v.encoder.layers[0].self_attn
+    _stale_image_case(sa.k_proj, lambda: sa._packed.refresh().weight)
