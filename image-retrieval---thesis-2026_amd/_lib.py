@@ -41,6 +41,7 @@ RESAMPLE_MAX_LDS = 65536
 RESAMPLE_TILE_W, RESAMPLE_TILE_H = 32, 16
 RESAMPLE_DESC_WORDS = 8
 RESAMPLE_OUT_U8, RESAMPLE_OUT_F32 = 0, 1
+RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 0, 1
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
@@ -193,6 +194,8 @@ SYMBOLS = {
     "mirx_resample_taps": (_int, [_int, _int]),
     "mirx_resample_plan": (_int, [_int, _int, _int, _int, _vp, _i64]),
     "mirx_resample_batch": (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
+    "mirx_resample_taps_filter": (_int, [_int, _int, _int]),
+    "mirx_resample_plan_filter": (_int, [_int, _int, _int, _int, _int, _vp, _i64]),
 }
 
 _lib = None

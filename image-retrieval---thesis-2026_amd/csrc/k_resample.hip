@@ -1,9 +1,9 @@
-// k_resample.hip -- batched Resize(shorter side) + CenterCrop of 8-bit images, bit-equal to Pillow's BILINEAR (gfx950, wave64;
-// include/mirx.h).
+// k_resample.hip -- batched Resize(shorter side) + CenterCrop, or Resize((S, S)), of 8-bit images, bit-equal to Pillow's BILINEAR
+// and BICUBIC (gfx950, wave64; include/mirx.h).
 //
 // Pillow resizes an 8-bit image in two separable passes, horizontal first into an 8-bit intermediate, then vertical: per output
-// index a run of source taps [first, first + count) with double-precision triangle weights, normalised by their sum, quantised
-// to 22 fractional bits, and out = clip((2^21 + sum pixel * coeff) >> 22, 0, 255) in 32-bit integers.  The weights depend on the
+// index a run of source taps [first, first + count) with double-precision filter weights (triangle, or the a = -0.5 cubic, whose
+// outer lobes are negative), normalised by their sum, quantised to 22 fractional bits, and out = clip((2^21 + sum pixel * coeff) >> 22, 0, 255) in 32-bit integers.  The weights depend on the
 // sizes alone, so the HOST plans them (resample_plan, below: plain double arithmetic in Pillow's order, no device) and the kernel
 // does integer multiply-adds only.  Only the S outputs inside the crop window are planned: the resized image outside the crop
 // never exists.
@@ -52,6 +52,7 @@ struct RsNorm {
     float mean[3], stdv[3];
 };
 
+// v is a signed sum (the cubic's outer coefficients are negative): an arithmetic shift, as in Pillow's clip8
 __device__ inline int rs_clip8(int v) {
     v >>= RS_BITS;
     return v < 0 ? 0 : (v > 255 ? 255 : v);
@@ -183,23 +184,58 @@ __global__ __launch_bounds__(RS_THREADS) void k_resample(const unsigned char *__
 }  // namespace
 
 // ---- host: the plan -----------------------------------------------------------------------------------------------------------
-// Pillow's coefficient count for an axis resized from in_size to out_size with the triangle filter (support 1).
-int resample_taps(int in_size, int out_size) {
-    double fs = (double)in_size / out_size;
-    if (fs < 1.0) fs = 1.0;
-    return (int)ceil(fs) * 2 + 1;
+namespace {
+
+// Pillow's filters (Resample.c): the triangle of support 1 and the a = -0.5 cubic of support 2.  One operation per statement,
+// in Pillow's association (this file is compiled with -ffp-contract=off).
+inline double rs_triangle(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
 }
 
-// table = int32 [4 + 2 n + n ksize]: {ksize, n, in_size, 0}, bounds [n][2] = (first tap, tap count), coefficients [n][ksize]
+inline double rs_bicubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) {
+        double t = (a + 2.0) * x;
+        t = t - (a + 3.0);
+        t = t * x;
+        t = t * x;
+        return t + 1.0;
+    }
+    if (x < 2.0) {
+        double t = x - 5.0;
+        t = t * x;
+        t = t + 8.0;
+        t = t * x;
+        t = t - 4.0;
+        return t * a;
+    }
+    return 0.0;
+}
+
+inline double rs_support(int filter) { return filter == MIRX_RESAMPLE_BICUBIC ? 2.0 : 1.0; }
+
+}  // namespace
+
+// Pillow's coefficient count for an axis resized from in_size to out_size with a filter of support 1 (triangle) or 2 (cubic).
+int resample_taps(int in_size, int out_size, int filter) {
+    double fs = (double)in_size / out_size;
+    if (fs < 1.0) fs = 1.0;
+    const double support = rs_support(filter) * fs;
+    return (int)ceil(support) * 2 + 1;
+}
+
+// table = int32 [4 + 2 n + n ksize]: {ksize, n, in_size, filter}, bounds [n][2] = (first tap, tap count), coefficients [n][ksize]
 // (zero past the count), for the outputs [first, first + n) of the axis.  Double arithmetic in Pillow's order, one operation per
 // statement (this file is compiled with -ffp-contract=off).
-void resample_plan(int in_size, int out_size, int first, int n, int32_t *table) {
-    const int ksize = resample_taps(in_size, out_size);
+void resample_plan(int in_size, int out_size, int first, int n, int filter, int32_t *table) {
+    const int ksize = resample_taps(in_size, out_size, filter);
     const double scale = (double)in_size / out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs;
+    const double support = rs_support(filter) * fs;
     const double ss = 1.0 / fs;
-    table[0] = ksize, table[1] = n, table[2] = in_size, table[3] = 0;
+    table[0] = ksize, table[1] = n, table[2] = in_size, table[3] = filter;
     int32_t *bounds = table + RS_HDR, *coef = bounds + 2 * n;
     double w[MIRX_RESAMPLE_MAX_TAPS];
     for (int i = 0; i < n; ++i) {
@@ -211,9 +247,8 @@ void resample_plan(int in_size, int out_size, int first, int n, int32_t *table) 
         const int cnt = xmax - xmin;
         double ww = 0.0;
         for (int x = 0; x < cnt; ++x) {
-            double a = (x + xmin - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            w[x] = a < 1.0 ? 1.0 - a : 0.0;
+            const double a = (x + xmin - center + 0.5) * ss;
+            w[x] = filter == MIRX_RESAMPLE_BICUBIC ? rs_bicubic(a) : rs_triangle(a);
             ww += w[x];
         }
         int32_t *k = coef + (int64_t)i * ksize;
@@ -223,7 +258,8 @@ void resample_plan(int in_size, int out_size, int first, int n, int32_t *table) 
                 continue;
             }
             const double v = ww != 0.0 ? w[x] / ww : w[x];
-            k[x] = (int32_t)(0.5 + v * (double)(1 << RS_BITS));      // a triangle weight is never negative
+            // a triangle weight is never negative; the cubic is negative for 1 < |x| < 2, and Pillow rounds away from zero
+            k[x] = v < 0.0 ? (int32_t)(-0.5 + v * (double)(1 << RS_BITS)) : (int32_t)(0.5 + v * (double)(1 << RS_BITS));
         }
         bounds[2 * i] = xmin, bounds[2 * i + 1] = cnt;
     }
@@ -234,12 +270,14 @@ namespace {
 
 struct RsTable {
     int64_t off;
-    int in_size, ksize;
+    int in_size, ksize, filter;
     int64_t max_span;      // y use only: the largest source-row span of a tile row
 };
 
 // One axis table at blob + off, for an axis of in_size source pixels and s outputs: inside the blob, every tap run inside
-// [0, in_size), every coefficient >= 0 and every run's sum <= 2^23 (255 * 2^23 + 2^21 < 2^31: the 32-bit sums cannot overflow).
+// [0, in_size), and by the filter in header word 3: triangle, every coefficient >= 0 and every run's sum <= 2^23; cubic, signed
+// coefficients and every run's sum of magnitudes <= 2^23 (255 * 2^23 + 2^21 < 2^31: the 32-bit sums cannot overflow, in
+// either direction and at any prefix of a run).
 const char *rs_check_table(const unsigned char *blob, int64_t blob_bytes, int64_t head_bytes, int64_t off, int in_size, int s,
                            RsTable &tb) {
     if (off < head_bytes || (off & 15) || off > blob_bytes - RS_HDR * 4) return "resample: a table offset is misaligned or outside the buffer";
@@ -247,6 +285,9 @@ const char *rs_check_table(const unsigned char *blob, int64_t blob_bytes, int64_
     const int ksize = t[0];
     if (ksize < 1 || ksize > MIRX_RESAMPLE_MAX_TAPS) return "resample: tap count over the cap (MIRX_RESAMPLE_MAX_TAPS = 65: scale > 32)";
     if (t[1] != s || t[2] != in_size) return "resample: a table was planned for another output or source size";
+    const int filter = t[3];
+    if (filter != MIRX_RESAMPLE_BILINEAR && filter != MIRX_RESAMPLE_BICUBIC)
+        return "resample: unknown filter in a table's header (word 3: 0 = bilinear, 1 = bicubic)";
     const int64_t words = RS_HDR + 2 * (int64_t)s + (int64_t)s * ksize;
     if (off + words * 4 > blob_bytes) return "resample: a table runs past the buffer";
     const int32_t *bounds = t + RS_HDR, *coef = bounds + 2 * s;
@@ -256,12 +297,14 @@ const char *rs_check_table(const unsigned char *blob, int64_t blob_bytes, int64_
         int64_t sum = 0;
         for (int x = 0; x < c; ++x) {
             const int32_t k = coef[(int64_t)i * ksize + x];
-            if (k < 0) return "resample: negative coefficient";
-            sum += k;
+            if (k < 0 && filter == MIRX_RESAMPLE_BILINEAR) return "resample: negative coefficient";
+            sum += k < 0 ? -(int64_t)k : k;
         }
-        if (sum > (1 << (RS_BITS + 1))) return "resample: a coefficient run sums to more than 2^23";
+        if (sum > (1 << (RS_BITS + 1)))
+            return filter == MIRX_RESAMPLE_BILINEAR ? "resample: a coefficient run sums to more than 2^23"
+                                                    : "resample: a bicubic coefficient run's magnitudes sum to more than 2^23";
     }
-    tb.off = off, tb.in_size = in_size, tb.ksize = ksize, tb.max_span = 0;
+    tb.off = off, tb.in_size = in_size, tb.ksize = ksize, tb.filter = filter, tb.max_span = 0;
     for (int y0 = 0; y0 < s; y0 += RS_TH) {
         int r0 = INT32_MAX, r1 = 0;
         for (int j = y0; j < std::min(s, y0 + RS_TH); ++j) {
@@ -311,6 +354,7 @@ const char *resample_check(const void *blob_host, int64_t blob_bytes, int64_t b,
             ys.push_back(t);
             ty = &ys.back();
         }
+        if (tx->filter != ty->filter) return "resample: the x and y tables of an image name different filters";
         need = std::max<int64_t>(need, (int64_t)tx->ksize * RS_TW * 4 + ty->max_span * ch * RS_TW);
     }
     if (need > MIRX_RESAMPLE_MAX_LDS) return "resample: a tile's source rows need more LDS than the cap (MIRX_RESAMPLE_MAX_LDS = 65536)";

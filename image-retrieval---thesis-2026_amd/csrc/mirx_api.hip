@@ -1596,27 +1596,37 @@ int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv
 }
 
 // ---- batched Resize + CenterCrop (k_resample.hip) -------------------------------------------------------------------------------
-static const char *resample_axis_limits(int in_size, int out_size) {
+static const char *resample_axis_limits(int in_size, int out_size, int filter) {
+    if (filter != MIRX_RESAMPLE_BILINEAR && filter != MIRX_RESAMPLE_BICUBIC)
+        return "resample: unknown filter (MIRX_RESAMPLE_BILINEAR = 0, MIRX_RESAMPLE_BICUBIC = 1)";
     if (in_size < 1 || in_size > MIRX_RESAMPLE_MAX_SIDE) return "resample: source side outside [1, MIRX_RESAMPLE_MAX_SIDE = 8192]";
     if (out_size < 1 || out_size > MIRX_RESAMPLE_MAX_RESIZED) return "resample: resized side outside [1, 2^24]";
-    if (resample_taps(in_size, out_size) > MIRX_RESAMPLE_MAX_TAPS) return "resample: tap count over the cap (MIRX_RESAMPLE_MAX_TAPS = 65: scale > 32)";
+    if (resample_taps(in_size, out_size, filter) > MIRX_RESAMPLE_MAX_TAPS)
+        return filter == MIRX_RESAMPLE_BILINEAR ? "resample: tap count over the cap (MIRX_RESAMPLE_MAX_TAPS = 65: scale > 32)"
+                                                : "resample: tap count over the cap (MIRX_RESAMPLE_MAX_TAPS = 65: bicubic scale > 16)";
     return nullptr;
 }
 
-int mirx_resample_taps(int in_size, int out_size) {
-    if (const char *msg = resample_axis_limits(in_size, out_size)) return fail(MIRX_EINVAL, msg);
-    return resample_taps(in_size, out_size);
+int mirx_resample_taps_filter(int in_size, int out_size, int filter) {
+    if (const char *msg = resample_axis_limits(in_size, out_size, filter)) return fail(MIRX_EINVAL, msg);
+    return resample_taps(in_size, out_size, filter);
 }
 
-int mirx_resample_plan(int in_size, int out_size, int first, int n, int32_t *table, int64_t table_words) {
-    if (const char *msg = resample_axis_limits(in_size, out_size)) return fail(MIRX_EINVAL, msg);
+int mirx_resample_plan_filter(int in_size, int out_size, int first, int n, int filter, int32_t *table, int64_t table_words) {
+    if (const char *msg = resample_axis_limits(in_size, out_size, filter)) return fail(MIRX_EINVAL, msg);
     MIRX_CHECK(n >= 1 && n <= MIRX_RESAMPLE_MAX_OUT && first >= 0 && first <= out_size - n,
                "resample_plan: the window [first, first + n) must lie inside the resized axis, n in [1, 1024]");
     MIRX_CHECK(table && aligned_to(table, 4), "resample_plan: null or misaligned table");
-    MIRX_CHECK(table_words >= 4 + 2 * (int64_t)n + (int64_t)n * resample_taps(in_size, out_size),
+    MIRX_CHECK(table_words >= 4 + 2 * (int64_t)n + (int64_t)n * resample_taps(in_size, out_size, filter),
                "resample_plan: table smaller than 4 + 2 n + n * mirx_resample_taps()");
-    resample_plan(in_size, out_size, first, n, table);
+    resample_plan(in_size, out_size, first, n, filter, table);
     return MIRX_OK;
+}
+
+int mirx_resample_taps(int in_size, int out_size) { return mirx_resample_taps_filter(in_size, out_size, MIRX_RESAMPLE_BILINEAR); }
+
+int mirx_resample_plan(int in_size, int out_size, int first, int n, int32_t *table, int64_t table_words) {
+    return mirx_resample_plan_filter(in_size, out_size, first, n, MIRX_RESAMPLE_BILINEAR, table, table_words);
 }
 
 int mirx_resample_batch(const void *blob_host, const void *blob_dev, int64_t blob_bytes, int64_t b, int s, int out_kind,

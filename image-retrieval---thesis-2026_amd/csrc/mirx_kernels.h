@@ -130,9 +130,10 @@ int64_t sbsm_workspace_bytes(int64_t rows, int nr, int w);
 hipError_t launch_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv, int nr, const int32_t *col_iv, int nc, int h,
                                   int w, void *workspace, float *sal, hipStream_t st);
 
-// ---- k_resample.hip: batched Resize + CenterCrop of 8-bit images, bit-equal to Pillow's BILINEAR (include/mirx.h) ----
-int resample_taps(int in_size, int out_size);                                          // host only
-void resample_plan(int in_size, int out_size, int first, int n, int32_t *table);       // host only; taps <= MIRX_RESAMPLE_MAX_TAPS
+// ---- k_resample.hip: batched Resize + CenterCrop of 8-bit images, bit-equal to Pillow's BILINEAR / BICUBIC (include/mirx.h) ----
+// filter = MIRX_RESAMPLE_BILINEAR or MIRX_RESAMPLE_BICUBIC (checked by the caller)
+int resample_taps(int in_size, int out_size, int filter);                                          // host only
+void resample_plan(int in_size, int out_size, int first, int n, int filter, int32_t *table);       // host only; taps <= MIRX_RESAMPLE_MAX_TAPS
 const char *resample_check(const void *blob_host, int64_t blob_bytes, int64_t b, int s, int64_t *lds);   // host only; null = fine
 hipError_t launch_resample(const void *blob_dev, int64_t b, int s, int out_f32, const float *mean3, const float *std3, void *out,
                            int64_t lds, hipStream_t st);

@@ -6,21 +6,23 @@ attributes that take a LIST of PIL images of any mix of sizes and return the who
     tf.batch_pixels(images, device) -> uint8   [B, 3, S, S]      what tf.pixels(img) returns, stacked
     tf.batch(images, device)        -> float32 [B, 3, S, S]      what tf(img) returns, stacked
 
-Both equal the host path byte for byte (mirx_resample_batch, DESIGN 28: Pillow's BILINEAR for 8-bit images restated as a host
-plan of integer coefficients plus one integer kernel).  Which path an image takes is decided from what can be observed, with no
-option and no environment variable:
+Both equal the host path byte for byte (mirx_resample_batch, DESIGN 28 and 30: Pillow's BILINEAR and BICUBIC for 8-bit images
+restated as a host plan of integer coefficients plus one integer kernel), for the three shapes default_transform builds:
+Resize(int) + CenterCrop and the stretch Resize((S, S)) without a crop, each in either filter.  Which path an image takes is
+decided from what can be observed, with no option and no environment variable:
 
     device path   the target device is CUDA, the image's mode is "RGB" or "L", its sides are within the kernel's caps (8192
-                  pixels, a scale of at most 32) and the resized image covers the crop (resize >= img_size)
+                  pixels, a scale of at most 32 per axis, 16 for bicubic) and, for Resize(int), the resized image covers the
+                  crop (resize >= img_size)
     host path     everything else -- other modes ("P", "RGBA", "I;16", "F", ...), CPU devices, oversize sources: tf.pixels / tf
                   on the host, copied into the image's slot.  It is the only path without a GPU and the tests' reference.
 
 `tf.last_preprocess` = {"device": n, "host": m} says how many images of the last batch took each path.
 
 The sources of a batch are packed with np.asarray into one reused pinned staging buffer together with their descriptors and
-coefficient tables (plans are cached by (w, h, resize, S); images of one size share their tables) and reach the device in ONE
-copy; an event recorded behind the kernel guards the staging buffer and its device twin until the next batch reuses them.
-A lock serialises the launches of concurrent callers.
+coefficient tables (plans are cached by (w, h, resize, S, filter); images of one size share their tables) and reach the device
+in ONE copy; an event recorded behind the kernel guards the staging buffer and its device twin until the next batch reuses
+them.  A lock serialises the launches of concurrent callers.
 """
 import ctypes
 import threading
@@ -33,6 +35,7 @@ from . import _lib as L
 _DEVICE_MODES = ("RGB", "L")
 _CHUNK_BYTES = 256 << 20           # sources per launch: bounds the pinned buffer (64 RGB images of 1024 x 1024 are 192 MiB)
 _PLAN_CACHE_MAX = 512
+_FILTERS = {"bilinear": L.RESAMPLE_BILINEAR, "bicubic": L.RESAMPLE_BICUBIC}
 _plans = {}
 _stages = {}
 _lock = threading.Lock()
@@ -42,9 +45,25 @@ def _round16(n):
     return (n + 15) & ~15
 
 
+def filter_name(interpolation):
+    """"bilinear" or "bicubic" from either name or from PIL's Image.BILINEAR / Image.BICUBIC; anything else raises ValueError."""
+    from PIL import Image
+    if isinstance(interpolation, str):
+        if interpolation.lower() in _FILTERS:
+            return interpolation.lower()
+    elif interpolation == Image.BILINEAR:
+        return "bilinear"
+    elif interpolation == Image.BICUBIC:
+        return "bicubic"
+    raise ValueError(f"interpolation must be 'bilinear' or 'bicubic' (or PIL's Image.BILINEAR / Image.BICUBIC), got {interpolation!r}")
+
+
 def resized_geometry(w, h, resize, size):
     """(nw, nh, left, top): torchvision's Resize(int) output size and CenterCrop offsets, the expressions of
-    retriever.default_transform (Python's round: half to even)."""
+    retriever.default_transform (Python's round: half to even).  resize = (size, size) is the stretch Resize((S, S)): the
+    whole resized image, no crop."""
+    if isinstance(resize, tuple):
+        return size, size, 0, 0
     if w <= h:
         nw, nh = resize, int(resize * h / w)
     else:
@@ -52,16 +71,18 @@ def resized_geometry(w, h, resize, size):
     return nw, nh, int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
 
 
-def axis_table(in_size, out_size, first, n):
-    """The library's plan of one axis and crop window (mirx_resample_plan): int32 [4 + 2 n + n taps] padded to 16 bytes, or None
-    when the axis is over a cap."""
+def axis_table(in_size, out_size, first, n, interpolation="bilinear"):
+    """The library's plan of one axis and crop window (mirx_resample_plan_filter): int32 [4 + 2 n + n taps] padded to 16 bytes,
+    or None when the axis is over a cap."""
     lib = L.load()
-    taps = lib.mirx_resample_taps(int(in_size), int(out_size))
+    filt = _FILTERS[filter_name(interpolation)]
+    taps = lib.mirx_resample_taps_filter(int(in_size), int(out_size), filt)
     if taps < 0:
         return None
     words = 4 + 2 * n + n * taps
     table = np.zeros((words + 3) & ~3, dtype=np.int32)
-    L.check(lib.mirx_resample_plan(int(in_size), int(out_size), int(first), int(n), table.ctypes.data, words), "mirx_resample_plan")
+    L.check(lib.mirx_resample_plan_filter(int(in_size), int(out_size), int(first), int(n), filt, table.ctypes.data, words),
+            "mirx_resample_plan_filter")
     return table
 
 
@@ -71,18 +92,24 @@ def table_parts(table):
     return taps, table[4:4 + 2 * n].reshape(n, 2), table[4 + 2 * n:4 + 2 * n + n * taps].reshape(n, taps)
 
 
-def plan(w, h, resize, size):
+def plan(w, h, resize, size, interpolation="bilinear"):
     """(x table, y table) for a w x h source, or None when the device path does not take it (a cap, or a crop window that
-    reaches outside the resized image).  Cached."""
-    key = (w, h, resize, size)
+    reaches outside the resized image).  resize is the int of Resize(int) + CenterCrop(size), or (size, size) for the stretch
+    (each axis planned over the whole output with its own scale).  Cached."""
+    interpolation = filter_name(interpolation)
+    if isinstance(resize, (tuple, list)):
+        if tuple(resize) != (size, size):
+            raise ValueError(f"a resize pair must be (size, size) = ({size}, {size}), got {resize!r}")
+        resize = (size, size)
+    key = (w, h, resize, size, interpolation)
     if key in _plans:
         return _plans[key]
     got = None
     nw, nh, left, top = resized_geometry(w, h, resize, size)
     if (1 <= w <= L.RESAMPLE_MAX_SIDE and 1 <= h <= L.RESAMPLE_MAX_SIDE and 1 <= size <= L.RESAMPLE_MAX_OUT
             and left >= 0 and top >= 0 and left + size <= nw and top + size <= nh):
-        xt = axis_table(w, nw, left, size)
-        yt = axis_table(h, nh, top, size) if xt is not None else None
+        xt = axis_table(w, nw, left, size, interpolation)
+        yt = axis_table(h, nh, top, size, interpolation) if xt is not None else None
         if yt is not None:
             _, yb, _ = table_parts(yt)
             span = max(int((yb[y0:y0 + L.RESAMPLE_TILE_H].sum(axis=1)).max() - yb[y0:y0 + L.RESAMPLE_TILE_H, 0].min())
@@ -170,7 +197,7 @@ def resample_into(items, size, out, mean=None, std=None):
         _launch(stage, items, size, f32, norm, out)
 
 
-def _run(tf, images, device, size, resize, f32, norm):
+def _run(tf, images, device, size, resize, interpolation, f32, norm):
     dev = torch.device(device)
     images = list(images)
     dtype = torch.float32 if f32 else torch.uint8
@@ -179,7 +206,7 @@ def _run(tf, images, device, size, resize, f32, norm):
     if dev.type == "cuda":
         for i, im in enumerate(images):
             if getattr(im, "mode", None) in _DEVICE_MODES:
-                p = plan(im.size[0], im.size[1], resize, size)
+                p = plan(im.size[0], im.size[1], resize, size, interpolation)
                 if p is not None:
                     on_dev.append((i, im, p))
     tf.last_preprocess = {"device": len(on_dev), "host": len(images) - len(on_dev)}
@@ -210,13 +237,13 @@ def _run(tf, images, device, size, resize, f32, norm):
         return out
 
 
-def attach(tf, img_size, resize):
+def attach(tf, img_size, resize, interpolation="bilinear"):
     """Give a default_transform function its batch attributes (see the module docstring)."""
     def batch_pixels(images, device):
-        return _run(tf, images, device, img_size, resize, False, (None, None))
+        return _run(tf, images, device, img_size, resize, interpolation, False, (None, None))
 
     def batch(images, device):
-        return _run(tf, images, device, img_size, resize, True, (tf.mean, tf.std))
+        return _run(tf, images, device, img_size, resize, interpolation, True, (tf.mean, tf.std))
 
     tf.batch_pixels, tf.batch = batch_pixels, batch
     tf.last_preprocess = {"device": 0, "host": 0}

@@ -225,13 +225,25 @@ IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 SIGLIP_MEAN, SIGLIP_STD = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
 
 
-def default_transform(img_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize=None):
+def default_transform(img_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize=None, interpolation="bilinear"):
     """convert('RGB') -> Resize(shorter side) -> CenterCrop -> ToTensor -> Normalize(mean, std): the pipeline of
     milvus_retrieval.py:176-198 without torchvision (PIL + torch only).  Resize defaults follow the reference
     (448 -> 512, 384 -> 432, otherwise 256); MedSigLIP normalises with mean = std = 0.5 (milvus_retrieval.py:177-178),
-    every other model with the ImageNet statistics."""
+    every other model with the ImageNet statistics.
+
+    resize = (img_size, img_size) is the drivers' square stretch instead, Resize((S, S)) without a crop (test.py:1323,
+    evaluate_saliency.py:249, test_ath.py:18, ...); any other pair raises ValueError.  interpolation is "bilinear" or
+    "bicubic" (PIL's Image.BILINEAR / Image.BICUBIC are accepted): Resize(S + 32, BICUBIC) + CenterCrop(S) is
+    get_transforms_medsiglip (compute_saliency.py:131-148), Resize((384, 384), BICUBIC) compute_saliency_convnextv2.py:154."""
+    from .preprocess import attach, filter_name
+    interpolation = filter_name(interpolation)
     if resize is None:
         resize = {448: 512, 384: 432}.get(img_size, 256)
+    stretch = isinstance(resize, (tuple, list))
+    if stretch:
+        if tuple(resize) != (img_size, img_size):
+            raise ValueError(f"resize must be an int or the pair (img_size, img_size) = ({img_size}, {img_size}), got {resize!r}")
+        resize = (img_size, img_size)
     # numpy float32 arithmetic (the same IEEE operations as ToTensor + Normalize, bit for bit): torch's CPU operators cost
     # 10+ ms per call on a 150 k-element image when the intra-op thread pool is larger than the cores the process may use
     mean = np.asarray(mean, dtype=np.float32).reshape(3, 1, 1)
@@ -240,13 +252,16 @@ def default_transform(img_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize
     def pixels(img):
         """convert -> Resize -> CenterCrop: the 8-bit pixels [3, S, S] that ToTensor + Normalize would then turn into floats"""
         from PIL import Image
+        flt = Image.BICUBIC if interpolation == "bicubic" else Image.BILINEAR
         img = img.convert("RGB")
+        if stretch:
+            return np.ascontiguousarray(np.asarray(img.resize(resize, flt), dtype=np.uint8).transpose(2, 0, 1))
         w, h = img.size
         if w <= h:
             nw, nh = resize, int(resize * h / w)
         else:
             nw, nh = int(resize * w / h), resize
-        img = img.resize((nw, nh), Image.BILINEAR)
+        img = img.resize((nw, nh), flt)
         left, top = int(round((nw - img_size) / 2.0)), int(round((nh - img_size) / 2.0))
         img = img.crop((left, top, left + img_size, top + img_size))
         return np.ascontiguousarray(np.asarray(img, dtype=np.uint8).transpose(2, 0, 1))
@@ -261,9 +276,9 @@ def default_transform(img_size=224, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize
     tf.pixels = pixels
     tf.mean, tf.std = tuple(float(v) for v in mean.ravel()), tuple(float(v) for v in std.ravel())
     # tf.batch_pixels(images, device) / tf.batch(images, device): the same two results for a list of images, resized on the
-    # device in one launch and bit-equal to the above; tf.last_preprocess counts the images per path (mirx.preprocess)
-    from .preprocess import attach
-    return attach(tf, img_size, resize)
+    # device in one launch and bit-equal to the above; tf.last_preprocess counts the images per path (mirx.preprocess, DESIGN 28,
+    # 30)
+    return attach(tf, img_size, resize, interpolation)
 
 
 class MilvusRetriever:

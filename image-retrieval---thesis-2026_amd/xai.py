@@ -286,3 +286,12 @@ from .simatt import SimAtt, simatt_maps, simatt_pairs  # noqa: E402,F401
 from .insdel import GaussianBlur, InsDel, InsDelResult, insdel_curves  # noqa: E402,F401
 # SBSM occlusion saliency on interval-described window sets (explanations.py:15-152), native on CUDA float32 images: sbsm.py
 from .sbsm import grid_of_masks, sbsm_accumulate, sbsm_compose, sbsm_gain, window_intervals  # noqa: E402,F401
+
+
+def get_transforms_medsiglip(img_size=224):
+    """(None, val_transform) of compute_saliency.py:131-148 / evaluate_saliency.py:13-31, so the drivers'
+    `_, tf = get_transforms_medsiglip(...)` runs as written: Resize(img_size + 32, BICUBIC) + CenterCrop(img_size) + ToTensor().
+    (u / 255 - 0) / 1 is u / 255 bit for bit, so ToTensor alone is default_transform with mean 0 and std 1; batches are
+    resized on the device (tf.batch).  The training transform is out of scope."""
+    from .retriever import default_transform
+    return None, default_transform(img_size, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), resize=img_size + 32, interpolation="bicubic")

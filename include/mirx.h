@@ -1144,6 +1144,15 @@ int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv
  * mirx_resample_plan: fills `table` (HOST int32 [4 + 2 n + n * taps]) for the outputs [first, first + n) of the axis, the crop
  *   window: {taps, n, in_size, 0}, bounds [n][2] = (first tap, tap count), coefficients [n][taps] (zero past the count).  Host
  *   only, no HIP call; double arithmetic in the order above, compiled without contraction.
+ * mirx_resample_taps_filter, mirx_resample_plan_filter: the same two for a named filter.  Pillow computes every
+ *   filter F of support `sup` the same way: support = sup * fs, taps [max(0, (int)(c - support + 0.5)), min(in_size,
+ *   (int)(c + support + 0.5))), weights F((x - c + 0.5) * (1 / fs)) summed in tap order and divided by the sum, coefficients
+ *   (int)(0.5 + w * 2^22) for w >= 0 and (int)(-0.5 + w * 2^22) for w < 0, (int)ceil(support) * 2 + 1 slots per output.
+ *   MIRX_RESAMPLE_BILINEAR: sup = 1, the triangle above; its tables equal mirx_resample_plan's byte for byte (header word 3 = 0).
+ *   MIRX_RESAMPLE_BICUBIC: sup = 2, a = -0.5, x = |x|: x < 1: ((a + 2) x - (a + 3)) x x + 1; x < 2: (((x - 5) x + 8) x - 4) a;
+ *   else 0, in this association, one operation per statement; header word 3 = 1.  With first = 0, n = out_size and one call
+ *   per axis, each with its own sizes, the tables describe Resize((s, s)) without a crop.  taps <= MIRX_RESAMPLE_MAX_TAPS
+ *   stops bicubic at a scale of 16.  Any other filter: MIRX_EINVAL.
  * mirx_resample_batch: one launch for b images of any mix of sizes -> out = device [b, 3, s, s], uint8 (MIRX_RESAMPLE_OUT_U8:
  *   the pixels a model that normalises 8-bit input itself takes) or fp32 (MIRX_RESAMPLE_OUT_F32: (u / 255 - mean[c]) / std[c],
  *   IEEE fp32, correctly rounded division; mean3 / std3 = HOST float [3], unused for uint8).  Everything the kernel reads is one
@@ -1155,7 +1164,9 @@ int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv
  *   this s and this image's side, every tap range inside [0, w) or [0, h), every coefficient >= 0 and every run's sum <= 2^23
  *   (so the 32-bit sums cannot overflow), the LDS of the largest tile (x coefficients + the source rows a 16-row tile taps, 32
  *   columns, 8 bits) <= MIRX_RESAMPLE_MAX_LDS.  Output alignment: 4 elements when s % 4 == 0 (vector stores), 1 otherwise.
- *   out must not overlap blob_dev.
+ *   out must not overlap blob_dev.  A table names its filter in header word 3: for MIRX_RESAMPLE_BICUBIC coefficients may be
+ *   negative and the rule on a run is sum |coeff| <= 2^23 (255 * 2^23 + 2^21 < 2^31 either way); any other value than the two
+ *   filters, or an image whose x and y tables name different filters, is refused.
  * Caps: source side <= MIRX_RESAMPLE_MAX_SIDE, taps <= MIRX_RESAMPLE_MAX_TAPS (scale <= 32: an 8192-pixel side at resize 256), s
  * <= MIRX_RESAMPLE_MAX_OUT, b <= MIRX_RESAMPLE_MAX_BATCH.  Anything over a cap, or failing a check: MIRX_EINVAL with a message,
  * nothing launched.  One stream, no host synchronisation, no atomic.
@@ -1172,8 +1183,12 @@ int mirx_sbsm_accumulate(const double *gain, int64_t rows, const int32_t *row_iv
 #define MIRX_RESAMPLE_DESC_WORDS 8
 #define MIRX_RESAMPLE_OUT_U8 0
 #define MIRX_RESAMPLE_OUT_F32 1
+#define MIRX_RESAMPLE_BILINEAR 0
+#define MIRX_RESAMPLE_BICUBIC 1
 int mirx_resample_taps(int in_size, int out_size);
 int mirx_resample_plan(int in_size, int out_size, int first, int n, int32_t *table, int64_t table_words);
+int mirx_resample_taps_filter(int in_size, int out_size, int filter);
+int mirx_resample_plan_filter(int in_size, int out_size, int first, int n, int filter, int32_t *table, int64_t table_words);
 int mirx_resample_batch(const void *blob_host, const void *blob_dev, int64_t blob_bytes, int64_t b, int s, int out_kind,
                         const float *mean3, const float *std3, void *out, void *stream);
 

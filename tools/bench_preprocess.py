@@ -1,6 +1,6 @@
-"""Device-side Resize / CenterCrop against the host path, on one GPU, in one process (DESIGN 28).
+"""Device-side Resize / CenterCrop against the host path, on one GPU, in one process (DESIGN 28, 30).
 
-    python tools/bench_preprocess.py [--rows 200000] [--window 0.3] [--windows 3] [--out profiles/<name>.txt]
+    python tools/bench_preprocess.py [--rows 200000] [--window 0.3] [--windows 3] [--only all|base|forms] [--out profiles/<name>.txt]
 
 The device path is default_transform as it is (tf.batch_pixels / tf.batch: mirx.preprocess, mirx_resample_batch).  The host path
 is the same transform with its batch attributes removed, which sends every call site down the code it had before they existed
@@ -15,6 +15,9 @@ the spread (max - min) / median of either path.
   encode_npy_paths  one chunk of 64 .npy files of 1024 x 1024 through the ConvNeXtV2 NIH model at 384 (resize 432)
   kernel, copy      per source and for the 64-image batches: the launch alone and the host-to-device copy alone, each between
                     device events (median of 20 after 3 warm-up runs)
+  forms the square stretch and BICUBIC, same model and gallery, each transform against itself without its batch
+                    attributes: search 300 x 280 RGB stretched to 224; search 1024 x 1024 L, bicubic 480 -> 448; search
+                    2048 x 2500 L, bicubic stretch to 384; batch_search of 64 x 1024 x 1024 L, bicubic stretch to 384
 One JSON line per case; --out also writes everything to a file."""
 import argparse
 import json
@@ -85,13 +88,13 @@ def _events(fn, reps=20, warm=3):
     return statistics.median(ms)
 
 
-def kernel_and_copy(name, images, resize, size, f32):
+def kernel_and_copy(name, images, resize, size, f32, interpolation="bilinear"):
     """The launch alone and the copy alone for one packed batch."""
     from mirx import _lib as L
     from mirx import preprocess as P
     from mirx.retriever import IMAGENET_MEAN, IMAGENET_STD
     import ctypes
-    items = [(im, P.plan(im.size[0], im.size[1], resize, size)) for im in images]
+    items = [(im, P.plan(im.size[0], im.size[1], resize, size, interpolation)) for im in images]
     tables, layout, nbytes = P.blob_layout(items)
     pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
     P.blob_fill(pinned.numpy(), items, tables, layout)
@@ -115,11 +118,42 @@ def kernel_and_copy(name, images, resize, size, f32):
             "copy_ms": round(t_copy, 4), "host_pack_ms": round(t_pack, 4)}
 
 
+def forms(args, emit, mgr, model):
+    """The rows of DESIGN 30: each new shape on the device path against the same transform on the host path."""
+    from mirx.retriever import MilvusRetriever, default_transform
+    cases = [("search 300x280 RGB, stretch to 224", _image(300, 280, "RGB", 0), 1, dict(img_size=224, resize=(224, 224))),
+             ("search 1024x1024 L, bicubic 480 -> 448", _image(1024, 1024, "L", 1), 1,
+              dict(img_size=448, resize=480, interpolation="bicubic")),
+             ("search 2048x2500 L, bicubic stretch to 384", _image(2048, 2500, "L", 2), 1,
+              dict(img_size=384, resize=(384, 384), interpolation="bicubic")),
+             ("batch_search 64 x 1024x1024 L, bicubic stretch to 384", _image(1024, 1024, "L", 1), 64,
+              dict(img_size=384, resize=(384, 384), interpolation="bicubic"))]
+    for name, img, count, kw in cases:
+        r_dev = MilvusRetriever(mgr, "densenet121", model, default_transform(**kw))
+        r_host = MilvusRetriever(mgr, "densenet121", model, _host_only(default_transform(**kw)))
+        r_dev.load_collection()
+        r_host.load_collection()
+        if count == 1:
+            a, qa = r_dev.search(img, top_k=10)
+            b, qb = r_host.search(img, top_k=10)
+            assert a == b and torch.equal(qa, qb), name
+            dev_fn, host_fn = (lambda: r_dev.search(img, top_k=10)), (lambda: r_host.search(img, top_k=10))
+        else:
+            batch = [img] * count
+            assert r_dev.batch_search(batch, top_k=10) == r_host.batch_search(batch, top_k=10), name
+            dev_fn, host_fn = (lambda: r_dev.batch_search(batch, top_k=10)), (lambda: r_host.batch_search(batch, top_k=10))
+        assert r_dev.last_preprocess == {"device": count, "host": 0}, name
+        emit(_ab(name, dev_fn, host_fn, args))
+        emit(kernel_and_copy("kernel " + name.split(" ", 1)[1], [img] * count, kw["resize"], kw["img_size"], count > 1,
+                             kw.get("interpolation", "bilinear")))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=200_000)
     ap.add_argument("--window", type=float, default=0.3)
     ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--only", choices=("all", "base", "forms"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from mirx import nih
@@ -132,7 +166,13 @@ def main():
         lines.append(json.dumps(rec))
         print(lines[-1], flush=True)
 
-    emit({"device": torch.cuda.get_device_name(0), "rows": args.rows, "window_s": args.window, "windows": args.windows})
+    def finish():
+        if args.out:
+            with open(args.out, "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+
+    emit({"device": torch.cuda.get_device_name(0), "rows": args.rows, "window_s": args.window, "windows": args.windows,
+          "only": args.only})
     torch.manual_seed(0)
     model = DenseNet121().eval().to(dev)
     mgr = MilvusManager(device=0)
@@ -144,6 +184,10 @@ def main():
         n = min(50_000, args.rows - s0)
         emb = torch.nn.functional.normalize(torch.randn((n, 1024), generator=g, device=dev), dim=1)
         col.insert([[f"img_{s0 + i}.png" for i in range(n)], ["normal"] * n, emb])
+    if args.only in ("all", "forms"):
+        forms(args, emit, mgr, model)
+    if args.only == "forms":
+        return finish()
     r_dev = MilvusRetriever(mgr, "densenet121", model, default_transform(224))
     r_host = MilvusRetriever(mgr, "densenet121", model, _host_only(default_transform(224)))
     r_dev.load_collection()
@@ -190,9 +234,7 @@ def main():
         for p in paths:
             nih.load_npy_as_pil(p)
         emit({"case": "load_npy_as_pil 64 files (both paths pay it)", "ms": round((time.perf_counter() - t0) * 1e3, 3)})
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    finish()
 
 
 if __name__ == "__main__":
