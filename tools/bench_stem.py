@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times the two-fp16-term DenseNet stem (development tool): ms per 1024 images; with MIRX_LIB_PATH pointing at a diagnostic
-build (-DMIRX_STEM_EXP=1 no K loop, 2 no conv-tile epilogue, 4 no pooling) it shows what each phase costs."""
+build (-DMIRX_STEM_EXP=1 no K loop, 2 no conv-tile epilogue, 4 no pooling, 8 no weight DMA; -DMIRX_STEM_NCH=3 / 4: three / two
+workgroups per CU) it shows what each phase costs."""
 import ctypes
 import os
 import sys
