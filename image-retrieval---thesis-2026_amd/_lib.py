@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MIRX_LIB_PATH", os.path.join(_HERE, "libmirx.so"))   # override: kernel experiments only
 
 METRIC_IP = 0
+ESTATE = -4                        # MIRX_ESTATE: call not valid in the index's current state
 METRIC_NEG_L2 = 1
 TIER_AUTO = 0
 TIER_EXACT_ONLY = 3
@@ -18,6 +19,7 @@ OPT_SAMPLE_RANK = 2
 OPT_FORCE_TAU = 3
 OPT_PROFILE = 4
 OPT_RANK_SORT = 5                  # which sort rank_all runs
+OPT_COMPACT_CHUNK_ROWS = 6         # test hook: rows per compaction chunk of mirx_index_remove_ids (0 = default)
 RANK_SORT_AUTO = 0                 # bitonic up to 65536 rows, radix above
 RANK_SORT_BITONIC = 1
 RANK_SORT_RADIX = 2
@@ -74,6 +76,8 @@ SYMBOLS = {
     "mirx_index_dim": (_int, [_vp]),
     "mirx_index_set_option": (_int, [_vp, _int, _i64]),
     "mirx_index_get_rows": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "mirx_index_remove_ids": (_int, [_vp, _vp, _i64, ctypes.POINTER(_i64), _vp]),
+    "mirx_compact_tile": (_int, []),
     "mirx_index_search": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "mirx_index_search_f64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "mirx_index_search_begin": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),

@@ -124,33 +124,37 @@ class MilvusCollectionAdapter:
         self.collection = collection
 
     # -- metadata ------------------------------------------------------------------------------------------------
+    # Rows are read through the collection's accessors (field / live_ids / entity / position): deleted rows do not show.
     def _paths(self):
-        return self.collection._meta[self.config.image_path_field]
+        return self.collection.field(self.config.image_path_field)
 
     def list_image_paths(self, batch_size=1000):
         return [p for p in self._paths() if p]
 
-    def _row(self, i, include_embedding, vec=None):
+    def _row(self, pos, include_embedding, vec=None):
+        """the live row at index position `pos`"""
         cfg = self.config
+        i = int(self.collection.live_ids()[pos])
+        meta = self.collection.entity(i)
         row = {cfg.id_field: i}
         for f in cfg.output_fields:
-            if f in self.collection._meta:
-                row[f] = self.collection._meta[f][i]
-        row.setdefault(cfg.image_path_field, self._paths()[i])
-        if cfg.label_field in self.collection._meta:
-            row.setdefault(cfg.label_field, self.collection._meta[cfg.label_field][i])
+            if f in meta:
+                row[f] = meta[f]
+        row.setdefault(cfg.image_path_field, meta[cfg.image_path_field])
+        if cfg.label_field in meta:
+            row.setdefault(cfg.label_field, meta[cfg.label_field])
         if include_embedding:
             if vec is None:
-                vec = self.collection.index.rows(i, 1)[0][0].cpu().numpy()
+                vec = self.collection.index.rows(pos, 1)[0][0].cpu().numpy()
             row[cfg.vector_field] = vec
         return row
 
     def _rows_of(self, wanted):
-        """image_path -> list of row numbers, for the requested paths only."""
+        """image_path -> list of index positions, for the requested paths only."""
         hits = {}
-        for i, p in enumerate(self._paths()):
+        for pos, p in enumerate(self._paths()):
             if p in wanted:
-                hits.setdefault(p, []).append(i)
+                hits.setdefault(p, []).append(pos)
         return hits
 
     def fetch_record_by_image_path(self, image_path, include_embedding=True):

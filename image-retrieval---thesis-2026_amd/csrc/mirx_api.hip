@@ -76,13 +76,15 @@ struct mirx_index {
     bool ids_ascend = true;
     int64_t last_id = INT64_MIN;
     bool idperm_valid = false;
+    int64_t next_auto = 0;                // auto ids go on from here: past the rows removed since (never below `size`)
+    int64_t compact_chunk = 0;            // MIRX_OPT_COMPACT_CHUNK_ROWS; 0 = as many rows as COMPACT_SCRATCH_BYTES hold
     std::vector<hipEvent_t> ev_pool;      // lazily created, reused
     struct Span { int stage; hipEvent_t a, b; };
     std::vector<Span> spans;              // of the last search
     size_t ev_used = 0;
     // workspace
     DevBuf q32p, q16, qnorm, tau, cnt, cand, ovf_cnt, ovf, groupmax, fail_list, retry_list, tau2, q16r, taur,
-        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm;
+        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart;
     int *fail_count = nullptr;            // device
     mirx_search_stats *stats_dev = nullptr;
     int *fail_count_host = nullptr;       // pinned
@@ -101,6 +103,7 @@ struct mirx_index {
         mirx::FinalizeArgs fa{};
     } pend;
     hipEvent_t pend_ev = nullptr;
+    bool begun = false;                   // between mirx_index_search_begin and _end, whether or not a pass is pending
 };
 
 namespace {
@@ -109,6 +112,7 @@ constexpr int64_t QUERY_BATCH = 8192;          // queries per internal pass
 constexpr int64_t TIER1_MIN_ROWS = 32768;      // below this the exact scan answers directly
 constexpr int TIER1_MAX_K = 64;
 constexpr size_t EXACT_WS_BYTES = (size_t)1 << 30;   // fp64 score tile workspace per pass
+constexpr size_t COMPACT_SCRATCH_BYTES = (size_t)256 << 20;   // most a removal's chunk scratch takes by default
 
 struct DeviceGuard {
     int prev = -1;
@@ -614,7 +618,8 @@ void mirx_index_destroy(mirx_index *ix) {
     if (ix->pend_ev) (void)hipEventDestroy(ix->pend_ev);
     for (DevBuf *b : {&ix->q32p, &ix->q16, &ix->qnorm, &ix->tau, &ix->cnt, &ix->cand, &ix->ovf_cnt, &ix->ovf, &ix->groupmax,
                       &ix->fail_list, &ix->retry_list, &ix->tau2, &ix->q16r, &ix->taur, &ix->scores, &ix->stage,
-                      &ix->rankwork, &ix->spill, &ix->rkeys, &ix->rpay, &ix->rhist, &ix->idperm})
+                      &ix->rankwork, &ix->spill, &ix->rkeys, &ix->rpay, &ix->rhist, &ix->idperm, &ix->creq, &ix->cpos,
+                      &ix->cpart})
         b->release();
     delete ix;
 }
@@ -649,6 +654,10 @@ int mirx_index_set_option(mirx_index *ix, int option, int64_t value) {
             MIRX_CHECK(value == MIRX_RANK_SORT_AUTO || value == MIRX_RANK_SORT_BITONIC || value == MIRX_RANK_SORT_RADIX,
                        "set_option: rank sort must be 0 (auto), 1 (bitonic) or 2 (radix)");
             ix->rank_sort = (int)value;
+            return MIRX_OK;
+        case MIRX_OPT_COMPACT_CHUNK_ROWS:
+            MIRX_CHECK(value >= 0 && value <= 0x7FFFFF00ll, "set_option: compaction chunk rows out of range (0 = default)");
+            ix->compact_chunk = value;
             return MIRX_OK;
         default:
             return fail(MIRX_EINVAL, "set_option: unknown option");
@@ -692,7 +701,9 @@ int mirx_index_add(mirx_index *ix, const float *rows, int64_t n, const int64_t *
         }
     } else {
         host_ids.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) host_ids[(size_t)i] = ix->size + i;
+        const int64_t first = std::max(ix->next_auto, ix->size);   // == size until a removal shrinks it
+        for (int64_t i = 0; i < n; ++i) host_ids[(size_t)i] = first + i;
+        ix->next_auto = first + n;
         MIRX_HIP(hipMemcpy(ix->ids + ix->size, host_ids.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
         idh = host_ids.data();
     }
@@ -708,6 +719,72 @@ int mirx_index_add(mirx_index *ix, const float *rows, int64_t n, const int64_t *
     ix->size += n;
     return MIRX_OK;
 }
+
+int mirx_index_remove_ids(mirx_index *ix, const int64_t *ids, int64_t n, int64_t *out_removed_or_null, void *stream) {
+    MIRX_CHECK(ix && n >= 0 && (ids || n == 0), "remove_ids: bad argument");
+    MIRX_CHECK(n <= 0x7FFFFF00ll, "remove_ids: more than 2^31 ids in one request");
+    if (ix->pend.active || ix->begun)
+        return fail(MIRX_ESTATE, "remove_ids: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
+    if (out_removed_or_null) *out_removed_or_null = 0;
+    if (n == 0 || ix->size == 0) return MIRX_OK;
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "remove_ids: cannot select device");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t size = ix->size;
+    bool ids_dev = false;
+    is_device_pointer(ids, &ids_dev);
+    int64_t chunk = ix->compact_chunk;
+    if (chunk == 0)
+        chunk = std::max<int64_t>(ROW_ALIGN, (int64_t)(COMPACT_SCRATCH_BYTES / compact_scratch_bytes(1, ix->dimp)) / ROW_ALIGN * ROW_ALIGN);
+    chunk = std::min(chunk, size);
+    // every allocation before the first row moves: a failure leaves the index as it was
+    hipError_t e;
+    if ((e = ix->creq.ensure(ids_dev ? 0 : (size_t)n * sizeof(int64_t))) != hipSuccess ||
+        (e = ix->rkeys.ensure((size_t)2 * n * sizeof(uint64_t))) != hipSuccess ||
+        (e = ix->rpay.ensure((size_t)2 * n * sizeof(int32_t))) != hipSuccess ||
+        (e = ix->rhist.ensure((size_t)256 * rank_sort_tiles(n) * sizeof(unsigned))) != hipSuccess ||
+        (e = ix->cpos.ensure((size_t)(size + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ix->cpart.ensure((size_t)compact_tiles(size) * sizeof(int32_t))) != hipSuccess ||
+        (e = ix->stage.ensure(compact_scratch_bytes(chunk, ix->dimp))) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIRX_ENOMEM, std::string("remove_ids: ") + hipGetErrorString(e));
+    }
+    // the request as ascending keys (id ^ sign bit, duplicates and all), sorted on the device by the ranking's radix sort: what
+    // the membership kernel searches.  A host list is uploaded first; the copy is done with it when the call returns.
+    const int64_t *req = ids;
+    if (!ids_dev) {
+        MIRX_HIP(hipMemcpyAsync(ix->creq.p, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        req = ix->creq.as<int64_t>();
+    }
+    uint64_t *keys = ix->rkeys.as<uint64_t>();
+    MIRX_HIP(launch_rank_sort_build_ids(req, n, keys, ix->rpay.as<int32_t>(), st));
+    MIRX_HIP(launch_rank_sort(keys, ix->rpay.as<int32_t>(), keys + n, ix->rpay.as<int32_t>() + n, ix->rhist.as<unsigned>(), n, 1, st));
+    int32_t *pos = ix->cpos.as<int32_t>();
+    MIRX_HIP(launch_compact_scan(ix->ids, size, keys, n, pos, ix->cpart.as<int32_t>(), st));
+    int32_t kept32 = 0;
+    MIRX_HIP(hipMemcpyAsync(&kept32, pos + size, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    const int64_t kept = kept32;
+    if (kept < 0 || kept > size) return fail(MIRX_EHIP, "remove_ids: the scan returned an impossible count");
+    if (kept == size) return MIRX_OK;
+    for (int64_t c0 = 0; c0 < size; c0 += chunk)
+        MIRX_HIP(launch_compact_chunk(ix->g32, ix->g16, ix->ids, ix->gbias, ix->stage.p, chunk, pos, c0, std::min(size, c0 + chunk),
+                                      ix->dimp, st));
+    // rows from the new size up to the capacity read as zeros again (ids -1), as grow() left them
+    const size_t gone = (size_t)(size - kept);
+    MIRX_HIP(hipMemsetAsync(ix->g32 + kept * ix->dimp, 0, gone * ix->dimp * sizeof(float), st));
+    MIRX_HIP(hipMemsetAsync(ix->g16 + kept * ix->dimp, 0, gone * ix->dimp * sizeof(uint16_t), st));
+    MIRX_HIP(hipMemsetAsync(ix->ids + kept, 0xFF, gone * sizeof(int64_t), st));
+    MIRX_HIP(hipMemsetAsync(ix->gbias + kept, 0, gone * sizeof(float), st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    ix->next_auto = std::max(ix->next_auto, size);                      // auto ids handed out so far are never handed out again
+    ix->size = kept;
+    ix->idperm_valid = false;
+    if (out_removed_or_null) *out_removed_or_null = size - kept;
+    return MIRX_OK;
+}
+
+int mirx_compact_tile(void) { return COMPACT_TILE; }
 
 int mirx_index_get_rows(const mirx_index *ix, int64_t first, int64_t n, float *out_rows,
                         int64_t *out_ids_or_null) {
@@ -736,14 +813,17 @@ int mirx_index_search_f64(mirx_index *ix, const float *q, int64_t nq, int k,
 
 int mirx_index_search_begin(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                             float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream) {
-    return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids,
-                       reinterpret_cast<hipStream_t>(stream), /*wait_last=*/false);
+    const int rc = search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids,
+                               reinterpret_cast<hipStream_t>(stream), /*wait_last=*/false);
+    if (rc == MIRX_OK) ix->begun = true;
+    return rc;
 }
 
 int mirx_index_search_end(mirx_index *ix) {
     MIRX_CHECK(ix, "search_end: null index");
     DeviceGuard dg(ix->device);
     if (!dg.ok) return fail(MIRX_EHIP, "search_end: cannot select the index device");
+    ix->begun = false;
     return batch_back(ix);
 }
 

@@ -79,6 +79,8 @@ __host__ __device__ inline uint64_t rank_key(double s) {
 constexpr uint64_t RANK_KEY_LAST = ~0ull;
 // Elements one workgroup of the radix ranking's scatter orders at a time (mirx_rank_sort_tile, tests reach its boundaries).
 constexpr int RANK_TILE = 4096;
+// Rows one workgroup of the compaction's scan covers (mirx_compact_tile, tests reach its boundaries).
+constexpr int COMPACT_TILE = 2048;
 
 // CUs of the CURRENT device, cached per device (a process that drives several GPUs sizes every persistent grid for the one it
 // launches on).  Host threads launch concurrently: the cache is atomic, and two threads that both miss store the same value.

@@ -98,6 +98,19 @@ hipError_t launch_rank_sort_write(const int32_t *pay, int64_t n, int64_t kout, c
                                   const int64_t *ids, const int64_t *exclude, int drop_excluded, int metric, int nq,
                                   int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st);
 
+// ---- k_compact.hip: order-preserving removal of rows (mirx_index_remove_ids) -------------------------------------------------
+int64_t compact_tiles(int64_t n);                // COMPACT_TILE-row tiles of an n-row gallery
+size_t compact_scratch_bytes(int64_t chunk_rows, int dimp);
+// pos[r] (n + 1 entries) = rows in front of row r whose id is not in the request; pos[n] = the survivors.  req[0 .. nreq) = the
+// requested ids as keys id ^ sign bit, ascending as unsigned (launch_rank_sort_build_ids + launch_rank_sort), duplicates allowed.
+// part = compact_tiles(n) words.  Three launches: mark + tile sums, scan of the tile sums, apply.
+hipError_t launch_compact_scan(const int64_t *ids, int64_t n, const uint64_t *req, int64_t nreq, int32_t *pos, int32_t *part,
+                               hipStream_t st);
+// the survivors of source rows [c0, c1), c1 - c0 <= chunk_rows, to rows pos[c0] .. of g32 / g16 / ids / gbias through `scratch`
+// (compact_scratch_bytes): a gather launch, then a place launch.  Chunks must be issued in ascending order.
+hipError_t launch_compact_chunk(float *g32, uint16_t *g16, int64_t *ids, float *gbias, void *scratch, int64_t chunk_rows,
+                                const int32_t *pos, int64_t c0, int64_t c1, int dimp, hipStream_t st);
+
 // ---- k_anomaly.hip: class centroids, nearest-centroid distances, segmented binary ranking metrics (include/mirx.h) -----------
 int64_t an_chunk_rows(int64_t n, int d);          // rows per chunk of the centroid sums: a function of n and d alone
 int64_t class_centroids_workspace_bytes(int64_t n, int d, int k);

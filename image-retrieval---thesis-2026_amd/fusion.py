@@ -136,14 +136,15 @@ class CollectionEmbeddingSource(EmbeddingSource):
 
     def table(self):
         n = self.collection.num_entities
-        meta = self.collection._meta
         if n == 0:
             return _Table(self.name, [], [], np.zeros((0, self.collection.dim), np.float32))
         rows = self.collection.index.rows(0, n)[0].cpu().numpy()
-        keep = [i for i in range(n) if meta["image_path"][i] is not None]
-        labels = meta.get("label", [None] * n)
-        return _Table(self.name, [meta["image_path"][i] for i in keep], [labels[i] for i in keep], rows[keep],
-                      raw=[{"id": i} for i in keep])
+        # the live rows in index order, through the collection's accessors (deleted rows do not show)
+        ids, paths = self.collection.live_ids(), self.collection.field("image_path")
+        labels = self.collection.field("label") if self.collection.has_field("label") else [None] * n
+        keep = [p for p in range(n) if paths[p] is not None]
+        return _Table(self.name, [paths[p] for p in keep], [labels[p] for p in keep], rows[keep],
+                      raw=[{"id": int(ids[p])} for p in keep])
 
 
 MilvusEmbeddingSource = CollectionEmbeddingSource

@@ -90,6 +90,20 @@ class FlatIndex:
         _lib.check(self._lib.mirx_index_add(self._h, ctypes.c_void_p(rows.data_ptr()), rows.shape[0], idp),
                    "mirx_index_add")
 
+    def remove(self, ids):
+        """Remove every row whose id occurs in `ids` (tensor on the cpu or this GPU, or anything `torch.as_tensor` accepts);
+        ids that are absent are ignored, duplicates count once.  The survivors keep their order: searches afterwards equal
+        those of a fresh index built from them.  -> the number of rows removed."""
+        ids = torch.as_tensor(ids).detach().to(torch.int64).reshape(-1).contiguous()
+        if ids.is_cuda and ids.device != self.device:
+            ids = ids.to(self.device)
+        removed = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mirx_index_remove_ids(self._h, ctypes.c_void_p(ids.data_ptr()) if ids.numel() else None,
+                                                       ids.numel(), ctypes.byref(removed), _stream_ptr(self.device)),
+                       "mirx_index_remove_ids")
+        return int(removed.value)
+
     def _prep_queries(self, q, exclude_ids):
         q = torch.as_tensor(q)
         if q.dim() == 1:

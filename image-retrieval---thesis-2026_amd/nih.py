@@ -143,28 +143,62 @@ def _specs():
 BACKBONE_SPECS = _specs()
 
 _COLLECTIONS = {}        # name -> Collection: the in-process stand-in for the cluster's catalogue
+_STORED = {}             # (store root, name) -> Collection opened from / created in a mirx.store.Store
+
+
+def _as_store(store):
+    from .store import Store
+    return store if isinstance(store, Store) else Store(store)
 
 
 def create_nih_collection(collection_name, drop_old=False, metric_type="COSINE", index_type="IVF_FLAT", nlist=1024,
-                          device=None):
+                          device=None, store=None):
     """Schema id / image_path / image_name / label_text / label_vector_json / embedding[256]; index_type and nlist are
-    accepted for compatibility (the search is exhaustive)."""
+    accepted for compatibility (the search is exhaustive).  store: a mirx.store.Store or a directory -- the collection
+    persists there (flush() commits; another process finds it with get_nih_collection(name, store=...)); None keeps it in
+    this process."""
+    if store is None:
+        if drop_old:
+            _COLLECTIONS.pop(collection_name, None)
+        col = _COLLECTIONS.get(collection_name)
+        if col is None:
+            col = Collection(collection_name, EMBEDDING_DIM, "NIH multi-label gallery embeddings", metric_type=metric_type,
+                             device=device, extra_fields=_NIH_FIELDS, has_label=False)
+            _COLLECTIONS[collection_name] = col
+        col.load()
+        return col
+    store = _as_store(store)
+    key = (store.root, collection_name)
     if drop_old:
-        _COLLECTIONS.pop(collection_name, None)
-    col = _COLLECTIONS.get(collection_name)
+        _STORED.pop(key, None)
+        store.drop(collection_name)
+    col = _STORED.get(key)
     if col is None:
-        col = Collection(collection_name, EMBEDDING_DIM, "NIH multi-label gallery embeddings", metric_type=metric_type,
-                         device=device, extra_fields=_NIH_FIELDS, has_label=False)
-        _COLLECTIONS[collection_name] = col
+        schema = ["id", "image_path"] + list(_NIH_FIELDS) + ["embedding"]
+        if store.has(collection_name):
+            stored = store.open(collection_name, dim=EMBEDDING_DIM, schema=schema)
+        else:
+            stored = store.create(collection_name, EMBEDDING_DIM, metric_type, schema, "NIH multi-label gallery embeddings")
+        col = _STORED[key] = Collection.from_stored(stored, device=device)
     col.load()
     return col
 
 
-def get_nih_collection(collection_name):
-    """`Collection(name)` of the reference (query_nih_zilliz.py:30): an existing gallery by name."""
-    if collection_name not in _COLLECTIONS:
-        raise ValueError(f"Collection {collection_name} does not exist")
-    return _COLLECTIONS[collection_name]
+def get_nih_collection(collection_name, store=None):
+    """`Collection(name)` of the reference (query_nih_zilliz.py:30): an existing gallery by name -- of this process, or with
+    store= (a mirx.store.Store or a directory) one that any process flushed there.  Metadata is readable at once; search()
+    makes the rows resident."""
+    if store is None:
+        if collection_name not in _COLLECTIONS:
+            raise ValueError(f"Collection {collection_name} does not exist")
+        return _COLLECTIONS[collection_name]
+    store = _as_store(store)
+    key = (store.root, collection_name)
+    if key not in _STORED:
+        if not store.has(collection_name):
+            raise ValueError(f"Collection {collection_name} does not exist")
+        _STORED[key] = Collection.from_stored(store.open(collection_name), device=None)
+    return _STORED[key]
 
 
 def build_model_and_transform(model_name, checkpoint_path, backbone_name, device, num_labels=14):

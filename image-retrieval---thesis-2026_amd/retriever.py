@@ -16,6 +16,8 @@ Errors follow the reference: unknown model type -> ValueError; connect() swallow
 and returns False; everything else raises ordinary exceptions (callers wrap each query in
 try/except, evaluate_test_dataset_milvus.py:586-590).
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -53,11 +55,67 @@ class Hit:
         self.entity = _Entity(fields)
 
 
-class Collection:
-    """The slice of pymilvus.Collection the reference uses: insert / flush / load / search /
-    num_entities / name / description, backed by a FlatIndex."""
+class MutationResult:
+    """pymilvus' MutationResult as far as delete() is concerned: .delete_count."""
 
-    def __init__(self, name, dim, description="", metric_type="COSINE", device=None, extra_fields=(), has_label=True):
+    def __init__(self, delete_count):
+        self.delete_count = int(delete_count)
+
+    def __repr__(self):
+        return f"(delete count: {self.delete_count})"
+
+
+_DELETE_FORMS = 'id in [..], id == n, image_path in ["..", ..], image_path == ".."'
+
+
+def parse_delete_expr(expr):
+    """-> ("id", [int, ..]) or ("image_path", [str, ..]) for the pymilvus forms `id in [..]`, `id == n`,
+    `image_path in ["..", ..]` and `image_path == ".."`; ValueError for anything else."""
+    import ast
+    import re
+    if not isinstance(expr, str):
+        raise ValueError(f"delete: the expression must be a string, got {type(expr).__name__}")
+    text = expr.strip()
+    if not text:
+        raise ValueError("delete: empty expression")
+    m = re.match(r"^([A-Za-z_][A-Za-z0-9_]*)\s*(==|\bin\b)\s*(.+)$", text, flags=re.S)
+    if not m:
+        raise ValueError(f"delete: cannot parse {expr!r}: the supported forms are {_DELETE_FORMS}")
+    field, op, rhs = m.group(1), m.group(2), m.group(3).strip()
+    if field not in ("id", "image_path"):
+        raise ValueError(f"delete: cannot delete by field {field!r}: only id and image_path")
+    try:
+        value = ast.literal_eval(rhs)
+    except (ValueError, SyntaxError, MemoryError, RecursionError):
+        raise ValueError(f"delete: the right-hand side of {expr!r} is not a literal: the supported forms are {_DELETE_FORMS}") from None
+    if op == "in":
+        if not isinstance(value, list):
+            raise ValueError(f"delete: `{field} in` needs a [..] list, got {rhs!r}")
+        values = value
+    else:
+        if isinstance(value, (list, tuple, set, dict)):
+            raise ValueError(f"delete: `{field} ==` needs one value, got {rhs!r}")
+        values = [value]
+    want = int if field == "id" else str
+    for v in values:
+        if type(v) is not want:
+            raise ValueError(f"delete: {field} takes {'integers' if want is int else 'strings'}, got {v!r}")
+    return field, values
+
+
+class Collection:
+    """The slice of pymilvus.Collection the reference uses: insert / flush / load / search / delete / compact /
+    num_entities / name / description, backed by a FlatIndex.
+
+    In memory (stored=None) the index is the only copy of the rows.  With `stored` (a mirx.store.StoredCollection) the
+    collection is persistent: flush() commits inserts and deletions to disk, load() makes the rows resident, and metadata
+    (num_entities, schema, entity(), field()) is served from the host without a GPU.  Until load(), insert() and delete()
+    of a persistent collection touch no device either.
+
+    Rows are known by their int64 id.  Ids are assigned by insert(), ascending, and never reused: a deleted row's id stays
+    retired.  Metadata is read through entity() / field() / live_ids() / position(), which hide deleted rows."""
+
+    def __init__(self, name, dim, description="", metric_type="COSINE", device=None, extra_fields=(), has_label=True, stored=None):
         self.name = name
         self.description = description
         self.dim = dim
@@ -71,37 +129,160 @@ class Collection:
             self.schema = ["id", "image_path"] + list(extra_fields) + ["embedding"]
         self._device = device
         self._index = None
+        # one slot per row ever inserted and not yet compacted away: _ids[slot] (ascending), _meta[field][slot]; _dead = the
+        # ids of deleted slots.  While nothing was compacted away a row's id IS its slot (_slot_of is None).
         self._meta = {f: [] for f in self.schema if f not in ("id", "embedding")}
+        self._ids = []
+        self._dead = set()
+        self._slot_of = None
+        self._next_id = 0
+        self._live = None                                   # cache: ids of the live slots in order (numpy int64)
+        self._stored = stored
+        self._resident = stored is None                     # whether _index mirrors the live rows
 
+    @classmethod
+    def from_stored(cls, stored, device=None):
+        """The committed state of a mirx.store.StoredCollection; no row is read and no device touched before load()."""
+        col = cls(stored.name, stored.dim, stored.description, stored.metric_type, device, stored=stored)
+        col.schema = list(stored.schema)
+        col._meta = stored.read_columns()
+        col._ids = [int(i) for i in stored.read_ids()]
+        present = set(col._ids)
+        col._dead = {int(i) for i in stored.read_deleted()} & present
+        col._next_id = max(stored.next_id, col._ids[-1] + 1 if col._ids else 0)
+        if col._ids != list(range(len(col._ids))):
+            col._slot_of = {i: s for s, i in enumerate(col._ids)}
+        return col
+
+    # -- the one way to a row's metadata ---------------------------------------------------------------------------------
+    def _slot(self, id_):
+        """slot of a live id, else None"""
+        if id_ in self._dead:
+            return None
+        if self._slot_of is None:
+            return id_ if 0 <= id_ < len(self._ids) else None
+        return self._slot_of.get(id_)
+
+    def entity(self, id_, fields=None):
+        """{field: value} of the live row `id_` (every scalar field, or those of `fields` the schema has); None when the id
+        is unknown or deleted."""
+        s = self._slot(int(id_))
+        if s is None:
+            return None
+        return {f: self._meta[f][s] for f in (self._meta if fields is None else fields) if f in self._meta}
+
+    def live_ids(self):
+        """ids of the live rows in index order (numpy int64)"""
+        if self._live is None:
+            ids = np.asarray(self._ids, dtype=np.int64)
+            if self._dead:
+                ids = ids[~np.isin(ids, np.fromiter(self._dead, dtype=np.int64, count=len(self._dead)))]
+            self._live = ids
+        return self._live
+
+    def field(self, name):
+        """values of one scalar field for the live rows, in index order (aligned with live_ids())"""
+        col = self._meta[name]
+        if not self._dead:
+            return col
+        return [v for v, i in zip(col, self._ids) if i not in self._dead]
+
+    def has_field(self, name):
+        return name in self._meta
+
+    def position(self, id_):
+        """row number of the live row `id_` in the resident index (the p of index.rows(p, 1)), else None"""
+        if self._slot(int(id_)) is None:
+            return None
+        live = self.live_ids()
+        p = int(np.searchsorted(live, int(id_)))
+        return p if p < live.shape[0] and live[p] == int(id_) else None
+
+    def query(self, expr="id >= 0", output_fields=None, limit=None, offset=0):
+        """pymilvus' collection.query for the expressions this package meets: "id >= 0" (every live row, the paging loop of
+        ChestMIR/chestmir_eval.py:380-395) and the forms of delete().  -> row dicts with id and the output fields."""
+        if isinstance(expr, str) and expr.replace(" ", "") == "id>=0":
+            ids = self.live_ids()
+        else:
+            ids = np.asarray(self._match(expr), dtype=np.int64)
+        ids = ids[int(offset):] if limit is None else ids[int(offset):int(offset) + int(limit)]
+        fields = [f for f in (output_fields or []) if f != "id"]
+        return [dict(self.entity(int(i), fields), id=int(i)) for i in ids]
+
+    def _match(self, expr):
+        """live ids an expression of delete() names, ascending"""
+        field, values = parse_delete_expr(expr)
+        if field == "id":
+            return sorted({v for v in values if self._slot(v) is not None})
+        wanted = set(values)
+        return [int(i) for i, p in zip(self._ids, self._meta["image_path"]) if p in wanted and i not in self._dead]
+
+    # -- pymilvus surface ------------------------------------------------------------------------------------------------
     def _ensure(self):
+        if not self._resident:
+            self.load()
         if self._index is None:
             self._index = FlatIndex(self.dim, self.metric_type, self._device)
         return self._index
 
     @property
     def num_entities(self):
-        return len(self._meta["image_path"])
+        return len(self._ids) - len(self._dead)
 
     @property
     def index(self):
         return self._ensure()
 
+    @property
+    def is_persistent(self):
+        return self._stored is not None
+
     def create_index(self, field_name="embedding", index_params=None):
         metric = (index_params or {}).get("metric_type", self.metric_type)
-        if self._index is not None and len(self._index) and metric != self.metric_type:
+        if self._ids and metric != self.metric_type:
             raise ValueError("metric_type cannot change after rows were inserted")
         self.metric_type = metric
+        if self._stored is not None:
+            self._stored.set_metric(metric)
         return True
 
     def load(self):
-        self._ensure()
+        """Make the rows resident.  A collection opened from disk streams its file in bounded pieces (mirx.store.
+        LOAD_CHUNK_BYTES) into FlatIndex.add(rows, ids) with the stored ids, deleted rows dropped on the host."""
+        if self._resident:
+            if self._index is None:
+                self._index = FlatIndex(self.dim, self.metric_type, self._device)
+            return
+        index = FlatIndex(self.dim, self.metric_type, self._device)
+        index.reserve(self.num_entities)
+        dead = np.fromiter(self._dead, dtype=np.int64, count=len(self._dead)) if self._dead else None
+        for ids, rows in self._stored.chunks():
+            if dead is not None:
+                keep = ~np.isin(ids, dead)
+                ids, rows = ids[keep], rows[keep]
+            if ids.shape[0]:
+                index.add(torch.from_numpy(np.ascontiguousarray(rows)), torch.from_numpy(np.ascontiguousarray(ids)))
+        if len(index) != self.num_entities:
+            raise RuntimeError(f"{self.name}: {len(index)} rows loaded, {self.num_entities} live rows expected")
+        self._index, self._resident = index, True
+
+    def release(self):
+        """pymilvus' collection.release(): a persistent collection gives its device memory back (load() reads it again);
+        in memory the index is the only copy and stays."""
+        if self._stored is not None:
+            self._index, self._resident = None, False
 
     def flush(self):
+        """Commit inserts and deletions to disk (ingest_embeddings.py:532-534, "Flush to persist data"); in memory there is
+        nothing to commit.  Costs the rows added since the last flush; never rewrites old data (compact() does)."""
+        if self._stored is not None:
+            self._stored.flush()
         return None
 
     def insert(self, columns):
         """columns = one list per schema field after `id`, in schema order: [image_paths, labels, embeddings]
-        (ingest_embeddings.py:402-408) for the default schema.  Returns the assigned ids (auto_id: previous size + i)."""
+        (ingest_embeddings.py:402-408) for the default schema.  Returns the assigned ids (auto_id: one past the largest id
+        ever assigned, so the row number while nothing was deleted)."""
         fields = self.schema[1:]
         if len(columns) != len(fields):
             raise ValueError(f"expected {len(fields)} columns ({', '.join(fields)}), got {len(columns)}")
@@ -112,11 +293,52 @@ class Collection:
             raise ValueError(f"embedding dimension mismatch: expected {self.dim}, got {tuple(emb.shape)}")
         if any(len(c) != emb.shape[0] for c in cols.values()):
             raise ValueError("column lengths differ")
-        first = self.num_entities
-        self._ensure().add(emb)
+        cols = {f: ([str(p) for p in col] if f == "image_path" else list(col)) for f, col in cols.items()}
+        ids = list(range(self._next_id, self._next_id + emb.shape[0]))
+        if self._resident:
+            self._ensure().add(emb, torch.tensor(ids, dtype=torch.int64))
+        if self._stored is not None:
+            self._stored.append(ids, emb.detach().to(torch.float32).cpu().numpy(), cols)
         for f, col in cols.items():
-            self._meta[f].extend((str(p) for p in col) if f == "image_path" else col)
-        return list(range(first, first + emb.shape[0]))
+            self._meta[f].extend(col)
+        if self._slot_of is not None:
+            self._slot_of.update((i, len(self._ids) + k) for k, i in enumerate(ids))
+        self._ids.extend(ids)
+        self._next_id += emb.shape[0]
+        self._live = None
+        return ids
+
+    def delete(self, expr):
+        """pymilvus' collection.delete(expr) for `id in [..]`, `id == n`, `image_path in ["..", ..]` and
+        `image_path == ".."` (anything else: ValueError).  The rows leave the resident index at once (FlatIndex.remove) and
+        every metadata reader; a persistent collection commits the deletion with the next flush().  -> .delete_count = the
+        live rows removed."""
+        ids = self._match(expr)
+        if ids:
+            if self._resident and self._index is not None:
+                removed = self._index.remove(torch.tensor(ids, dtype=torch.int64))
+                if removed != len(ids):
+                    raise RuntimeError(f"{self.name}: the index removed {removed} rows for {len(ids)} live ids")
+            self._dead.update(ids)
+            self._live = None
+            if self._stored is not None:
+                self._stored.delete(ids)
+        return MutationResult(len(ids))
+
+    def compact(self):
+        """pymilvus' collection.compact(): forget the deleted rows' metadata and, for a persistent collection, rewrite its
+        files without them (includes a flush).  Deleted ids stay retired; the resident index is compact already."""
+        if self._stored is not None:
+            self._stored.compact()
+        if self._dead:
+            keep = [i not in self._dead for i in self._ids]
+            for f, col in self._meta.items():
+                self._meta[f] = [v for v, k in zip(col, keep) if k]
+            self._ids = [i for i, k in zip(self._ids, keep) if k]
+            self._dead = set()
+            self._slot_of = {i: s for s, i in enumerate(self._ids)}
+            self._live = None
+        return None
 
     def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None):
         """-> list (one per query) of lists of Hit, best first.  `distance` follows Milvus:
@@ -141,13 +363,38 @@ class Collection:
                 if i < 0 or not np.isfinite(sc[qi, j]):
                     continue
                 dist = float(sc[qi, j]) if self.metric_type in ("COSINE", "IP") else float(-sc[qi, j])
-                hits.append(Hit(i, dist, {f: self._meta[f][i] for f in fields if f in self._meta}))
+                hits.append(Hit(i, dist, self.entity(i, fields)))
             out.append(hits)
         return out
 
 
+_NETWORK_SCHEMES = ("http", "https", "tcp", "grpc")
+
+
+def store_root_of(uri):
+    """The directory a MilvusManager uri names, or None for "in memory": None and every uri with a network scheme (http,
+    https, tcp, grpc -- never contacted, this package opens no socket) keep the gallery in the process; a filesystem path
+    or a file:// uri names a mirx.store.Store."""
+    if uri is None or uri == "":
+        return None
+    uri = os.fspath(uri)
+    if "://" in uri:
+        from urllib.parse import unquote, urlparse
+        parts = urlparse(uri)
+        if parts.scheme.lower() in _NETWORK_SCHEMES:
+            return None
+        if parts.scheme.lower() != "file":
+            raise ValueError(f"uri {uri!r}: a filesystem path, a file:// uri or a {'/'.join(_NETWORK_SCHEMES)} uri is expected")
+        if parts.netloc not in ("", "localhost"):
+            raise ValueError(f"uri {uri!r}: a file:// uri names a local path")
+        return unquote(parts.path)
+    return uri
+
+
 class MilvusManager:
-    """Same surface as milvus_setup.MilvusManager; "connecting" binds a GPU instead of a server."""
+    """Same surface as milvus_setup.MilvusManager; "connecting" binds a GPU instead of a server.  With a filesystem path or
+    a file:// uri the collections persist in a mirx.store.Store under it; with uri=None or a network uri they live in this
+    object, as before, and nothing is written anywhere."""
 
     def __init__(self, uri=None, token=None, user="", password="", dataset="default", device=None):
         self.uri, self.token, self.user, self.password = uri, token, user, password
@@ -155,7 +402,16 @@ class MilvusManager:
         self.collections = {}
         self.device = device
         self._store = {}
+        root = store_root_of(uri)
+        self._disk = None
+        if root is not None:
+            from .store import Store
+            self._disk = Store(root)
         self.connected = False
+
+    @property
+    def is_persistent(self):
+        return self._disk is not None
 
     def get_model_config(self, model_type):
         if model_type not in MODEL_CONFIGS:
@@ -182,15 +438,44 @@ class MilvusManager:
     def disconnect(self):
         self.connected = False
 
+    # -- pymilvus.utility analogues (milvus_setup.py:150-158 uses has_collection / drop_collection) ------------------------
+    def has_collection(self, name):
+        return name in self._store or (self._disk is not None and self._disk.has(name))
+
+    def list_collections(self):
+        return sorted(set(self._store) | set(self._disk.names() if self._disk is not None else ()))
+
+    def drop_collection(self, name):
+        """Forget `name` (and remove it from disk for a persistent manager); a name that does not exist is no error."""
+        col = self._store.pop(name, None)
+        for model_type in [m for m, c in self.collections.items() if c is col or c.name == name]:
+            del self.collections[model_type]
+        if self._disk is not None:
+            self._disk.drop(name)
+
+    def _open(self, name):
+        """the collection `name` from this manager's catalogue (memory first, then disk), or None"""
+        if name not in self._store and self._disk is not None and self._disk.has(name):
+            self._store[name] = Collection.from_stored(self._disk.open(name), device=self.device)
+        return self._store.get(name)
+
     def create_collection(self, model_type, drop_old=False):
         config = self.get_model_config(model_type)
         name = config["collection_name"]
-        if drop_old and name in self._store:
-            del self._store[name]
-        if name not in self._store:
-            self._store[name] = Collection(name, config["embedding_dim"], config["description"], device=self.device)
-        self.collections[model_type] = self._store[name]
-        return self._store[name]
+        if drop_old:
+            self.drop_collection(name)
+        col = self._open(name)
+        if col is None:
+            stored = None
+            if self._disk is not None:
+                stored = self._disk.create(name, config["embedding_dim"], "COSINE", ["id", "image_path", "label", "embedding"],
+                                           config["description"])
+            col = Collection(name, config["embedding_dim"], config["description"], device=self.device, stored=stored)
+            self._store[name] = col
+        elif col.dim != config["embedding_dim"]:
+            raise ValueError(f"Collection {name} holds {col.dim}-dimensional rows, {model_type} embeds {config['embedding_dim']}")
+        self.collections[model_type] = col
+        return col
 
     def create_index(self, model_type, index_type="IVF_FLAT", metric_type="COSINE", nlist=1024):
         if model_type not in self.collections:
@@ -202,15 +487,20 @@ class MilvusManager:
     def load_collection(self, model_type):
         if model_type not in self.collections:
             name = self.get_model_config(model_type)["collection_name"]
-            if name not in self._store:
+            col = self._open(name)
+            if col is None:
                 raise ValueError(f"Collection {name} does not exist")
-            self.collections[model_type] = self._store[name]
+            self.collections[model_type] = col
         self.collections[model_type].load()
         return self.collections[model_type]
 
     def get_collection_info(self, model_type):
         if model_type not in self.collections:
-            self.load_collection(model_type)
+            name = self.get_model_config(model_type)["collection_name"]
+            col = self._open(name)
+            if col is None:
+                raise ValueError(f"Collection {name} does not exist")
+            self.collections[model_type] = col               # metadata only: nothing is loaded for it
         c = self.collections[model_type]
         return {"name": c.name, "num_entities": c.num_entities, "description": c.description, "schema": c.schema}
 

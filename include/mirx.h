@@ -56,6 +56,7 @@ extern "C" {
 #define MIRX_OPT_FORCE_TAU 3     /* test hook: float bits of a fixed threshold; 0x7fc00000 = off  */
 #define MIRX_OPT_PROFILE 4       /* 1: record HIP events around every stage of a search           */
 #define MIRX_OPT_RANK_SORT 5     /* which sort mirx_index_rank_all runs: MIRX_RANK_SORT_*          */
+#define MIRX_OPT_COMPACT_CHUNK_ROWS 6   /* test hook: rows per compaction chunk of mirx_index_remove_ids; 0 = default */
 
 /* values of MIRX_OPT_RANK_SORT.  Both sorts return the same ranking; forcing one lets a test run either on any gallery. */
 #define MIRX_RANK_SORT_AUTO 0     /* bitonic network up to 65536 rows, radix sort above            */
@@ -127,6 +128,27 @@ int mirx_index_set_option(mirx_index *ix, int option, int64_t value);
 /* Copy rows [first, first+n) of the fp32 master back out (device or host destination). */
 int mirx_index_get_rows(const mirx_index *ix, int64_t first, int64_t n, float *out_rows,
                         int64_t *out_ids_or_null);
+
+/*
+ * Remove every row whose id occurs in ids[0 .. n) (host or device pointer).  Replaces collection.delete(expr="id in [..]")
+ * of pymilvus, the counterpart of the reference's collection.insert (ingest_embeddings.py:399-411) that the reference itself
+ * only reaches through drop_old (milvus_setup.py:150-158): one wrong or leaked image no longer costs a re-embedding of the
+ * gallery.  Duplicates in the request count once, ids that are not in the index are ignored, and when a user id repeats in
+ * the index all its rows go.  The survivors keep their order in every buffer, rows from the new size up to the capacity read
+ * as zeros again and the capacity stays, so mirx_index_search / _search_f64 / _rank_top / _rank_all afterwards return exactly
+ * the ids and fp64 scores of a fresh index built from the survivors in order (stats may differ: the bound on the rows' norms
+ * is kept, it is still an upper bound).  Auto ids of later mirx_index_add calls go on past the largest auto id handed out so
+ * far: a removed row's id is not used again.
+ *   out_removed_or_null  host: the number of rows removed
+ * Work: the request is sorted on the device (the ranking's radix sort), then a binary search of each row's id in it, an
+ * exclusive scan of the keep flags (three launches) and 16-byte row moves, chunk by chunk through a scratch of at most 256 MiB (MIRX_OPT_COMPACT_CHUNK_ROWS sets the chunk's rows
+ * for tests); no atomics, workgroups synchronise at launch boundaries only, two calls on equal indexes leave equal buffers.
+ * Synchronous: enqueued on `stream`, returns when the index is compact.  Every allocation happens before the first row moves:
+ * MIRX_ENOMEM leaves the index untouched.  Between mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.
+ * mirx_compact_tile: rows per workgroup of the scan (the sizes around its multiples are the scan's edges); no device touched.
+ */
+int mirx_index_remove_ids(mirx_index *ix, const int64_t *ids, int64_t n, int64_t *out_removed_or_null, void *stream);
+int mirx_compact_tile(void);
 
 /*
  * Exhaustive top-k.  Replaces collection.search(data=[q], anns_field="embedding", limit=k)
