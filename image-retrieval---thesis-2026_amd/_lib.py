@@ -20,6 +20,7 @@ OPT_FORCE_TAU = 3
 OPT_PROFILE = 4
 OPT_RANK_SORT = 5                  # which sort rank_all runs
 OPT_COMPACT_CHUNK_ROWS = 6         # test hook: rows per compaction chunk of mirx_index_remove_ids (0 = default)
+OPT_MASK_GATHER_BYTES = 7          # test hook: scratch limit of a masked search's gather of its allowed rows (-1 = default)
 RANK_SORT_AUTO = 0                 # bitonic up to 65536 rows, radix above
 RANK_SORT_BITONIC = 1
 RANK_SORT_RADIX = 2
@@ -82,6 +83,8 @@ SYMBOLS = {
     "mirx_index_search_f64": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "mirx_index_search_begin": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "mirx_index_search_end": (_int, [_vp]),
+    "mirx_index_search_masked": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mirx_index_rank_top_masked": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mirx_index_last_stats": (_int, [_vp, _vp, ctypes.POINTER(SearchStats)]),
     "mirx_index_last_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "mirx_index_rank_all": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(CP_THREADS) void compact_apply(int32_t *__restrict_
 // One source chunk [c0, c1), one wave per row: a row is dimp / 4 16-byte pieces of the fp32 master and dimp / 8 of the bf16
 // copy, plus its id and bias.  MODE 0 (gather): surviving row r -> scratch row pos[r] - pos[c0].  MODE 1 (place): scratch row
 // j < pos[c1] - pos[c0] -> gallery row pos[c0] + j.  A chunk in front of the first removed row (pos[c1] == c1) has nothing to
-// move and both modes return.
+// move and both modes return.  s16 / sbias may be null (launch_compact_gather: a gather of the fp32 rows and ids alone).
 template <int MODE>
 __global__ __launch_bounds__(CP_THREADS) void compact_move(float *g32, uint16_t *g16, int64_t *ids, float *gbias, float *s32,
                                                             uint16_t *s16, int64_t *sid, float *sbias,
@@ -143,15 +143,20 @@ __global__ __launch_bounds__(CP_THREADS) void compact_move(float *g32, uint16_t 
             srow = j;
         }
         uint4 *ga = reinterpret_cast<uint4 *>(g32 + grow * dimp), *sa = reinterpret_cast<uint4 *>(s32 + srow * dimp);
-        uint4 *gb = reinterpret_cast<uint4 *>(g16 + grow * dimp), *sb = reinterpret_cast<uint4 *>(s16 + srow * dimp);
         if (MODE == 0) {
             for (int u = lane; u < u32; u += WAVE) sa[u] = ga[u];
-            for (int u = lane; u < u16; u += WAVE) sb[u] = gb[u];
+            if (s16) {
+                const uint4 *gb = reinterpret_cast<const uint4 *>(g16 + grow * dimp);
+                uint4 *sb = reinterpret_cast<uint4 *>(s16 + srow * dimp);
+                for (int u = lane; u < u16; u += WAVE) sb[u] = gb[u];
+            }
             if (lane == 0) {
                 sid[srow] = ids[grow];
-                sbias[srow] = gbias[grow];
+                if (sbias) sbias[srow] = gbias[grow];
             }
         } else {
+            uint4 *gb = reinterpret_cast<uint4 *>(g16 + grow * dimp);
+            const uint4 *sb = reinterpret_cast<const uint4 *>(s16 + srow * dimp);
             for (int u = lane; u < u32; u += WAVE) ga[u] = sa[u];
             for (int u = lane; u < u16; u += WAVE) gb[u] = sb[u];
             if (lane == 0) {
@@ -175,8 +180,26 @@ hipError_t launch_compact_scan(const int64_t *ids, int64_t n, const uint64_t *re
     const int64_t ntiles = compact_tiles(n);
     if (ntiles <= 0 || ntiles > 0x7FFFFFFF) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_mark, dim3((unsigned)ntiles), dim3(CP_THREADS), 0, st, ids, n, req, nreq, pos, part);
+    return launch_compact_scan_flags(pos, n, part, st);
+}
+
+hipError_t launch_compact_scan_flags(int32_t *pos, int64_t n, int32_t *part, hipStream_t st) {
+    const int64_t ntiles = compact_tiles(n);
+    if (ntiles <= 0 || ntiles > 0x7FFFFFFF) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_partials, dim3(1), dim3(CP_THREADS), 0, st, part, ntiles, pos + n);
     hipLaunchKernelGGL(compact_apply, dim3((unsigned)ntiles), dim3(CP_THREADS), 0, st, pos, n, part);
+    return hipGetLastError();
+}
+
+hipError_t launch_compact_gather(const float *g32, const int64_t *ids, const int32_t *pos, int64_t n, int dimp, float *s32,
+                                 int64_t *sid, hipStream_t st) {
+    if (n <= 0) return hipErrorInvalidValue;
+    constexpr int WAVES = CP_THREADS / WAVE;
+    const unsigned grid = (unsigned)std::min<int64_t>((n + WAVES - 1) / WAVES, 8 * (int64_t)current_device_cus());
+    // the gather mode only reads the gallery
+    hipLaunchKernelGGL(compact_move<0>, dim3(grid), dim3(CP_THREADS), 0, st, const_cast<float *>(g32), (uint16_t *)nullptr,
+                       const_cast<int64_t *>(ids), (float *)nullptr, s32, (uint16_t *)nullptr, sid, (float *)nullptr, pos,
+                       (int64_t)0, n, dimp);
     return hipGetLastError();
 }
 

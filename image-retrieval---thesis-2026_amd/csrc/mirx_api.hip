@@ -5,6 +5,7 @@
 //   -> finalize (sort candidates, completeness guard, fp64 re-rank, top-k)
 //   -> exact scan (fp64 score tiles + row top-k) for the queries the guard rejected.
 // The only host<->device synchronisation is one read of the rejected-query count.
+// A masked search (mirx_index_search_masked) runs the same sequence over a SearchRows that stands for the allowed rows.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -57,6 +58,19 @@ struct DevBuf {
 
 using namespace mirx;
 
+// What a search scans.  The index itself for the plain calls; a masked call passes a stand-in for its allowed rows:
+//   tier 1    the index's rows with `bias` (-inf on masked rows) in the sample and filter GEMMs, and for the queries the guard
+//             rejects the exact scan over all rows with the masked ones neutralised (mpos, ids = the masked ids)
+//   exact     either that neutralised scan, or g32 / ids = the allowed rows gathered into scratch, n of them
+struct SearchRows {
+    const float *g32 = nullptr;           // rows the exact scan scores
+    const int64_t *ids = nullptr;         // their ids (INT64_MAX on a masked row when mpos is set)
+    int64_t n = 0;
+    const int32_t *mpos = nullptr;        // scanned keep positions (n + 1): row r is masked iff mpos[r + 1] == mpos[r]
+    const float *bias = nullptr;          // tier 1: the per-row bias of both GEMMs instead of the index's
+    bool tier1 = false;
+};
+
 struct mirx_index {
     int dim = 0, dimp = 0, metric = 0, device = 0;
     int64_t size = 0, cap = 0;
@@ -78,13 +92,14 @@ struct mirx_index {
     bool idperm_valid = false;
     int64_t next_auto = 0;                // auto ids go on from here: past the rows removed since (never below `size`)
     int64_t compact_chunk = 0;            // MIRX_OPT_COMPACT_CHUNK_ROWS; 0 = as many rows as COMPACT_SCRATCH_BYTES hold
+    int64_t mask_gather_bytes = -1;       // MIRX_OPT_MASK_GATHER_BYTES; -1 = EXACT_WS_BYTES
     std::vector<hipEvent_t> ev_pool;      // lazily created, reused
     struct Span { int stage; hipEvent_t a, b; };
     std::vector<Span> spans;              // of the last search
     size_t ev_used = 0;
     // workspace
     DevBuf q32p, q16, qnorm, tau, cnt, cand, ovf_cnt, ovf, groupmax, fail_list, retry_list, tau2, q16r, taur,
-        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart;
+        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart, mallow, mbias, mids, mrows;
     int *fail_count = nullptr;            // device
     mirx_search_stats *stats_dev = nullptr;
     int *fail_count_host = nullptr;       // pinned
@@ -101,6 +116,7 @@ struct mirx_index {
         hipStream_t st = nullptr;
         mirx::GemmArgs ga{};
         mirx::FinalizeArgs fa{};
+        SearchRows rows{};
     } pend;
     hipEvent_t pend_ev = nullptr;
     bool begun = false;                   // between mirx_index_search_begin and _end, whether or not a pass is pending
@@ -209,11 +225,11 @@ struct StageTimer {
 };
 
 // Exact scan for `nlist` queries given by a device list (or 0..nlist-1 when list == null).
-int exact_pass(mirx_index *ix, const float *q32p, const int32_t *list_dev, int64_t nlist, int k,
+int exact_pass(mirx_index *ix, const SearchRows &sr, const float *q32p, const int32_t *list_dev, int64_t nlist, int k,
                const int64_t *exclude, double *out_f64, int64_t *out_ids, float *out_val,
                hipStream_t st) {
     if (nlist <= 0) return MIRX_OK;
-    const int64_t ld = round_up(std::max<int64_t>(ix->size, 1), 64);
+    const int64_t ld = round_up(std::max<int64_t>(sr.n, 1), 64);
     int64_t per = (int64_t)(EXACT_WS_BYTES / ((size_t)ld * sizeof(double)));
     per = std::max<int64_t>(4, std::min<int64_t>(per, 4096)) / 4 * 4;
     per = std::min<int64_t>(per, round_up(nlist, 4));
@@ -227,9 +243,10 @@ int exact_pass(mirx_index *ix, const float *q32p, const int32_t *list_dev, int64
         double *of = list_dev ? out_f64 : out_f64 + b * k;
         int64_t *oi = list_dev ? out_ids : out_ids + b * k;
         float *ov = out_val ? (list_dev ? out_val : out_val + b * k) : nullptr;
-        MIRX_HIP(launch_scores_f64(qb, lst, cnt, ix->g32, ix->size, ix->dimp, ix->metric,
+        MIRX_HIP(launch_scores_f64(qb, lst, cnt, sr.g32, sr.n, ix->dimp, ix->metric,
                                    ix->scores.as<double>(), ld, st));
-        MIRX_HIP(launch_row_topk(ix->scores.as<double>(), ld, ix->size, ix->ids, lst, cnt, exb, k,
+        if (sr.mpos) MIRX_HIP(launch_mask_scores(ix->scores.as<double>(), ld, sr.n, sr.mpos, cnt, st));
+        MIRX_HIP(launch_row_topk(ix->scores.as<double>(), ld, sr.n, sr.ids, lst, cnt, exb, k,
                                  ix->metric, of, oi, ov, st));
     }
     return MIRX_OK;
@@ -239,7 +256,7 @@ int exact_pass(mirx_index *ix, const float *q32p, const int32_t *list_dev, int64
 // sample the thresholds, filter GEMM, finalize -- then the two counters (queries to retry / to scan exactly) start their
 // way to pinned host memory and an event marks that point.  Nothing here blocks the host.
 int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_t *exb, float *ovb, double *ofb,
-                int64_t *oib, bool tier1, hipStream_t st) {
+                int64_t *oib, const SearchRows &sr, hipStream_t st) {
     const int bn = gemm_query_tile(nb);
     const int64_t nb_pad = round_up(nb, bn);
     ix->pend.active = false;
@@ -251,10 +268,10 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
         MIRX_HIP(launch_prep_queries(qb, nb, nb_pad, ix->dim, ix->dimp, ix->q32p.as<float>(),
                                      ix->q16.as<uint16_t>(), ix->qnorm.as<float>(), st));
     }
-    if (!tier1) {
+    if (!sr.tier1) {
         // (an empty gallery lands here too: every slot becomes (-1, -inf))
         StageTimer t(ix, st, MIRX_STAGE_EXACT);
-        int rc = exact_pass(ix, ix->q32p.as<float>(), nullptr, nb, k, exb, ofb, oib, ovb, st);
+        int rc = exact_pass(ix, sr, ix->q32p.as<float>(), nullptr, nb, k, exb, ofb, oib, ovb, st);
         if (rc) return rc;
         ix->stats_host.exact_answered += nb;
         return MIRX_OK;
@@ -275,7 +292,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     GemmArgs ga{};
     ga.g16 = ix->g16;
     ga.q16 = ix->q16.as<uint16_t>();
-    ga.gbias = ix->metric == MIRX_METRIC_NEG_L2 ? ix->gbias : nullptr;
+    ga.gbias = sr.bias ? sr.bias : (ix->metric == MIRX_METRIC_NEG_L2 ? ix->gbias : nullptr);
     ga.nq_pad = nb_pad;
     ga.dimp = ix->dimp;
     ga.tau = ix->tau.as<float>();
@@ -370,6 +387,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     ix->pend.st = st;
     ix->pend.ga = ga;
     ix->pend.fa = fa;
+    ix->pend.rows = sr;
     return MIRX_OK;
 }
 
@@ -433,7 +451,7 @@ int batch_back(mirx_index *ix) {
     const int nfail = ix->fail_count_host[0];
     if (nfail > 0) {
         StageTimer t(ix, st, MIRX_STAGE_EXACT);
-        int rc = exact_pass(ix, ix->q32p.as<float>(), ix->fail_list.as<int32_t>(), nfail, k, ix->pend.exb, ix->pend.ofb,
+        int rc = exact_pass(ix, ix->pend.rows, ix->q32p.as<float>(), ix->fail_list.as<int32_t>(), nfail, k, ix->pend.exb, ix->pend.ofb,
                             ix->pend.oib, ix->pend.ovb, st);
         if (rc) return rc;
         ix->stats_host.exact_answered += nfail;
@@ -441,9 +459,16 @@ int batch_back(mirx_index *ix) {
     return MIRX_OK;
 }
 
+// The tier-1 sequence answers when the tiers are on auto, `rows` rows can rank (the gallery, or a masked call's allowed rows)
+// and the candidate lists hold k plus the excluded id; else the exact scan answers directly.
+bool tier1_route(const mirx_index *ix, int64_t rows, int k, const int64_t *exclude) {
+    return ix->tiers == MIRX_TIER_AUTO && rows >= TIER1_MIN_ROWS && k + (exclude ? 1 : 0) <= TIER1_MAX_K;
+}
+
 // wait_last = false: the last internal batch is left pending (mirx_index_search_begin); batch_back completes it.
 int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude,
-                float *out_val, double *out_f64_user, int64_t *out_ids, hipStream_t st, bool wait_last = true) {
+                float *out_val, double *out_f64_user, int64_t *out_ids, hipStream_t st, bool wait_last = true,
+                const SearchRows *masked = nullptr) {
     MIRX_CHECK(ix, "search: null index");
     MIRX_CHECK(!ix->pend.active, "search: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
     MIRX_CHECK(k >= 1 && k <= MAX_K, "search: k must be in [1, 1024]");
@@ -458,8 +483,15 @@ int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t
     ix->ev_used = 0;
     if (nq == 0) return MIRX_OK;
 
-    const bool tier1 = ix->tiers == MIRX_TIER_AUTO && ix->size >= TIER1_MIN_ROWS &&
-                       k + (exclude ? 1 : 0) <= TIER1_MAX_K;
+    SearchRows sr;
+    if (masked) {
+        sr = *masked;
+    } else {
+        sr.g32 = ix->g32;
+        sr.ids = ix->ids;
+        sr.n = ix->size;
+        sr.tier1 = tier1_route(ix, ix->size, k, exclude);
+    }
     for (int64_t q0 = 0; q0 < nq; q0 += QUERY_BATCH) {
         const int64_t nb = std::min<int64_t>(QUERY_BATCH, nq - q0);
         const float *qb = q + q0 * ix->dim;
@@ -474,7 +506,7 @@ int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t
             MIRX_HIP(ix->stage.ensure((size_t)nb * k * sizeof(double)));
             ofb = ix->stage.as<double>();
         }
-        int rc = batch_front(ix, qb, nb, k, exb, ovb, ofb, oib, tier1, st);
+        int rc = batch_front(ix, qb, nb, k, exb, ovb, ofb, oib, sr, st);
         if (rc) return rc;
         if (wait_last || q0 + QUERY_BATCH < nq) {
             rc = batch_back(ix);
@@ -507,8 +539,9 @@ int build_id_permutation(mirx_index *ix, hipStream_t st) {
 // Ranks 0 .. kout-1 of every query by the radix sort.  Per query of a batch: n fp64 scores, two key and two payload buffers =
 // 32 bytes per row, batches sized to RANK_WS_BYTES (16 queries at 2^20 rows); a gallery whose single query does not fit is
 // bounded by the allocation alone.
+// mpos (rank_top under a mask): the scanned keep positions; masked rows sort behind every score and their slots read (-1, -inf).
 int rank_radix(mirx_index *ix, const float *q, int64_t nq, int64_t kout, const int64_t *exclude, bool drop_excluded,
-               int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st) {
+               int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st, const int32_t *mpos = nullptr) {
     const int64_t n = ix->size;
     if (!ix->ids_ascend && !ix->idperm_valid) {
         int rc = build_id_permutation(ix, st);
@@ -539,11 +572,50 @@ int rank_radix(mirx_index *ix, const float *q, int64_t nq, int64_t kout, const i
                                    ix->scores.as<double>(), ld, st));
         MIRX_HIP(launch_rank_sort_build(ix->scores.as<double>(), ld, n, ix->ids, perm, exb, drop_excluded ? 1 : 0, cnt, ka, pa,
                                         st));
+        if (mpos) MIRX_HIP(launch_mask_rank_keys(ka, pa, n, mpos, cnt, st));
         MIRX_HIP(launch_rank_sort(ka, pa, kb, pb, ix->rhist.as<unsigned>(), n, cnt, st));
         MIRX_HIP(launch_rank_sort_write(pa, n, kout, ix->scores.as<double>(), ld, ix->ids, exb, drop_excluded ? 1 : 0,
                                         ix->metric, cnt, out_ids + b * kout, out_val ? out_val + b * kout : nullptr,
                                         out_f64 ? out_f64 + b * kout : nullptr, st));
+        if (mpos)
+            MIRX_HIP(launch_mask_rank_tail(pa, n, kout, mpos, cnt, out_ids + b * kout, out_val ? out_val + b * kout : nullptr,
+                                           out_f64 ? out_f64 + b * kout : nullptr, st));
     }
+    return MIRX_OK;
+}
+
+// The one pass over a masked call's allow bytes (k_mask.hip) and the scan of its keep flags (k_compact.hip): leaves the bias
+// vector in ix->mbias (capacity floats), the masked ids in ix->mids, the scanned positions in ix->cpos (size + 1) and the number
+// of allowed rows in *n_allowed.  Every buffer, with `gather_bytes` of ix->mrows for the caller's gather of the allowed rows, is
+// allocated before the first launch; one host wait, for the count.
+int mask_prepare(mirx_index *ix, const uint8_t *allow, size_t gather_bytes, hipStream_t st, int64_t *n_allowed, const char *who) {
+    const int64_t size = ix->size;
+    bool allow_dev = false;
+    is_device_pointer(allow, &allow_dev);
+    hipError_t e;
+    if ((e = ix->mallow.ensure(allow_dev ? 0 : (size_t)size)) != hipSuccess ||
+        (e = ix->mbias.ensure((size_t)ix->cap * sizeof(float))) != hipSuccess ||
+        (e = ix->mids.ensure((size_t)size * sizeof(int64_t))) != hipSuccess ||
+        (e = ix->mrows.ensure(gather_bytes)) != hipSuccess ||
+        (e = ix->cpos.ensure((size_t)(size + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ix->cpart.ensure((size_t)compact_tiles(size) * sizeof(int32_t))) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIRX_ENOMEM, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    const uint8_t *am = allow;
+    if (!allow_dev) {
+        MIRX_HIP(hipMemcpyAsync(ix->mallow.p, allow, (size_t)size, hipMemcpyHostToDevice, st));
+        am = ix->mallow.as<uint8_t>();
+    }
+    int32_t *pos = ix->cpos.as<int32_t>();
+    MIRX_HIP(launch_mask_pass(am, size, ix->cap, ix->metric == MIRX_METRIC_NEG_L2 ? ix->gbias : nullptr, ix->ids,
+                              ix->mbias.as<float>(), ix->mids.as<int64_t>(), pos, ix->cpart.as<int32_t>(), st));
+    MIRX_HIP(launch_compact_scan_flags(pos, size, ix->cpart.as<int32_t>(), st));
+    int32_t total = 0;
+    MIRX_HIP(hipMemcpyAsync(&total, pos + size, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    if (total < 0 || total > size) return fail(MIRX_EHIP, std::string(who) + ": the scan returned an impossible count");
+    *n_allowed = total;
     return MIRX_OK;
 }
 
@@ -619,7 +691,7 @@ void mirx_index_destroy(mirx_index *ix) {
     for (DevBuf *b : {&ix->q32p, &ix->q16, &ix->qnorm, &ix->tau, &ix->cnt, &ix->cand, &ix->ovf_cnt, &ix->ovf, &ix->groupmax,
                       &ix->fail_list, &ix->retry_list, &ix->tau2, &ix->q16r, &ix->taur, &ix->scores, &ix->stage,
                       &ix->rankwork, &ix->spill, &ix->rkeys, &ix->rpay, &ix->rhist, &ix->idperm, &ix->creq, &ix->cpos,
-                      &ix->cpart})
+                      &ix->cpart, &ix->mallow, &ix->mbias, &ix->mids, &ix->mrows})
         b->release();
     delete ix;
 }
@@ -654,6 +726,10 @@ int mirx_index_set_option(mirx_index *ix, int option, int64_t value) {
             MIRX_CHECK(value == MIRX_RANK_SORT_AUTO || value == MIRX_RANK_SORT_BITONIC || value == MIRX_RANK_SORT_RADIX,
                        "set_option: rank sort must be 0 (auto), 1 (bitonic) or 2 (radix)");
             ix->rank_sort = (int)value;
+            return MIRX_OK;
+        case MIRX_OPT_MASK_GATHER_BYTES:
+            MIRX_CHECK(value >= -1, "set_option: mask gather bytes must be -1 (default) or a byte count");
+            ix->mask_gather_bytes = value;
             return MIRX_OK;
         case MIRX_OPT_COMPACT_CHUNK_ROWS:
             MIRX_CHECK(value >= 0 && value <= 0x7FFFFF00ll, "set_option: compaction chunk rows out of range (0 = default)");
@@ -819,6 +895,56 @@ int mirx_index_search_begin(mirx_index *ix, const float *q, int64_t nq, int k, c
     return rc;
 }
 
+int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                             const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
+                             int64_t *out_ids, void *stream) {
+    MIRX_CHECK(ix, "search_masked: null index");
+    if (ix->pend.active || ix->begun)
+        return fail(MIRX_ESTATE, "search_masked: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
+    MIRX_CHECK(n_allow == ix->size, "search_masked: the mask needs one byte per row of the index (n_allow != size)");
+    MIRX_CHECK(allow || n_allow == 0, "search_masked: null mask");
+    MIRX_CHECK(k >= 1 && k <= MAX_K, "search_masked: k must be in [1, 1024]");
+    MIRX_CHECK(nq >= 0, "search_masked: nq < 0");
+    MIRX_CHECK(nq == 0 || (q && out_ids && (out_scores_or_null || out_rank_scores_or_null)), "search_masked: null buffer");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nq == 0 || ix->size == 0)
+        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "search_masked: cannot select the index device");
+    // the gather's scratch is sized before the count is known: with the filter route open only fewer than TIER1_MIN_ROWS
+    // allowed rows are ever gathered, else any number whose rows fit the limit
+    const size_t row_bytes = (size_t)ix->dimp * sizeof(float) + sizeof(int64_t);
+    const size_t gather_max = ix->mask_gather_bytes < 0 ? EXACT_WS_BYTES : (size_t)ix->mask_gather_bytes;
+    const int64_t most_rows = tier1_route(ix, TIER1_MIN_ROWS, k, exclude_ids_or_null) ? std::min(ix->size, TIER1_MIN_ROWS - 1) : ix->size;
+    int64_t n_allowed = 0;
+    int rc = mask_prepare(ix, allow, std::min((size_t)most_rows * row_bytes, gather_max), st, &n_allowed, "search_masked");
+    if (rc) return rc;
+    if (n_allowed == ix->size)            // nothing masked: the plain search, bit for bit
+        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
+    SearchRows sr;
+    sr.tier1 = tier1_route(ix, n_allowed, k, exclude_ids_or_null);
+    const size_t gather_bytes = (size_t)n_allowed * row_bytes;
+    if (sr.tier1 || (n_allowed > 0 && gather_bytes > gather_max)) {
+        // all rows, the masked ones neutralised: tier 1 by the bias, the exact scan by -inf scores and the masked ids
+        sr.g32 = ix->g32;
+        sr.ids = ix->mids.as<int64_t>();
+        sr.n = ix->size;
+        sr.mpos = ix->cpos.as<int32_t>();
+        sr.bias = sr.tier1 ? ix->mbias.as<float>() : nullptr;
+    } else if (n_allowed > 0) {
+        // few allowed rows: gather them (ascending, so ids keep their order) and scan only those
+        if (gather_bytes > ix->mrows.bytes) return fail(MIRX_EHIP, "search_masked: the gather scratch is smaller than the count needs");
+        float *s32 = ix->mrows.as<float>();
+        int64_t *sid = reinterpret_cast<int64_t *>(s32 + n_allowed * ix->dimp);
+        MIRX_HIP(launch_compact_gather(ix->g32, ix->ids, ix->cpos.as<int32_t>(), ix->size, ix->dimp, s32, sid, st));
+        sr.g32 = s32;
+        sr.ids = sid;
+        sr.n = n_allowed;
+    }                                     // else nothing is allowed: n = 0, every slot reads (-1, -inf) and no row is scored
+    return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
+                       /*wait_last=*/true, &sr);
+}
+
 int mirx_index_search_end(mirx_index *ix) {
     MIRX_CHECK(ix, "search_end: null index");
     DeviceGuard dg(ix->device);
@@ -905,6 +1031,31 @@ int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, c
     if (!dg.ok) return fail(MIRX_EHIP, "rank_top: cannot select the index device");
     return rank_radix(ix, q, nq, k, exclude_ids_or_null, /*drop_excluded=*/true, out_ids, out_scores_or_null,
                       out_rank_scores_or_null, reinterpret_cast<hipStream_t>(stream));
+}
+
+int mirx_index_rank_top_masked(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
+                               const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,
+                               double *out_rank_scores_or_null, int64_t *out_ids, void *stream) {
+    MIRX_CHECK(ix, "rank_top_masked: null index");
+    if (ix->pend.active || ix->begun)
+        return fail(MIRX_ESTATE, "rank_top_masked: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
+    MIRX_CHECK(n_allow == ix->size, "rank_top_masked: the mask needs one byte per row of the index (n_allow != size)");
+    MIRX_CHECK(allow || n_allow == 0, "rank_top_masked: null mask");
+    MIRX_CHECK(k >= 1, "rank_top_masked: k must be at least 1");
+    MIRX_CHECK(nq >= 0, "rank_top_masked: nq < 0");
+    MIRX_CHECK(out_ids, "rank_top_masked: out_ids is null");
+    MIRX_CHECK(out_scores_or_null || out_rank_scores_or_null, "rank_top_masked: both score outputs are null");
+    MIRX_CHECK(q || nq == 0, "rank_top_masked: null queries");
+    MIRX_CHECK(k <= ix->size, "rank_top_masked: k is larger than the index");
+    if (nq == 0) return MIRX_OK;
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "rank_top_masked: cannot select the index device");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int64_t n_allowed = 0;
+    int rc = mask_prepare(ix, allow, 0, st, &n_allowed, "rank_top_masked");
+    if (rc) return rc;
+    return rank_radix(ix, q, nq, k, exclude_ids_or_null, /*drop_excluded=*/true, out_ids, out_scores_or_null,
+                      out_rank_scores_or_null, st, n_allowed == ix->size ? nullptr : ix->cpos.as<int32_t>());
 }
 
 uint64_t mirx_rank_key(double score) { return rank_key(score); }

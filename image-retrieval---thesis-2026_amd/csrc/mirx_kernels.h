@@ -106,10 +106,32 @@ size_t compact_scratch_bytes(int64_t chunk_rows, int dimp);
 // part = compact_tiles(n) words.  Three launches: mark + tile sums, scan of the tile sums, apply.
 hipError_t launch_compact_scan(const int64_t *ids, int64_t n, const uint64_t *req, int64_t nreq, int32_t *pos, int32_t *part,
                                hipStream_t st);
+// the same from keep flags: pos[r] = 0 / 1 for r < n and part[tile] = the flags' sum over each COMPACT_TILE rows on entry (what the
+// mark launch leaves, or k_mask.hip's pass); the two scan launches
+hipError_t launch_compact_scan_flags(int32_t *pos, int64_t n, int32_t *part, hipStream_t st);
+// the kept rows of [0, n), pos[n] < n of them, in order: fp32 row r -> s32 row pos[r], its id -> sid[pos[r]] (one gather launch;
+// the gallery is only read)
+hipError_t launch_compact_gather(const float *g32, const int64_t *ids, const int32_t *pos, int64_t n, int dimp, float *s32,
+                                 int64_t *sid, hipStream_t st);
 // the survivors of source rows [c0, c1), c1 - c0 <= chunk_rows, to rows pos[c0] .. of g32 / g16 / ids / gbias through `scratch`
 // (compact_scratch_bytes): a gather launch, then a place launch.  Chunks must be issued in ascending order.
 hipError_t launch_compact_chunk(float *g32, uint16_t *g16, int64_t *ids, float *gbias, void *scratch, int64_t chunk_rows,
                                 const int32_t *pos, int64_t c0, int64_t c1, int dimp, hipStream_t st);
+
+// ---- k_mask.hip: a search under a row mask (mirx_index_search_masked / mirx_index_rank_top_masked) ---------------------------
+// One pass over allow[0 .. n) (device, non-zero = eligible): bias[r] for r < cap (gbias[r], or 0 without gbias, for allowed rows
+// and the rows past n; -inf for masked rows), and for r < n the keep flag pos[r], mids[r] = the id or INT64_MAX, and the flags'
+// sums per COMPACT_TILE rows in part[] -- ready for launch_compact_scan_flags.
+hipError_t launch_mask_pass(const uint8_t *allow, int64_t n, int64_t cap, const float *gbias, const int64_t *ids, float *bias,
+                            int64_t *mids, int32_t *pos, int32_t *part, hipStream_t st);
+// pos = the scanned positions (n + 1 entries; row r is masked iff pos[r + 1] == pos[r]) in the three below
+// scores [nq, ld]: the entries of masked rows -> -inf
+hipError_t launch_mask_scores(double *scores, int64_t ld, int64_t n, const int32_t *pos, int nq, hipStream_t st);
+// keys / pay [nq, n] as launch_rank_sort_build leaves them: a masked row's key -> RANK_KEY_LAST
+hipError_t launch_mask_rank_keys(uint64_t *keys, const int32_t *pay, int64_t n, const int32_t *pos, int nq, hipStream_t st);
+// after launch_rank_sort_write: output slots whose row is masked -> (-1, -inf)
+hipError_t launch_mask_rank_tail(const int32_t *pay, int64_t n, int64_t kout, const int32_t *pos, int nq, int64_t *out_ids,
+                                 float *out_val, double *out_f64, hipStream_t st);
 
 // ---- k_anomaly.hip: class centroids, nearest-centroid distances, segmented binary ranking metrics (include/mirx.h) -----------
 int64_t an_chunk_rows(int64_t n, int d);          // rows per chunk of the centroid sums: a function of n and d alone

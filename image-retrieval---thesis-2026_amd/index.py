@@ -6,6 +6,7 @@ Torch is plumbing only: tensors own the query/result memory, `data_ptr()` crosse
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -118,17 +119,45 @@ class FlatIndex:
                 raise ValueError("exclude_ids needs one id per query")
         return q, ex
 
-    def search(self, q, k, exclude_ids=None, return_f64=False):
+    def _prep_allow(self, allow):
+        """a row mask as contiguous bytes (bool / uint8 tensor or array, on the cpu or this GPU; non-zero = eligible)"""
+        if isinstance(allow, np.ndarray) and not allow.flags.writeable:
+            allow = allow.copy()                                   # (torch warns about tensors over read-only arrays)
+        a = torch.as_tensor(allow).detach()
+        if a.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"allow must be a bool or uint8 mask, got {a.dtype}")
+        a = a.reshape(-1).contiguous()
+        if a.dtype == torch.bool:
+            a = a.view(torch.uint8)
+        if a.is_cuda and a.device != self.device:
+            a = a.to(self.device)
+        return a
+
+    def search(self, q, k, exclude_ids=None, return_f64=False, allow=None):
         """-> (scores [nq,k] float32 reported values, ids [nq,k] int64) on the index device.
 
         With return_f64=True the first tensor holds the fp64 ranking scores instead
-        (dot product, or NEGATIVE SQUARED distance for the L2 metric).  k above 1024 goes to rank_top."""
+        (dot product, or NEGATIVE SQUARED distance for the L2 metric).  k above 1024 goes to rank_top.
+        allow: a bool / uint8 mask with one entry per row of the index, in row order (cpu or this GPU): only rows whose entry
+        is non-zero can be returned, and the answer is that of a fresh index holding just those rows (ids and scores to the
+        bit); slots past the eligible rows read (-inf, -1).  The mask belongs to this call alone."""
         if int(k) > _lib.MAX_SEARCH_K:
-            return self.rank_top(q, k, exclude_ids=exclude_ids, return_f64=return_f64)
+            return self.rank_top(q, k, exclude_ids=exclude_ids, return_f64=return_f64, allow=allow)
         q, ex = self._prep_queries(q, exclude_ids)
         nq = q.shape[0]
         ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         exp = ctypes.c_void_p(ex.data_ptr()) if ex is not None else None
+        if allow is not None:
+            am = self._prep_allow(allow)
+            sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+            scp = ctypes.c_void_p(sc.data_ptr())
+            with torch.cuda.device(self.device):
+                rc = self._lib.mirx_index_search_masked(self._h, ctypes.c_void_p(q.data_ptr()), nq, int(k), exp,
+                                                        ctypes.c_void_p(am.data_ptr()) if am.numel() else None, am.numel(),
+                                                        None if return_f64 else scp, scp if return_f64 else None,
+                                                        ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
+            _lib.check(rc, "mirx_index_search_masked")
+            return sc, ids
         with torch.cuda.device(self.device):
             st = _stream_ptr(self.device)
             if return_f64:
@@ -167,22 +196,31 @@ class FlatIndex:
         _, _, sc, s64, ids = handle
         return (s64 if return_f64 else sc), ids
 
-    def rank_top(self, q, k, exclude_ids=None, return_f64=False):
+    def rank_top(self, q, k, exclude_ids=None, return_f64=False, allow=None):
         """The first k entries, 1 <= k <= ntotal, of the full ranking, with search()'s outputs and conventions: -> (scores [nq,k],
         ids [nq,k]); the excluded id is left out and slots past the eligible rows read (-inf, -1).  Sorts the whole gallery per
-        query (a radix sort, 32 bytes of workspace per row and query): for k <= 1024 search() is the faster call."""
+        query (a radix sort, 32 bytes of workspace per row and query): for k <= 1024 search() is the faster call.  allow: search()'s
+        row mask; the cost stays that of the unmasked call (every row is scored and sorted, masked rows end behind the rest)."""
         q, ex = self._prep_queries(q, exclude_ids)
+        am = None if allow is None else self._prep_allow(allow)
         nq, k = q.shape[0], int(k)
         ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=self.device)
         sc = torch.empty((nq, max(k, 0)), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
         scp = ctypes.c_void_p(sc.data_ptr())
+        exp = ctypes.c_void_p(ex.data_ptr()) if ex is not None else None
         with torch.cuda.device(self.device):
-            rc = self._lib.mirx_index_rank_top(
-                self._h, ctypes.c_void_p(q.data_ptr()), nq, k,
-                ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
-                None if return_f64 else scp, scp if return_f64 else None,
-                ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
-        _lib.check(rc, "mirx_index_rank_top")
+            if am is None:
+                rc = self._lib.mirx_index_rank_top(
+                    self._h, ctypes.c_void_p(q.data_ptr()), nq, k, exp,
+                    None if return_f64 else scp, scp if return_f64 else None,
+                    ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
+            else:
+                rc = self._lib.mirx_index_rank_top_masked(
+                    self._h, ctypes.c_void_p(q.data_ptr()), nq, k, exp,
+                    ctypes.c_void_p(am.data_ptr()) if am.numel() else None, am.numel(),
+                    None if return_f64 else scp, scp if return_f64 else None,
+                    ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
+        _lib.check(rc, "mirx_index_rank_top" if am is None else "mirx_index_rank_top_masked")
         return sc, ids
 
     def rank_all(self, q, exclude_ids=None, with_scores=False):

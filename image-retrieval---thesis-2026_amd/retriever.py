@@ -137,6 +137,7 @@ class Collection:
         self._slot_of = None
         self._next_id = 0
         self._live = None                                   # cache: ids of the live slots in order (numpy int64)
+        self._expr = None                                   # cache: mirx.expr.ExprCache of the current rows (see _changed)
         self._stored = stored
         self._resident = stored is None                     # whether _index mirrors the live rows
 
@@ -198,13 +199,37 @@ class Collection:
         p = int(np.searchsorted(live, int(id_)))
         return p if p < live.shape[0] and live[p] == int(id_) else None
 
+    def _changed(self):
+        """the live rows changed (insert / delete / compact): drop what was derived from them"""
+        self._live = None
+        self._expr = None
+
+    def expr_mask(self, expr):
+        """The rows a filter expression (mirx.expr: comparisons of id and the scalar fields with literals, in / not in,
+        and / or / not) selects: a read-only bool array aligned with live_ids(), the resident index's row order.  Column
+        codes are built once per state of the collection and the last expression's mask is kept until the rows change."""
+        from .expr import ExprCache
+        if self._expr is None:
+            self._expr = ExprCache(self.live_ids(), self.field)
+        return self._expr.evaluate(expr, ["id"] + list(self._meta))
+
+    def _device_mask(self, expr):
+        """expr_mask(expr) as a uint8 tensor on the index's device, uploaded once per expression and collection state"""
+        index = self._ensure()
+        mask = self.expr_mask(expr)
+        cache = self._expr
+        if cache.device_mask is None or cache.device_mask.device != index.device:
+            cache.device_mask = torch.from_numpy(mask.astype(np.uint8)).to(index.device)
+        return cache.device_mask
+
     def query(self, expr="id >= 0", output_fields=None, limit=None, offset=0):
-        """pymilvus' collection.query for the expressions this package meets: "id >= 0" (every live row, the paging loop of
-        ChestMIR/chestmir_eval.py:380-395) and the forms of delete().  -> row dicts with id and the output fields."""
+        """pymilvus' collection.query: "id >= 0" (every live row, the paging loop of ChestMIR/chestmir_eval.py:380-395) takes
+        a short cut, any other filter expression (mirx.expr; the forms of delete() are among them) is evaluated on the host
+        columns.  -> row dicts with id and the output fields, ascending by id."""
         if isinstance(expr, str) and expr.replace(" ", "") == "id>=0":
             ids = self.live_ids()
         else:
-            ids = np.asarray(self._match(expr), dtype=np.int64)
+            ids = self.live_ids()[self.expr_mask(expr)]
         ids = ids[int(offset):] if limit is None else ids[int(offset):int(offset) + int(limit)]
         fields = [f for f in (output_fields or []) if f != "id"]
         return [dict(self.entity(int(i), fields), id=int(i)) for i in ids]
@@ -265,12 +290,16 @@ class Collection:
         if len(index) != self.num_entities:
             raise RuntimeError(f"{self.name}: {len(index)} rows loaded, {self.num_entities} live rows expected")
         self._index, self._resident = index, True
+        if self._expr is not None:
+            self._expr.device_mask = None
 
     def release(self):
         """pymilvus' collection.release(): a persistent collection gives its device memory back (load() reads it again);
         in memory the index is the only copy and stays."""
         if self._stored is not None:
             self._index, self._resident = None, False
+            if self._expr is not None:
+                self._expr.device_mask = None
 
     def flush(self):
         """Commit inserts and deletions to disk (ingest_embeddings.py:532-534, "Flush to persist data"); in memory there is
@@ -305,7 +334,7 @@ class Collection:
             self._slot_of.update((i, len(self._ids) + k) for k, i in enumerate(ids))
         self._ids.extend(ids)
         self._next_id += emb.shape[0]
-        self._live = None
+        self._changed()
         return ids
 
     def delete(self, expr):
@@ -320,7 +349,7 @@ class Collection:
                 if removed != len(ids):
                     raise RuntimeError(f"{self.name}: the index removed {removed} rows for {len(ids)} live ids")
             self._dead.update(ids)
-            self._live = None
+            self._changed()
             if self._stored is not None:
                 self._stored.delete(ids)
         return MutationResult(len(ids))
@@ -337,12 +366,14 @@ class Collection:
             self._ids = [i for i, k in zip(self._ids, keep) if k]
             self._dead = set()
             self._slot_of = {i: s for s, i in enumerate(self._ids)}
-            self._live = None
+            self._changed()
         return None
 
-    def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None):
+    def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None, expr=None):
         """-> list (one per query) of lists of Hit, best first.  `distance` follows Milvus:
-        COSINE/IP -> similarity, L2 -> Euclidean distance (>= 0)."""
+        COSINE/IP -> similarity, L2 -> Euclidean distance (>= 0).  expr (pymilvus' scalar filter, mirx.expr) restricts the
+        search to the rows it selects -- exactly, on the device (FlatIndex.search(allow=)) -- so there are fewer than `limit`
+        hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes."""
         q = torch.as_tensor(np.asarray(data, dtype=np.float32) if not torch.is_tensor(data) else data)
         if q.dim() == 1:
             q = q[None]
@@ -350,10 +381,11 @@ class Collection:
         if self.num_entities == 0:
             return [[] for _ in range(q.shape[0])]
         limit = min(int(limit), self.num_entities)
+        allow = None if expr is None else self._device_mask(expr)
         if limit > 1024:
-            sc, ids = self._ensure().rank_top(q, limit, exclude_ids=exclude_ids)
+            sc, ids = self._ensure().rank_top(q, limit, exclude_ids=exclude_ids, allow=allow)
         else:
-            sc, ids = self._ensure().search(q, limit, exclude_ids=exclude_ids)
+            sc, ids = self._ensure().search(q, limit, exclude_ids=exclude_ids, allow=allow)
         ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
         out = []
         for qi in range(q.shape[0]):
@@ -636,9 +668,9 @@ class MilvusRetriever:
             norms = torch.cat([out[i:i + 1].norm(2, 1, True) for i in range(out.shape[0])])
             return out / norms.clamp_min(1e-12).expand_as(out)
 
-    def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE"):
+    def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE", expr=None):
         """-> (results, query_embedding).  results: best-first dicts {id, image_path, label,
-        distance, similarity}; similarity = distance for COSINE/IP, 1 - d^2/2 for L2."""
+        distance, similarity}; similarity = distance for COSINE/IP, 1 - d^2/2 for L2.  expr: Collection.search's filter."""
         if isinstance(query_image_path, str):
             from PIL import Image
             img = Image.open(query_image_path).convert("RGB")
@@ -653,7 +685,7 @@ class MilvusRetriever:
             # Milvus rejects a search whose metric differs from the index's (milvus_retrieval.py:75-86)
             raise ValueError(f"metric type not match: index has {self.collection.metric_type}, search asked {metric_type}")
         hits = self.collection.search(data=query_embedding, anns_field="embedding", param=search_params,
-                                      limit=top_k, output_fields=["image_path", "label"])[0]
+                                      limit=top_k, output_fields=["image_path", "label"], expr=expr)[0]
         return [self._format(h, metric_type) for h in hits], query_embedding
 
     @staticmethod
@@ -663,8 +695,9 @@ class MilvusRetriever:
         return {"id": hit.id, "image_path": hit.entity.get("image_path"), "label": hit.entity.get("label"),
                 "distance": d, "similarity": sim}
 
-    def batch_search(self, query_image_paths, top_k=10, search_params=None):
-        """One batched embed + one batched search (the reference loops search(); results equal, to the bit: _embed_rows)."""
+    def batch_search(self, query_image_paths, top_k=10, search_params=None, expr=None):
+        """One batched embed + one batched search (the reference loops search(); results equal, to the bit: _embed_rows).
+        expr: Collection.search's filter, one for the whole batch."""
         if len(query_image_paths) == 0:
             return []
         from PIL import Image
@@ -675,7 +708,7 @@ class MilvusRetriever:
             emb = self._embed_rows(torch.stack([self.transform(i) for i in imgs]))
         if self.collection is None:
             self.load_collection()
-        all_hits = self.collection.search(data=emb, limit=top_k, output_fields=["image_path", "label"])
+        all_hits = self.collection.search(data=emb, limit=top_k, output_fields=["image_path", "label"], expr=expr)
         return [[self._format(h, self.collection.metric_type) for h in hits] for hits in all_hits]
 
     def adapter(self, name=None):

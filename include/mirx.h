@@ -57,6 +57,7 @@ extern "C" {
 #define MIRX_OPT_PROFILE 4       /* 1: record HIP events around every stage of a search           */
 #define MIRX_OPT_RANK_SORT 5     /* which sort mirx_index_rank_all runs: MIRX_RANK_SORT_*          */
 #define MIRX_OPT_COMPACT_CHUNK_ROWS 6   /* test hook: rows per compaction chunk of mirx_index_remove_ids; 0 = default */
+#define MIRX_OPT_MASK_GATHER_BYTES 7    /* test hook: most scratch a masked search gathers its allowed rows into; -1 = default (1 GiB) */
 
 /* values of MIRX_OPT_RANK_SORT.  Both sorts return the same ranking; forcing one lets a test run either on any gallery. */
 #define MIRX_RANK_SORT_AUTO 0     /* bitonic network up to 65536 rows, radix sort above            */
@@ -187,6 +188,36 @@ int mirx_index_search_begin(mirx_index *ix, const float *q, int64_t nq, int k, c
                             float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
 int mirx_index_search_end(mirx_index *ix);
 
+/*
+ * The search under a row mask: pymilvus' collection.search(..., expr=...) once the expression has been evaluated per row.
+ *   allow    n_allow bytes, one per row of the index in row order, non-zero = eligible; a host or a device pointer (as the ids
+ *            of mirx_index_remove_ids).  n_allow != mirx_index_size: MIRX_EINVAL.
+ * The other arguments are those of mirx_index_search_begin (either score output may be NULL, not both).  The mask is an argument,
+ * not index state: nothing of it outlives the call.  Between mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.
+ * Result: exactly what mirx_index_search / _search_f64 return on a fresh index that holds only the allowed rows, in order, with
+ * their ids -- ids, fp64 rank scores and reported fp32 values bit for bit, ties by lowest id, the excluded id skipped; slots
+ * past the number of eligible rows read (-1, -inf); a masked row's id appears in no output.  A mask of all ones is the unmasked
+ * call (it is handed over to it), a mask of all zeros fills every slot with (-1, -inf) and scores nothing.
+ * Work: one pass over the mask (counts the allowed rows, writes a per-row fp32 bias for every row up to the capacity, the keep
+ * flags and the masked ids) and the removal's scan of the flags, then one host wait for the count, which picks the route:
+ *   - at least 32768 allowed rows, k (+1 with exclude ids) <= 64, tiers on auto: the tier-1 sequence of the plain search with
+ *     that bias in the sample and the filter GEMM (-inf on a masked row: it passes no threshold, so it is never a candidate);
+ *     the queries the completeness guard rejects are scanned exactly over all rows with the masked entries neutralised;
+ *   - otherwise the exact scan over the allowed rows alone, gathered (fp32 rows and ids, ascending) into a scratch of at most
+ *     1 GiB; allowed rows that do not fit it are scanned in place with the masked entries neutralised instead, at the cost of
+ *     the unmasked exact tier (MIRX_OPT_MASK_GATHER_BYTES lowers the limit for tests).
+ * Workspace besides the plain search's: 16 bytes per row (bias, positions, masked ids), the mask itself when it comes from the
+ * host, and the gather scratch.  All of it is allocated before the first launch; the gather scratch, whose need only the count
+ * tells, at its upper bound: the rows of 32767 allowed rows when the filter route is open to the call, else of the whole index,
+ * and never more than the 1 GiB limit.  The plain search's own workspace is allocated where the plain search allocates it, batch
+ * by batch, after the mask pass: a MIRX_ENOMEM there leaves outputs of earlier batches written, as in mirx_index_search.  No
+ * floating-point atomics; the result does not depend on scheduling.  mirx_index_last_stats / _last_timings describe the masked call (the mask
+ * pass itself is not among the timed stages).
+ */
+int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                             const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,
+                             double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
+
 /* Waits for `stream`, then copies the counters of the last search. */
 int mirx_index_last_stats(mirx_index *ix, void *stream, mirx_search_stats *out);
 
@@ -223,6 +254,17 @@ int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq,
  */
 int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
                         float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
+
+/*
+ * mirx_index_rank_top under a row mask (allow / n_allow as in mirx_index_search_masked; 1 <= k <= size): the first k entries of
+ * the ranking of the allowed rows, the excluded id left out, (-1, -inf) in the slots past the eligible rows -- what
+ * mirx_index_rank_top returns on a fresh index of the allowed rows, bit for bit.  Cost: that of the unmasked call whatever the
+ * mask -- every row is scored and sorted (32 bytes of workspace per row and query), masked rows carry the key behind every
+ * score's -- plus the mask pass and two small passes per batch of queries.  MIRX_ESTATE as for mirx_index_search_masked.
+ */
+int mirx_index_rank_top_masked(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
+                               const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,
+                               double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
 
 /*
  * For tests.  mirx_rank_key: the radix sort's 64-bit key of an fp64 ranking score -- key(a) < key(b) iff a > b, and
