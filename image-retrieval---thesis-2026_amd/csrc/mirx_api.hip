@@ -321,7 +321,14 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
         ms = std::min<int64_t>(ms, (int64_t)(16384 / gpt) * ROW_ALIGN);
         const int64_t stride = std::max<int64_t>(ix->size / ms, 1);
         const int ngroups = (int)(ms / ROW_ALIGN) * gpt;
-        const int rank_j = (int)std::max<int64_t>(1, std::min<int64_t>(ix->sample_rank, (32 * (int64_t)ix->sample_rank) / stride));
+        int rank_j = (int)std::max<int64_t>(1, std::min<int64_t>(ix->sample_rank, (32 * (int64_t)ix->sample_rank) / stride));
+        // j * stride candidates are expected, and a query left with fewer than k_eff of them has no k-th score to retry
+        // from: it goes to the exact scan.  At the smallest galleries (stride 8) j = 8 gives ~64, so from k_eff = 17 on
+        // ask for 4 k_eff of them -- at most half the groups deep, where the j-th maximum still tracks the j-th score.
+        // k_eff <= 16 keeps j at any stride, and so does every k at stride >= 32 (k_eff <= TIER1_MAX_K = 64).
+        const int64_t k_eff = (int64_t)k + (exb ? 1 : 0);
+        const int64_t rank_k = std::min<int64_t>((4 * k_eff + stride - 1) / stride, ngroups / 2);
+        rank_j = (int)std::max<int64_t>(rank_j, rank_k);
         MIRX_HIP(ix->groupmax.ensure((size_t)nb_pad * ngroups * sizeof(float)));
         GemmArgs gs = ga;
         gs.n_rows = ms;

@@ -52,7 +52,7 @@ extern "C" {
 #define MIRX_TIER_EXACT_ONLY 3  /* fp64 exact scan for every query (small galleries, tests) */
 
 #define MIRX_OPT_TIERS 1
-#define MIRX_OPT_SAMPLE_RANK 2   /* j: threshold = j-th largest sampled group maximum (default 8)  */
+#define MIRX_OPT_SAMPLE_RANK 2   /* j: threshold = j-th largest sampled group maximum (default 8; deeper where 4 (k + 1 excluded id) candidates need it) */
 #define MIRX_OPT_FORCE_TAU 3     /* test hook: float bits of a fixed threshold; 0x7fc00000 = off  */
 #define MIRX_OPT_PROFILE 4       /* 1: record HIP events around every stage of a search           */
 #define MIRX_OPT_RANK_SORT 5     /* which sort mirx_index_rank_all runs: MIRX_RANK_SORT_*          */
