@@ -967,6 +967,11 @@ int mirx_rollout_finish(float *workspace, int64_t workspace_floats, int layers, 
  * mirx_gradcam_cosine_bwd: out [b, e] = d/dp sum_r cosine_similarity(normalize(p), q_r) for q [bq, e].
  * Every output of image b is a fixed-order function of image b's inputs alone (no atomics): bit-identical whatever b is and
  * however the images are chunked.  workspace = device fp32, >= mirx_gradcam_workspace_floats(b, n, d, heads).
+ * Workspace of one image, in floats and in this order (image i's slot starts at i times the total):
+ *   stats [2 n] (mean, 1 / std per token) | P [n * heads] | dP [n * heads] | dsum [16] (sum_t P dP per head) |
+ *   partials [ceil(n / 4) * d] (the column sum of g_x per block of MIRX_GRADCAM_TOKENS_PER_BLOCK tokens) | wbar [d] | cam [n] |
+ *   minmax [1024] (a (min, max) pair per 16 output rows); the total is rounded up to a multiple of 4.
+ *   pool writes stats and P; tokens reads them and writes dP, dsum and partials; finish reads partials and writes the rest.
  * Limits (MIRX_EINVAL, nothing launched): 0 <= b <= 65535, 1 <= n <= 1024 (a square for finish), 1 <= heads <= 16,
  * 1 <= d <= 8192 with d % heads == 0, eps finite >= 0, buffers 4-byte aligned, 1 <= H, W <= 8192, 1 <= len, e <= 8192,
  * 1 <= bq <= 65535, gemv m, k, mg, rmod >= 1 and strides >= 0.

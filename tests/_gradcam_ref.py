@@ -81,8 +81,15 @@ def _gelu_d(h):
     return 0.5 * (1.0 + t) + 0.5 * h * (1.0 - t * t) * _KB * (1.0 + 3.0 * 0.044715 * h * h)
 
 
-def grad_x(W, x, q, heads):
-    """d/dx sum_r cos(model(x), q_r) for one image's tokens x [N, D] (W: float64 state dict, q [Bq, E])."""
+TRACE_KEYS = ("mu", "r", "y", "S", "P", "ybar", "o", "a", "t", "h", "z", "p1", "l1", "rr", "p2",
+              "g_p2", "g_rr", "g_p1", "g_z", "g_h", "g_a", "g_o", "w", "e", "dP", "dsum", "g_y", "g_x")
+
+
+def trace(W, x, q, heads):
+    """Every intermediate (float64) of d/dx sum_r cos(model(x), q_r) for one image's tokens x [N, D] (W: float64 state dict,
+    q [Bq, E]), under the names of DESIGN 21: the forward mu, r (1 / std), y, S, P, ybar, o, a, t, h, z, p1, l1, rr, p2; the
+    backward g_p2 ... g_o, w [H, D], e [H] (the gradient at the value projection), dP, dsum = sum_n P dP, g_y, g_x; and the
+    folded probe U [H, D], c [H]."""
     P = "backbone."
     D = x.shape[1]
     dh = D // heads
@@ -123,9 +130,38 @@ def grad_x(W, x, q, heads):
     w = np.stack([wv[h * dh:(h + 1) * dh].T @ g_o[h * dh:(h + 1) * dh] for h in range(heads)])        # [H, D]
     d = np.array([g_o[h * dh:(h + 1) * dh] @ bv[h * dh:(h + 1) * dh] for h in range(heads)])
     dP = y @ w.T + d
-    dS = Pm * (dP - (Pm * dP).sum(0, keepdims=True))
+    dsum = (Pm * dP).sum(0, keepdims=True)
+    dS = Pm * (dP - dsum)
     g_y = dS @ U + Pm @ w
-    return _ln_bwd(g_y, xh, r, W[P + "post_layernorm.weight"])
+    g_x = _ln_bwd(g_y, xh, r, W[P + "post_layernorm.weight"])
+    return dict(mu=x.mean(-1), r=r[:, 0], y=y, S=S, P=Pm, ybar=Yb, o=o, a=a, t=t, h=hpre, z=z, p1=p1, l1=l1, rr=rr, p2=p2,
+                g_p2=g_p2, g_rr=g_rr, g_p1=g_p1, g_z=g_z, g_h=g_h, g_a=g_a, g_o=g_o, w=w, e=d, dP=dP, dsum=dsum[0], g_y=g_y,
+                g_x=g_x, U=U, c=c)
+
+
+def grad_x(W, x, q, heads):
+    """d/dx sum_r cos(model(x), q_r) for one image's tokens x [N, D] (W: float64 state dict, q [Bq, E])."""
+    return trace(W, x, q, heads)["g_x"]
+
+
+TOKENS_PER_BLOCK = 4          # include/mirx.h MIRX_GRADCAM_TOKENS_PER_BLOCK
+MINMAX_FLOATS = 1024          # 2 * ceil(MIRX_GRADCAM_MAX_SIZE / 16): a (min, max) pair per 16 output rows
+
+
+def slot_layout(n, d, heads):
+    """The per-image Grad-CAM workspace of libmirx (include/mirx.h), in floats: offsets of
+    stats [2n] | P [n heads] | dP [n heads] | dsum [16] | partials [ceil(n / 4) d] | wbar [d] | cam [n] | minmax [1024]
+    and "per", the total rounded up to a multiple of 4.  Image i's slot starts at i * per."""
+    s = {"stats": 0}
+    s["P"] = s["stats"] + 2 * n
+    s["dP"] = s["P"] + n * heads
+    s["dsum"] = s["dP"] + n * heads
+    s["partials"] = s["dsum"] + 16
+    s["wbar"] = s["partials"] + (n + TOKENS_PER_BLOCK - 1) // TOKENS_PER_BLOCK * d
+    s["cam"] = s["wbar"] + d
+    s["minmax"] = s["cam"] + n
+    s["per"] = (s["minmax"] + MINMAX_FLOATS + 3) // 4 * 4
+    return s
 
 
 def upsample(m, size):
