@@ -4,7 +4,7 @@ CrispyChillies/Image-Retrieval---Thesis-2026: test.py evaluate(), MilvusRetrieve
 Layout
   csrc/        HIP kernels + the C ABI (include/mirx.h) -> libmirx.so (built in-tree)
   _lib.py      ctypes binding of libmirx.so (fails loudly when the library is missing)
-  index.py     FlatIndex: device-resident gallery, exact top-k / full ranking
+  index.py     FlatIndex: device-resident gallery, exact top-k / full ranking / range search (every row within a radius)
   model.py     DenseNet121 / ... embedders with the reference's forward() contract
   retriever.py MilvusManager / MilvusRetriever-shaped in-process retrieval
   metrics.py   retrieval_accuracy, compute_map, precision_at_k, ... (reference names)

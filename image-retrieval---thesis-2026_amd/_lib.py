@@ -21,6 +21,7 @@ OPT_PROFILE = 4
 OPT_RANK_SORT = 5                  # which sort rank_all runs
 OPT_COMPACT_CHUNK_ROWS = 6         # test hook: rows per compaction chunk of mirx_index_remove_ids (0 = default)
 OPT_MASK_GATHER_BYTES = 7          # test hook: scratch limit of a masked search's gather of its allowed rows (-1 = default)
+OPT_RANGE_MAX_HITS = 8             # test hook: most hits one range search may return (0 = default, 2^28)
 RANK_SORT_AUTO = 0                 # bitonic up to 65536 rows, radix above
 RANK_SORT_BITONIC = 1
 RANK_SORT_RADIX = 2
@@ -63,6 +64,13 @@ class SearchStats(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class RangeStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("nq", "filter_answered", "exact_answered", "candidates", "hits")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 # name -> (restype, argtypes): every symbol include/mirx.h declares
 _vp, _i64, _int = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
 SYMBOLS = {
@@ -85,6 +93,10 @@ SYMBOLS = {
     "mirx_index_search_end": (_int, [_vp]),
     "mirx_index_search_masked": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mirx_index_rank_top_masked": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mirx_index_range_search": (_int, [_vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _i64, _vp,
+                                       ctypes.POINTER(_i64), _vp]),
+    "mirx_index_range_fetch": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mirx_index_range_last_stats": (_int, [_vp, ctypes.POINTER(RangeStats)]),
     "mirx_index_last_stats": (_int, [_vp, _vp, ctypes.POINTER(SearchStats)]),
     "mirx_index_last_timings": (_int, [_vp, ctypes.POINTER(ctypes.c_float)]),
     "mirx_index_rank_all": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

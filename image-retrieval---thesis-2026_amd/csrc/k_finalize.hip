@@ -26,23 +26,6 @@ __device__ inline float f32_from_orderable(uint32_t e) {
     return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
 }
 
-template <typename T, typename Before>
-__device__ inline void bitonic_lds(T *a, int m, Before before) {
-    for (int size = 2; size <= m; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (int t = threadIdx.x; t < (m >> 1); t += blockDim.x) {
-                const int i = 2 * t - (t & (stride - 1));
-                const int j = i + stride;
-                const bool best_first = (i & size) == 0;
-                const T x = a[i], y = a[j];
-                if (before(y, x) == best_first) { a[i] = y; a[j] = x; }
-            }
-        }
-    }
-    __syncthreads();
-}
-
 // tau[q] = rank_j-th largest sampled group maximum of query q; +inf for padding queries.
 __global__ __launch_bounds__(256) void k_select_tau(const float *__restrict__ groupmax, int ngroups,
                                                     int64_t nq, int rank_j, float *__restrict__ tau) {
@@ -111,11 +94,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinalizeArgs A) {
             const float kth = f32_from_orderable((uint32_t)(keys[k_eff - 1] >> 32));
             const float gmax = __uint_as_float(*A.gnorm_max_bits);
             const float qn = A.qnorm[qi];
-            // |s~ - s| <= eps: bf16 rounding of both operands (2^-8 + 2^-18), fp32 accumulation
-            // of dimp products (dimp * 2^-23, a 2x margin over gamma_n), and for metric 1 the
-            // fp32 bias and its add.  Every product below is nudged upward.
-            float eps = qn * gmax * (0.00390625f + 3.8147e-6f + (float)A.dimp * 1.1920929e-7f) * 1.00001f;
-            if (METRIC == 1) eps += 1.1920929e-7f * (gmax * gmax + qn * gmax) * 1.00001f;
+            const float eps = filter_eps<METRIC>(qn, gmax, A.dimp);        // |s~ - s| <= eps
             lo = kth - 2.0f * eps;
             lo -= fabsf(lo) * 2.4e-7f + 1e-37f;            // round toward -inf with margin
             ok = (A.tau[slot_q] < lo) ? 1 : 0;

@@ -6,6 +6,8 @@
 //   -> exact scan (fp64 score tiles + row top-k) for the queries the guard rejected.
 // The only host<->device synchronisation is one read of the rejected-query count.
 // A masked search (mirx_index_search_masked) runs the same sequence over a SearchRows that stands for the allowed rows.
+// A range search (mirx_index_range_search) runs prep -> threshold from the radius -> filter GEMM -> its own finalize, the radix
+// ranking for what that cannot answer, and a CSR assembly (k_range.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -93,13 +95,22 @@ struct mirx_index {
     int64_t next_auto = 0;                // auto ids go on from here: past the rows removed since (never below `size`)
     int64_t compact_chunk = 0;            // MIRX_OPT_COMPACT_CHUNK_ROWS; 0 = as many rows as COMPACT_SCRATCH_BYTES hold
     int64_t mask_gather_bytes = -1;       // MIRX_OPT_MASK_GATHER_BYTES; -1 = EXACT_WS_BYTES
+    int64_t range_max_hits = 0;           // MIRX_OPT_RANGE_MAX_HITS; 0 = RANGE_MAX_HITS
+    // the last range search: its hits stay in rres until mirx_index_range_fetch; any other use of the index drops them
+    bool range_valid = false;
+    int64_t range_total = 0;
+    mirx_range_stats range_stats{};
+    unsigned long long *range_stats_dev = nullptr;   // [2] filter-answered queries, candidates
+    int64_t *range_total_dev = nullptr;              // [1] what the scan leaves
+    int64_t *range_total_host = nullptr;             // pinned
     std::vector<hipEvent_t> ev_pool;      // lazily created, reused
     struct Span { int stage; hipEvent_t a, b; };
     std::vector<Span> spans;              // of the last search
     size_t ev_used = 0;
     // workspace
     DevBuf q32p, q16, qnorm, tau, cnt, cand, ovf_cnt, ovf, groupmax, fail_list, retry_list, tau2, q16r, taur,
-        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart, mallow, mbias, mids, mrows;
+        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart, mallow, mbias, mids, mrows,
+        rstage, rcount, rxoff, rfirst, rexcl, rseg, rres;
     int *fail_count = nullptr;            // device
     mirx_search_stats *stats_dev = nullptr;
     int *fail_count_host = nullptr;       // pinned
@@ -252,6 +263,36 @@ int exact_pass(mirx_index *ix, const SearchRows &sr, const float *q32p, const in
     return MIRX_OK;
 }
 
+// The filter GEMM's workspace for a batch of nb_pad queries and the arguments every filter launch over the whole gallery shares
+// (thresholds in ix->tau, which the caller fills; the counters are the caller's to zero).
+int filter_args(mirx_index *ix, int64_t nb_pad, int bn, const float *bias_or_null, GemmArgs *out) {
+    int regions = 0, slots = 0;
+    gemm_plan(ix->size, nb_pad, bn, &regions, &slots);
+    MIRX_HIP(ix->tau.ensure((size_t)nb_pad * sizeof(float)));
+    MIRX_HIP(ix->cnt.ensure((size_t)nb_pad * regions * sizeof(int)));
+    MIRX_HIP(ix->cand.ensure((size_t)nb_pad * regions * slots * sizeof(Cand)));
+    MIRX_HIP(ix->ovf_cnt.ensure((size_t)nb_pad * sizeof(int)));
+    MIRX_HIP(ix->ovf.ensure((size_t)nb_pad * CAND_OVF * sizeof(Cand)));
+    MIRX_HIP(ix->spill.ensure(gemm_spill_bytes()));
+    MIRX_HIP(ix->fail_list.ensure((size_t)nb_pad * sizeof(int32_t)));
+    GemmArgs ga{};
+    ga.g16 = ix->g16;
+    ga.q16 = ix->q16.as<uint16_t>();
+    ga.gbias = bias_or_null ? bias_or_null : (ix->metric == MIRX_METRIC_NEG_L2 ? ix->gbias : nullptr);
+    ga.nq_pad = nb_pad;
+    ga.dimp = ix->dimp;
+    ga.tau = ix->tau.as<float>();
+    ga.regions = regions;
+    ga.slots = slots;
+    ga.region_cnt = ix->cnt.as<int>();
+    ga.cand = ix->cand.as<Cand>();
+    ga.ovf_cnt = ix->ovf_cnt.as<int>();
+    ga.ovf = ix->ovf.as<Cand>();
+    ga.spill = ix->spill.p;
+    *out = ga;
+    return MIRX_OK;
+}
+
 // One internal batch (<= QUERY_BATCH queries), first half: everything that needs no host decision -- prepare the queries,
 // sample the thresholds, filter GEMM, finalize -- then the two counters (queries to retry / to scan exactly) start their
 // way to pinned host memory and an event marks that point.  Nothing here blocks the host.
@@ -278,31 +319,14 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     }
 
     // ---- tier 1 ---------------------------------------------------------------------
-    MIRX_HIP(ix->tau.ensure((size_t)nb_pad * sizeof(float)));
-    int regions = 0, slots = 0;
-    gemm_plan(ix->size, nb_pad, bn, &regions, &slots);
-    MIRX_HIP(ix->cnt.ensure((size_t)nb_pad * regions * sizeof(int)));
-    MIRX_HIP(ix->cand.ensure((size_t)nb_pad * regions * slots * sizeof(Cand)));
-    MIRX_HIP(ix->ovf_cnt.ensure((size_t)nb_pad * sizeof(int)));
-    MIRX_HIP(ix->ovf.ensure((size_t)nb_pad * CAND_OVF * sizeof(Cand)));
-    MIRX_HIP(ix->spill.ensure(gemm_spill_bytes()));
-    MIRX_HIP(ix->fail_list.ensure((size_t)nb_pad * sizeof(int32_t)));
+    GemmArgs ga{};
+    {
+        int rc = filter_args(ix, nb_pad, bn, sr.bias, &ga);
+        if (rc) return rc;
+    }
+    const int regions = ga.regions, slots = ga.slots;
     MIRX_HIP(ix->retry_list.ensure((size_t)nb_pad * sizeof(int32_t)));
     MIRX_HIP(ix->tau2.ensure((size_t)nb_pad * sizeof(float)));
-    GemmArgs ga{};
-    ga.g16 = ix->g16;
-    ga.q16 = ix->q16.as<uint16_t>();
-    ga.gbias = sr.bias ? sr.bias : (ix->metric == MIRX_METRIC_NEG_L2 ? ix->gbias : nullptr);
-    ga.nq_pad = nb_pad;
-    ga.dimp = ix->dimp;
-    ga.tau = ix->tau.as<float>();
-    ga.regions = regions;
-    ga.slots = slots;
-    ga.region_cnt = ix->cnt.as<int>();
-    ga.cand = ix->cand.as<Cand>();
-    ga.ovf_cnt = ix->ovf_cnt.as<int>();
-    ga.ovf = ix->ovf.as<Cand>();
-    ga.spill = ix->spill.p;
     if (ix->force_tau_bits != 0x7fc00000u) {
         // test hook: one fixed threshold for every query
         std::vector<float> t((size_t)nb_pad, INFINITY);
@@ -481,6 +505,7 @@ int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t
     MIRX_CHECK(k >= 1 && k <= MAX_K, "search: k must be in [1, 1024]");
     MIRX_CHECK(nq >= 0, "search: nq < 0");
     MIRX_CHECK(nq == 0 || (q && out_ids && (out_val || out_f64_user)), "search: null buffer");
+    ix->range_valid = false;
     DeviceGuard dg(ix->device);
     if (!dg.ok) return fail(MIRX_EHIP, "search: cannot select the index device");
     MIRX_HIP(hipMemsetAsync(ix->stats_dev, 0, sizeof(mirx_search_stats), st));
@@ -550,6 +575,7 @@ int build_id_permutation(mirx_index *ix, hipStream_t st) {
 int rank_radix(mirx_index *ix, const float *q, int64_t nq, int64_t kout, const int64_t *exclude, bool drop_excluded,
                int64_t *out_ids, float *out_val, double *out_f64, hipStream_t st, const int32_t *mpos = nullptr) {
     const int64_t n = ix->size;
+    ix->range_valid = false;
     if (!ix->ids_ascend && !ix->idperm_valid) {
         int rc = build_id_permutation(ix, st);
         if (rc) return rc;
@@ -626,6 +652,195 @@ int mask_prepare(mirx_index *ix, const uint8_t *allow, size_t gather_bytes, hipS
     return MIRX_OK;
 }
 
+// ---- range search (k_range.hip) -----------------------------------------------------------------------------------------
+constexpr int64_t RANGE_MAX_HITS = (int64_t)1 << 28;   // most hits of one call by default (16 bytes each in ix->rres)
+
+int64_t range_limit(const mirx_index *ix) { return ix->range_max_hits > 0 ? ix->range_max_hits : RANGE_MAX_HITS; }
+
+// At least `need` bytes in `b` with its first `used` bytes kept (DevBuf::ensure drops the contents).  Waits for the stream.
+int grow_keep(DevBuf &b, size_t used, size_t need, hipStream_t st, const char *who) {
+    if (need <= b.bytes) return MIRX_OK;
+    size_t want = std::max(need, 2 * b.bytes);
+    void *np = nullptr;
+    if (hipMalloc(&np, want) != hipSuccess) {
+        (void)hipGetLastError();
+        want = need;
+        if (hipMalloc(&np, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MIRX_ENOMEM, std::string(who) + ": the hits do not fit the device");
+        }
+    }
+    if (used > 0 && b.p) MIRX_HIP(hipMemcpyAsync(np, b.p, used, hipMemcpyDeviceToDevice, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    if (b.p) (void)hipFree(b.p);
+    b.p = np;
+    b.bytes = want;
+    return MIRX_OK;
+}
+
+struct RangeCall {
+    double lo, hi;
+    const int64_t *exclude;      // of the current batch, or null
+    const uint8_t *allow;        // device, or null
+    int64_t res_total;           // hits of the batches in front of the current one
+    int64_t seg_total;           // records the exact route has written for the current batch
+};
+
+// Exact route for `m` queries of the current batch, given by a device list of their numbers in the batch (or 0 .. m-1 when
+// list == null); ix->q32p holds the batch's prepared queries.  Leaves count[qx], xoff[qx] and the records in ix->rseg.
+int range_exact(mirx_index *ix, RangeCall &rc, const int32_t *list_dev, int64_t m, hipStream_t st) {
+    if (m <= 0) return MIRX_OK;
+    const int64_t n = ix->size;
+    if (!ix->ids_ascend && !ix->idperm_valid) {
+        int r = build_id_permutation(ix, st);
+        if (r) return r;
+    }
+    const int32_t *perm = ix->ids_ascend ? nullptr : ix->idperm.as<int32_t>();
+    const int64_t ld = round_up(n, 64);
+    int64_t per = (int64_t)RANK_WS_BYTES / (ld * 32);
+    per = std::max<int64_t>(1, std::min<int64_t>(per, std::min<int64_t>(1024, m)));
+    if (ix->scores.ensure((size_t)per * ld * sizeof(double)) != hipSuccess ||
+        ix->rkeys.ensure((size_t)2 * per * n * sizeof(uint64_t)) != hipSuccess ||
+        ix->rpay.ensure((size_t)2 * per * n * sizeof(int32_t)) != hipSuccess ||
+        ix->rhist.ensure((size_t)per * 256 * rank_sort_tiles(n) * sizeof(unsigned)) != hipSuccess ||
+        ix->rfirst.ensure((size_t)per * sizeof(int32_t)) != hipSuccess ||
+        ix->rexcl.ensure((size_t)per * sizeof(int64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIRX_ENOMEM, "range_search: the sort workspace (32 bytes per gallery row) does not fit the device");
+    }
+    uint64_t *ka = ix->rkeys.as<uint64_t>(), *kb = ka + per * n;
+    int32_t *pa = ix->rpay.as<int32_t>(), *pb = pa + per * n;
+    int32_t *count = ix->rcount.as<int32_t>();
+    int64_t *xoff = ix->rxoff.as<int64_t>();
+    for (int64_t b = 0; b < m; b += per) {
+        const int cnt = (int)std::min<int64_t>(per, m - b);
+        const int32_t *lst = list_dev ? list_dev + b : nullptr;
+        const float *qb = list_dev ? ix->q32p.as<float>() : ix->q32p.as<float>() + b * ix->dimp;
+        const int64_t *exb = nullptr;
+        if (rc.exclude && list_dev) {
+            MIRX_HIP(launch_range_gather_exclude(rc.exclude, lst, cnt, ix->rexcl.as<int64_t>(), st));
+            exb = ix->rexcl.as<int64_t>();
+        } else if (rc.exclude) {
+            exb = rc.exclude + b;
+        }
+        MIRX_HIP(launch_scores_f64(qb, lst, cnt, ix->g32, n, ix->dimp, ix->metric, ix->scores.as<double>(), ld, st));
+        MIRX_HIP(launch_rank_sort_build(ix->scores.as<double>(), ld, n, ix->ids, perm, exb, /*drop_excluded=*/1, cnt, ka, pa, st));
+        if (rc.allow) MIRX_HIP(launch_range_mask_keys(ka, pa, n, rc.allow, cnt, st));
+        MIRX_HIP(launch_rank_sort(ka, pa, kb, pb, ix->rhist.as<unsigned>(), n, cnt, st));
+        MIRX_HIP(launch_range_cut(ka, n, cnt, rc.lo, rc.hi, lst, b, ix->rfirst.as<int32_t>(), count, st));
+        MIRX_HIP(launch_range_scan(count, lst, b, cnt, rc.seg_total, xoff, nullptr, ix->range_total_dev, st));
+        MIRX_HIP(hipMemcpyAsync(ix->range_total_host, ix->range_total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        MIRX_HIP(hipStreamSynchronize(st));
+        const int64_t seg_total = ix->range_total_host[0];
+        if (seg_total < rc.seg_total) return fail(MIRX_EHIP, "range_search: the scan returned an impossible count");
+        if (rc.res_total + seg_total > range_limit(ix))
+            return fail(MIRX_ENOMEM, "range_search: more hits than one call may return (MIRX_OPT_RANGE_MAX_HITS; default 2^28)");
+        int r = grow_keep(ix->rseg, (size_t)rc.seg_total * sizeof(Hit), (size_t)seg_total * sizeof(Hit), st, "range_search");
+        if (r) return r;
+        MIRX_HIP(launch_range_emit(pa, n, ix->scores.as<double>(), ld, ix->ids, cnt, lst, b, ix->rfirst.as<int32_t>(), count, xoff,
+                                   ix->rseg.as<Hit>(), st));
+        rc.seg_total = seg_total;
+        ix->range_stats.exact_answered += cnt;
+    }
+    return MIRX_OK;
+}
+
+// One internal batch of a range search: counts, staging rows / exact segments, lims[0 .. nb] of the batch, compaction into
+// ix->rres behind the rc.res_total hits of earlier batches.
+int range_batch(mirx_index *ix, RangeCall &rc, const float *qb, int64_t nb, bool filter, int64_t *lims, hipStream_t st) {
+    const int bn = gemm_query_tile(nb);
+    const int64_t nb_pad = round_up(nb, bn);
+    MIRX_HIP(ix->q32p.ensure((size_t)nb_pad * ix->dimp * sizeof(float)));
+    MIRX_HIP(ix->q16.ensure((size_t)nb_pad * ix->dimp * sizeof(uint16_t)));
+    MIRX_HIP(ix->qnorm.ensure((size_t)nb_pad * sizeof(float)));
+    MIRX_HIP(ix->rcount.ensure((size_t)nb * sizeof(int32_t)));
+    MIRX_HIP(ix->rxoff.ensure((size_t)nb * sizeof(int64_t)));
+    MIRX_HIP(launch_prep_queries(qb, nb, nb_pad, ix->dim, ix->dimp, ix->q32p.as<float>(), ix->q16.as<uint16_t>(),
+                                 ix->qnorm.as<float>(), st));
+    MIRX_HIP(hipMemsetAsync(ix->rcount.p, 0, (size_t)nb * sizeof(int32_t), st));
+    MIRX_HIP(hipMemsetAsync(ix->rxoff.p, 0xFF, (size_t)nb * sizeof(int64_t), st));      // -1: the staging row
+    rc.seg_total = 0;
+    int32_t *count = ix->rcount.as<int32_t>();
+    int64_t batch_total = -1;
+    if (filter) {
+        // the candidate machinery of batch_front (filter_args), unchanged; only tau and the finalize differ
+        GemmArgs ga{};
+        {
+            int r = filter_args(ix, nb_pad, bn, nullptr, &ga);
+            if (r) return r;
+        }
+        const int regions = ga.regions, slots = ga.slots;
+        if (ix->rstage.ensure((size_t)nb * RANGE_CAP * sizeof(Hit)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MIRX_ENOMEM, "range_search: the staging rows (20 KiB per query of a batch) do not fit the device");
+        }
+        MIRX_HIP(launch_range_tau(ix->q32p.as<float>(), ix->qnorm.as<float>(), ix->gnorm_max_bits, rc.lo, ix->dimp, ix->metric, nb,
+                                  nb_pad, ix->tau.as<float>(), st));
+        MIRX_HIP(hipMemsetAsync(ix->cnt.p, 0, (size_t)nb_pad * regions * sizeof(int), st));
+        MIRX_HIP(hipMemsetAsync(ix->ovf_cnt.p, 0, (size_t)nb_pad * sizeof(int), st));
+        MIRX_HIP(hipMemsetAsync(ix->fail_count, 0, 2 * sizeof(int), st));
+        ga.n_rows = ix->size;
+        ga.row_stride = 1;
+        MIRX_HIP(launch_gemm_filter(ga, bn, st));
+        RangeFinalizeArgs fa{};
+        fa.q32p = ix->q32p.as<float>();
+        fa.g32 = ix->g32;
+        fa.ids = ix->ids;
+        fa.regions = regions;
+        fa.slots = slots;
+        fa.region_cnt = ix->cnt.as<int>();
+        fa.cand = ix->cand.as<Cand>();
+        fa.ovf_cnt = ix->ovf_cnt.as<int>();
+        fa.ovf = ix->ovf.as<Cand>();
+        fa.exclude = rc.exclude;
+        fa.allow = rc.allow;
+        fa.n_rows = ix->size;
+        fa.dimp = ix->dimp;
+        fa.metric = ix->metric;
+        fa.nq = (int)nb;
+        fa.lo = rc.lo;
+        fa.hi = rc.hi;
+        fa.stage = ix->rstage.as<Hit>();
+        fa.count = count;
+        fa.fail_list = ix->fail_list.as<int32_t>();
+        fa.fail_count = ix->fail_count;
+        fa.stats = ix->range_stats_dev;
+        MIRX_HIP(launch_range_finalize(fa, st));
+        // the overflow counter and the batch's hit count (right when nothing overflowed) travel together: one host wait
+        MIRX_HIP(launch_range_scan(count, nullptr, 0, (int)nb, rc.res_total, lims, lims + nb, ix->range_total_dev, st));
+        MIRX_HIP(hipMemcpyAsync(ix->fail_count_host, ix->fail_count, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        MIRX_HIP(hipMemcpyAsync(ix->range_total_host, ix->range_total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        MIRX_HIP(hipStreamSynchronize(st));
+        const int nfail = ix->fail_count_host[0];
+        if (nfail < 0 || nfail > nb) return fail(MIRX_EHIP, "range_search: impossible overflow count");
+        if (nfail == 0) {
+            batch_total = ix->range_total_host[0];
+        } else {
+            int r = range_exact(ix, rc, ix->fail_list.as<int32_t>(), nfail, st);
+            if (r) return r;
+        }
+    } else {
+        int r = range_exact(ix, rc, nullptr, nb, st);
+        if (r) return r;
+    }
+    if (batch_total < 0) {
+        MIRX_HIP(launch_range_scan(count, nullptr, 0, (int)nb, rc.res_total, lims, lims + nb, ix->range_total_dev, st));
+        MIRX_HIP(hipMemcpyAsync(ix->range_total_host, ix->range_total_dev, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        MIRX_HIP(hipStreamSynchronize(st));
+        batch_total = ix->range_total_host[0];
+    }
+    if (batch_total < rc.res_total) return fail(MIRX_EHIP, "range_search: the scan returned an impossible count");
+    if (batch_total > range_limit(ix))
+        return fail(MIRX_ENOMEM, "range_search: more hits than one call may return (MIRX_OPT_RANGE_MAX_HITS; default 2^28)");
+    int r = grow_keep(ix->rres, (size_t)rc.res_total * sizeof(Hit), (size_t)batch_total * sizeof(Hit), st, "range_search");
+    if (r) return r;
+    if (batch_total > rc.res_total)
+        MIRX_HIP(launch_range_compact(ix->rstage.as<Hit>(), ix->rseg.as<Hit>(), ix->rxoff.as<int64_t>(), count, lims, (int)nb,
+                                      ix->rres.as<Hit>(), st));
+    rc.res_total = batch_total;
+    return MIRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -693,12 +908,16 @@ void mirx_index_destroy(mirx_index *ix) {
     if (ix->fail_count) (void)hipFree(ix->fail_count);
     if (ix->stats_dev) (void)hipFree(ix->stats_dev);
     if (ix->fail_count_host) (void)hipHostFree(ix->fail_count_host);
+    if (ix->range_stats_dev) (void)hipFree(ix->range_stats_dev);
+    if (ix->range_total_dev) (void)hipFree(ix->range_total_dev);
+    if (ix->range_total_host) (void)hipHostFree(ix->range_total_host);
     for (hipEvent_t e : ix->ev_pool) (void)hipEventDestroy(e);
     if (ix->pend_ev) (void)hipEventDestroy(ix->pend_ev);
     for (DevBuf *b : {&ix->q32p, &ix->q16, &ix->qnorm, &ix->tau, &ix->cnt, &ix->cand, &ix->ovf_cnt, &ix->ovf, &ix->groupmax,
                       &ix->fail_list, &ix->retry_list, &ix->tau2, &ix->q16r, &ix->taur, &ix->scores, &ix->stage,
                       &ix->rankwork, &ix->spill, &ix->rkeys, &ix->rpay, &ix->rhist, &ix->idperm, &ix->creq, &ix->cpos,
-                      &ix->cpart, &ix->mallow, &ix->mbias, &ix->mids, &ix->mrows})
+                      &ix->cpart, &ix->mallow, &ix->mbias, &ix->mids, &ix->mrows, &ix->rstage, &ix->rcount, &ix->rxoff,
+                      &ix->rfirst, &ix->rexcl, &ix->rseg, &ix->rres})
         b->release();
     delete ix;
 }
@@ -738,6 +957,10 @@ int mirx_index_set_option(mirx_index *ix, int option, int64_t value) {
             MIRX_CHECK(value >= -1, "set_option: mask gather bytes must be -1 (default) or a byte count");
             ix->mask_gather_bytes = value;
             return MIRX_OK;
+        case MIRX_OPT_RANGE_MAX_HITS:
+            MIRX_CHECK(value >= 0, "set_option: range max hits must be 0 (default) or a count");
+            ix->range_max_hits = value;
+            return MIRX_OK;
         case MIRX_OPT_COMPACT_CHUNK_ROWS:
             MIRX_CHECK(value >= 0 && value <= 0x7FFFFF00ll, "set_option: compaction chunk rows out of range (0 = default)");
             ix->compact_chunk = value;
@@ -750,6 +973,7 @@ int mirx_index_set_option(mirx_index *ix, int option, int64_t value) {
 int mirx_index_add(mirx_index *ix, const float *rows, int64_t n, const int64_t *ids_or_null) {
     MIRX_CHECK(ix && n >= 0 && (rows || n == 0), "index_add: bad argument");
     if (n == 0) return MIRX_OK;
+    ix->range_valid = false;
     MIRX_CHECK(ix->size + n <= 0x7FFFFF00ll, "index_add: more than 2^31 rows per index");
     DeviceGuard dg(ix->device);
     if (!dg.ok) return fail(MIRX_EHIP, "index_add: cannot select device");
@@ -809,6 +1033,7 @@ int mirx_index_remove_ids(mirx_index *ix, const int64_t *ids, int64_t n, int64_t
     if (ix->pend.active || ix->begun)
         return fail(MIRX_ESTATE, "remove_ids: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
     if (out_removed_or_null) *out_removed_or_null = 0;
+    ix->range_valid = false;
     if (n == 0 || ix->size == 0) return MIRX_OK;
     DeviceGuard dg(ix->device);
     if (!dg.ok) return fail(MIRX_EHIP, "remove_ids: cannot select device");
@@ -952,6 +1177,97 @@ int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, 
                        /*wait_last=*/true, &sr);
 }
 
+int mirx_index_range_search(mirx_index *ix, const float *q, int64_t nq, double lo, double hi, const int64_t *exclude_ids_or_null,
+                            const uint8_t *allow_or_null, int64_t n_allow, int64_t *out_lims, int64_t *out_total, void *stream) {
+    MIRX_CHECK(ix, "range_search: null index");
+    if (ix->pend.active || ix->begun)
+        return fail(MIRX_ESTATE, "range_search: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
+    ix->range_valid = false;
+    MIRX_CHECK(nq >= 0, "range_search: nq < 0");
+    MIRX_CHECK(nq <= 0x7FFFFF00ll, "range_search: more than 2^31 queries in one call");
+    MIRX_CHECK(!(lo != lo) && !(hi != hi), "range_search: a bound is NaN");
+    MIRX_CHECK(out_lims && out_total, "range_search: null output");
+    MIRX_CHECK(q || nq == 0, "range_search: null queries");
+    MIRX_CHECK(allow_or_null ? n_allow == ix->size : n_allow == 0,
+               "range_search: the mask needs one byte per row of the index (n_allow != size)");
+    *out_total = 0;
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "range_search: cannot select the index device");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!ix->range_stats_dev) {
+        hipError_t e;
+        if ((e = hipMalloc(&ix->range_stats_dev, 2 * sizeof(unsigned long long))) != hipSuccess ||
+            (e = hipMalloc(&ix->range_total_dev, sizeof(int64_t))) != hipSuccess ||
+            (e = hipHostMalloc(&ix->range_total_host, sizeof(int64_t))) != hipSuccess)
+            return fail(MIRX_ENOMEM, std::string("range_search: ") + hipGetErrorString(e));
+    }
+    MIRX_HIP(hipMemsetAsync(ix->range_stats_dev, 0, 2 * sizeof(unsigned long long), st));
+    ix->range_stats = mirx_range_stats{};
+    ix->range_stats.nq = nq;
+    ix->range_total = 0;
+    MIRX_HIP(hipMemsetAsync(out_lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st));
+    if (nq == 0 || ix->size == 0 || !(hi > lo)) {          // nothing can be a hit: lims of zeros, no launch
+        ix->range_valid = true;
+        return MIRX_OK;
+    }
+    const uint8_t *allow = allow_or_null;
+    if (allow) {
+        bool allow_dev = false;
+        is_device_pointer(allow, &allow_dev);
+        if (!allow_dev) {
+            if (ix->mallow.ensure((size_t)ix->size) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(MIRX_ENOMEM, "range_search: the mask does not fit the device");
+            }
+            MIRX_HIP(hipMemcpyAsync(ix->mallow.p, allow, (size_t)ix->size, hipMemcpyHostToDevice, st));
+            allow = ix->mallow.as<uint8_t>();
+        }
+    }
+    const bool filter = ix->tiers == MIRX_TIER_AUTO && ix->size >= TIER1_MIN_ROWS && lo > -INFINITY;
+    RangeCall rc{};
+    rc.lo = lo;
+    rc.hi = hi;
+    rc.allow = allow;
+    for (int64_t q0 = 0; q0 < nq; q0 += QUERY_BATCH) {
+        const int64_t nb = std::min<int64_t>(QUERY_BATCH, nq - q0);
+        rc.exclude = exclude_ids_or_null ? exclude_ids_or_null + q0 : nullptr;
+        int r = range_batch(ix, rc, q + q0 * ix->dim, nb, filter, out_lims + q0, st);
+        if (r) return r;
+    }
+    ix->range_total = rc.res_total;
+    ix->range_stats.hits = rc.res_total;
+    ix->range_valid = true;
+    *out_total = rc.res_total;
+    return MIRX_OK;
+}
+
+int mirx_index_range_fetch(mirx_index *ix, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids, void *stream) {
+    MIRX_CHECK(ix, "range_fetch: null index");
+    if (!ix->range_valid)
+        return fail(MIRX_ESTATE, "range_fetch: no range search precedes this call (or another call on the index has reused its scratch)");
+    if (ix->range_total == 0) return MIRX_OK;
+    MIRX_CHECK(out_ids && (out_values_or_null || out_f64_or_null), "range_fetch: null output");
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "range_fetch: cannot select the index device");
+    MIRX_HIP(launch_range_fetch(ix->rres.as<Hit>(), ix->range_total, ix->metric, out_values_or_null, out_f64_or_null, out_ids,
+                                reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_index_range_last_stats(mirx_index *ix, mirx_range_stats *out) {
+    MIRX_CHECK(ix && out, "range_last_stats: null argument");
+    *out = ix->range_stats;
+    if (!ix->range_stats_dev) return MIRX_OK;
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "range_last_stats: cannot select the index device");
+    unsigned long long d[2] = {0, 0};
+    MIRX_HIP(hipDeviceSynchronize());
+    MIRX_HIP(hipMemcpy(d, ix->range_stats_dev, sizeof(d), hipMemcpyDeviceToHost));
+    out->filter_answered = (int64_t)d[0];
+    out->candidates = (int64_t)d[1];
+    return MIRX_OK;
+}
+
 int mirx_index_search_end(mirx_index *ix) {
     MIRX_CHECK(ix, "search_end: null index");
     DeviceGuard dg(ix->device);
@@ -993,6 +1309,7 @@ int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq, const int64_
                        (ix->rank_sort == MIRX_RANK_SORT_AUTO && ix->size > RANK_BITONIC_MAX_ROWS);
     MIRX_CHECK(radix || ix->size <= RANK_BITONIC_MAX_ROWS,
                "rank_all: the bitonic sort (MIRX_OPT_RANK_SORT = 1) takes at most 65536 rows");
+    ix->range_valid = false;
     if (nq == 0 || ix->size == 0) return MIRX_OK;
     DeviceGuard dg(ix->device);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -89,6 +89,25 @@ __device__ inline int pow2_ceil(int v) {
     return p;
 }
 
+// Bitonic network over a[0 .. m) in LDS (m a power of two), every thread of the workgroup taking part: before(x, y) = x ranks
+// in front of y.  Ends behind a barrier.
+template <typename T, typename Before>
+__device__ inline void bitonic_lds(T *a, int m, Before before) {
+    for (int size = 2; size <= m; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int t = threadIdx.x; t < (m >> 1); t += blockDim.x) {
+                const int i = 2 * t - (t & (stride - 1));
+                const int j = i + stride;
+                const bool best_first = (i & size) == 0;
+                const T x = a[i], y = a[j];
+                if (before(y, x) == best_first) { a[i] = y; a[j] = x; }
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // fp32 -> bf16, round to nearest even (finite inputs).
 __device__ inline uint16_t f32_to_bf16(float f) {
     uint32_t u = __float_as_uint(f);
@@ -122,6 +141,16 @@ __device__ inline double lane_tree_score(const float *__restrict__ q, const floa
     }
     acc = wave_butterfly_sum(acc);
     return METRIC == 0 ? acc : -acc;
+}
+
+// The filter GEMM's error bound: |s~ - s'| <= eps for every row, s' the score the GEMM approximates.  bf16 rounding of
+// both operands (2^-8 + 2^-18), fp32 accumulation of dimp products (dimp * 2^-23, a 2x margin over gamma_n), and for metric 1 the
+// fp32 bias and its add.  Every product is nudged upward.  qn / gmax: upper bounds of ||q|| and of the largest ||g||.
+template <int METRIC>
+__device__ inline float filter_eps(float qn, float gmax, int dimp) {
+    float eps = qn * gmax * (0.00390625f + 3.8147e-6f + (float)dimp * 1.1920929e-7f) * 1.00001f;
+    if (METRIC == 1) eps += 1.1920929e-7f * (gmax * gmax + qn * gmax) * 1.00001f;
+    return eps;
 }
 
 // What the search boundary reports for an fp64 ranking score: metric 0 the dot product, metric 1 -sqrt of the squared distance.

@@ -352,6 +352,54 @@ hipError_t launch_select_tau(const float *groupmax, int ngroups, int64_t nq, int
                              int rank_j, float *tau, hipStream_t st);
 hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st);
 
+// ---- k_range.hip: range search (mirx_index_range_search): every row with lo < s <= hi, per query, best first -------------------
+constexpr int RANGE_CAP = CAND_CAP + CAND_OVF;   // most candidates the filter route re-scores per query; more -> exact route
+// tau[q] of the filter GEMM from the lower bound: below lo' - eps, rounded down; +inf for the padding queries
+hipError_t launch_range_tau(const float *q32p, const float *qnorm, const unsigned *gnorm_max_bits, double lo, int dimp, int metric,
+                            int64_t nq, int64_t nq_pad, float *tau, hipStream_t st);
+struct RangeFinalizeArgs {
+    const float *q32p;       // [nq, dimp]
+    const float *g32;        // [rows, dimp]
+    const int64_t *ids;      // [rows]
+    int regions, slots;      // the filter GEMM's candidate buffers, as in FinalizeArgs
+    const int *region_cnt;
+    const Cand *cand;
+    const int *ovf_cnt;
+    const Cand *ovf;
+    const int64_t *exclude;  // [nq] or null
+    const uint8_t *allow;    // [rows] or null
+    int64_t n_rows;
+    int dimp, metric, nq;
+    double lo, hi;
+    Hit *stage;              // [nq, RANGE_CAP]   the query's hits, best first
+    int32_t *count;          // [nq]              hits of the query (0 for a failed query)
+    int32_t *fail_list;      // [nq]              queries whose candidates overflowed: the exact route answers them
+    int *fail_count;         // [1]
+    unsigned long long *stats;   // [2]           queries answered here, candidates gathered
+};
+hipError_t launch_range_finalize(const RangeFinalizeArgs &a, hipStream_t st);
+// out[i] = exclude[list[i]]
+hipError_t launch_range_gather_exclude(const int64_t *exclude, const int32_t *list, int n, int64_t *out, hipStream_t st);
+// keys / pay [nq, n] as launch_rank_sort_build leaves them: the key of a row with allow[row] == 0 -> RANK_KEY_LAST
+hipError_t launch_range_mask_keys(uint64_t *keys, const int32_t *pay, int64_t n, const uint8_t *allow, int nq, hipStream_t st);
+// sorted keys [nq, n]: segment i's hits are the positions [first[i], first[i] + count[qx]) whose score s has lo < s <= hi;
+// qx = list ? list[i] : q_first + i in this and the two below
+hipError_t launch_range_cut(const uint64_t *keys, int64_t n, int nq, double lo, double hi, const int32_t *list, int64_t q_first,
+                            int32_t *first, int32_t *count, hipStream_t st);
+// exclusive scan of count[qx], i < m: off[qx] = base + the sum in front of i; tail_or_null[0] = total_out[0] = base + the sum
+hipError_t launch_range_scan(const int32_t *count, const int32_t *list, int64_t q_first, int m, int64_t base, int64_t *off,
+                             int64_t *tail_or_null, int64_t *total_out, hipStream_t st);
+// the cut's hits as (score, id) records at seg + off[qx], in sorted order
+hipError_t launch_range_emit(const int32_t *pay, int64_t n, const double *scores, int64_t ld, const int64_t *ids, int nq,
+                             const int32_t *list, int64_t q_first, const int32_t *first, const int32_t *count, const int64_t *off,
+                             Hit *seg, hipStream_t st);
+// CSR assembly: query i's count[i] records -> out + lims[i], from seg + xoff[i] when xoff[i] >= 0, else from its staging row
+hipError_t launch_range_compact(const Hit *stage, const Hit *seg, const int64_t *xoff, const int32_t *count, const int64_t *lims,
+                                int nq, Hit *out, hipStream_t st);
+// the records as the caller's arrays: fp32 reported values and / or fp64 ranking scores, ids
+hipError_t launch_range_fetch(const Hit *res, int64_t total, int metric, float *out_val, double *out_f64, int64_t *out_ids,
+                              hipStream_t st);
+
 // ---- k_conv_t2.hip: ResNet-50's convolutions on channels-last terms rows (mirx_conv_terms) and their glue ------------------
 hipError_t launch_conv_t2(const void *xt, const float *x_scale, const float *x_range, int64_t n, int h, int w, int cin, int ksz,
                           int stride, const void *wt, const float *oscale, const float *bias, int cout, float w_abs_sum,

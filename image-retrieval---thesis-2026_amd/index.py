@@ -25,6 +25,39 @@ def metric_code(metric):
         raise ValueError(f"Unknown metric type: {metric}") from None
 
 
+def _bound(value, name):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a number, got {type(value).__name__}")
+    value = float(value)
+    if value != value:
+        raise ValueError(f"{name} is NaN")
+    return value
+
+
+def range_bounds(metric_type, radius, range_filter=None):
+    """pymilvus' `radius` / `range_filter` search parameters as the bounds (lo, hi) of FlatIndex.range_search, in fp64.
+
+    COSINE / IP keep radius < similarity <= range_filter: lo = radius, hi = range_filter (+inf when absent).
+    L2 keeps range_filter <= distance < radius in the Euclidean units of Hit.distance; the index ranks by the NEGATIVE SQUARED
+    distance, so lo = -(radius ** 2) and hi = -(range_filter ** 2) (0.0 when absent).
+    Membership is decided on the fp64 ranking score (what search(return_f64=True) returns), not on the rounded fp32 `distance`
+    a hit reports: a row whose fp32 distance rounds onto the radius can fall on either side of it.
+    ValueError as pymilvus: range_filter <= radius for COSINE / IP; range_filter >= radius or a negative value for L2; a NaN;
+    a value that is not a number."""
+    metric = metric_code(metric_type)
+    radius = _bound(radius, "radius")
+    rf = None if range_filter is None else _bound(range_filter, "range_filter")
+    if metric == METRIC_NEG_L2:
+        if radius < 0 or (rf is not None and rf < 0):
+            raise ValueError("L2 radius / range_filter are distances: they must not be negative")
+        if rf is not None and rf >= radius:
+            raise ValueError(f"L2 range_filter ({rf}) must be less than radius ({radius})")
+        return -(radius * radius), (0.0 if rf is None else -(rf * rf))
+    if rf is not None and rf <= radius:
+        raise ValueError(f"COSINE / IP range_filter ({rf}) must be greater than radius ({radius})")
+    return radius, (float("inf") if rf is None else rf)
+
+
 def _stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -238,6 +271,44 @@ class FlatIndex:
                 ctypes.c_void_p(sc.data_ptr()) if sc is not None else None, _stream_ptr(self.device))
         _lib.check(rc, "mirx_index_rank_all")
         return (ids, sc) if with_scores else ids
+
+    def range_search(self, q, lo, hi=float("inf"), exclude_ids=None, allow=None, return_f64=False):
+        """Every row whose fp64 ranking score s (dot product; NEGATIVE SQUARED distance for L2) has lo < s <= hi -- not the
+        best k.  -> (lims int64 [nq + 1], scores [total], ids int64 [total]) on the index device: the hits of query i are
+        ids[lims[i]:lims[i + 1]], best first (score descending, equal scores by ascending id: rank_all's order).  scores holds
+        the fp32 reported values, or the fp64 ranking scores with return_f64=True.  exclude_ids / allow as in search(): a row is
+        a hit only when its mask entry is non-zero and its id is not the query's excluded id.  lo = -inf returns every eligible
+        row, hi <= lo nothing; a NaN bound raises ValueError.  range_bounds() maps pymilvus' radius / range_filter onto lo, hi.
+        The answer does not depend on the route (filter GEMM + fp64 re-score of every candidate, or the exact scan)."""
+        lo, hi = _bound(lo, "lo"), _bound(hi, "hi")
+        q, ex = self._prep_queries(q, exclude_ids)
+        am = None if allow is None else self._prep_allow(allow)
+        if am is not None and am.numel() != len(self):
+            raise ValueError(f"allow needs one entry per row of the index ({len(self)}), got {am.numel()}")
+        nq = q.shape[0]
+        lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
+        total = ctypes.c_int64(0)
+        with torch.cuda.device(self.device):
+            st = _stream_ptr(self.device)
+            _lib.check(self._lib.mirx_index_range_search(
+                self._h, ctypes.c_void_p(q.data_ptr()), nq, lo, hi,
+                ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
+                ctypes.c_void_p(am.data_ptr()) if am is not None and am.numel() else None, am.numel() if am is not None else 0,
+                ctypes.c_void_p(lims.data_ptr()), ctypes.byref(total), st), "mirx_index_range_search")
+            n = int(total.value)
+            sc = torch.empty((n,), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+            ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+            scp = ctypes.c_void_p(sc.data_ptr()) if n else None
+            _lib.check(self._lib.mirx_index_range_fetch(self._h, None if return_f64 else scp, scp if return_f64 else None,
+                                                        ctypes.c_void_p(ids.data_ptr()) if n else None, st),
+                       "mirx_index_range_fetch")
+        return lims, sc, ids
+
+    def range_last_stats(self):
+        s = _lib.RangeStats()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mirx_index_range_last_stats(self._h, ctypes.byref(s)), "mirx_index_range_last_stats")
+        return s.as_dict()
 
     def last_stats(self):
         s = _lib.SearchStats()

@@ -9,7 +9,7 @@ Mirrors (paths into /root/reference):
   NIH helpers                                       mirx.nih (nih_zilliz_utils.py)
 The "server" is a device-resident FlatIndex (libmirx); searches are EXACT (the reference's
 IVF_FLAT nlist=1024 / nprobe=10 index is approximate, milvus_setup.py:191-213) and
-`search_params` / `nprobe` are accepted and ignored.  Metadata (image_path, label) stays on
+`search_params` / `nprobe` are accepted and ignored, except `radius` / `range_filter` (a range search).  Metadata (image_path, label) stays on
 the host, keyed by the int64 ids the index returns.
 
 Errors follow the reference: unknown model type -> ValueError; connect() swallows failures
@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex
+from .index import FlatIndex, range_bounds
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -369,35 +369,76 @@ class Collection:
             self._changed()
         return None
 
+    def _queries(self, data):
+        q = torch.as_tensor(np.asarray(data, dtype=np.float32) if not torch.is_tensor(data) else data)
+        return q[None] if q.dim() == 1 else q
+
+    def _hits(self, ids, sc, fields):
+        """Hits of one query from its ids and fp32 reported values (numpy), empty slots skipped"""
+        hits = []
+        for i, v in zip(ids.tolist(), sc.tolist()):
+            if i < 0 or not np.isfinite(v):
+                continue
+            hits.append(Hit(i, v if self.metric_type in ("COSINE", "IP") else -v, self.entity(i, fields)))
+        return hits
+
+    @staticmethod
+    def _range_params(param):
+        """(radius, range_filter) of pymilvus' search `param` -- under param["params"] or at its top level -- or None when it
+        names no radius"""
+        if not isinstance(param, dict):
+            return None
+        inner = param.get("params") if isinstance(param.get("params"), dict) else {}
+        if "radius" not in inner and "radius" not in param:
+            return None
+        get = lambda k: inner[k] if k in inner else param.get(k)
+        return get("radius"), get("range_filter")
+
+    def range_search(self, data, radius, range_filter=None, expr=None, exclude_ids=None, output_fields=None):
+        """pymilvus' range search (search param {"radius": .., "range_filter": ..}) without a limit: -> one list of Hit per
+        query, best first, holding EVERY live row within the range -- COSINE / IP: radius < similarity <= range_filter; L2:
+        range_filter <= distance < radius in the Euclidean units of Hit.distance (mirx.index.range_bounds; decided on the fp64
+        ranking score, not on the rounded `distance`).  expr and exclude_ids as in search()."""
+        lo, hi = range_bounds(self.metric_type, radius, range_filter)
+        q = self._queries(data)
+        if self.num_entities == 0:
+            return [[] for _ in range(q.shape[0])]
+        allow = None if expr is None else self._device_mask(expr)
+        lims, sc, ids = self._ensure().range_search(q, lo, hi, exclude_ids=exclude_ids, allow=allow)
+        lims, sc, ids = lims.cpu().numpy(), sc.cpu().numpy(), ids.cpu().numpy()
+        fields = output_fields or []
+        return [self._hits(ids[lims[i]:lims[i + 1]], sc[lims[i]:lims[i + 1]], fields) for i in range(q.shape[0])]
+
     def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None, expr=None):
         """-> list (one per query) of lists of Hit, best first.  `distance` follows Milvus:
         COSINE/IP -> similarity, L2 -> Euclidean distance (>= 0).  expr (pymilvus' scalar filter, mirx.expr) restricts the
         search to the rows it selects -- exactly, on the device (FlatIndex.search(allow=)) -- so there are fewer than `limit`
-        hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes."""
-        q = torch.as_tensor(np.asarray(data, dtype=np.float32) if not torch.is_tensor(data) else data)
-        if q.dim() == 1:
-            q = q[None]
+        hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes.
+        param: {"params": {"radius": r, "range_filter": f}} (or the two keys at the top level) makes it pymilvus' range search:
+        the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored."""
+        q = self._queries(data)
         fields = output_fields or []
         if self.num_entities == 0:
             return [[] for _ in range(q.shape[0])]
         limit = min(int(limit), self.num_entities)
+        rng = self._range_params(param)
+        if rng is not None and rng[1] is not None:
+            return [hits[:limit] for hits in self.range_search(q, rng[0], rng[1], expr=expr, exclude_ids=exclude_ids,
+                                                               output_fields=output_fields)]
+        lo = None if rng is None else range_bounds(self.metric_type, rng[0])[0]
         allow = None if expr is None else self._device_mask(expr)
-        if limit > 1024:
-            sc, ids = self._ensure().rank_top(q, limit, exclude_ids=exclude_ids, allow=allow)
+        find = self._ensure().rank_top if limit > 1024 else self._ensure().search
+        if lo is None:
+            sc, ids = find(q, limit, exclude_ids=exclude_ids, allow=allow)
+            ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
         else:
-            sc, ids = self._ensure().search(q, limit, exclude_ids=exclude_ids, allow=allow)
-        ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
-        out = []
-        for qi in range(q.shape[0]):
-            hits = []
-            for j in range(ids.shape[1]):
-                i = int(ids[qi, j])
-                if i < 0 or not np.isfinite(sc[qi, j]):
-                    continue
-                dist = float(sc[qi, j]) if self.metric_type in ("COSINE", "IP") else float(-sc[qi, j])
-                hits.append(Hit(i, dist, self.entity(i, fields)))
-            out.append(hits)
-        return out
+            # a radius alone: the best `limit` rows, then those outside the radius dropped by their fp64 ranking scores -- the
+            # first `limit` hits of range_search without collecting the rest
+            s64, ids = find(q, limit, exclude_ids=exclude_ids, allow=allow, return_f64=True)
+            ids, s64 = ids.cpu().numpy(), s64.cpu().numpy()
+            ids = np.where(s64 > lo, ids, -1)
+            sc = (s64 if self.metric_type in ("COSINE", "IP") else -np.sqrt(np.maximum(-s64, 0.0))).astype(np.float32)
+        return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
 
 
 _NETWORK_SCHEMES = ("http", "https", "tcp", "grpc")
@@ -708,7 +749,8 @@ class MilvusRetriever:
             emb = self._embed_rows(torch.stack([self.transform(i) for i in imgs]))
         if self.collection is None:
             self.load_collection()
-        all_hits = self.collection.search(data=emb, limit=top_k, output_fields=["image_path", "label"], expr=expr)
+        all_hits = self.collection.search(data=emb, param=search_params, limit=top_k, output_fields=["image_path", "label"],
+                                          expr=expr)
         return [[self._format(h, self.collection.metric_type) for h in hits] for hits in all_hits]
 
     def adapter(self, name=None):

@@ -58,6 +58,7 @@ extern "C" {
 #define MIRX_OPT_RANK_SORT 5     /* which sort mirx_index_rank_all runs: MIRX_RANK_SORT_*          */
 #define MIRX_OPT_COMPACT_CHUNK_ROWS 6   /* test hook: rows per compaction chunk of mirx_index_remove_ids; 0 = default */
 #define MIRX_OPT_MASK_GATHER_BYTES 7    /* test hook: most scratch a masked search gathers its allowed rows into; -1 = default (1 GiB) */
+#define MIRX_OPT_RANGE_MAX_HITS 8       /* test hook: most hits one mirx_index_range_search call may return; 0 = default (2^28) */
 
 /* values of MIRX_OPT_RANK_SORT.  Both sorts return the same ranking; forcing one lets a test run either on any gallery. */
 #define MIRX_RANK_SORT_AUTO 0     /* bitonic network up to 65536 rows, radix sort above            */
@@ -217,6 +218,56 @@ int mirx_index_search_end(mirx_index *ix);
 int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                              const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,
                              double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
+
+/* Counters of the most recent range search on an index. */
+typedef struct mirx_range_stats {
+    int64_t nq;               /* queries in the call                                                     */
+    int64_t filter_answered;  /* answered by the filter GEMM + fp64 re-score of every candidate          */
+    int64_t exact_answered;   /* answered by the exact scan (routed there, or their candidates overflowed) */
+    int64_t candidates;       /* rows that passed the threshold, summed over the filter's queries        */
+    int64_t hits;             /* rows returned, summed over queries                                      */
+} mirx_range_stats;
+
+/*
+ * Exact range search: EVERY row within a radius, not the best k.  pymilvus' collection.search(..., param={"params":
+ * {"radius": .., "range_filter": ..}}) (the reference only ever passes nprobe / ef there, milvus/milvus_retrieval.py:80-86);
+ * the near-duplicate / leakage self-join over a gallery with exclude_ids = the row's own id.
+ * Membership is decided on the fp64 ranking score s (what mirx_index_search_f64 returns: the lane-tree dot product for
+ * MIRX_METRIC_IP, MINUS THE SQUARED distance for MIRX_METRIC_NEG_L2 -- not the rounded fp32 value that is reported):
+ *     row r is a hit of query i  <=>  lo < s(i, r) <= hi,  allow[r] != 0 (when a mask is given),  id[r] != exclude_ids[i]
+ *   q            device, [nq, dim] fp32
+ *   lo, hi       the bounds; lo = -inf returns every eligible row, hi = +inf is "no upper bound"; a NaN: MIRX_EINVAL;
+ *                hi <= lo: every query is empty and nothing is launched
+ *   exclude_ids  device, nq int64, or NULL
+ *   allow        n_allow bytes, one per row, non-zero = eligible, a host or a device pointer, or NULL with n_allow = 0;
+ *                otherwise n_allow != mirx_index_size: MIRX_EINVAL (the conventions of mirx_index_search_masked)
+ *   out_lims     device, [nq + 1] int64: the hits of query i are the entries lims[i] .. lims[i + 1] of what
+ *                mirx_index_range_fetch copies out; lims[0] = 0, lims[nq] = *out_total
+ *   out_total    host: the number of hits
+ * Within a query the hits are ordered by score descending, equal scores by ascending id (mirx_index_rank_all's order).
+ * Routes (the answer never depends on the route; no hit is decided from an approximate score):
+ *   filter  tiers on auto, size >= 32768, lo > -inf: the filter GEMM of mirx_index_search, unchanged, with a threshold derived
+ *           from lo and the GEMM's error bound instead of from a sample (every row with s > lo passes it); EVERY candidate is
+ *           re-scored in fp64 and tested.  A query with more than 1280 candidates (or an overflowed overflow list) goes to
+ *   exact   fp64 scores of all rows, the radix ranking of mirx_index_rank_top with masked / excluded rows behind every score,
+ *           then the span [first s <= hi, first s <= lo) of the sorted keys by binary search.  Also: small galleries,
+ *           MIRX_TIER_EXACT_ONLY, lo = -inf.  Cost and workspace per query are those of mirx_index_rank_top.
+ * Synchronous in the host sense: one host wait per internal batch of 8192 queries on the filter route (the overflow counter and
+ * the batch's hit count travel together), one more per sub-batch of the exact route.  The hits stay in a scratch of the index
+ * (16 bytes per hit, besides the staging rows of a filter batch: 1280 * 16 bytes per query) until mirx_index_range_fetch copies
+ * them out.  More than 2^28 hits in a call (MIRX_OPT_RANGE_MAX_HITS lowers it for tests): MIRX_ENOMEM, the index stays usable.
+ * Between mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.  No atomics decide a position: two calls return the
+ * same arrays.
+ *
+ * mirx_index_range_fetch: the `total` hits of the last range search as arrays of length total (device): fp32 reported values
+ *   (metric 0: dot, metric 1: -L2) and / or the fp64 ranking scores (either may be NULL, not both), and ids.  Without a
+ *   preceding range search, or after any other search / rank / add / remove call on the index: MIRX_ESTATE.
+ * mirx_index_range_last_stats: waits for the device, then copies the counters of the last range search.
+ */
+int mirx_index_range_search(mirx_index *ix, const float *q, int64_t nq, double lo, double hi, const int64_t *exclude_ids_or_null,
+                            const uint8_t *allow_or_null, int64_t n_allow, int64_t *out_lims, int64_t *out_total, void *stream);
+int mirx_index_range_fetch(mirx_index *ix, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids, void *stream);
+int mirx_index_range_last_stats(mirx_index *ix, mirx_range_stats *out);
 
 /* Waits for `stream`, then copies the counters of the last search. */
 int mirx_index_last_stats(mirx_index *ix, void *stream, mirx_search_stats *out);
