@@ -182,3 +182,48 @@ def case_expected(case, inputs):
     if case["qg"]:
         return rollout(atts, case["fusion"], case["ratio"], *SIZE, inputs["tokens"], inputs["q_feat"], proj_of(inputs))
     return rollout(atts, case["fusion"], case["ratio"], *SIZE)
+
+
+# ---- the layer kernel's float64 reference, its error bound and the near-tie audit (the GPU tests) ----------------------
+DEV = torch.device("cuda:0")
+U = 2.0 ** -24
+
+
+def _score_bound(qkv, heads, dh, scale):
+    """max over (image, head, i, j) of gamma_dh * scale * sum_d |q_d k_d|: the f32 scores' error bound."""
+    b, n, _ = qkv.shape
+    x = qkv.double().abs().view(b, n, 3, heads, dh)
+    m = torch.einsum("bihd,bjhd->bhij", x[:, :, 0], x[:, :, 1]).max().item()
+    return ((dh + 3) * U / (1 - dh * U)) * scale * m               # + 3 u: the scale product and the max subtraction
+
+
+def _fused64(qkv, heads, dh, scale, fusion):
+    """float64 softmax((q k^T) * scale) of the f32 qkv, fused over the heads -> [b, n, n] (torch float64 on the GPU)."""
+    b, n, _ = qkv.shape
+    x = qkv.to(DEV).double().view(b, n, 3, heads, dh)
+    s = torch.einsum("bihd,bjhd->bhij", x[:, :, 0], x[:, :, 1]) * scale
+    p = torch.softmax(s, dim=-1)
+    return {"mean": lambda: p.mean(1), "max": lambda: p.amax(1), "min": lambda: p.amin(1)}[fusion]()
+
+
+def _audited_expected(F64, got, k, tol):
+    """The float64 row stage of F64 [b, n, n] with the kept set the kernel chose (got [b, n, n], its A_l): every entry where
+    the two kept sets differ must be a near-tie, |F64 - thr| <= tol * thr.  Returns (expected A_l, number of flips)."""
+    n = F64.shape[-1]
+    eye = torch.eye(n, dtype=torch.float64, device=F64.device)
+    if k == 0:
+        mask = torch.ones_like(F64, dtype=torch.bool)
+        flips = 0
+    else:
+        thr = torch.kthvalue(F64, k, dim=-1).values.unsqueeze(-1)
+        kept64 = F64 > thr
+        mask = got.double() > 0
+        off = ~eye.bool()
+        mask = torch.where(off, mask, kept64)                       # the diagonal: the float64 decision
+        diff = (mask != kept64) & off
+        flips = int(diff.sum())
+        if flips:
+            gap = ((F64 - thr).abs() / thr)[diff]
+            assert float(gap.max()) <= tol, (flips, float(gap.max()), tol)
+    a = F64 * mask + eye
+    return a / (a.sum(-1, keepdim=True) + 1e-8), flips
