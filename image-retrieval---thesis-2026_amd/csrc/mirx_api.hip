@@ -1106,6 +1106,14 @@ int mirx_index_get_rows(const mirx_index *ix, int64_t first, int64_t n, float *o
     return MIRX_OK;
 }
 
+int mirx_index_get_ids(const mirx_index *ix, int64_t first, int64_t n, int64_t *out_ids) {
+    MIRX_CHECK(ix && first >= 0 && n >= 0 && first + n <= ix->size && (out_ids || n == 0), "get_ids: bad range");
+    if (n == 0) return MIRX_OK;
+    DeviceGuard dg(ix->device);
+    MIRX_HIP(hipMemcpy(out_ids, ix->ids + first, (size_t)n * sizeof(int64_t), hipMemcpyDefault));
+    return MIRX_OK;
+}
+
 int mirx_index_search(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                       float *out_scores, int64_t *out_ids, void *stream) {
     return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores, nullptr, out_ids,
@@ -1814,6 +1822,76 @@ int mirx_rank_metrics(const int64_t *ranks, int64_t nq, int64_t n, int64_t row_s
     }
     a.out_ap = out_ap; a.out_cnt = out_cnt; a.out_nrel = out_nrel; a.out_maxpos = out_maxpos;
     MIRX_HIP(launch_rank_metrics(a, rel_kind, ap_kind, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+static const char *group_limits(int limit, int group_size) {
+    if (limit < 1 || limit > MIRX_GROUP_MAX_LIMIT) return "limit must be in [1, 1024]";
+    if (group_size < 1 || group_size > MIRX_GROUP_MAX_SIZE) return "group_size must be in [1, 64]";
+    if ((int64_t)limit * group_size > MIRX_GROUP_MAX_HITS) return "limit * group_size must not exceed 16384";
+    return nullptr;
+}
+
+int mirx_group_walk(const int64_t *ranks, const int64_t *table_index_or_null, const double *scores_or_null, int64_t nq, int64_t depth,
+                    int64_t row_stride, const int64_t *group_of, int64_t n_table, const int64_t *group_rows, int64_t n_groups,
+                    int64_t live_groups, const int64_t *excl_group_or_null, int limit, int group_size, int64_t *out_ids,
+                    double *out_scores_or_null, int64_t *out_codes, int32_t *out_kept, int32_t *out_state, void *stream) {
+    if (const char *why = group_limits(limit, group_size)) return fail(MIRX_EINVAL, std::string("group_walk: ") + why);
+    MIRX_CHECK(nq >= 0 && depth >= 0 && row_stride >= depth && n_table >= 0, "group_walk: bad sizes");
+    MIRX_CHECK(n_groups >= 0 && n_groups <= 0x7FFFFFFFll && live_groups >= 0 && live_groups <= n_groups,
+               "group_walk: 0 <= live_groups <= n_groups < 2^31");
+    MIRX_CHECK(nq == 0 || (out_ids && out_codes && out_kept && out_state), "group_walk: null output");
+    MIRX_CHECK(nq == 0 || depth == 0 || ranks, "group_walk: null ranks");
+    MIRX_CHECK(nq == 0 || ((group_of || n_table == 0) && (group_rows || n_groups == 0)), "group_walk: null table");
+    MIRX_CHECK(!out_scores_or_null || scores_or_null || depth == 0, "group_walk: out_scores without scores");
+    GroupWalkArgs a{};
+    a.ranks = ranks; a.table_index = table_index_or_null; a.scores = out_scores_or_null ? scores_or_null : nullptr;
+    a.nq = nq; a.depth = depth; a.row_stride = row_stride;
+    a.group_of = group_of; a.n_table = n_table; a.group_rows = group_rows; a.n_groups = n_groups; a.live_groups = live_groups;
+    a.excl_group = excl_group_or_null; a.limit = limit; a.group_size = group_size;
+    a.out_ids = out_ids; a.out_scores = out_scores_or_null; a.out_codes = out_codes; a.out_kept = out_kept; a.out_state = out_state;
+    MIRX_HIP(launch_group_walk(a, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
+int mirx_group_count(const int64_t *groups, const uint8_t *allow_or_null, int64_t n, int64_t n_groups, int64_t *out_counts, void *stream) {
+    MIRX_CHECK(n >= 0 && n_groups >= 0 && n_groups <= 0x7FFFFFFFll, "group_count: bad sizes");
+    MIRX_CHECK((groups || n == 0) && (out_counts || n_groups == 0), "group_count: null buffer");
+    if (n_groups == 0) return MIRX_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    MIRX_HIP(hipMemsetAsync(out_counts, 0, (size_t)n_groups * sizeof(int64_t), st));
+    MIRX_HIP(launch_group_count(groups, allow_or_null, n, n_groups, out_counts, st));
+    return MIRX_OK;
+}
+
+int mirx_index_group_fill(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null, int limit, int group_size,
+                          const int64_t *pair_query, const int64_t *pair_slot, const int64_t *pair_first, const int64_t *pair_len,
+                          int64_t n_pairs, const int64_t *members, int64_t n_members, int max_members, int64_t *out_ids,
+                          double *out_rank_scores, void *stream) {
+    MIRX_CHECK(ix, "group_fill: null index");
+    if (const char *why = group_limits(limit, group_size)) return fail(MIRX_EINVAL, std::string("group_fill: ") + why);
+    MIRX_CHECK(nq >= 0 && nq <= 0x7FFFFF00ll && n_pairs >= 0 && n_pairs <= 0x7FFFFFFFll && n_members >= 0, "group_fill: bad sizes");
+    MIRX_CHECK(max_members >= 1 && max_members <= MIRX_GROUP_FILL_MAX, "group_fill: max_members must be in [1, 4096]");
+    MIRX_CHECK(n_pairs == 0 || (q && pair_query && pair_slot && pair_first && pair_len && members && out_ids && out_rank_scores),
+               "group_fill: null buffer");
+    if (ix->pend.active || ix->begun)
+        return fail(MIRX_ESTATE, "group_fill: a search begun with mirx_index_search_begin is still pending (call mirx_index_search_end)");
+    if (n_pairs == 0 || nq == 0) return MIRX_OK;
+    ix->range_valid = false;
+    DeviceGuard dg(ix->device);
+    if (!dg.ok) return fail(MIRX_EHIP, "group_fill: cannot select the index device");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    MIRX_HIP(ix->q32p.ensure((size_t)nq * ix->dimp * sizeof(float)));
+    MIRX_HIP(ix->q16.ensure((size_t)nq * ix->dimp * sizeof(uint16_t)));
+    MIRX_HIP(ix->qnorm.ensure((size_t)nq * sizeof(float)));
+    MIRX_HIP(launch_prep_queries(q, nq, nq, ix->dim, ix->dimp, ix->q32p.as<float>(), ix->q16.as<uint16_t>(), ix->qnorm.as<float>(), st));
+    GroupFillArgs a{};
+    a.q32p = ix->q32p.as<float>(); a.g32 = ix->g32; a.ids = ix->ids; a.exclude = exclude_ids_or_null;
+    a.nq = nq; a.n_rows = ix->size; a.dimp = ix->dimp; a.limit = limit; a.group_size = group_size;
+    a.pair_query = pair_query; a.pair_slot = pair_slot; a.pair_first = pair_first; a.pair_len = pair_len; a.n_pairs = n_pairs;
+    a.members = members; a.n_members = n_members; a.max_members = max_members;
+    a.out_ids = out_ids; a.out_f64 = out_rank_scores;
+    MIRX_HIP(launch_group_fill(a, ix->metric, st));
     return MIRX_OK;
 }
 

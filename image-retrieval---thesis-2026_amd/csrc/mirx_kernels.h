@@ -400,6 +400,46 @@ hipError_t launch_range_compact(const Hit *stage, const Hit *seg, const int64_t 
 hipError_t launch_range_fetch(const Hit *res, int64_t total, int metric, float *out_val, double *out_f64, int64_t *out_ids,
                               hipStream_t st);
 
+// ---- k_group.hip: grouping search (mirx_group_walk / mirx_group_count / mirx_index_group_fill) -----------------------------
+struct GroupWalkArgs {
+    const int64_t *ranks;        // [nq, row_stride >= depth] ranked ids, best first; a -1 ends the ranking
+    const int64_t *table_index;  // laid out alike: the entry's index into group_of, or null when the id is that index
+    const double *scores;        // laid out alike, or null
+    int64_t nq, depth, row_stride;
+    const int64_t *group_of;     // [n_table] group code per entry
+    int64_t n_table;
+    const int64_t *group_rows;   // [n_groups] eligible rows per code
+    int64_t n_groups, live_groups;
+    const int64_t *excl_group;   // [nq] code of the query's excluded row or -1; or null
+    int limit, group_size;
+    int table;                   // slots of the hash table (filled by the launcher: group_walk_table(limit))
+    int64_t *out_ids;            // [nq, limit, group_size]
+    double *out_scores;          // alike, or null
+    int64_t *out_codes;          // [nq, limit]
+    int32_t *out_kept;           // [nq, limit]
+    int32_t *out_state;          // [nq, 2]: groups open; bit 0 complete, bit 1 groups final
+};
+int group_walk_table(int limit);                 // power of two >= max(64, 2 * limit)
+hipError_t launch_group_walk(const GroupWalkArgs &a, hipStream_t st);
+// counts[c] += the rows r < n with groups[r] == c and allow[r] != 0 (allow null = every row); codes outside [0, n_groups) are skipped
+hipError_t launch_group_count(const int64_t *groups, const uint8_t *allow, int64_t n, int64_t n_groups, int64_t *counts, hipStream_t st);
+struct GroupFillArgs {
+    const float *q32p;           // [nq, dimp] prepared queries
+    const float *g32;            // [n_rows, dimp]
+    const int64_t *ids;          // [n_rows]
+    const int64_t *exclude;      // [nq] or null
+    int64_t nq, n_rows;
+    int dimp, limit, group_size;
+    const int64_t *pair_query, *pair_slot, *pair_first, *pair_len;   // [n_pairs]: members[first .. first + len) are the group's rows
+    int64_t n_pairs;
+    const int64_t *members;      // [n_members] row positions
+    int64_t n_members;
+    int max_members;             // >= every pair_len (sizes the LDS; a longer span is cut to it)
+    int64_t *out_ids;            // [nq, limit, group_size]
+    double *out_f64;             // alike
+};
+hipError_t launch_group_fill(const GroupFillArgs &a, int metric, hipStream_t st);
+
 // ---- k_conv_t2.hip: ResNet-50's convolutions on channels-last terms rows (mirx_conv_terms) and their glue ------------------
 hipError_t launch_conv_t2(const void *xt, const float *x_scale, const float *x_range, int64_t n, int h, int w, int cin, int ksz,
                           int stride, const void *wt, const float *oscale, const float *bias, int cout, float w_abs_sum,

@@ -107,6 +107,7 @@ class ExprCache:
         self.text = None
         self.mask = None
         self.device_mask = None
+        self.device_codes = {}            # name -> the column's codes on the index's device (grouping search)
 
     def _coded(self, name):
         got = self.codes.get(name)

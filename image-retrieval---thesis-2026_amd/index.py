@@ -58,8 +58,36 @@ def range_bounds(metric_type, radius, range_filter=None):
     return radius, (float("inf") if rf is None else rf)
 
 
+# Routing of FlatIndex.search_grouped: these only affect speed, never the answer.
+GROUP_DIRECT_MAX = 16                      # at most this many groups with eligible rows: one masked search per group
+GROUP_FILL_MAX = _lib.GROUP_FILL_MAX       # largest group mirx_index_group_fill completes; a larger one is reached by deepening
+GROUP_FIRST_DEPTH = 64                     # the first walked prefix (k + excluded id <= 64 keeps search() on the filter-GEMM tier)
+GROUP_DEEPEN_FACTOR = 8                    # each deeper prefix is this many times the previous one
+GROUP_DEEPEN_BYTES = 256 << 20             # most ids + fp64 scores one rank_top call of the deepening returns
+_GROUP_ROUTES = ("auto", "direct", "walk", "deepen")
+
+
+def group_bounds(limit, group_size):
+    """limit / group_size of a grouping search as ints, ValueError outside the contract's bounds"""
+    for name, v in (("limit", limit), ("group_size", group_size)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {type(v).__name__}")
+    limit, group_size = int(limit), int(group_size)
+    if not 1 <= limit <= _lib.GROUP_MAX_LIMIT:
+        raise ValueError(f"grouping search: limit (the number of groups) must be in [1, {_lib.GROUP_MAX_LIMIT}], got {limit}")
+    if not 1 <= group_size <= _lib.GROUP_MAX_SIZE:
+        raise ValueError(f"grouping search: group_size must be in [1, {_lib.GROUP_MAX_SIZE}], got {group_size}")
+    if limit * group_size > _lib.GROUP_MAX_HITS:
+        raise ValueError(f"grouping search: limit * group_size must not exceed {_lib.GROUP_MAX_HITS}, got {limit * group_size}")
+    return limit, group_size
+
+
 def _stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 class FlatIndex:
@@ -83,6 +111,8 @@ class FlatIndex:
         _lib.check(self._lib.mirx_index_create(self.dim, self.metric, self.device.index, ctypes.byref(h)),
                    "mirx_index_create")
         self._h = h
+        self._ids = self._id_table = None                    # ids() and what search_grouped derives from them, until the rows change
+        self._group_stats = {}
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -121,6 +151,7 @@ class FlatIndex:
             idp = ctypes.c_void_p(ids.data_ptr())
         if rows.is_cuda:
             torch.cuda.current_stream(self.device).synchronize()
+        self._ids = self._id_table = None
         _lib.check(self._lib.mirx_index_add(self._h, ctypes.c_void_p(rows.data_ptr()), rows.shape[0], idp),
                    "mirx_index_add")
 
@@ -132,6 +163,7 @@ class FlatIndex:
         if ids.is_cuda and ids.device != self.device:
             ids = ids.to(self.device)
         removed = ctypes.c_int64(0)
+        self._ids = self._id_table = None
         with torch.cuda.device(self.device):
             _lib.check(self._lib.mirx_index_remove_ids(self._h, ctypes.c_void_p(ids.data_ptr()) if ids.numel() else None,
                                                        ids.numel(), ctypes.byref(removed), _stream_ptr(self.device)),
@@ -303,6 +335,240 @@ class FlatIndex:
                                                         ctypes.c_void_p(ids.data_ptr()) if n else None, st),
                        "mirx_index_range_fetch")
         return lims, sc, ids
+
+    # -- grouping search -------------------------------------------------------------------------------------
+    def ids(self):
+        """The ids of the index's rows, in row order: int64 on the index device, no row is copied.  Kept until add() / remove()."""
+        n = len(self)
+        if self._ids is None or self._ids.shape[0] != n:
+            out = torch.empty((n,), dtype=torch.int64, device=self.device)
+            if n:
+                with torch.cuda.device(self.device):
+                    torch.cuda.current_stream(self.device).synchronize()
+                    _lib.check(self._lib.mirx_index_get_ids(self._h, 0, n, ctypes.c_void_p(out.data_ptr())), "mirx_index_get_ids")
+            self._ids, self._id_table = out, None
+        return self._ids
+
+    def _group_id_table(self):
+        """(identity, sorted ids, their rows): how a ranked id becomes a row position.  identity = the ids are 0 .. n-1, the id
+        is the position.  A repeated id cannot be grouped (its rows would be told apart by nothing): ValueError."""
+        ids = self.ids()
+        if self._id_table is None:
+            n = ids.shape[0]
+            if bool((ids == torch.arange(n, dtype=torch.int64, device=self.device)).all()):
+                self._id_table = (True, None, None)
+            else:
+                sorted_ids, order = torch.sort(ids)
+                if n > 1 and bool((sorted_ids[1:] == sorted_ids[:-1]).any()):
+                    raise ValueError("search_grouped: an id repeats in the index; grouping needs one row per id")
+                self._id_table = (False, sorted_ids, order)
+        return self._id_table
+
+    def _positions(self, ids):
+        """row position of each id of an int64 tensor on the device, -1 for ids the index does not hold (the -1 padding too)"""
+        identity, sorted_ids, order = self._group_id_table()
+        n = len(self)
+        if identity:
+            return torch.where((ids >= 0) & (ids < n), ids, torch.full_like(ids, -1))
+        p = torch.searchsorted(sorted_ids, ids.contiguous()).clamp_(max=n - 1)
+        return torch.where(sorted_ids[p] == ids, order[p], torch.full_like(ids, -1))
+
+    def _group_walk(self, rid, s64, g, rows, live, eg, limit, group_size):
+        """mirx_group_walk over the ranked prefixes rid / s64 [m, depth] -> (ids, fp64 scores, codes, kept, state)"""
+        m, depth = rid.shape
+        rid, s64 = rid.contiguous(), s64.contiguous()
+        tix = None if self._group_id_table()[0] else self._positions(rid).contiguous()
+        ids = torch.empty((m, limit, group_size), dtype=torch.int64, device=self.device)
+        sc = torch.empty((m, limit, group_size), dtype=torch.float64, device=self.device)
+        codes = torch.empty((m, limit), dtype=torch.int64, device=self.device)
+        kept = torch.empty((m, limit), dtype=torch.int32, device=self.device)
+        state = torch.empty((m, 2), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mirx_group_walk(_ptr(rid), _ptr(tix), _ptr(s64), m, depth, depth, _ptr(g), g.shape[0], _ptr(rows),
+                                                 rows.shape[0], live, _ptr(eg), limit, group_size, _ptr(ids), _ptr(sc), _ptr(codes),
+                                                 _ptr(kept), _ptr(state), _stream_ptr(self.device)), "mirx_group_walk")
+        return ids, sc, codes, kept, state
+
+    def _group_count(self, g, am, n_groups):
+        """mirx_group_count: eligible rows per code, int64 [n_groups]"""
+        rows = torch.empty((n_groups,), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mirx_group_count(_ptr(g), _ptr(am), g.shape[0], n_groups, _ptr(rows), _stream_ptr(self.device)),
+                       "mirx_group_count")
+        return rows
+
+    def _group_fill(self, q, ex, limit, group_size, pq, ps, pf, pl, members, ids, s64):
+        """mirx_index_group_fill: the pairs' groups, best group_size members each, into ids / s64 [nq, limit, group_size]"""
+        pq, ps, pf, pl = (t.contiguous() for t in (pq, ps, pf, pl))
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.mirx_index_group_fill(
+                self._h, _ptr(q), q.shape[0], _ptr(ex), limit, group_size, _ptr(pq), _ptr(ps), _ptr(pf), _ptr(pl), pq.shape[0],
+                _ptr(members), members.shape[0], int(pl.max()), _ptr(ids), _ptr(s64), _stream_ptr(self.device)),
+                "mirx_index_group_fill")
+
+    def search_grouped(self, q, groups, limit, group_size=1, exclude_ids=None, allow=None, return_f64=False, route="auto"):
+        """Grouping search: the best hits per GROUP instead of the best rows (pymilvus' group_by_field / group_size with
+        strict_group_size=True).  groups: one integer code >= 0 per row of the index, in row order, like `allow`.  Per query,
+        over rank_all's order (fp64 score descending, equal scores by ascending id) restricted to the eligible rows (mask entry
+        non-zero, id not the query's excluded id): the min(limit, groups with an eligible row) groups whose best row ranks
+        highest, ordered by that row, each with its first min(group_size, its eligible rows) rows in ranking order.
+        -> (ids [nq, limit, group_size] int64, -1 in empty slots; scores alike: fp32 reported values, or the fp64 ranking scores
+        with return_f64=True, -inf in empty slots; group_codes [nq, limit] int64, -1 in empty slots) on the index device.  The
+        scores are the bits search() returns for the same (query, row).
+        1 <= limit <= 1024, 1 <= group_size <= 64, limit * group_size <= 16384.  ValueError: negative or non-integer codes,
+        len(groups) != len(index), an id that repeats in the index.
+        route: "auto", or one of "direct" / "walk" / "deepen" to force it -- the answer never depends on the route:
+          direct  at most GROUP_DIRECT_MAX groups have eligible rows: one masked search(k=group_size) per group, the groups
+                  ordered by their best row (two stable sorts);
+          walk    a ranked prefix from search() (63 / 64 deep: the filter-GEMM tier; min(1024, 4 * limit) when limit is too large
+                  for that: the exact tier), walked by mirx_group_walk; queries whose groups are decided but short have those
+                  groups completed by mirx_index_group_fill (groups of up to GROUP_FILL_MAX rows), the others go to
+          deepen  rank_top() prefixes of 8x the previous depth, walked again, the last the whole ranking: slow and exact.
+        group_last_stats() says which route answered how many queries."""
+        if route not in _GROUP_ROUTES:
+            raise ValueError(f"route must be one of {', '.join(_GROUP_ROUTES)}, got {route!r}")
+        limit, group_size = group_bounds(limit, group_size)
+        n = len(self)
+        g = groups if torch.is_tensor(groups) else torch.as_tensor(np.asarray(groups))
+        if g.dtype in (torch.bool,) or g.is_floating_point() or g.is_complex():
+            raise ValueError(f"groups must be integer codes, got {g.dtype}")
+        g = g.detach().reshape(-1)
+        if g.shape[0] != n:
+            raise ValueError(f"groups needs one code per row of the index ({n}), got {g.shape[0]}")
+        g = g.to(device=self.device, dtype=torch.int64).contiguous()
+        q, ex = self._prep_queries(q, exclude_ids)
+        am = None if allow is None else self._prep_allow(allow).to(self.device)
+        if am is not None and am.numel() != n:
+            raise ValueError(f"allow needs one entry per row of the index ({n}), got {am.numel()}")
+        nq = q.shape[0]
+        ids = torch.full((nq, limit, group_size), -1, dtype=torch.int64, device=self.device)
+        s64 = torch.full((nq, limit, group_size), float("-inf"), dtype=torch.float64, device=self.device)
+        codes = torch.full((nq, limit), -1, dtype=torch.int64, device=self.device)
+        stats = {"nq": nq, "route": route, "direct": 0, "walk": 0, "fill": 0, "deepen": 0, "passes": 0, "max_depth": 0,
+                 "groups": 0}
+        self._group_stats = stats
+        uniq = None
+        if n:
+            if int(g.min()) < 0:
+                raise ValueError("groups holds a negative code")
+            self._group_id_table()                               # (a repeated id raises before anything is searched)
+            if int(g.max()) >= 2 * n + 1024:                     # sparse codes: the count table is indexed by code
+                uniq, g = torch.unique(g, return_inverse=True)
+                g = g.contiguous()
+        if n and nq:
+            n_groups = int(g.max()) + 1
+            rows = self._group_count(g, am, n_groups)
+            live = int((rows > 0).sum())
+            stats["groups"] = live
+            if live:
+                eg = None
+                if ex is not None:                               # the group each query's excluded row takes a row from
+                    pos = self._positions(ex)
+                    ok = pos >= 0
+                    if am is not None:
+                        ok &= am[pos.clamp(min=0)] != 0
+                    eg = torch.where(ok, g[pos.clamp(min=0)], torch.full_like(pos, -1)).contiguous()
+                if route == "direct" or (route == "auto" and live <= GROUP_DIRECT_MAX):
+                    self._grouped_direct(q, ex, am, g, rows, limit, group_size, ids, s64, codes, stats)
+                else:
+                    self._grouped_walk(q, ex, am, g, rows, live, eg, limit, group_size, ids, s64, codes, stats,
+                                       deepen_only=route == "deepen")
+        if uniq is not None:
+            codes = torch.where(codes >= 0, uniq[codes.clamp(min=0)], codes)
+        if return_f64:
+            return ids, s64, codes
+        val = s64 if self.metric == METRIC_IP else -torch.sqrt(torch.clamp(-s64, min=0.0))
+        return ids, val.to(torch.float32), codes
+
+    def _grouped_direct(self, q, ex, am, g, rows, limit, group_size, ids, s64, codes, stats):
+        """one masked search per group with eligible rows, then the groups of each query in the order of their best rows"""
+        live_codes = torch.nonzero(rows > 0).flatten()
+        allowed = None if am is None else am != 0
+        ss, ii = [], []
+        for c in live_codes.tolist():
+            mask = g == c
+            if allowed is not None:
+                mask &= allowed
+            s, i = self.search(q, group_size, exclude_ids=ex, return_f64=True, allow=mask)
+            ss.append(s)
+            ii.append(i)
+        s_all, i_all = torch.stack(ss, 1), torch.stack(ii, 1)          # [nq, groups, group_size]
+        # (best score descending, best id ascending): a stable sort by id, then a stable sort by score.  A group without an
+        # eligible row for the query (its only one was the excluded id) reads (-inf, -1), lands last and is dropped.
+        o1 = torch.sort(i_all[:, :, 0], dim=1, stable=True).indices
+        o2 = torch.sort(s_all[:, :, 0].gather(1, o1), dim=1, descending=True, stable=True).indices
+        order = o1.gather(1, o2)[:, :limit]
+        t = order.shape[1]
+        pick = order[:, :, None].expand(-1, -1, group_size)
+        ids[:, :t] = i_all.gather(1, pick)
+        s64[:, :t] = s_all.gather(1, pick)
+        codes[:, :t] = torch.where(ids[:, :t, 0] >= 0, live_codes[order], torch.full_like(order, -1))
+        stats["direct"] = q.shape[0]
+        stats["passes"] = int(live_codes.shape[0])
+        stats["max_depth"] = group_size
+
+    def _grouped_walk(self, q, ex, am, g, rows, live, eg, limit, group_size, ids, s64, codes, stats, deepen_only):
+        n, nq = len(self), q.shape[0]
+        depth = GROUP_FIRST_DEPTH
+        todo = torch.arange(nq, device=self.device)
+        if not deepen_only:
+            depth = GROUP_FIRST_DEPTH - (1 if ex is not None else 0)      # k (+1 with exclude ids) <= 64: the filter-GEMM tier
+            if limit > depth // 4:
+                depth = min(1024, 4 * limit)                              # the exact tier (DESIGN 34)
+            depth = min(depth, n)
+            sc, rid = self.search(q, depth, exclude_ids=ex, return_f64=True, allow=am)
+            w_ids, w_sc, w_codes, w_kept, state = self._group_walk(rid, sc, g, rows, live, eg, limit, group_size)
+            ids.copy_(w_ids), s64.copy_(w_sc), codes.copy_(w_codes)
+            stats["passes"] += 1
+            stats["max_depth"] = depth
+            complete, final = (state[:, 1] & 1) != 0, (state[:, 1] & 2) != 0
+            stats["walk"] = int(complete.sum())
+            deep = ~final
+            fill_q = torch.nonzero(final & ~complete).flatten()
+            if fill_q.numel():
+                # the groups of these queries are decided; the ones that are short get their rows from the group's member list
+                c = codes[fill_q]
+                cnt = rows[c.clamp(min=0)]
+                short = (c >= 0) & (w_kept[fill_q] < (cnt - (0 if eg is None else (c == eg[fill_q][:, None]).to(cnt.dtype)))
+                                    .clamp(max=group_size))
+                too_big = (short & (cnt > GROUP_FILL_MAX)).any(1)         # such a group is cheaper to reach by deepening
+                deep[fill_q[too_big]] = True
+                short &= ~too_big[:, None]
+                a, slot = torch.nonzero(short, as_tuple=True)
+                if a.numel():
+                    elig = torch.arange(n, device=self.device) if am is None else torch.nonzero(am).flatten()
+                    members = elig[torch.argsort(g[elig], stable=True)].contiguous()      # eligible rows, group after group
+                    first = torch.cumsum(rows, 0) - rows
+                    pc = c[a, slot]
+                    self._group_fill(q, ex, limit, group_size, fill_q[a], slot, first[pc], rows[pc], members, ids, s64)
+                stats["fill"] = int(fill_q.numel() - too_big.sum())
+            todo = torch.nonzero(deep).flatten()
+        stats["deepen"] = int(todo.numel())
+        whole = False                                                     # the last prefix was the whole ranking
+        while todo.numel():
+            if whole:
+                raise MirxError("search_grouped: the whole ranking left a query incomplete (the group counts and the ranking disagree)")
+            depth = min(n, depth * GROUP_DEEPEN_FACTOR)
+            whole = depth == n
+            per = max(1, GROUP_DEEPEN_BYTES // (16 * depth))
+            rest = []
+            for b in range(0, todo.numel(), per):
+                sub = todo[b:b + per]
+                sc, rid = self.rank_top(q[sub], depth, exclude_ids=None if ex is None else ex[sub], return_f64=True, allow=am)
+                w_ids, w_sc, w_codes, _, state = self._group_walk(rid, sc, g, rows, live, None if eg is None else eg[sub].contiguous(),
+                                                                  limit, group_size)
+                done = (state[:, 1] & 1) != 0
+                ids[sub[done]], s64[sub[done]], codes[sub[done]] = w_ids[done], w_sc[done], w_codes[done]
+                rest.append(sub[~done])
+                stats["passes"] += 1
+            stats["max_depth"] = depth
+            todo = torch.cat(rest)
+
+    def group_last_stats(self):
+        """What the last search_grouped did: nq; route = the `route` argument; direct / walk / fill / deepen = the queries each
+        route answered (walk: complete after the first prefix; fill: completed by mirx_index_group_fill; deepen: needed deeper
+        prefixes); passes = search / rank_top calls made; max_depth = the deepest prefix; groups = codes with an eligible row."""
+        return dict(self._group_stats)
 
     def range_last_stats(self):
         s = _lib.RangeStats()

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex, range_bounds
+from .index import FlatIndex, group_bounds, range_bounds
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -292,6 +292,7 @@ class Collection:
         self._index, self._resident = index, True
         if self._expr is not None:
             self._expr.device_mask = None
+            self._expr.device_codes = {}
 
     def release(self):
         """pymilvus' collection.release(): a persistent collection gives its device memory back (load() reads it again);
@@ -300,6 +301,7 @@ class Collection:
             self._index, self._resident = None, False
             if self._expr is not None:
                 self._expr.device_mask = None
+                self._expr.device_codes = {}
 
     def flush(self):
         """Commit inserts and deletions to disk (ingest_embeddings.py:532-534, "Flush to persist data"); in memory there is
@@ -409,15 +411,56 @@ class Collection:
         fields = output_fields or []
         return [self._hits(ids[lims[i]:lims[i + 1]], sc[lims[i]:lims[i + 1]], fields) for i in range(q.shape[0])]
 
-    def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None, expr=None):
+    def _device_codes(self, name):
+        """The dictionary codes of scalar field `name` (mirx.expr.ExprCache.codes: one int64 per live row, aligned with
+        live_ids()) as a tensor on the index's device, and the distinct values they stand for; built and uploaded once per
+        collection state, like _device_mask."""
+        from .expr import ExprCache
+        index = self._ensure()
+        if self._expr is None:
+            self._expr = ExprCache(self.live_ids(), self.field)
+        cache = self._expr
+        distinct, codes = cache._coded(name)
+        dev = cache.device_codes.get(name)
+        if dev is None or dev.device != index.device:
+            dev = cache.device_codes[name] = torch.from_numpy(codes).to(index.device)
+        return distinct, dev
+
+    def _search_grouped(self, q, limit, group_by_field, group_size, fields, exclude_ids, expr):
+        distinct, codes = self._device_codes(group_by_field)
+        allow = None if expr is None else self._device_mask(expr)
+        ids, sc, _ = self._ensure().search_grouped(q, codes, limit, group_size, exclude_ids=exclude_ids, allow=allow)
+        ids, sc = ids.cpu().numpy().reshape(q.shape[0], -1), sc.cpu().numpy().reshape(q.shape[0], -1)
+        fields = list(fields) + ([] if group_by_field in fields else [group_by_field])
+        return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
+
+    def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None, expr=None,
+               group_by_field=None, group_size=1, strict_group_size=True):
         """-> list (one per query) of lists of Hit, best first.  `distance` follows Milvus:
         COSINE/IP -> similarity, L2 -> Euclidean distance (>= 0).  expr (pymilvus' scalar filter, mirx.expr) restricts the
         search to the rows it selects -- exactly, on the device (FlatIndex.search(allow=)) -- so there are fewer than `limit`
         hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes.
         param: {"params": {"radius": r, "range_filter": f}} (or the two keys at the top level) makes it pymilvus' range search:
-        the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored."""
+        the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored.
+        group_by_field (a scalar field of the schema) makes it pymilvus' grouping search: `limit` counts GROUPS (at most 1024),
+        the result per query is one flat list of Hit, group after group, best group first and rank order inside a group, each
+        group holding its best min(group_size, its eligible rows) rows (group_size <= 64, limit * group_size <= 16384); a
+        hit's entity always carries the group field.  Exact (FlatIndex.search_grouped): strict_group_size=True is the only
+        deterministic reading, so False is accepted and returns the same.  expr and exclude_ids work as without grouping; a
+        radius does not combine with grouping (ValueError: range_search is the other call)."""
         q = self._queries(data)
         fields = output_fields or []
+        if group_by_field is not None:
+            if not self.has_field(group_by_field):
+                raise ValueError(f"group_by_field {group_by_field!r} is not a scalar field of {self.name} "
+                                 f"(fields: {', '.join(self._meta)})")
+            limit, group_size = group_bounds(limit, group_size)
+            if self._range_params(param) is not None:
+                raise ValueError("group_by_field does not combine with a radius / range_filter: range search "
+                                 "(Collection.range_search) is the other call")
+            if self.num_entities == 0:
+                return [[] for _ in range(q.shape[0])]
+            return self._search_grouped(q, limit, group_by_field, group_size, fields, exclude_ids, expr)
         if self.num_entities == 0:
             return [[] for _ in range(q.shape[0])]
         limit = min(int(limit), self.num_entities)
@@ -709,9 +752,11 @@ class MilvusRetriever:
             norms = torch.cat([out[i:i + 1].norm(2, 1, True) for i in range(out.shape[0])])
             return out / norms.clamp_min(1e-12).expand_as(out)
 
-    def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE", expr=None):
+    def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE", expr=None, group_by=None, group_size=1):
         """-> (results, query_embedding).  results: best-first dicts {id, image_path, label,
-        distance, similarity}; similarity = distance for COSINE/IP, 1 - d^2/2 for L2.  expr: Collection.search's filter."""
+        distance, similarity}; similarity = distance for COSINE/IP, 1 - d^2/2 for L2.  expr: Collection.search's filter.
+        group_by (a scalar field) / group_size: Collection.search's grouping search -- top_k counts groups, the dicts come group
+        after group and gain a "group" key with the field's value (without group_by the dicts keep the reference's keys)."""
         if isinstance(query_image_path, str):
             from PIL import Image
             img = Image.open(query_image_path).convert("RGB")
@@ -726,19 +771,28 @@ class MilvusRetriever:
             # Milvus rejects a search whose metric differs from the index's (milvus_retrieval.py:75-86)
             raise ValueError(f"metric type not match: index has {self.collection.metric_type}, search asked {metric_type}")
         hits = self.collection.search(data=query_embedding, anns_field="embedding", param=search_params,
-                                      limit=top_k, output_fields=["image_path", "label"], expr=expr)[0]
-        return [self._format(h, metric_type) for h in hits], query_embedding
+                                      limit=top_k, output_fields=["image_path", "label"], expr=expr,
+                                      **self._grouping(group_by, group_size))[0]
+        return [self._format(h, metric_type, group_by) for h in hits], query_embedding
 
     @staticmethod
-    def _format(hit, metric_type):
+    def _grouping(group_by, group_size):
+        """Collection.search's grouping keywords, none when no grouping is asked for"""
+        return {} if group_by is None else {"group_by_field": group_by, "group_size": group_size}
+
+    @staticmethod
+    def _format(hit, metric_type, group_by=None):
         d = hit.distance
         sim = d if metric_type in ("COSINE", "IP") else 1.0 - (d * d) / 2.0
-        return {"id": hit.id, "image_path": hit.entity.get("image_path"), "label": hit.entity.get("label"),
-                "distance": d, "similarity": sim}
+        out = {"id": hit.id, "image_path": hit.entity.get("image_path"), "label": hit.entity.get("label"),
+               "distance": d, "similarity": sim}
+        if group_by is not None:
+            out["group"] = hit.entity.get(group_by)
+        return out
 
-    def batch_search(self, query_image_paths, top_k=10, search_params=None, expr=None):
+    def batch_search(self, query_image_paths, top_k=10, search_params=None, expr=None, group_by=None, group_size=1):
         """One batched embed + one batched search (the reference loops search(); results equal, to the bit: _embed_rows).
-        expr: Collection.search's filter, one for the whole batch."""
+        expr: Collection.search's filter, one for the whole batch.  group_by / group_size: as in search()."""
         if len(query_image_paths) == 0:
             return []
         from PIL import Image
@@ -750,8 +804,8 @@ class MilvusRetriever:
         if self.collection is None:
             self.load_collection()
         all_hits = self.collection.search(data=emb, param=search_params, limit=top_k, output_fields=["image_path", "label"],
-                                          expr=expr)
-        return [[self._format(h, self.collection.metric_type) for h in hits] for hits in all_hits]
+                                          expr=expr, **self._grouping(group_by, group_size))
+        return [[self._format(h, self.collection.metric_type, group_by) for h in hits] for hits in all_hits]
 
     def adapter(self, name=None):
         """This retriever's collection seen through retrieval_analysis' MilvusCollectionAdapter (mirx.adapter)."""

@@ -688,6 +688,76 @@ int mirx_rank_metrics(const int64_t *ranks, int64_t nq, int64_t n, int64_t row_s
                       void *stream);
 
 /*
+ * Grouping search: the best hits PER GROUP instead of the best rows -- pymilvus' collection.search(..., group_by_field=..,
+ * group_size=.., strict_group_size=True), which the reference's callers get from their Milvus service and its own scripts never
+ * exercise ("the nearest case of every diagnosis", "ten different patients, not ten follow-ups of one").  The contract, per
+ * query i, over the index's ranking (fp64 ranking score descending, equal scores by ascending id: mirx_index_rank_all's order):
+ *   - a row is ELIGIBLE when its mask entry is non-zero (if a mask is given) and its id is not the query's excluded id;
+ *   - every row carries an integer group code >= 0; c_i(g) = eligible rows of group g, G_i = groups with c_i(g) > 0,
+ *     T_i = min(limit, G_i);
+ *   - the result is the T_i groups whose best eligible row ranks highest, ordered by that row, each holding its first
+ *     min(group_size, c_i(g)) eligible rows in ranking order -- a group is never short while it has rows left.
+ *   Equivalently, walk the ranking of the eligible rows: a group opens at its first row while fewer than `limit` groups are
+ *   open; a row is kept while its group is open and holds fewer than group_size rows.
+ * Limits of every call below (MIRX_EINVAL, nothing launched): 1 <= limit <= MIRX_GROUP_MAX_LIMIT, 1 <= group_size <=
+ * MIRX_GROUP_MAX_SIZE, limit * group_size <= MIRX_GROUP_MAX_HITS (Milvus' own top-k ceiling).  The three calls are the device
+ * passes; which prefix to walk, which groups to fill and when to deepen is the caller's (mirx.index.FlatIndex.search_grouped).
+ *
+ * mirx_group_walk: that walk over a ranked PREFIX, one wavefront per query, 64 entries at a time (a free function over ranked
+ * lists, like mirx_rank_metrics; all pointers device).
+ *   ranks        [nq, row_stride >= depth] int64, best first: what mirx_index_search / _rank_top return with the excluded id and
+ *                the masked rows left out; the first -1 ends the list (the prefix then IS the whole eligible ranking)
+ *   table_index  laid out alike, or NULL: the index into group_of of each entry; NULL when the ranked id itself is that index
+ *                (ids 0 .. n-1).  The ids written to out_ids are always those of `ranks`.
+ *   scores       laid out alike, or NULL: the fp64 ranking scores, copied to out_scores beside each kept id
+ *   group_of     [n_table] int64 group code per entry; an entry outside [0, n_table) or a code outside [0, n_groups) is skipped
+ *   group_rows   [n_groups] int64 = c(g), the eligible rows per code regardless of the query (mirx_group_count)
+ *   live_groups  the number of codes with group_rows > 0
+ *   excl_group   [nq] int64 or NULL: the code of the query's excluded row when that row is otherwise eligible, else -1; that
+ *                group counts one row less for the query and vanishes from G_i when it was its only one
+ *   out_ids      [nq, limit, group_size] int64, -1 in empty slots; out_scores alike (fp64, -inf in empty slots) or NULL
+ *   out_codes    [nq, limit] int64, -1 in empty slots; out_kept [nq, limit] int32 rows held per group slot
+ *   out_state    [nq, 2] int32: [0] groups open; [1] bit 0 COMPLETE: T_i groups are open and each holds min(group_size, c_i(g))
+ *                rows, or the list ended -- the outputs are the contract's answer; bit 1 GROUPS FINAL: T_i groups are open, so
+ *                membership and order of the groups are decided and only rows are missing (set whenever bit 0 is)
+ * The open groups live in a per-wave LDS hash table (power-of-two slots, >= 2 * limit; linear probing from code mod slots).
+ * Inside a chunk the lanes whose row can no longer be kept (group open and full; group not open and no slot left -- both
+ * absorbing) drop out at once, the others act in lane order, each looking its group up at its turn.  The walk stops, wave-
+ * uniformly, once complete.  No atomics; the outputs do not depend on scheduling.
+ *
+ * mirx_group_count: out_counts[c] = rows r < n with groups[r] == c and allow_or_null[r] != 0 (NULL = every row), for c in
+ * [0, n_groups), n_groups < 2^31; codes outside that range are skipped.  Device pointers; out_counts is zeroed by the call.
+ * Integer atomics (the sums do not depend on their order).
+ *
+ * mirx_index_group_fill: completes groups that are final but short without ranking the gallery.  For each of n_pairs pairs
+ * (pair_query, pair_slot) the member rows of the pair's group are members[pair_first .. pair_first + pair_len) -- row POSITIONS
+ * of the index, eligible rows only, any order (pair_len <= max_members <= MIRX_GROUP_FILL_MAX; a longer span is cut).  The
+ * call prepares the nq queries as the searches do; one workgroup per pair scores every
+ * member with the ranking's own lane-tree fp64 score (the bits of mirx_index_search_f64), skips the excluded id and writes the
+ * best group_size by (score descending, id ascending) to out_ids / out_rank_scores [nq, limit, group_size] at (query, slot);
+ * slots past the members read (-1, -inf).  q: device [nq, dim]; every other pointer device int64.  Between
+ * mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.  Drops a pending range result like any search.
+ *
+ * mirx_index_get_ids: ids of rows [first, first + n) (device or host destination), without copying rows.
+ */
+#define MIRX_GROUP_MAX_LIMIT 1024
+#define MIRX_GROUP_MAX_SIZE 64
+#define MIRX_GROUP_MAX_HITS 16384
+#define MIRX_GROUP_FILL_MAX 4096
+int mirx_group_walk(const int64_t *ranks, const int64_t *table_index_or_null, const double *scores_or_null, int64_t nq,
+                    int64_t depth, int64_t row_stride, const int64_t *group_of, int64_t n_table, const int64_t *group_rows,
+                    int64_t n_groups, int64_t live_groups, const int64_t *excl_group_or_null, int limit, int group_size,
+                    int64_t *out_ids, double *out_scores_or_null, int64_t *out_codes, int32_t *out_kept, int32_t *out_state,
+                    void *stream);
+int mirx_group_count(const int64_t *groups, const uint8_t *allow_or_null, int64_t n, int64_t n_groups, int64_t *out_counts,
+                     void *stream);
+int mirx_index_group_fill(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null, int limit,
+                          int group_size, const int64_t *pair_query, const int64_t *pair_slot, const int64_t *pair_first,
+                          const int64_t *pair_len, int64_t n_pairs, const int64_t *members, int64_t n_members, int max_members,
+                          int64_t *out_ids, double *out_rank_scores, void *stream);
+int mirx_index_get_ids(const mirx_index *ix, int64_t first, int64_t n, int64_t *out_ids);
+
+/*
  * x <- x / max(||x||_2, 1e-12) row-wise, in place.  Replaces F.normalize(x, dim=1)
  * (model.py:83,116,493,634; milvus_retrieval.py:63).  x: device [n, dim] fp32.
  */
