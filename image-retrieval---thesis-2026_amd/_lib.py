@@ -27,6 +27,9 @@ RANK_SORT_BITONIC = 1
 RANK_SORT_RADIX = 2
 MAX_SEARCH_K = 1024                # mirx_index_search's k limit; FlatIndex.search goes to rank_top above it
 GROUP_MAX_LIMIT, GROUP_MAX_SIZE, GROUP_MAX_HITS, GROUP_FILL_MAX = 1024, 64, 16384, 4096   # the grouping calls' limits (include/mirx.h)
+FUSE_MAX_REQUESTS, FUSE_MAX_ENTRIES, FUSE_MAX_LIMIT = 8, 4096, 1024   # mirx_fuse_ranked's limits (include/mirx.h)
+FUSE_RRF, FUSE_WEIGHTED = 0, 1     # mirx_fuse_ranked `ranker`
+FUSE_NORMS = {"RAW": 0, "COSINE": 1, "IP": 2, "L2": 3}   # and its per-request `norms`
 TUNE_CONV1X1_SMALL_MAX_WG = 1      # mirx_set_tuning keys
 TUNE_CONV3X3_SMALL_MAX_WG = 2
 TUNE_CONV1X1_RING = 3
@@ -112,6 +115,8 @@ SYMBOLS = {
     "mirx_group_count": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),
     "mirx_index_group_fill": (_int, [_vp, _vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp]),
     "mirx_index_get_ids": (_int, [_vp, _i64, _i64, _vp]),
+    "mirx_fuse_ranked": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _int, _int, ctypes.c_double, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp,
+                                _vp]),
     "mirx_linear_split2h": (_int, [_vp, _i64, _int, _vp, _vp, _int, _int, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp]),
     "mirx_rows_to_terms": (_int, [_vp, _i64, _int, _i64, ctypes.c_float, _vp, _vp]),
     "mirx_layernorm_patch2_nhwc": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, ctypes.c_float, _vp, _vp]),

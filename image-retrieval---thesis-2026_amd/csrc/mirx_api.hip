@@ -1895,6 +1895,46 @@ int mirx_index_group_fill(mirx_index *ix, const float *q, int64_t nq, const int6
     return MIRX_OK;
 }
 
+int mirx_fuse_ranked(const int64_t *codes, const float *distances_or_null, int64_t nq, int64_t row_stride, int64_t n_codes,
+                     const int32_t *segment_offsets, int n_requests, int ranker, double rrf_k, const double *weights_or_null,
+                     const int32_t *norms_or_null, int limit, int64_t *out_codes, double *out_scores, int32_t *out_request,
+                     int32_t *out_slot, int32_t *out_count, void *stream) {
+    MIRX_CHECK(n_requests >= 1 && n_requests <= MIRX_FUSE_MAX_REQUESTS, "fuse_ranked: n_requests must be in [1, 8]");
+    MIRX_CHECK(limit >= 1 && limit <= MIRX_FUSE_MAX_LIMIT, "fuse_ranked: limit must be in [1, 1024]");
+    MIRX_CHECK(segment_offsets, "fuse_ranked: null segment_offsets");
+    MIRX_CHECK(segment_offsets[0] == 0, "fuse_ranked: segment_offsets must start at 0");
+    FuseArgs a{};
+    for (int r = 0; r < n_requests; ++r) {
+        MIRX_CHECK(segment_offsets[r + 1] > segment_offsets[r], "fuse_ranked: segment_offsets must ascend (every list has a slot)");
+        MIRX_CHECK(segment_offsets[r + 1] <= MIRX_FUSE_MAX_ENTRIES, "fuse_ranked: the lists hold more than 4096 entries together");
+    }
+    for (int r = 0; r <= n_requests; ++r) a.offsets[r] = segment_offsets[r];
+    a.m = segment_offsets[n_requests]; a.n_requests = n_requests;
+    MIRX_CHECK(nq >= 0 && nq <= 0x7FFFFFFFll && row_stride >= a.m, "fuse_ranked: bad sizes (0 <= nq < 2^31, row_stride >= m)");
+    MIRX_CHECK(n_codes >= 0 && n_codes <= 0x7FFFFFFFll, "fuse_ranked: n_codes must be in [0, 2^31)");
+    MIRX_CHECK(ranker == MIRX_FUSE_RRF || ranker == MIRX_FUSE_WEIGHTED, "fuse_ranked: unknown ranker");
+    if (ranker == MIRX_FUSE_RRF) {
+        MIRX_CHECK(rrf_k > 0.0 && rrf_k < 16384.0, "fuse_ranked: rrf_k must be in (0, 16384)");
+        a.rrf_k = rrf_k;
+    } else {
+        MIRX_CHECK(weights_or_null && norms_or_null, "fuse_ranked: the weighted ranker needs weights and norms");
+        for (int r = 0; r < n_requests; ++r) {
+            MIRX_CHECK(weights_or_null[r] >= 0.0 && weights_or_null[r] <= 1.0, "fuse_ranked: a weight must be in [0, 1]");
+            MIRX_CHECK(norms_or_null[r] >= MIRX_FUSE_NORM_RAW && norms_or_null[r] <= MIRX_FUSE_NORM_L2, "fuse_ranked: unknown norm");
+            a.weights[r] = weights_or_null[r];
+            a.norms[r] = norms_or_null[r];
+        }
+        MIRX_CHECK(nq == 0 || distances_or_null, "fuse_ranked: the weighted ranker needs distances");
+    }
+    MIRX_CHECK(nq == 0 || codes, "fuse_ranked: null codes");
+    MIRX_CHECK(nq == 0 || (out_codes && out_scores && out_request && out_slot && out_count), "fuse_ranked: null output");
+    a.codes = codes; a.distances = distances_or_null; a.nq = nq; a.row_stride = row_stride; a.n_codes = n_codes;
+    a.ranker = ranker; a.limit = limit;
+    a.out_codes = out_codes; a.out_scores = out_scores; a.out_request = out_request; a.out_slot = out_slot; a.out_count = out_count;
+    MIRX_HIP(launch_fuse_ranked(a, reinterpret_cast<hipStream_t>(stream)));
+    return MIRX_OK;
+}
+
 int mirx_l2_normalize(float *x, int64_t n, int dim, void *stream) {
     MIRX_CHECK(x && n >= 0 && dim >= 1, "l2_normalize: bad argument");
     MIRX_HIP(launch_l2_normalize(x, n, dim, reinterpret_cast<hipStream_t>(stream)));

@@ -440,6 +440,27 @@ struct GroupFillArgs {
 };
 hipError_t launch_group_fill(const GroupFillArgs &a, int metric, hipStream_t st);
 
+// ---- k_fuse.hip: hybrid search's rank / score fusion (mirx_fuse_ranked) ------------------------------------------------------
+struct FuseArgs {
+    const int64_t *codes;        // [nq, row_stride >= m] document codes of the concatenated lists, -1 = empty slot
+    const float *distances;      // laid out alike
+    int64_t nq, row_stride, n_codes;
+    int m, n_requests;           // m = offsets[n_requests] <= MIRX_FUSE_MAX_ENTRIES
+    int offsets[MIRX_FUSE_MAX_REQUESTS + 1];   // request r owns positions [offsets[r], offsets[r + 1])
+    int ranker;                  // MIRX_FUSE_RRF / MIRX_FUSE_WEIGHTED
+    int limit;
+    double rrf_k;
+    double weights[MIRX_FUSE_MAX_REQUESTS];
+    int norms[MIRX_FUSE_MAX_REQUESTS];         // MIRX_FUSE_NORM_* per request
+    int64_t *out_codes;          // [nq, limit], -1 past the documents
+    double *out_scores;          // [nq, limit], -inf past the documents
+    int32_t *out_request;        // [nq, limit] request and slot of the document's first entry, -1 past the documents
+    int32_t *out_slot;
+    int32_t *out_count;          // [nq] = min(limit, distinct documents)
+};
+int fuse_sort_width(int m);                      // power of two >= m: the slots of the LDS sorts, 16 bytes each
+hipError_t launch_fuse_ranked(const FuseArgs &a, hipStream_t st);
+
 // ---- k_conv_t2.hip: ResNet-50's convolutions on channels-last terms rows (mirx_conv_terms) and their glue ------------------
 hipError_t launch_conv_t2(const void *xt, const float *x_scale, const float *x_range, int64_t n, int h, int w, int cin, int ksz,
                           int stride, const void *wt, const float *oscale, const float *bias, int cout, float w_abs_sum,

@@ -627,3 +627,91 @@ def topk_merge(scores_f64, ids, metric=METRIC_IP):
                                        ctypes.c_void_p(o32.data_ptr()), ctypes.c_void_p(oid.data_ptr()),
                                        _stream_ptr(dev)), "mirx_topk_merge")
     return o64, o32, oid
+
+
+# -- hybrid search's fusion ----------------------------------------------------------------------------------
+def fuse_bounds(segments, limit):
+    """The list lengths (one per request) and the limit of a fusion as ints, ValueError outside the contract's bounds:
+    1 to 8 requests, every list at least one slot, at most 4096 slots together, 1 <= limit <= 1024."""
+    try:
+        segments = list(segments)
+    except TypeError:
+        raise ValueError(f"segments must be a sequence of list lengths, got {type(segments).__name__}") from None
+    for name, v in [("limit", limit)] + [("a request's limit", s) for s in segments]:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {type(v).__name__}")
+    segments, limit = [int(s) for s in segments], int(limit)
+    if not 1 <= len(segments) <= _lib.FUSE_MAX_REQUESTS:
+        raise ValueError(f"hybrid search: the number of requests must be in [1, {_lib.FUSE_MAX_REQUESTS}], got {len(segments)}")
+    if min(segments) < 1:
+        raise ValueError(f"hybrid search: a request's limit must be at least 1, got {min(segments)}")
+    if sum(segments) > _lib.FUSE_MAX_ENTRIES:
+        raise ValueError(f"hybrid search: the requests' limits must not exceed {_lib.FUSE_MAX_ENTRIES} together, got {sum(segments)}")
+    if not 1 <= limit <= _lib.FUSE_MAX_LIMIT:
+        raise ValueError(f"hybrid search: limit must be in [1, {_lib.FUSE_MAX_LIMIT}], got {limit}")
+    return segments, limit
+
+
+def fuse_ranker(ranker, n_requests):
+    """A ranker in kernel form -- ("rrf", k) or ("weighted", weights, norms), norms among RAW / COSINE / IP / L2 -- as
+    (kind, k, weights, norms) for mirx_fuse_ranked; ValueError for anything else."""
+    if not isinstance(ranker, (tuple, list)) or not ranker or ranker[0] not in ("rrf", "weighted"):
+        raise ValueError('ranker must be ("rrf", k) or ("weighted", weights, norms)')
+    if ranker[0] == "rrf":
+        if len(ranker) != 2:
+            raise ValueError('the RRF ranker is ("rrf", k)')
+        k = _bound(ranker[1], "RRF k")
+        if not 0 < k < 16384:
+            raise ValueError(f"RRF k must be in (0, 16384), got {k}")
+        return _lib.FUSE_RRF, k, None, None
+    if len(ranker) != 3:
+        raise ValueError('the weighted ranker is ("weighted", weights, norms)')
+    weights = [_bound(w, "a weight") for w in ranker[1]]
+    norms = list(ranker[2])
+    if len(weights) != n_requests or len(norms) != n_requests:
+        raise ValueError(f"the weighted ranker needs one weight and one norm per request ({n_requests}), got {len(weights)} and "
+                         f"{len(norms)}")
+    for w in weights:
+        if not 0.0 <= w <= 1.0:
+            raise ValueError(f"a weight must be in [0, 1], got {w}")
+    for n in norms:
+        if n not in _lib.FUSE_NORMS:
+            raise ValueError(f"unknown norm {n!r}: one of {', '.join(_lib.FUSE_NORMS)}")
+    return _lib.FUSE_WEIGHTED, 0.0, weights, [_lib.FUSE_NORMS[n] for n in norms]
+
+
+def fuse_ranked(codes, distances, segments, ranker, limit, n_codes=None):
+    """Fuse ranked lists into one ranking per query (mirx_fuse_ranked; the contract is in include/mirx.h).
+
+    codes [nq, m] int64 and distances [nq, m] float32 on one GPU: the requests' lists side by side, request r in the next
+    segments[r] columns, best first; a code of -1 is an empty slot.  ranker: ("rrf", k), or ("weighted", weights, norms)
+    with one weight in [0, 1] and one norm of RAW / COSINE / IP / L2 per request.  n_codes: one past the largest code (codes
+    at or above it count as empty; default 2^31 - 1).
+    -> (codes [nq, limit] int64, fp64 scores [nq, limit], request [nq, limit] int32, slot [nq, limit] int32, count [nq]
+    int32): the best min(limit, distinct codes) documents by (score descending, code ascending), where each was first found,
+    and how many there are; (-1, -inf, -1, -1) past them."""
+    segments, limit = fuse_bounds(segments, limit)
+    kind, k, weights, norms = fuse_ranker(ranker, len(segments))
+    m = sum(segments)
+    if not (torch.is_tensor(codes) and codes.is_cuda and codes.dtype == torch.int64 and codes.dim() == 2 and codes.shape[1] == m):
+        raise ValueError(f"codes must be a CUDA int64 [nq, {m}] tensor")
+    if not (torch.is_tensor(distances) and distances.dtype == torch.float32 and distances.shape == codes.shape
+            and distances.device == codes.device):
+        raise ValueError("distances must be a float32 tensor shaped like codes, on the same device")
+    n_codes = 2 ** 31 - 1 if n_codes is None else int(n_codes)
+    codes, distances = codes.contiguous(), distances.contiguous()
+    dev, nq = codes.device, codes.shape[0]
+    out_codes = torch.empty((nq, limit), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((nq, limit), dtype=torch.float64, device=dev)
+    out_req = torch.empty((nq, limit), dtype=torch.int32, device=dev)
+    out_slot = torch.empty((nq, limit), dtype=torch.int32, device=dev)
+    out_count = torch.empty((nq,), dtype=torch.int32, device=dev)
+    offsets = (ctypes.c_int32 * (len(segments) + 1))(*np.concatenate([[0], np.cumsum(segments)]).tolist())
+    w = (ctypes.c_double * len(segments))(*weights) if weights is not None else None
+    nm = (ctypes.c_int32 * len(segments))(*norms) if norms is not None else None
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(lib.mirx_fuse_ranked(_ptr(codes), _ptr(distances), nq, m, n_codes, offsets, len(segments), kind, k, w, nm, limit,
+                                        _ptr(out_codes), _ptr(out_scores), _ptr(out_req), _ptr(out_slot), _ptr(out_count),
+                                        _stream_ptr(dev)), "mirx_fuse_ranked")
+    return out_codes, out_scores, out_req, out_slot, out_count

@@ -7,6 +7,8 @@ Mirrors (paths into /root/reference):
   collection.insert([paths, labels, embeddings])    ingest_embeddings.py:399-411
   search_by_embeddings                              retrieval_analysis/milvus_adapter.py:218-275 (mirx.adapter)
   NIH helpers                                       mirx.nih (nih_zilliz_utils.py)
+  hybrid_search / AnnSearchRequest / rankers        pymilvus' hybrid search over the per-model collections the reference joins
+                                                    on image_path (fusion_eval/, retrieval_analysis/); DESIGN 35
 The "server" is a device-resident FlatIndex (libmirx); searches are EXACT (the reference's
 IVF_FLAT nlist=1024 / nprobe=10 index is approximate, milvus_setup.py:191-213) and
 `search_params` / `nprobe` are accepted and ignored, except `radius` / `range_filter` (a range search).  Metadata (image_path, label) stays on
@@ -138,6 +140,8 @@ class Collection:
         self._next_id = 0
         self._live = None                                   # cache: ids of the live slots in order (numpy int64)
         self._expr = None                                   # cache: mirx.expr.ExprCache of the current rows (see _changed)
+        self._version = 0                                   # counts _changed(): what a hybrid search's join table was built from
+        self._joins = {}                                    # cache: the join tables of hybrid searches this collection leads
         self._stored = stored
         self._resident = stored is None                     # whether _index mirrors the live rows
 
@@ -203,6 +207,8 @@ class Collection:
         """the live rows changed (insert / delete / compact): drop what was derived from them"""
         self._live = None
         self._expr = None
+        self._version += 1
+        self._joins = {}
 
     def expr_mask(self, expr):
         """The rows a filter expression (mirx.expr: comparisons of id and the scalar fields with literals, in / not in,
@@ -483,6 +489,237 @@ class Collection:
             sc = (s64 if self.metric_type in ("COSINE", "IP") else -np.sqrt(np.maximum(-s64, 0.0))).astype(np.float32)
         return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
 
+    def _ranked(self, q, limit, exclude_ids=None, expr=None, param=None):
+        """The lists of search(q, limit=limit, exclude_ids=.., expr=.., param=..) as tensors on the index's device, for a
+        collection with rows: (ids [nq, w] int64, distance [nq, w] float32 in the units of Hit.distance), w = min(limit,
+        rows); a slot past a list's hits holds id -1 or a distance that is not finite.  The plain top-k never leaves the
+        device; a radius / range_filter request goes through search() itself and is copied back (rare, and exact by
+        construction)."""
+        limit = min(int(limit), self.num_entities)
+        index = self._ensure()
+        if self._range_params(param) is not None:
+            lists = self.search(q, param=param, limit=limit, exclude_ids=exclude_ids, expr=expr)
+            ids = np.full((len(lists), limit), -1, dtype=np.int64)
+            dist = np.zeros((len(lists), limit), dtype=np.float32)
+            for qi, hits in enumerate(lists):
+                ids[qi, :len(hits)] = [h.id for h in hits]
+                dist[qi, :len(hits)] = [h.distance for h in hits]
+            return torch.from_numpy(ids).to(index.device), torch.from_numpy(dist).to(index.device)
+        allow = None if expr is None else self._device_mask(expr)
+        find = index.rank_top if limit > 1024 else index.search
+        sc, ids = find(q, limit, exclude_ids=exclude_ids, allow=allow)
+        return ids, (sc if self.metric_type in ("COSINE", "IP") else -sc)
+
+
+# -- hybrid search (DESIGN 35): several requests, one fused ranking ---------------------------------------------------------
+class AnnSearchRequest:
+    """pymilvus' AnnSearchRequest: one search of a hybrid search.  `anns_field` names the collection the request searches
+    (a model type for MilvusManager.hybrid_search, a key of the mapping for hybrid_search); data, param, limit and expr are
+    those of Collection.search."""
+
+    def __init__(self, data, anns_field, param=None, limit=10, expr=None):
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)):
+            raise ValueError(f"AnnSearchRequest: limit must be an integer, got {type(limit).__name__}")
+        if int(limit) < 1:
+            raise ValueError(f"AnnSearchRequest: limit must be at least 1, got {limit}")
+        if param is not None and not isinstance(param, dict):
+            raise ValueError(f"AnnSearchRequest: param must be a dict or None, got {type(param).__name__}")
+        if expr is not None and not isinstance(expr, str):
+            raise ValueError(f"AnnSearchRequest: expr must be a string or None, got {type(expr).__name__}")
+        self.data, self.anns_field, self.param, self.limit, self.expr = data, anns_field, param, int(limit), expr
+
+
+class RRFRanker:
+    """pymilvus' RRFRanker: reciprocal rank fusion, score = sum over the requests whose list holds the document of
+    1 / (k + rank), rank counted from 1.  0 < k < 16384."""
+
+    def __init__(self, k=60):
+        if isinstance(k, bool) or not isinstance(k, (int, float, np.integer, np.floating)):
+            raise ValueError(f"RRFRanker: k must be a number, got {type(k).__name__}")
+        if not 0 < float(k) < 16384:
+            raise ValueError(f"RRFRanker: k must be in (0, 16384), got {k}")
+        self.k = float(k)
+
+    def kernel_form(self, metric_types):
+        """the ranker as mirx.index.fuse_ranked takes it, for requests on collections of these metric types"""
+        return ("rrf", self.k)
+
+
+class WeightedRanker:
+    """pymilvus' WeightedRanker: score = sum of weight_r * n_r(distance_r), one weight in [0, 1] per request.  With
+    norm_score=True every distance is first mapped into [0, 1] by its collection's metric -- COSINE (1 + d) / 2, IP
+    0.5 + atan(d) / pi, L2 1 - 2 atan(d) / pi; norm_score=False adds the raw similarities, which only COSINE and IP
+    collections allow (an L2 distance grows as the match gets worse)."""
+
+    def __init__(self, *weights, norm_score=True):
+        if not weights:
+            raise ValueError("WeightedRanker: one weight per request is needed")
+        for w in weights:
+            if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)):
+                raise ValueError(f"WeightedRanker: a weight must be a number, got {type(w).__name__}")
+            if not 0.0 <= float(w) <= 1.0:
+                raise ValueError(f"WeightedRanker: a weight must be in [0, 1], got {w}")
+        self.weights = [float(w) for w in weights]
+        self.norm_score = bool(norm_score)
+
+    def kernel_form(self, metric_types):
+        metric_types = list(metric_types)
+        if len(metric_types) != len(self.weights):
+            raise ValueError(f"WeightedRanker: {len(self.weights)} weights for {len(metric_types)} requests")
+        for m in metric_types:
+            if m not in ("COSINE", "IP", "L2"):
+                raise ValueError(f"WeightedRanker: unknown metric type {m!r}")
+        if not self.norm_score:
+            if "L2" in metric_types:
+                raise ValueError("WeightedRanker: norm_score=False adds raw similarities and does not combine with an L2 collection")
+            return ("weighted", self.weights, ["RAW"] * len(metric_types))
+        return ("weighted", self.weights, metric_types)
+
+
+def join_codes(columns, join_field="image_path"):
+    """Document codes of a hybrid search.  columns: one (name, keys, ids) per collection in request order, keys / ids those of
+    its live rows in index order.  Rows whose keys are equal are one document; a document's code is the index of its key's
+    first appearance, collection after collection, row after row.
+    -> (codes: one int64 array per collection aligned with its rows, owners: per code the (collection number, id) of the row
+    that introduced it, id_of: per collection {key: id}).  A key that repeats inside one collection: ValueError."""
+    code_of, owners, codes, id_of = {}, [], [], []
+    for ci, (name, keys, ids) in enumerate(columns):
+        own = {}
+        arr = np.empty((len(keys),), dtype=np.int64)
+        for p, (key, id_) in enumerate(zip(keys, ids)):
+            if key in own:
+                raise ValueError(f"hybrid search: {join_field} {key!r} repeats among the live rows of {name}; "
+                                 f"joining needs one row per {join_field} and collection")
+            own[key] = int(id_)
+            code = code_of.get(key)
+            if code is None:
+                code = code_of[key] = len(owners)
+                owners.append((ci, int(id_)))
+            arr[p] = code
+        codes.append(arr)
+        id_of.append(own)
+    return codes, owners, id_of
+
+
+class _JoinTable:
+    """join_codes of some collections in their current state, and its per-collection code arrays on the device"""
+
+    def __init__(self, cols, join_field):
+        for c in cols:
+            if not c.has_field(join_field):
+                raise ValueError(f"join_field {join_field!r} is not a scalar field of {c.name} (fields: {', '.join(c._meta)})")
+        self.cols = cols
+        self.versions = tuple(c._version for c in cols)
+        self.codes, self.owners, self.id_of = join_codes([(c.name, c.field(join_field), c.live_ids().tolist()) for c in cols],
+                                                         join_field)
+        self._device = {}
+
+    def device_codes(self, ci, device):
+        dev = self._device.get(ci)
+        if dev is None or dev.device != device:
+            dev = self._device[ci] = torch.from_numpy(self.codes[ci]).to(device)
+        return dev
+
+
+def _join_table(cols, join_field):
+    """the join table of these collections (distinct, in request order), built once per state of all of them: it is kept by
+    the first one and dropped when any of them changes"""
+    key = (join_field,) + tuple(id(c) for c in cols[1:])
+    table = cols[0]._joins.get(key)
+    if table is None or table.versions != tuple(c._version for c in cols):
+        table = cols[0]._joins[key] = _JoinTable(cols, join_field)
+    return table
+
+
+def _request_collections(collections, reqs):
+    if isinstance(collections, dict):
+        cols = []
+        for r in reqs:
+            if r.anns_field not in collections:
+                raise ValueError(f"Collection for {r.anns_field} not loaded")
+            cols.append(collections[r.anns_field])
+        return cols
+    cols = list(collections)
+    if len(cols) != len(reqs):
+        raise ValueError(f"hybrid search: {len(cols)} collections for {len(reqs)} requests (one per request, or a mapping that the "
+                         f"requests' anns_field names)")
+    return cols
+
+
+def hybrid_search(collections, reqs, rerank, limit, join_field="image_path", output_fields=None, exclude_keys=None,
+                  group_by_field=None):
+    """pymilvus' hybrid_search across collections: run every request, fuse the ranked lists on the device, -> one list of Hit
+    per query, best first.
+
+    collections: {name: Collection} that each request's anns_field names, or one Collection per request; the same collection
+    may serve several requests (several query vectors, one gallery).  reqs: 1 to 8 AnnSearchRequest with equally many
+    queries, their limits at most 4096 together.  rerank: RRFRanker or WeightedRanker.  limit: 1 to 1024 documents.
+    Rows of different collections are one DOCUMENT when their `join_field` values are equal (join_codes).  Request r's list
+    is exactly what its collection's search(data, limit=, expr=, param=, exclude_ids=) returns; a document's fp64 score is
+    the sum of its lists' contributions in request order (the ranker's docstring; include/mirx.h for the arithmetic).
+    The result holds the min(limit, distinct documents) best documents, equal scores by first appearance of the key.  A Hit's
+    id and entity are those of the document's row in the first requested collection that holds it, its `distance` is the
+    fused score, its entity always carries the join field.
+    exclude_keys: one join-field value per query (or None): that document leaves every list before the fusion -- the
+    reference's exclude_self by image_path; a key a collection does not hold excludes nothing there.
+    Grouping does not combine with hybrid search (ValueError)."""
+    from .index import fuse_bounds, fuse_ranked
+    reqs = list(reqs)
+    for r in reqs:
+        if not isinstance(r, AnnSearchRequest):
+            raise ValueError(f"hybrid search: the requests must be AnnSearchRequest, got {type(r).__name__}")
+    segments, limit = fuse_bounds([r.limit for r in reqs], limit)
+    if group_by_field is not None or any("group_by_field" in (r.param or {}) for r in reqs):
+        raise ValueError("hybrid search does not combine with group_by_field: grouping search (Collection.search) is the other call")
+    if not isinstance(rerank, (RRFRanker, WeightedRanker)):
+        raise ValueError(f"hybrid search: rerank must be an RRFRanker or a WeightedRanker, got {type(rerank).__name__}")
+    cols = _request_collections(collections, reqs)
+    form = rerank.kernel_form([c.metric_type for c in cols])
+    queries = [c._queries(r.data) for c, r in zip(cols, reqs)]
+    nq = queries[0].shape[0]
+    if any(q.shape[0] != nq for q in queries):
+        raise ValueError(f"hybrid search: every request needs the same number of queries, got {[q.shape[0] for q in queries]}")
+    if exclude_keys is not None:
+        exclude_keys = list(exclude_keys)
+        if len(exclude_keys) != nq:
+            raise ValueError("exclude_keys needs one key per query")
+    distinct = []
+    for c in cols:
+        if not any(c is d for d in distinct):
+            distinct.append(c)
+    which = [next(i for i, d in enumerate(distinct) if d is c) for c in cols]
+    table = _join_table(distinct, join_field)
+    if not table.owners:
+        return [[] for _ in range(nq)]
+    device = next(c for c in distinct if c.num_entities).index.device
+    codes = torch.full((nq, sum(segments)), -1, dtype=torch.int64, device=device)
+    dist = torch.zeros((nq, sum(segments)), dtype=torch.float32, device=device)
+    off = 0
+    for c, ci, r, q, width in zip(cols, which, reqs, queries, segments):
+        if c.num_entities:
+            ex = None
+            if exclude_keys is not None:
+                ex = torch.tensor([table.id_of[ci].get(k, -1) for k in exclude_keys], dtype=torch.int64)
+            ids, d = c._ranked(q, r.limit, ex, r.expr, r.param)
+            pos = c.index._positions(ids)
+            code = table.device_codes(ci, ids.device)[pos.clamp(min=0)]
+            code = torch.where((pos >= 0) & torch.isfinite(d), code, torch.full_like(code, -1))
+            codes[:, off:off + ids.shape[1]] = code.to(device)
+            dist[:, off:off + ids.shape[1]] = torch.where(code >= 0, d, torch.zeros_like(d)).to(device)
+        off += width
+    out_codes, out_scores, _, _, count = fuse_ranked(codes, dist, segments, form, limit, n_codes=len(table.owners))
+    out_codes, out_scores, count = out_codes.cpu().tolist(), out_scores.cpu().tolist(), count.cpu().tolist()
+    fields = list(output_fields or [])
+    fields += [] if join_field in fields else [join_field]
+    results = []
+    for qi in range(nq):
+        hits = []
+        for code, score in zip(out_codes[qi][:count[qi]], out_scores[qi][:count[qi]]):
+            ci, id_ = table.owners[code]
+            hits.append(Hit(id_, score, distinct[ci].entity(id_, fields)))
+        results.append(hits)
+    return results
+
 
 _NETWORK_SCHEMES = ("http", "https", "tcp", "grpc")
 
@@ -625,6 +862,13 @@ class MilvusManager:
             self.create_collection(model_type, drop_old=drop_old)
             self.create_index(model_type, metric_type=metric_type)
             self.load_collection(model_type)
+
+    def hybrid_search(self, reqs, rerank, limit, join_field="image_path", output_fields=None, exclude_keys=None,
+                      group_by_field=None):
+        """hybrid_search (above) over this manager's collections: a request's anns_field names the model type whose
+        collection it searches ("convnextv2", "dinov2", ..; created or loaded before, else ValueError)."""
+        return hybrid_search(self.collections, reqs, rerank, limit, join_field=join_field, output_fields=output_fields,
+                             exclude_keys=exclude_keys, group_by_field=group_by_field)
 
 
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)

@@ -758,6 +758,49 @@ int mirx_index_group_fill(mirx_index *ix, const float *q, int64_t nq, const int6
 int mirx_index_get_ids(const mirx_index *ix, int64_t first, int64_t n, int64_t *out_ids);
 
 /*
+ * Hybrid search: fuses the ranked lists of several search requests into one ranking per query -- pymilvus'
+ * hybrid_search(reqs, rerank=RRFRanker() | WeightedRanker(..), limit).  The reference keeps one collection per backbone and
+ * joins them on image_path (fusion_eval/, retrieval_analysis/); the caller (mirx.retriever.hybrid_search) turns every ranked id
+ * into a DOCUMENT CODE, equal for rows of different collections that carry the same key.  A free function over ranked lists,
+ * like mirx_rank_metrics.
+ *   codes, distances   device [nq, row_stride >= m]: the lists of the n_requests requests side by side, request r in columns
+ *                      [segment_offsets[r], segment_offsets[r + 1]), best first; m = segment_offsets[n_requests].  A code
+ *                      outside [0, n_codes) marks an empty slot (-1 by convention).  distances: the fp32 value a hit reports
+ *                      (similarity for COSINE / IP, Euclidean distance for L2), finite wherever the code is valid; read by the
+ *                      weighted ranker only (may be NULL for MIRX_FUSE_RRF).
+ *   segment_offsets    HOST int32 [n_requests + 1], 0 = offsets[0] < offsets[1] < .. (every list has at least one slot)
+ *   ranker             MIRX_FUSE_RRF: an entry in slot s of its list (rank s + 1) contributes 1 / (rrf_k + rank), 0 < rrf_k < 16384.
+ *                      MIRX_FUSE_WEIGHTED: it contributes weights[r] * n_r(d), d its distance widened to fp64, weights HOST
+ *                      double [n_requests] in [0, 1], norms HOST int32 [n_requests]: MIRX_FUSE_NORM_RAW n = d, _COSINE n =
+ *                      (1 + d) * 0.5, _IP n = 0.5 + atan(d) / pi, _L2 n = 1 - 2 * atan(d) / pi.  (weights / norms may be NULL
+ *                      for MIRX_FUSE_RRF.)
+ * A document's score is 0.0 plus its entries' contributions, added one by one in ascending position (hence ascending request),
+ * every operation a separate correctly rounded fp64 operation (no fused multiply-add): a float64 restatement reproduces the bits
+ * of the RRF, RAW and COSINE forms; the atan forms agree to the device's atan (a few ulp).  Per query the result is the
+ * min(limit, distinct codes) documents with the highest score, equal scores by ascending code:
+ *   out_codes   [nq, limit] int64, -1 past them;  out_scores [nq, limit] fp64, -inf past them
+ *   out_request, out_slot  [nq, limit] int32: the request and the slot in its list of the document's first entry, -1 past them
+ *   out_count   [nq] int32
+ * One workgroup per query, two bitonic sorts in LDS (16 bytes per slot of the next power of two >= m: 64 KiB at the limit); no
+ * atomics, one fixed order of additions: equal inputs give equal outputs, call after call.
+ * Limits (MIRX_EINVAL before any device call): 1 <= n_requests <= MIRX_FUSE_MAX_REQUESTS, m <= MIRX_FUSE_MAX_ENTRIES,
+ * 1 <= limit <= MIRX_FUSE_MAX_LIMIT, 0 <= n_codes < 2^31, 0 <= nq < 2^31.
+ */
+#define MIRX_FUSE_MAX_REQUESTS 8
+#define MIRX_FUSE_MAX_ENTRIES 4096
+#define MIRX_FUSE_MAX_LIMIT 1024
+#define MIRX_FUSE_RRF 0
+#define MIRX_FUSE_WEIGHTED 1
+#define MIRX_FUSE_NORM_RAW 0
+#define MIRX_FUSE_NORM_COSINE 1
+#define MIRX_FUSE_NORM_IP 2
+#define MIRX_FUSE_NORM_L2 3
+int mirx_fuse_ranked(const int64_t *codes, const float *distances_or_null, int64_t nq, int64_t row_stride, int64_t n_codes,
+                     const int32_t *segment_offsets, int n_requests, int ranker, double rrf_k, const double *weights_or_null,
+                     const int32_t *norms_or_null, int limit, int64_t *out_codes, double *out_scores, int32_t *out_request,
+                     int32_t *out_slot, int32_t *out_count, void *stream);
+
+/*
  * x <- x / max(||x||_2, 1e-12) row-wise, in place.  Replaces F.normalize(x, dim=1)
  * (model.py:83,116,493,634; milvus_retrieval.py:63).  x: device [n, dim] fp32.
  */
