@@ -1,13 +1,12 @@
 """ResNet50 on the MI355X: the channels-last terms convolution (mirx_conv_terms) on every convolution shape of ResNet-50,
 its glue kernels, and the model end to end against a float64 restatement."""
-import math
-
 import pytest
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from oracle.densenet import randomize_bn_stats
+from _convterms_ref import _decode, _pow2_scale
+from _convterms_ref import _run_and_check as _check_hw
 from _resnet_ref import embed
 
 pytestmark = pytest.mark.gpu
@@ -26,99 +25,10 @@ SHAPES = [
 ]
 
 
-def _pow2_scale(b):
-    """2^(14 - floor(log2 b)) per element of b (float64 tensor), 1 where b == 0."""
-    e = torch.floor(torch.log2(torch.where(b > 0, b, torch.ones_like(b))))
-    return torch.where(b > 0, torch.exp2(14 - e), torch.ones_like(b))
-
-
-def _to_terms(x):
-    """x float64 [n, rows, c] -> (terms rows fp16 [n * rows, 2 c], scale row, range row) on the GPU, image b scaled by the power
-    of two that puts its max |x| in [2^14, 2^15), and the exactly represented values (float64) the kernel reads."""
-    from mirx.model import _terms_of
-    n, rows, c = x.shape
-    amax = x.abs().reshape(n, -1).amax(dim=1)
-    s = _pow2_scale(amax)
-    t = torch.cat([_terms_of(x[b].float(), float(s[b])).reshape(rows, 2 * c) for b in range(n)])
-    return (t.to(DEV), s.float().to(DEV), amax.float().to(DEV)), _decode(t, s, n)
-
-
-def _decode(t, s, n):
-    """terms rows [n * rows, 2 c] (any device), scale row [n] -> float64 [n, rows, c]."""
-    t = t.cpu()
-    rows = t.shape[0] // n
-    c = t.shape[1] // 2
-    v = t.view(n, rows, c // 32, 2, 32).double()
-    return ((v[:, :, :, 0] + v[:, :, :, 1]) / s.cpu().double().view(n, 1, 1, 1)).reshape(n, rows, c)
-
-
-def _conv_bn(cin, cout, k, s, seed):
-    g = torch.Generator().manual_seed(seed)
-    conv = nn.Conv2d(cin, cout, k, stride=s, padding=(k - 1) // 2, bias=False)
-    bn = nn.BatchNorm2d(cout)
-    with torch.no_grad():
-        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * math.sqrt(2.0 / (cin * k * k)))
-        bn.weight.copy_(0.75 + 0.5 * torch.rand(cout, generator=g))
-        bn.bias.copy_(0.1 * torch.randn(cout, generator=g))
-        bn.running_mean.copy_(0.1 * torch.randn(cout, generator=g))
-        bn.running_var.copy_(0.5 + torch.rand(cout, generator=g))
-    return conv.eval(), bn.eval()
-
-
-def _ref_conv(xd, conv, bn, side, res_d=None, relu=False):
-    """float64: xd [n, side * side, cin] -> [n, ho * wo, cout]"""
-    with torch.no_grad():
-        return _ref_conv_(xd, conv, bn, side, res_d, relu)
-
-
-def _ref_conv_(xd, conv, bn, side, res_d, relu):
-    n, _, cin = xd.shape
-    scale = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-    shift = bn.bias.double() - bn.running_mean.double() * scale
-    w = conv.weight.detach().double() * scale.view(-1, 1, 1, 1)
-    xi = xd.view(n, side, side, cin).permute(0, 3, 1, 2)
-    y = F.conv2d(xi, w, stride=conv.stride, padding=conv.padding) + shift.view(1, -1, 1, 1)
-    y = y.permute(0, 2, 3, 1).reshape(n, -1, w.shape[0])
-    if res_d is not None:
-        y = y + res_d
-    return F.relu(y) if relu else y
-
-
-def _input(n, side, c, seed, mags):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, side * side, c, generator=g, dtype=torch.float64)
-    x = x * torch.tensor([mags[b % len(mags)] for b in range(n)], dtype=torch.float64).view(n, 1, 1)
-    return x
-
-
 def _run_and_check(shape, n, seed, mags, res, relu, report=None):
-    from mirx.model import _conv_terms_weights, conv_terms
+    """shape = (cin, cout, k, stride, side): the square map of _convterms_ref._run_and_check"""
     cin, cout, k, s, side = shape
-    conv, bn = _conv_bn(cin, cout, k, s, seed)
-    cw = _conv_terms_weights(conv.to(DEV), bn.to(DEV))
-    x, xd = _input(n, side, cin, seed + 1, mags), None
-    xg, xd = _to_terms(x)
-    ho = (side + 2 * ((k - 1) // 2) - k) // s + 1
-    rg = rd = None
-    if res:
-        rg, rd = _to_terms(_input(n, ho, cout, seed + 2, mags[::-1]))
-    yt, ys, yr, y, h2, w2 = conv_terms(cw, xg, side, side, res=rg, relu=relu, terms_out=True, fp32_out=True)
-    torch.cuda.synchronize()
-    assert (h2, w2) == (ho, ho)
-    ref = _ref_conv(xd, conv.cpu(), bn.cpu(), side, rd, relu)
-    yf = y.cpu().double().view(n, ho * ho, cout)
-    ydec = _decode(yt, ys, n)
-    wsum = float(cw["wsum"])
-    for b in range(n):
-        mref = float(ref[b].abs().max())
-        err = float((yf[b] - ref[b]).abs().max())
-        assert err <= 1e-6 * mref, (shape, n, b, err / mref)
-        bound = float(xg[2][b]) * wsum + cw["bmax"] + (float(rg[2][b]) if res else 0.0)
-        terr = float((ydec[b] - ref[b]).abs().max())
-        assert terr <= 2.0 ** -20 * bound, (shape, n, b, terr / bound)
-        assert abs(float(yr[b]) - mref) <= 1e-6 * mref, (shape, b, float(yr[b]), mref)
-        if report is not None:
-            report.append(bound / mref)
+    _check_hw((cin, cout, k, s, side, side), n, seed, mags, res, relu, report)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "c%d-%d_k%ds%d_%d" % s)
@@ -292,3 +202,51 @@ def test_retrieval_round_trip():
     col.insert([[f"img{i}.png" for i in range(16)], list(range(16)), e])
     hits = col.search(e, limit=3)
     assert [h[0].id for h in hits] == list(range(16))
+
+
+# ---- the model at the sizes whose maps are odd, non-square or down to 1 x 1 (test_conv_terms_edges_gpu.py has the kernel) ------
+_SMALL = {}
+
+
+def _small_model():
+    if "m" not in _SMALL:
+        _SMALL["m"] = _model(None, seed=21)
+    return _SMALL["m"]
+
+
+@pytest.mark.parametrize("h,w", [(8, 8), (12, 20), (36, 52), (100, 100)])
+def test_end_to_end_small_and_odd(h, w):
+    """8 x 8: every map from layer2 on is 1 x 1; 12 x 20: 3 x 5 -> 2 x 3 -> 1 x 2 -> 1 x 1; 36 x 52: 9 x 13 -> 5 x 7 -> 3 x 4 ->
+    2 x 2; 100 x 100: 25 -> 13 -> 7 -> 4 (every stride-2 input odd)."""
+    m = _small_model()
+    x = _images(3, h, w, seed=22)
+    with torch.no_grad():
+        y = m(x.to(DEV))
+    err = float((y.cpu().double() - embed(x, m.state_dict())).abs().max())
+    print(f"resnet50 {h} x {w}: native {err:.3e}")
+    assert y.shape == (3, 2048)
+    assert err <= 1e-5
+
+
+def test_batch_independence_8x8_bit_identical():
+    """200 images of 8 x 8: from layer2 on 128 images share a pixel tile; images either side of that boundary alone"""
+    m = _small_model()
+    x = _images(200, 8, 8, seed=23).to(DEV)
+    with torch.no_grad():
+        full = m(x)
+        for i in (0, 127, 128, 199):
+            assert torch.equal(m(x[i:i + 1])[0], full[i]), i
+    assert torch.isfinite(full).all()
+
+
+def test_containment_8x8_of_a_nan_image():
+    m = _small_model()
+    x = _images(200, 8, 8, seed=24)
+    bad = x.clone()
+    bad[127] = float("nan")
+    with torch.no_grad():
+        clean = m(x.to(DEV))
+        dirty = m(bad.to(DEV))
+    keep = [i for i in range(200) if i != 127]
+    assert torch.equal(clean[keep], dirty[keep])
+    assert torch.isfinite(clean).all() and not torch.isfinite(dirty[127]).all()
