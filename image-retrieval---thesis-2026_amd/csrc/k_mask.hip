@@ -9,6 +9,8 @@
 //            (-inf, INT64_MAX), which k_row_topk never takes: it is not before the empty slot it would replace.
 //   keys     radix ranking: the key of a masked row becomes RANK_KEY_LAST, behind every score's (as the dropped excluded id)
 //   tail     radix ranking: an output slot whose row is masked reads (-1, -inf)
+// scores reads the scanned positions, which its caller needs anyway for the gather; keys and tail, shared by rank_top under a
+// mask and the range search's exact route, read the allow bytes themselves: a row is masked iff its byte is zero.
 //
 // Why -inf and not a large negative number: the filter tests `score + bias > tau` with a strict >, so -inf passes no threshold,
 // not even tau = -inf.  A sum can only be NaN where the bf16 dot product itself is +inf or NaN, and NaN > tau is false as well;
@@ -74,21 +76,21 @@ __global__ __launch_bounds__(256) void mask_scores(double *__restrict__ scores, 
 }
 
 __global__ __launch_bounds__(256) void mask_rank_keys(uint64_t *__restrict__ keys, const int32_t *__restrict__ pay, int64_t n,
-                                                      const int32_t *__restrict__ pos) {
+                                                      const uint8_t *__restrict__ allow) {
     const int64_t qi = blockIdx.y;
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
         const int32_t r = pay[qi * n + j];
-        if ((uint32_t)r < (uint64_t)n && row_masked(pos, r)) keys[qi * n + j] = RANK_KEY_LAST;
+        if ((uint32_t)r < (uint64_t)n && allow[r] == 0) keys[qi * n + j] = RANK_KEY_LAST;
     }
 }
 
 __global__ __launch_bounds__(256) void mask_rank_tail(const int32_t *__restrict__ pay, int64_t n, int64_t kout,
-                                                      const int32_t *__restrict__ pos, int64_t *__restrict__ out_ids,
+                                                      const uint8_t *__restrict__ allow, int64_t *__restrict__ out_ids,
                                                       float *__restrict__ out_val, double *__restrict__ out_f64) {
     const int64_t qi = blockIdx.y;
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < kout; j += (int64_t)gridDim.x * 256) {
         const int32_t r = pay[qi * n + j];
-        if ((uint32_t)r < (uint64_t)n && row_masked(pos, r)) {
+        if ((uint32_t)r < (uint64_t)n && allow[r] == 0) {
             out_ids[qi * kout + j] = -1;
             if (out_val) out_val[qi * kout + j] = -INFINITY;
             if (out_f64) out_f64[qi * kout + j] = -INFINITY;
@@ -116,16 +118,16 @@ hipError_t launch_mask_scores(double *scores, int64_t ld, int64_t n, const int32
     return hipGetLastError();
 }
 
-hipError_t launch_mask_rank_keys(uint64_t *keys, const int32_t *pay, int64_t n, const int32_t *pos, int nq, hipStream_t st) {
+hipError_t launch_mask_rank_keys(uint64_t *keys, const int32_t *pay, int64_t n, const uint8_t *allow, int nq, hipStream_t st) {
     if (nq <= 0 || n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(mask_rank_keys, dim3(grid_for(n), (unsigned)nq), dim3(256), 0, st, keys, pay, n, pos);
+    hipLaunchKernelGGL(mask_rank_keys, dim3(grid_for(n), (unsigned)nq), dim3(256), 0, st, keys, pay, n, allow);
     return hipGetLastError();
 }
 
-hipError_t launch_mask_rank_tail(const int32_t *pay, int64_t n, int64_t kout, const int32_t *pos, int nq, int64_t *out_ids,
+hipError_t launch_mask_rank_tail(const int32_t *pay, int64_t n, int64_t kout, const uint8_t *allow, int nq, int64_t *out_ids,
                                  float *out_val, double *out_f64, hipStream_t st) {
     if (nq <= 0 || kout <= 0) return hipSuccess;
-    hipLaunchKernelGGL(mask_rank_tail, dim3(grid_for(kout), (unsigned)nq), dim3(256), 0, st, pay, n, kout, pos, out_ids, out_val,
+    hipLaunchKernelGGL(mask_rank_tail, dim3(grid_for(kout), (unsigned)nq), dim3(256), 0, st, pay, n, kout, allow, out_ids, out_val,
                        out_f64);
     return hipGetLastError();
 }

@@ -135,15 +135,6 @@ __global__ __launch_bounds__(256) void k_range_gather_exclude(const int64_t *__r
     if (i < n) out[i] = exclude[list[i]];
 }
 
-__global__ __launch_bounds__(256) void k_range_mask_keys(uint64_t *__restrict__ keys, const int32_t *__restrict__ pay, int64_t n,
-                                                         const uint8_t *__restrict__ allow) {
-    const int64_t qi = blockIdx.y;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-        const uint32_t r = (uint32_t)pay[qi * n + j];
-        if ((int64_t)r < n && allow[r] == 0) keys[qi * n + j] = RANK_KEY_LAST;
-    }
-}
-
 // first position of the ascending keys[0 .. n) that is >= k
 __device__ inline int64_t key_lower_bound(const uint64_t *keys, int64_t n, uint64_t k) {
     int64_t a = 0, b = n;
@@ -275,12 +266,6 @@ hipError_t launch_range_finalize(const RangeFinalizeArgs &a, hipStream_t st) {
 hipError_t launch_range_gather_exclude(const int64_t *exclude, const int32_t *list, int n, int64_t *out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_range_gather_exclude, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, exclude, list, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_range_mask_keys(uint64_t *keys, const int32_t *pay, int64_t n, const uint8_t *allow, int nq, hipStream_t st) {
-    if (nq <= 0 || n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_range_mask_keys, dim3(grid_for(n, 1024), (unsigned)nq), dim3(256), 0, st, keys, pay, n, allow);
     return hipGetLastError();
 }
 

@@ -4,6 +4,11 @@
 
 namespace mirx {
 
+// ---- the search's routing constants: defined in mirx_api.hip, where the tests read their values; used in mirx_index.hip ----
+extern const int64_t QUERY_BATCH;
+extern const int64_t TIER1_MIN_ROWS;
+extern const int TIER1_MAX_K;
+
 // ---- k_prep.hip -------------------------------------------------------------------------
 // Rows [n, dim] fp32 (device) -> padded fp32 master, bf16 copy, per-row bias (metric 1:
 // -0.5*||g||^2, metric 0: 0) and an atomic running maximum of ||g|| (upper bound, fp32 bits).
@@ -124,13 +129,14 @@ hipError_t launch_compact_chunk(float *g32, uint16_t *g16, int64_t *ids, float *
 // sums per COMPACT_TILE rows in part[] -- ready for launch_compact_scan_flags.
 hipError_t launch_mask_pass(const uint8_t *allow, int64_t n, int64_t cap, const float *gbias, const int64_t *ids, float *bias,
                             int64_t *mids, int32_t *pos, int32_t *part, hipStream_t st);
-// pos = the scanned positions (n + 1 entries; row r is masked iff pos[r + 1] == pos[r]) in the three below
-// scores [nq, ld]: the entries of masked rows -> -inf
+// scores [nq, ld]: the entries of masked rows -> -inf; pos = the scanned positions (n + 1 entries; row r is masked iff
+// pos[r + 1] == pos[r])
 hipError_t launch_mask_scores(double *scores, int64_t ld, int64_t n, const int32_t *pos, int nq, hipStream_t st);
+// The radix ranking (rank_top under a mask, the range search's exact route) takes the allow bytes themselves: masked iff allow[r] == 0.
 // keys / pay [nq, n] as launch_rank_sort_build leaves them: a masked row's key -> RANK_KEY_LAST
-hipError_t launch_mask_rank_keys(uint64_t *keys, const int32_t *pay, int64_t n, const int32_t *pos, int nq, hipStream_t st);
+hipError_t launch_mask_rank_keys(uint64_t *keys, const int32_t *pay, int64_t n, const uint8_t *allow, int nq, hipStream_t st);
 // after launch_rank_sort_write: output slots whose row is masked -> (-1, -inf)
-hipError_t launch_mask_rank_tail(const int32_t *pay, int64_t n, int64_t kout, const int32_t *pos, int nq, int64_t *out_ids,
+hipError_t launch_mask_rank_tail(const int32_t *pay, int64_t n, int64_t kout, const uint8_t *allow, int nq, int64_t *out_ids,
                                  float *out_val, double *out_f64, hipStream_t st);
 
 // ---- k_anomaly.hip: class centroids, nearest-centroid distances, segmented binary ranking metrics (include/mirx.h) -----------
@@ -380,8 +386,6 @@ struct RangeFinalizeArgs {
 hipError_t launch_range_finalize(const RangeFinalizeArgs &a, hipStream_t st);
 // out[i] = exclude[list[i]]
 hipError_t launch_range_gather_exclude(const int64_t *exclude, const int32_t *list, int n, int64_t *out, hipStream_t st);
-// keys / pay [nq, n] as launch_rank_sort_build leaves them: the key of a row with allow[row] == 0 -> RANK_KEY_LAST
-hipError_t launch_range_mask_keys(uint64_t *keys, const int32_t *pay, int64_t n, const uint8_t *allow, int nq, hipStream_t st);
 // sorted keys [nq, n]: segment i's hits are the positions [first[i], first[i] + count[qx]) whose score s has lo < s <= hi;
 // qx = list ? list[i] : q_first + i in this and the two below
 hipError_t launch_range_cut(const uint64_t *keys, int64_t n, int nq, double lo, double hi, const int32_t *list, int64_t q_first,
@@ -419,6 +423,13 @@ struct GroupWalkArgs {
     int32_t *out_kept;           // [nq, limit]
     int32_t *out_state;          // [nq, 2]: groups open; bit 0 complete, bit 1 groups final
 };
+// why mirx_group_walk / mirx_index_group_fill refuse (limit, group_size), or null
+inline const char *group_limits(int limit, int group_size) {
+    if (limit < 1 || limit > MIRX_GROUP_MAX_LIMIT) return "limit must be in [1, 1024]";
+    if (group_size < 1 || group_size > MIRX_GROUP_MAX_SIZE) return "group_size must be in [1, 64]";
+    if ((int64_t)limit * group_size > MIRX_GROUP_MAX_HITS) return "limit * group_size must not exceed 16384";
+    return nullptr;
+}
 int group_walk_table(int limit);                 // power of two >= max(64, 2 * limit)
 hipError_t launch_group_walk(const GroupWalkArgs &a, hipStream_t st);
 // counts[c] += the rows r < n with groups[r] == c and allow[r] != 0 (allow null = every row); codes outside [0, n_groups) are skipped

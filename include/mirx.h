@@ -120,6 +120,8 @@ void mirx_index_destroy(mirx_index *ix);
  * Python Retriever.  rows: row-major [n, dim] fp32, host or device.  ids: n int64 (host or
  * device) or NULL for auto ids (previous size + i, Milvus auto_id analogue,
  * milvus_setup.py:170).  Synchronous: returns when the rows are resident.
+ * mirx_index_add and mirx_index_reserve (room for capacity_rows rows ahead of the adds) may move the rows to a larger
+ * allocation.  Between mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.
  */
 int mirx_index_add(mirx_index *ix, const float *rows, int64_t n, const int64_t *ids_or_null);
 int mirx_index_reserve(mirx_index *ix, int64_t capacity_rows);
@@ -181,7 +183,11 @@ int mirx_index_search_f64(mirx_index *ix, const float *q, int64_t nq, int k,
  *   mirx_index_search_end    waits for that event (a host wait; the stream is not drained), runs the rare follow-up passes
  *       the counters ask for on the same stream, and returns.  The outputs are complete when work enqueued on the stream
  *       up to this call has finished; stats / timings refer to this search.
- * Between the two calls the index must not be searched, ranked or extended, and the query / output buffers must stay valid.
+ * Between the two calls the index is busy and the query / output buffers must stay valid: the pending search holds pointers
+ * into the index's workspace and rows, so every call that uses the workspace or moves rows -- mirx_index_search, _search_f64,
+ * _search_begin, _search_masked, _range_search, _rank_all, _rank_top, _rank_top_masked, _group_fill, _add, _reserve,
+ * _remove_ids -- returns MIRX_ESTATE and changes nothing.  mirx_index_search_end, _range_fetch, _range_last_stats, _last_stats,
+ * _last_timings, _get_rows, _get_ids, _size, _dim and _set_option stay callable.
  * mirx_index_search == begin + end.  (No reference counterpart: MilvusRetriever.search is a blocking RPC,
  * milvus/milvus_retrieval.py:80-86.)
  */
@@ -289,7 +295,8 @@ int mirx_index_last_timings(mirx_index *ix, float *out_ms);
  * Up to 65536 rows the sort is a bitonic network, above that a segmented radix sort over 64-bit images of the fp64 scores
  * (MIRX_OPT_RANK_SORT forces either).  The radix sort works on batches of queries with 32 bytes of workspace per gallery row
  * and query, at most 512 MiB unless one query needs more; the size is bounded by 2^31 rows and by that allocation
- * (MIRX_ENOMEM).  NaN scores have no defined place in either sort.
+ * (MIRX_ENOMEM).  NaN scores have no defined place in either sort.  Between mirx_index_search_begin and mirx_index_search_end:
+ * MIRX_ESTATE.
  */
 int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq,
                         const int64_t *exclude_ids_or_null, int64_t *out_ids,
@@ -302,6 +309,7 @@ int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq,
  * with the excluded id is LEFT OUT, slots past the number of eligible rows read id -1 and -inf, and either score output may be
  * NULL (not both): out_scores fp32 reported values, out_rank_scores the fp64 ranking scores, [nq, k] each.  Always the radix
  * sort of the whole gallery (MIRX_OPT_RANK_SORT does not apply); cost and workspace are those of mirx_index_rank_all.
+ * Between mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.
  */
 int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
                         float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
@@ -310,8 +318,10 @@ int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, c
  * mirx_index_rank_top under a row mask (allow / n_allow as in mirx_index_search_masked; 1 <= k <= size): the first k entries of
  * the ranking of the allowed rows, the excluded id left out, (-1, -inf) in the slots past the eligible rows -- what
  * mirx_index_rank_top returns on a fresh index of the allowed rows, bit for bit.  Cost: that of the unmasked call whatever the
- * mask -- every row is scored and sorted (32 bytes of workspace per row and query), masked rows carry the key behind every
- * score's -- plus the mask pass and two small passes per batch of queries.  MIRX_ESTATE as for mirx_index_search_masked.
+ * mask, all ones included -- every row is scored and sorted (32 bytes of workspace per row and query), masked rows carry the key
+ * behind every score's -- plus two small passes per batch of queries that read the allow bytes themselves (a host mask is copied
+ * to the device first); the mask is neither counted nor scanned and the host does not wait.  MIRX_ESTATE as for
+ * mirx_index_search_masked.
  */
 int mirx_index_rank_top_masked(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
                                const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,

@@ -411,6 +411,31 @@ def test_self_join_under_a_mask(metric):
         ix.range_search(g, float("nan"))
 
 
+@pytest.mark.parametrize("metric", METRICS)
+def test_exact_route_agrees_with_rank_top(metric):
+    """The two callers of the radix ranking, on the shared case of tests/test_search_masked_gpu.py (three sort tiles and a tail,
+    ids in no order): with no bounds the exact route's hits of a query are the finite prefix of rank_top(k = n) under the same
+    mask and excluded ids -- ids and fp64 scores identical, in order -- and each query has as many as it has eligible rows."""
+    from test_search_masked_gpu import rank_top_case
+    g, ids, q, own, masks = rank_top_case(metric)
+    n = g.shape[0]
+    ix = _index(g, metric, ids)
+    for name, allow in masks.items():
+        for ex in (None, own):
+            tag = (metric, name, ex is not None)
+            lims, s64, got = _forced_exact(ix, lambda: ix.range_search(q, -INF, INF, exclude_ids=ex, allow=allow, return_f64=True))
+            ws, wi = ix.rank_top(q, n, exclude_ids=ex, return_f64=True, allow=allow)
+            lims, s64, got, ws, wi = (t.cpu().numpy() for t in (lims, s64, got, ws, wi))
+            eligible = [int(allow.sum()) - (int(allow[ids == e].any()) if ex is not None else 0) for e in own]
+            np.testing.assert_array_equal(np.diff(lims), eligible, err_msg=str(tag))
+            assert lims[0] == 0 and lims[-1] == got.shape[0], tag
+            for i in range(q.shape[0]):
+                finite = wi[i] != -1
+                assert finite[:eligible[i]].all() and not finite[eligible[i]:].any(), tag
+                np.testing.assert_array_equal(got[lims[i]:lims[i + 1]], wi[i][finite], err_msg=str(tag))
+                np.testing.assert_array_equal(_bits(s64[lims[i]:lims[i + 1]]), _bits(ws[i][finite]), err_msg=str(tag))
+
+
 # ---- 7. more than one internal batch ----------------------------------------------------------------------------------
 def test_more_than_one_internal_batch():
     metric = "COSINE"

@@ -426,7 +426,7 @@ def test_search_begin_end_equals_search():
             ix.set_option(L.OPT_FORCE_TAU, int(np.float32(tau).view(np.uint32)))
         h = ix.search_begin(q, 10)
         filler = torch.randn(2048, 2048, device="cuda") @ torch.randn(2048, 2048, device="cuda")   # queued behind the first pass
-        with pytest.raises(L.MirxError):
+        with pytest.raises(L.MirxError, match=r"\(%d\)" % L.ESTATE):
             ix.search(q, 10)                                    # the index is busy until search_end
         s, i = ix.search_end(h, return_f64=True)
         torch.cuda.synchronize()
@@ -437,3 +437,60 @@ def test_search_begin_end_equals_search():
         assert filler.shape == (2048, 2048)
     ix.set_option(L.OPT_FORCE_TAU, L.FORCE_TAU_OFF)
     assert ix._lib.mirx_index_search_end(ix._h) == 0           # nothing pending: a no-op
+
+
+@pytest.mark.parametrize("n,d", [(256, 32), (32768, 64)])          # exact tier (begun, nothing pending); filter tier (a pass pending)
+def test_index_is_busy_between_search_begin_and_search_end(n, d):
+    """Between mirx_index_search_begin and _end every call that uses the workspace or moves rows is refused with MIRX_ESTATE,
+    the read-only calls still work, search_end returns what the blocking search returns, and every refused call works afterwards."""
+    import ctypes
+    from mirx import _lib as L
+    from mirx.index import FlatIndex
+    assert n in (256, _constexpr("mirx_api.hip", "TIER1_MIN_ROWS"))
+    nq, k = 8, 4
+    g, q, extra = _unit(n, d, 51), _unit(nq, d, 52), _unit(3, d, 53)
+    ix = FlatIndex(d, "COSINE", 0)
+    ix.add(g)
+    want_s, want_i = ix.search(q, k, return_f64=True)
+    st = ix.last_stats()
+    assert st["tier1_answered"] > 0 if n > 256 else st["exact_answered"] == nq, st
+    allow = torch.ones(n, dtype=torch.bool)
+    allow[::3] = False
+    dev = dict(device="cuda:0")
+    qd = q.to("cuda:0")
+    pair = [torch.zeros(1, dtype=torch.int64, **dev) for _ in range(3)] + [torch.ones(1, dtype=torch.int64, **dev)]
+    members = torch.zeros(1, dtype=torch.int64, **dev)
+    fill_ids, fill_s = torch.empty((nq, 1, 1), dtype=torch.int64, **dev), torch.empty((nq, 1, 1), dtype=torch.float64, **dev)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def group_fill():
+        L.check(ix._lib.mirx_index_group_fill(ix._h, p(qd), nq, None, 1, 1, p(pair[0]), p(pair[1]), p(pair[2]), p(pair[3]), 1,
+                                              p(members), 1, 1, p(fill_ids), p(fill_s), None), "mirx_index_group_fill")
+
+    calls = {
+        "search": lambda: ix.search(q, k),
+        "search_f64": lambda: ix.search(q, k, return_f64=True),
+        "search_masked": lambda: ix.search(q, k, allow=allow),
+        "search_begin": lambda: ix.search_end(ix.search_begin(q, k)),
+        "rank_top": lambda: ix.rank_top(q, k),
+        "rank_top_masked": lambda: ix.rank_top(q, k, allow=allow),
+        "rank_all": lambda: ix.rank_all(q),
+        "range_search": lambda: ix.range_search(q, 0.5),
+        "group_fill": group_fill,
+        "reserve": lambda: ix.reserve(n + 1024),
+        "remove": lambda: ix.remove([1]),
+        "add": lambda: ix.add(extra),
+    }
+    h = ix.search_begin(q, k)
+    for name, call in calls.items():
+        with pytest.raises(L.MirxError, match=r"\(%d\).*mirx_index_search_end" % L.ESTATE):
+            call()
+        assert len(ix) == n, name
+    assert ix.last_stats()["nq"] == nq
+    row0, id0 = ix.rows(0, 1)
+    assert row0.shape == (1, d) and id0.tolist() == [0]
+    got_s, got_i = ix.search_end(h, return_f64=True)
+    assert torch.equal(got_i, want_i) and torch.equal(got_s, want_s)
+    for name, call in calls.items():                               # (the last two change the index)
+        call()
+    assert len(ix) == n - 1 + 3

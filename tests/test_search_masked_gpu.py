@@ -352,6 +352,47 @@ def test_rank_top_masked(metric):
           "all ones")
 
 
+def rank_top_case(metric):
+    """The radix path's shared case (tests/test_range_gpu.py runs the range search over it as well): three sort tiles and a tail
+    of 5 rows, d = 40 (rows padded to 128 floats), ids a fixed permutation -- not ascending, so the ranking starts from the id
+    permutation --, three queries near rows of the first tile, a middle one and the tail, each excluding its own row's id.
+    Masks: about half the rows, all, none, and one row of the tail (the only allowed row is the last query's excluded row).
+    -> gallery, ids, queries, exclude ids, {name: mask}"""
+    n = 3 * _L().load().mirx_rank_sort_tile() + 5
+    g = _gallery(n, 40, 61, metric)
+    ids = 7 + 3 * torch.randperm(n, generator=torch.Generator().manual_seed(62))
+    near = torch.tensor([5, n // 2, n - 1])
+    q = g[near] + 0.05 * _gallery(3, 40, 63, metric)
+    one = torch.zeros(n, dtype=torch.bool)
+    one[n - 1] = True
+    masks = {"half": torch.rand(n, generator=torch.Generator().manual_seed(64)) < 0.5, "all": torch.ones(n, dtype=torch.bool),
+             "none": torch.zeros(n, dtype=torch.bool), "one": one}
+    return g, ids, q, ids[near], masks
+
+
+@pytest.mark.parametrize("metric", METRICS)
+def test_rank_top_masked_on_allow_bytes(metric):
+    """k = n under every mask, host and device: the first `allowed` slots are rank_top's on a fresh index of the allowed rows with
+    their ids, bit for bit (fp64 and fp32), the slots past them read (-inf, -1); all ones is the unmasked call."""
+    g, ids, q, own, masks = rank_top_case(metric)
+    n = g.shape[0]
+    ix = _index(g, metric, ids)
+    for name, allow in masks.items():
+        na = int(allow.sum())
+        for ex in (None, own):
+            for f64 in (True, False):
+                tag = (metric, name, ex is not None, f64)
+                want = _index(g[allow], metric, ids[allow]).rank_top(q, na, exclude_ids=ex, return_f64=f64) if na else None
+                for am in (allow.numpy(), allow.to("cuda:0")):
+                    s, i = ix.rank_top(q, n, exclude_ids=ex, return_f64=f64, allow=am)
+                    assert s.shape == i.shape == (3, n), tag
+                    if na:
+                        _same((s[:, :na], i[:, :na]), want, tag)
+                    assert (i[:, na:] == -1).all() and (s[:, na:] == float("-inf")).all(), tag
+                    if name == "all":
+                        _same((s, i), ix.rank_top(q, n, exclude_ids=ex, return_f64=f64), tag)
+
+
 # ---- Collection.search(expr=) end to end -------------------------------------------------------------------------------
 def _hits(res):
     return [[(h.id, h.distance) for h in hits] for hits in res]
