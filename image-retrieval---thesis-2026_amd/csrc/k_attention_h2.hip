@@ -1,6 +1,6 @@
 // k_attention_h2.hip -- k_attention_s3 (flash attention, fp32 in / fp32 out, head_dim 64) with every operand carried as
 // TWO fp16 terms and THREE v_mfma_f32_32x32x16_f16 per product block instead of three bf16 terms and six MFMAs (see
-// k_linear_h2.hip for the arithmetic and the measured error).  fp16's range is the caller's contract: `qk_bound` >=
+// k_linear_split.hip for the arithmetic and the measured error).  fp16's range is the caller's contract: `qk_bound` >=
 // max |q|, |k| and `v_bound` >= max |v| over the packed projection (mirx.model derives them from the LayerNorm and
 // the projection's row norms); the launcher turns them into exact power-of-two scales: Q is staged as
 // q * (scale log2 e) * qs, K as k * ks, V as v * vs, the probabilities (in [0, 1]) as p * 1024, and the

@@ -27,16 +27,6 @@ constexpr int K_PLANE = KT * DH * 2;   // bytes of one term of the K tile (4 KiB
 constexpr int V_PLANE = DH * KT * 2;   // bytes of one term of the V^T tile (4 KiB)
 constexpr int BUF = 3 * K_PLANE + 3 * V_PLANE;   // 24 KiB
 
-#define MIRX_MFMA6(C, AH, AM, AL, BH, BM, BL)                                       \
-    {                                                                               \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AM, BM, C, 0, 0, 0);            \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AL, BH, C, 0, 0, 0);            \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BL, C, 0, 0, 0);            \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AM, BH, C, 0, 0, 0);            \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BM, C, 0, 0, 0);            \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BH, C, 0, 0, 0);            \
-    }
-
 __global__ __launch_bounds__(256, 3) void k_attention_s3(const float *__restrict__ qkv, int n, int heads,
                                                          float scale_log2e, float *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) char sm[2 * BUF];

@@ -1,6 +1,6 @@
 // k_conv1x1_h2.hip -- the dense-layer 1x1 convolution of k_conv1x1_s3.hip with every fp32 operand carried as TWO fp16
 // terms (x = xh + xl to 22 bits) and THREE v_mfma_f32_32x32x16_f16 per product block (xl wh + xh wl + xh wh; the
-// dropped xl wl is 2^-22 of the product) instead of three bf16 terms and six MFMAs -- the scheme of k_linear_h2.hip.
+// dropped xl wl is 2^-22 of the product) instead of three bf16 terms and six MFMAs -- SplitF16x2 of k_linear_split.hip.
 // Half the matrix-pipe time and 4 instead of 6 LDS bytes per element; the layer then runs against its HBM stream.
 //
 // fp16 has 5 exponent bits, so the kernel needs the RANGE of its input.  DenseNet activations have no a-priori bound,

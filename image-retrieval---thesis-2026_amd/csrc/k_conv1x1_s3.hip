@@ -157,13 +157,7 @@ __global__ __launch_bounds__(256, 3) void k_conv1x1_s3(const float *__restrict__
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
                 f32x16 c = acc[mi][ni];
-                // smallest terms first
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][2], b[ni][0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][2], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][1], b[ni][0], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][1], c, 0, 0, 0);
-                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[mi][0], b[ni][0], c, 0, 0, 0);
+                MIRX_MFMA6(c, a[mi][0], a[mi][1], a[mi][2], b[ni][0], b[ni][1], b[ni][2])
                 acc[mi][ni] = c;
             }
         store(cur ^ 1);

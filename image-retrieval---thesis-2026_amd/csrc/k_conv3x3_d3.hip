@@ -143,12 +143,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_d3(const float *__restrict__
 #define MIRX_D3_MFMA(T, TAP, B)                                                                    \
     {                                                                                              \
         f32x16 c_ = acc[T];                                                                        \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[TAP][1], B[1], c_, 0, 0, 0);               \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[TAP][2], B[0], c_, 0, 0, 0);               \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[TAP][0], B[2], c_, 0, 0, 0);               \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[TAP][1], B[0], c_, 0, 0, 0);               \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[TAP][0], B[1], c_, 0, 0, 0);               \
-        c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[TAP][0], B[0], c_, 0, 0, 0);               \
+        MIRX_MFMA6(c_, wf[TAP][0], wf[TAP][1], wf[TAP][2], B[0], B[1], B[2])                       \
         acc[T] = c_;                                                                               \
     }
     const bool two = live_blk[1];                          // wave-uniform: waves 0..2 own two column blocks

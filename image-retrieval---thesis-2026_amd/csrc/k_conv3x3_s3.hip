@@ -196,13 +196,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_wino_s3(const float *__restr
             const bf16x8 bh = __builtin_bit_cast(bf16x8, ph), bm = __builtin_bit_cast(bf16x8, pm),
                          bl = __builtin_bit_cast(bf16x8, pl);
             f32x16 c = acc[j];
-            // smallest terms first
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua[j][1], bm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua[j][2], bh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua[j][0], bl, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua[j][1], bh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua[j][0], bm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua[j][0], bh, c, 0, 0, 0);
+            MIRX_MFMA6(c, ua[j][0], ua[j][1], ua[j][2], bh, bm, bl)
             acc[j] = c;
         }
 #ifdef MIRX_W3_CYCLES

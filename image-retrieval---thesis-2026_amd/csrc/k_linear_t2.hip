@@ -1,7 +1,7 @@
-// k_linear_t2.hip -- token-major Linear on two fp16 terms per operand (k_linear_h2's arithmetic: three MFMAs per product
+// k_linear_t2.hip -- token-major Linear on two fp16 terms per operand (k_linear_split's fp16 arithmetic: three MFMAs per product
 // block, xl wh + xh wl + xh wh, fp32 accumulation), restructured so that the matrix pipe, not the operand delivery, paces it.
 //
-// Why a second kernel: k_linear_h2 takes fp32 activations, splits them in registers while it stages 16 features at a time and
+// Why a second kernel: k_linear_split takes fp32 activations, splits them in registers while it stages 16 features at a time and
 // synchronises once per 16-feature stage.  A diagnostic build WITHOUT its MFMAs takes 75 % of the full kernel's time (DESIGN
 // 6.4): loads, splits, LDS stores and barriers are the kernel; the MFMAs hide behind them.  Here
 //   * the ACTIVATIONS ARRIVE ALREADY SPLIT ("terms rows", below): the producer (LayerNorm, the previous Linear's epilogue,

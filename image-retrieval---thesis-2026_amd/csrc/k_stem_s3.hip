@@ -116,13 +116,7 @@ __global__ __launch_bounds__(256, 3) void k_stem_s3(const float *__restrict__ x,
             const bf16x8 xh = __builtin_bit_cast(bf16x8, bh), xm = __builtin_bit_cast(bf16x8, bm),
                          xl = __builtin_bit_cast(bf16x8, bl);
             f32x16 c = acc[t];
-            // smallest terms first
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, xm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, xh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xl, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, xh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xm, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, xh, c, 0, 0, 0);
+            MIRX_MFMA6(c, ah, am, al, xh, xm, xl)
             acc[t] = c;
         }
     }

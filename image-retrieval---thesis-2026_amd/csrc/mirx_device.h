@@ -20,13 +20,31 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 // a generic pointer into LDS as the address-space-3 pointer the LDS-DMA builtins take
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void *)(p))
 
-// one product block of two-fp16-term operands: the three cross terms that matter, smallest first
-#define MIRX_MFMA3(C, AH, AL, BH, BL)                                               \
+// ---- the term order of a product block: defined HERE and nowhere else -----------------------------------------------
+// The bit-identity tests pin the summation order, so every kernel of a scheme issues the same (A term, B term) sequence,
+// smallest products first.  SWAP (compile-time) exchanges the MFMA's operand SLOTS -- the result comes out transposed, rows
+// <-> lanes -- and leaves the SEQUENCE alone: calling a block with A and B exchanged instead would issue l*h and h*l in the
+// opposite order and round differently.
+#define MIRX_MFMA_TERM(OP, C, A, B, SWAP) C = (SWAP) ? OP(B, A, C, 0, 0, 0) : OP(A, B, C, 0, 0, 0);
+// two fp16 terms per operand: the three cross terms that matter (l*h, h*l, h*h)
+#define MIRX_MFMA3_SLOTS(C, AH, AL, BH, BL, SWAP)                                   \
     {                                                                               \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, C, 0, 0, 0);             \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, C, 0, 0, 0);             \
-        C = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, C, 0, 0, 0);             \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_f16, C, AL, BH, SWAP)     \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_f16, C, AH, BL, SWAP)     \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_f16, C, AH, BH, SWAP)     \
     }
+#define MIRX_MFMA3(C, AH, AL, BH, BL) MIRX_MFMA3_SLOTS(C, AH, AL, BH, BL, false)
+// three bf16 terms per operand: the six that matter (m*m, l*h, h*l, m*h, h*m, h*h)
+#define MIRX_MFMA6_SLOTS(C, AH, AM, AL, BH, BM, BL, SWAP)                           \
+    {                                                                               \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_bf16, C, AM, BM, SWAP)    \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_bf16, C, AL, BH, SWAP)    \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_bf16, C, AH, BL, SWAP)    \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_bf16, C, AM, BH, SWAP)    \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_bf16, C, AH, BM, SWAP)    \
+        MIRX_MFMA_TERM(__builtin_amdgcn_mfma_f32_32x32x16_bf16, C, AH, BH, SWAP)    \
+    }
+#define MIRX_MFMA6(C, AH, AM, AL, BH, BM, BL) MIRX_MFMA6_SLOTS(C, AH, AM, AL, BH, BM, BL, false)
 
 __device__ inline int lane_id() { return threadIdx.x & 63; }
 
@@ -292,6 +310,34 @@ __device__ inline void split3b_x8(const float (&v)[8], bf16x8 &h, bf16x8 &m, bf1
     m = __builtin_bit_cast(bf16x8, pm);
     l = __builtin_bit_cast(bf16x8, pl);
 }
+
+// ---- term schemes ---------------------------------------------------------------------------------------------------
+// What a kernel template needs to know about "an fp32 operand as a few 16-bit terms", highest term first (k_linear_split.hip):
+// T terms per operand, the MFMA fragment type, SCALED = the terms have fp16's range, so the caller's power-of-two scales apply
+// (x_scale while staging, its inverse on the accumulator), the split of a pair of values into T packed pairs, and the product
+// block c += a b in the scheme's term order (SWAP as above).
+struct SplitBf16x3 {
+    static constexpr int T = 3;
+    static constexpr bool SCALED = false;
+    typedef bf16x8 frag;
+    __device__ static void split_pair(float v0, float v1, float, unsigned (&t)[3]) { split3b_pair(v0, v1, t[0], t[1], t[2]); }
+    template <bool SWAP>
+    __device__ static void product(f32x16 &c, const frag (&a)[3], const frag (&b)[3]) {
+        MIRX_MFMA6_SLOTS(c, a[0], a[1], a[2], b[0], b[1], b[2], SWAP)
+    }
+};
+struct SplitF16x2 {
+    static constexpr int T = 2;
+    static constexpr bool SCALED = true;
+    typedef f16x8 frag;
+    __device__ static void split_pair(float v0, float v1, float x_scale, unsigned (&t)[2]) {
+        split2h_pair(v0 * x_scale, v1 * x_scale, t[0], t[1]);
+    }
+    template <bool SWAP>
+    __device__ static void product(f32x16 &c, const frag (&a)[2], const frag (&b)[2]) {
+        MIRX_MFMA3_SLOTS(c, a[0], a[1], b[0], b[1], SWAP)
+    }
+};
 
 // Four consecutive channels `ch ..` (ch % 4 == 0) of token row `row` of a [rows, c] matrix written as "terms rows" (k_linear_t2.hip:
 // per 32 features one 128-byte line, fp16 high terms | fp16 low terms of scale * value): the input format of the DMA-fed Linear.

@@ -200,14 +200,15 @@ hipError_t launch_conv1x1_h2_small(const float *x, int64_t xbs, int cin, const f
                                    float *out_amax, float y_ks, float y_kb, float *y_inv_out, int64_t xps, int64_t yps,
                                    hipStream_t st);
 
-// ---- k_linear_h2.hip: the token-major Linear on two fp16 terms per operand (3 MFMAs per product) ----
+// ---- k_linear_split.hip: the token-major Linear, fp32 operands split into 16-bit terms while they are staged ----
+// two fp16 terms per operand (3 MFMAs per product block); the caller supplies the power-of-two range scales
 hipError_t launch_linear_h2(const float *x, int64_t m, int k, const uint16_t *w2, const float *bias, int n, int act,
                             const float *res, const float *gamma, float x_scale, float out_scale, float *y,
                             int tokens_per_image, const float *xb_dev, hipStream_t st, bool rows_out = false,
                             float *sq_out = nullptr);
 hipError_t launch_grn_norm_partials(const float *part, int tpi, int64_t n_img, int c, float *gx, hipStream_t st);
 
-// ---- k_linear_s3.hip ---------------------------------------------------------------------
+// three bf16 terms per operand (6 MFMAs per product block), the same kernel template
 // tokens_per_image == 0: y / res are [m][n]; > 0: token t is pixel t % tpi of image t / tpi and y / res are NCHW
 hipError_t launch_linear_s3(const float *x, int64_t m, int k, const uint16_t *w3, const float *bias, int n, int act,
                             const float *res, const float *gamma, float *y, int tokens_per_image, hipStream_t st);

@@ -1,4 +1,4 @@
-"""mirx_linear_split3 (csrc/k_linear_s3.hip): the token-major Linear layer on three-term bf16 MFMA, against
+"""mirx_linear_split3 (csrc/k_linear_split.hip): the token-major Linear layer on three-term bf16 MFMA, against
 a float64 restatement of  y = epi(x W^T + b).  Tolerance: 3e-6 of the largest |y| (the dropped cross
 terms are <= 3 * 2^-24 per product; accumulation is fp32) -- the class of an fp32 GEMM."""
 import ctypes
@@ -171,6 +171,41 @@ def test_linear_split2h_nchw_matches_float64(n_img, tpi, k, n, use_res, xmax, lo
     assert bool(torch.isnan(y).all())
     assert lib.mirx_linear_split2h_nchw(_vp(x), n_img, tpi, k, _vp(w2), _vp(b), n, None, _vp(sc), xmax, None, 1.0 / ws, _vp(y),
                                         None) != 0
+
+
+@pytest.mark.parametrize("n_img,tpi,k,n", [(3, 50, 48, 200), (2, 129, 16, 128)])
+@pytest.mark.parametrize("use_res", [True, False])
+@pytest.mark.parametrize("xmax,loose", [(3.0, 1.0), (700.0, 64.0)])
+def test_linear_split2h_grn_rows_matches_float64(n_img, tpi, k, n, use_res, xmax, loose):
+    """mirx_linear_split2h_grn_rows (ConvNeXt block tail on a channels-last stream: the GRN input scale folded into the
+    staging, its maximum read from the device, ROW-MAJOR output with the skip added) against float64.  The arithmetic is
+    mirx_linear_split2h_nchw's and only the store addressing differs, so the bound is that test's.  (3, 50, 48, 200): a ragged
+    second token tile, image boundaries inside a tile (the scale row changes mid-tile), an odd stage count (the last stage
+    sits in buffer 0), n no multiple of 128; (2, 129, 16, 128): a single stage, a tile that straddles two images by one row."""
+    import mirx.model as mm
+    from mirx import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device="cpu").manual_seed(n_img + tpi + k)
+    x = (torch.randn(n_img * tpi, k, generator=g).clamp(-4, 4) / 4.0 * xmax).to(dev)
+    lin = torch.nn.Linear(k, n).to(dev)
+    with torch.no_grad():
+        lin.bias.normal_()
+    w2, ws = mm._linear_h2_weights(lin)
+    w, b = lin.weight.detach(), lin.bias.detach()
+    res = torch.randn(n_img * tpi, n, generator=g).to(dev) if use_res else None
+    sc = (0.25 + 3.0 * torch.rand(n_img, k, generator=g)).to(dev)
+    smax = sc.abs().amax().reshape(1)
+    xs = (x.double().reshape(n_img, tpi, k) * sc.double()[:, None, :]).reshape(n_img * tpi, k)
+    want = xs @ w.double().t() + b.double()
+    if use_res:
+        want = res.double() + want
+    y = torch.full((n_img * tpi, n), float("nan"), device=dev)
+    _lib.check(lib.mirx_linear_split2h_grn_rows(_vp(x), n_img, tpi, k, _vp(w2), _vp(b), n, _vp(res), _vp(sc), xmax * loose,
+                                                _vp(smax), 1.0 / ws, _vp(y), None), "mirx_linear_split2h_grn_rows")
+    torch.cuda.synchronize()
+    err = float((y.double() - want).abs().max())
+    assert err < 3e-6 * max(1.0, float(want.abs().max())), err
 
 
 @pytest.mark.parametrize("n,hw,c", [(3, 144, 512), (2, 577, 192), (1, 5, 4), (4, 2304, 1024)])

@@ -1,4 +1,4 @@
-"""Times mirx_linear_split2h (k_linear_h2) on the token-major backbones' layer shapes: ms and fp32-equivalent TFLOP/s
+"""Times mirx_linear_split2h (k_linear_split.hip, the two-fp16 scheme) on the token-major backbones' layer shapes: ms and fp32-equivalent TFLOP/s
 (3 fp16 MFMAs per product: the bar is 838.9).  MIRX_LIB_PATH selects a diagnostic build."""
 import argparse
 import ctypes

@@ -1,5 +1,5 @@
 """Checks and times mirx_linear_terms (k_linear_t2) on the token-major backbones' layer shapes against mirx_linear_split2h
-(k_linear_h2): error vs a float64 product, ms, fp32-equivalent TFLOP/s (bar: 838.9 = fp16 MFMA peak / 3)."""
+(k_linear_split.hip, the two-fp16 scheme): error vs a float64 product, ms, fp32-equivalent TFLOP/s (bar: 838.9 = fp16 MFMA peak / 3)."""
 import argparse
 import os
 import sys

@@ -70,7 +70,7 @@ def main():
     x = torch.randn(m, k, device=dev)
     w3 = _split3_weights(torch.randn(n, k, device=dev) * k ** -0.5)
     y = torch.empty(m, n, device=dev)
-    measure("k_linear_s3 43840 x 768 -> 2304", lambda: _lib.check(lib.mirx_linear_split3(vp(x), m, k, vp(w3), None, n, 0, None, None, vp(y), None), "l"))
+    measure("k_linear_split (three bf16) 43840 x 768 -> 2304", lambda: _lib.check(lib.mirx_linear_split3(vp(x), m, k, vp(w3), None, n, 0, None, None, vp(y), None), "l"))
     measure("torch F.linear fp32 (rocBLAS) same shape", lambda: torch.nn.functional.linear(x, torch.empty(n, k, device=dev).normal_()), ms=8)
     # attention
     qkv = torch.randn(32, 1370, 3, 12, 64, device=dev)
