@@ -10,7 +10,7 @@
 // not -inf) where the two tokens lie in different regions of timm's three slices per axis (shift > 0 only); ls[head] =
 // exp(min(logit_scale, ln 100)).  q and k are L2-normalised per (token, head) in fp32 (F.normalize, eps 1e-12).
 //
-// Arithmetic and LDS layouts are k_attention_h2g<32>'s (flash attention, 128 queries per workgroup, 32-key tiles double
+// Arithmetic and LDS layouts are k_attention_split<SplitF16x2, 32>'s (k_attention_split.hip: flash attention, 128 queries per workgroup, 32-key tiles double
 // buffered, every operand two fp16 terms, three v_mfma_f32_32x32x16_f16 per product block, online softmax in base 2):
 //   q^ is staged as q^ * ls log2(e) * 64 (<= 9 234), k^ as k^ * 2^14: |q^|, |k^| <= 1, so no bound is needed;
 //   v is staged at the power of two that puts the largest |v| of THIS (image, window, head) in [2^14, 2^15) -- a pre-pass over the
@@ -37,7 +37,7 @@ constexpr float MASK_L2 = -100.f * LOG2E;
 // region of timm's shifted-window mask along one axis: slices [0, side - ws), [side - ws, side - shift), [side - shift, side)
 __device__ inline int region1(int y, int side, int ws, int shift) { return y < side - ws ? 0 : (y < side - shift ? 1 : 2); }
 
-// grid: one workgroup per (query tile of 128, window, head, image), 1-D.  XCD-aware order as k_attention_h2: the query tiles of
+// grid: one workgroup per (query tile of 128, window, head, image), 1-D.  XCD-aware order as k_attention_split: the query tiles of
 // one (window, head, image) -- which stream the same K and V -- are dealt to the same XCD.
 template <int WS>
 __global__ __launch_bounds__(256, 2) void k_attention_win(const float *__restrict__ qkv, int side, int shift, int heads,

@@ -314,13 +314,14 @@ __device__ inline void split3b_x8(const float (&v)[8], bf16x8 &h, bf16x8 &m, bf1
 // ---- term schemes ---------------------------------------------------------------------------------------------------
 // What a kernel template needs to know about "an fp32 operand as a few 16-bit terms", highest term first (k_linear_split.hip):
 // T terms per operand, the MFMA fragment type, SCALED = the terms have fp16's range, so the caller's power-of-two scales apply
-// (x_scale while staging, its inverse on the accumulator), the split of a pair of values into T packed pairs, and the product
-// block c += a b in the scheme's term order (SWAP as above).
+// (x_scale while staging, its inverse on the accumulator), the split of a pair of values into T packed pairs and of eight values
+// into T fragments (k_attention_split.hip), and the product block c += a b in the scheme's term order (SWAP as above).
 struct SplitBf16x3 {
     static constexpr int T = 3;
     static constexpr bool SCALED = false;
     typedef bf16x8 frag;
     __device__ static void split_pair(float v0, float v1, float, unsigned (&t)[3]) { split3b_pair(v0, v1, t[0], t[1], t[2]); }
+    __device__ static void split_x8(const float (&v)[8], frag (&t)[3]) { split3b_x8(v, t[0], t[1], t[2]); }
     template <bool SWAP>
     __device__ static void product(f32x16 &c, const frag (&a)[3], const frag (&b)[3]) {
         MIRX_MFMA6_SLOTS(c, a[0], a[1], a[2], b[0], b[1], b[2], SWAP)
@@ -333,6 +334,7 @@ struct SplitF16x2 {
     __device__ static void split_pair(float v0, float v1, float x_scale, unsigned (&t)[2]) {
         split2h_pair(v0 * x_scale, v1 * x_scale, t[0], t[1]);
     }
+    __device__ static void split_x8(const float (&v)[8], frag (&t)[2]) { split2h_x8(v, t[0], t[1]); }
     template <bool SWAP>
     __device__ static void product(f32x16 &c, const frag (&a)[2], const frag (&b)[2]) {
         MIRX_MFMA3_SLOTS(c, a[0], a[1], b[0], b[1], SWAP)

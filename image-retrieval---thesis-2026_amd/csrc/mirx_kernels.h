@@ -266,10 +266,11 @@ int conv3x3_small_max_wg();
 // ---- k_attention.hip --------------------------------------------------------------------
 hipError_t launch_attention(const float *qkv, int64_t batch, int n, int heads, int head_dim, float scale, float *out,
                             hipStream_t st);
-// ---- k_attention_s3.hip: the same attention on three-term bf16 MFMAs (head_dim 64) ------------------
+// ---- k_attention_split.hip: the same attention on 16-bit MFMA terms, one kernel template for both schemes (head_dim 32 / 64 /
+// 72 / 96; one image's qkv rows below 2 GiB) -- _s3: three bf16 terms per operand
 hipError_t launch_attention_s3(const float *qkv, int64_t batch, int n, int heads, int head_dim, float scale, float *out,
                                hipStream_t st);
-// ---- k_attention_h2.hip: the same attention on two fp16 terms per operand (head_dim 64, caller-supplied bounds) --
+// _h2: two fp16 terms per operand (caller-supplied bounds), fp32 rows or terms rows out
 hipError_t launch_attention_h2(const float *qkv, int64_t batch, int n, int heads, int head_dim, float scale,
                                float qk_bound, float v_bound, float *out, hipStream_t st, void *out_terms = nullptr, float terms_scale = 1.f);
 

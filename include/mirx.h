@@ -655,6 +655,8 @@ int mirx_attention_qkv_f32(const float *qkv, int64_t batch, int n_tokens, int he
 /*
  * mirx_attention_qkv_f32 with both GEMMs on three-term bf16 MFMAs (Q, K, V and the probabilities each carried
  * as xh + xm + xl; fp32-grade, see mirx_conv1x1_bn_relu_split3): same arguments, result layout and head_dim set.
+ * Like the two-fp16-term entry points below it reads K and V through 32-bit buffer offsets, so one image's qkv rows must
+ * stay below 2 GiB: n_tokens * 3 * heads * head_dim * 4 < 2^31, else MIRX_EHIP (invalid value) before anything is launched.
  */
 int mirx_attention_qkv_f32_split3(const float *qkv, int64_t batch, int n_tokens, int heads, int head_dim,
                                   float scale, float *out, void *stream);

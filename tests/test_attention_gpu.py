@@ -46,7 +46,7 @@ def test_attention_matches_float64(b, n, heads, dh):
 @pytest.mark.parametrize("dh", [64, 72])
 def test_attention_split3_matches_float64(b, n, heads, dh):
     """mirx_attention_qkv_f32_split3: both GEMMs on three-term bf16 MFMAs; same tolerance as the fp32 kernel, and
-    a peaked case (logits ~ +-60).  head_dim 64 = the tuned kernel, 72 = the generic one."""
+    a peaked case (logits ~ +-60).  head_dim 64 = XOR-swizzled K rows and full staging lists, 72 = rotated rows, ragged lists."""
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(1000 * n + heads + 7)
     qkv = torch.randn((b, n, 3, heads, dh), generator=g, device=dev) * 1.5
@@ -94,6 +94,10 @@ def test_attention_argument_errors():
     rc = lib.mirx_attention_qkv_f32(ctypes.c_void_p(x.data_ptr()), 1, 4, 1, 40, 0.1, ctypes.c_void_p(x.data_ptr()), None)
     assert rc == -1 and b"head_dim" in lib.mirx_last_error()          # MIRX_EINVAL
     assert lib.mirx_attention_qkv_f32(None, 0, 0, 1, 64, 0.1, None, None) == 0
+    # one image's qkv rows reach 2 GiB (2^20 * 3 * 12 * 64 * 4 = 9 * 2^30): the split-term kernels address K / V with 32-bit buffer
+    # offsets, so the launcher refuses before anything touches memory -- the pointers only have to be non-null
+    rc = lib.mirx_attention_qkv_f32_split3(ctypes.c_void_p(x.data_ptr()), 1, 1 << 20, 12, 64, 0.125, ctypes.c_void_p(x.data_ptr()), None)
+    assert rc == -3 and b"invalid argument" in lib.mirx_last_error()  # MIRX_EHIP carrying hipErrorInvalidValue
 
 
 def test_vit_block_uses_the_kernel_and_matches_sdpa():
@@ -160,11 +164,53 @@ def test_attention_split2h_terms_output_carries_the_fp32_output(b, n, heads, dh)
     assert float((back[:, :c] - out.view(b * n, c).double()).abs().max()) <= bv * 2.0 ** -21
 
 
+@pytest.mark.parametrize("kind", ["split3", "split2h", "split2h_terms"])
+@pytest.mark.parametrize("dh", [64, 72])
+def test_attention_split_redealt_order_matches_float64(dh, kind):
+    """b, heads, n = 3, 3, 129: nine (image, head) pairs, so the XCD-aware order re-deals eight of them and leaves the ninth in
+    linear order; two query tiles; five key tiles, the last with a single valid key.  Both term schemes of k_attention_split
+    against float64: the fp32 outputs to the 3e-6 of the tests above, the terms rows to that plus the two-fp16-term bound
+    (bv * 2^-21) of test_attention_split2h_terms_output_carries_the_fp32_output."""
+    from mirx import _lib
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    b, heads, n = 3, 3, 129
+    g = torch.Generator(device=dev).manual_seed(129 + dh)
+    qkv = torch.randn((b, n, 3, heads, dh), generator=g, device=dev) * 1.5
+    ref = _ref(qkv)
+    tol = 3e-6 * max(1.0, float(ref.abs().max()))
+    c = heads * dh
+    bqk, bv = float(qkv[:, :, :2].abs().max()), float(qkv[:, :, 2].abs().max())
+    q = ctypes.c_void_p(qkv.data_ptr())
+    if kind == "split2h_terms":
+        cp = (c + 31) // 32 * 32
+        scale = 2.0 ** math.floor(math.log2(32768.0 / bv))
+        t = torch.full((b * n, 2 * cp), float("nan"), dtype=torch.float16, device=dev)
+        _lib.check(lib.mirx_attention_qkv_f32_split2h_terms(q, b, n, heads, dh, dh ** -0.5, bqk, bv, scale,
+                                                            ctypes.c_void_p(t.data_ptr()), None), kind)
+        torch.cuda.synchronize()
+        tt = t.view(b * n, cp // 32, 2, 32).double()
+        out = ((tt[:, :, 0] + tt[:, :, 1]).reshape(b * n, cp)[:, :c] / scale).view(b, n, c)
+        tol += bv * 2.0 ** -21
+    else:
+        o = torch.full((b, n, c), float("nan"), device=dev)
+        if kind == "split3":
+            rc = lib.mirx_attention_qkv_f32_split3(q, b, n, heads, dh, dh ** -0.5, ctypes.c_void_p(o.data_ptr()), None)
+        else:
+            rc = lib.mirx_attention_qkv_f32_split2h(q, b, n, heads, dh, dh ** -0.5, bqk, bv, ctypes.c_void_p(o.data_ptr()), None)
+        _lib.check(rc, kind)
+        torch.cuda.synchronize()
+        out = o.double()
+    assert torch.isfinite(out).all()
+    err = float((out - ref).abs().max())
+    assert err < tol, (kind, dh, err, tol)
+
+
 # ---- guard bands: what lies next to the operands -------------------------------------------------------------------
-# Every test above hands the kernels a tensor of its own, whose neighbouring bytes happen to be finite.  The two-term kernels
-# (k_attention_h2 for head_dim 64, k_attention_h2g for 32 / 72 / 96) read K / V through a buffer descriptor that spans one
-# image's n token rows, with the tile's offset as the load's scalar offset, and rely on the descriptor's range check to
-# turn the tail tile's rows >= n into zeros; the fp32 and three-term kernels clamp the key instead.  Here qkv is the head
+# Every test above hands the kernels a tensor of its own, whose neighbouring bytes happen to be finite.  The split-term kernels
+# (k_attention_split.hip: two fp16 or three bf16 terms, head_dim 32 / 64 / 72 / 96) read K / V through a buffer descriptor that
+# spans one image's n token rows, with the tile's offset as the load's scalar offset, and rely on the descriptor's range check to
+# turn the tail tile's rows >= n into zeros; the fp32 kernel clamps the key instead.  Here qkv is the head
 # of a buffer whose next two 32-token tiles are NaN: a tail-tile row read from beyond the last image reaches the P V
 # product as 0 x NaN.  The outputs, too, are the head of a buffer whose tail holds a sentinel that must come back
 # bit-unchanged.

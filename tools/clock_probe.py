@@ -75,7 +75,7 @@ def main():
     # attention
     qkv = torch.randn(32, 1370, 3, 12, 64, device=dev)
     o = torch.empty(32, 1370, 768, device=dev)
-    measure("k_attention_s3 (32 x 1370 x 12 x 64)", lambda: _lib.check(lib.mirx_attention_qkv_f32_split3(vp(qkv), 32, 1370, 12, 64, 0.125, vp(o), None), "a"))
+    measure("k_attention_split<SplitBf16x3, 64> (32 x 1370 x 12 x 64)", lambda: _lib.check(lib.mirx_attention_qkv_f32_split3(vp(qkv), 32, 1370, 12, 64, 0.125, vp(o), None), "a"))
     measure("k_attention fp32 MFMA, same shape", lambda: _lib.check(lib.mirx_attention_qkv_f32(vp(qkv), 32, 1370, 12, 64, 0.125, vp(o), None), "a"))
     # Winograd fp32 56x56
     xx = torch.relu(torch.randn(1024, 128, 56, 56, device=dev))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction mix of the largest loop of one kernel (development tool):
-tools/loop_mix.py k_attention_h2.hip 14k_attention_h2E [extra hipcc flags]  -- the second argument is a substring of the mangled name."""
+tools/loop_mix.py k_attention_split.hip SplitF16x2ELi64 [extra hipcc flags]  -- the second argument is a substring of the mangled name."""
 import collections
 import os
 import re
