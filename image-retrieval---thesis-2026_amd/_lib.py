@@ -96,6 +96,9 @@ SYMBOLS = {
     "mirx_index_search_begin": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "mirx_index_search_end": (_int, [_vp]),
     "mirx_index_search_masked": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mirx_index_search_deep": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_tier1_max_k": (_int, []),
+    "mirx_deep_min_rows": (_i64, [_int, _i64]),
     "mirx_index_rank_top_masked": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mirx_index_range_search": (_int, [_vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _i64, _vp,
                                        ctypes.POINTER(_i64), _vp]),

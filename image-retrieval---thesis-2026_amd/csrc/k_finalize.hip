@@ -18,14 +18,6 @@ namespace {
 
 constexpr int64_t ID_LAST = INT64_MAX;
 
-__device__ inline uint32_t f32_orderable(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float f32_from_orderable(uint32_t e) {
-    return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
-}
-
 // tau[q] = rank_j-th largest sampled group maximum of query q; +inf for padding queries.
 __global__ __launch_bounds__(256) void k_select_tau(const float *__restrict__ groupmax, int ngroups,
                                                     int64_t nq, int rank_j, float *__restrict__ tau) {

@@ -119,6 +119,12 @@ __host__ __device__ inline int region_slots(int regions) {
     return s < 8 ? 8 : (s > 64 ? 64 : s);
 }
 
+// the deep route's regions (mirx_index_search_deep): about 2 * DEEP_CAP slots per query in total
+__host__ __device__ inline int region_slots_deep(int regions) {
+    const int s = 2 * DEEP_CAP / (regions > 0 ? regions : 1);
+    return s < DEEP_MIN_SLOTS ? DEEP_MIN_SLOTS : s;
+}
+
 // MODE 0: threshold filter.  MODE 1: group maxima of sampled rows.
 template <int BN, int MODE, bool L2>
 __global__ __launch_bounds__(512, 2) void k_gemm(GemmArgs A) {
@@ -1031,7 +1037,8 @@ hipError_t launch_bn(const GemmArgs &a0, hipStream_t st) {
     const Plan plan = make_plan(a.n_rows, a.nq_pad, BN, device_cus() / 8 * 8);
     if (plan.ngt <= 0 || plan.nqt <= 0) return hipSuccess;
     a.nph = plan.nph;
-    if (MODE == 0 && (a.regions != plan.nph * (8 / (BN / 64)) || a.slots != region_slots(a.regions)))
+    if (MODE == 0 && (a.regions != plan.nph * (8 / (BN / 64)) ||
+                      (a.slots != region_slots(a.regions) && a.slots != region_slots_deep(a.regions))))
         return hipErrorInvalidValue;
     // a tile's byte span must fit the 32-bit buffer offsets
     if ((int64_t)BM * a.row_stride * a.dimp * 2 > 0x7FFFFFFF) return hipErrorInvalidValue;
@@ -1090,6 +1097,11 @@ void gemm_plan(int64_t n_rows, int64_t nq_pad, int bn, int *regions, int *slots)
     const Plan plan = make_plan(n_rows, nq_pad, bn, device_cus() / 8 * 8);
     *regions = plan.nph * (8 / (bn / 64));
     *slots = region_slots(*regions);
+}
+
+void gemm_plan_deep(int64_t n_rows, int64_t nq_pad, int bn, int *regions, int *slots) {
+    gemm_plan(n_rows, nq_pad, bn, regions, slots);
+    *slots = region_slots_deep(*regions);
 }
 
 hipError_t launch_gemm_filter(const GemmArgs &a, int bn, hipStream_t st) { return launch_mode<0>(a, bn, st); }

@@ -126,6 +126,15 @@ __device__ inline void bitonic_lds(T *a, int m, Before before) {
     __syncthreads();
 }
 
+// An unsigned image of an fp32 value that ascends with the value (the candidate sorts of k_finalize.hip / k_finalize_deep.hip).
+__device__ inline uint32_t f32_orderable(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float f32_from_orderable(uint32_t e) {
+    return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
+}
+
 // fp32 -> bf16, round to nearest even (finite inputs).
 __device__ inline uint16_t f32_to_bf16(float f) {
     uint32_t u = __float_as_uint(f);

@@ -7,6 +7,8 @@
 //   -> exact scan (fp64 score tiles + row top-k) for the queries the guard rejected.
 // The only host<->device synchronisation is one read of the rejected-query count.
 // A masked search (mirx_index_search_masked) runs the same sequence over a SearchRows that stands for the allowed rows.
+// The deep search (mirx_index_search_deep) runs it for k_eff past TIER1_MAX_K with SearchRows::deep set: gemm_plan_deep's candidate
+// regions, its own threshold rank and k_finalize_deep; where that route does not apply the call is handed to the two above.
 // A range search (mirx_index_range_search) runs prep -> threshold from the radius -> filter GEMM -> its own finalize, the radix
 // ranking for what that cannot answer, and a CSR assembly (k_range.hip).
 // The radix ranking (radix_plan / radix_sort_batch) serves mirx_index_rank_all / _rank_top / _rank_top_masked and the range
@@ -68,6 +70,7 @@ struct SearchRows {
     const int32_t *mpos = nullptr;        // scanned keep positions (n + 1): row r is masked iff mpos[r + 1] == mpos[r]
     const float *bias = nullptr;          // tier 1: the per-row bias of both GEMMs instead of the index's
     bool tier1 = false;
+    bool deep = false;                    // tier 1 with the deep route's plan, threshold target and finalize (mirx_index_search_deep)
 };
 
 struct mirx_index {
@@ -284,11 +287,33 @@ int exact_pass(mirx_index *ix, const SearchRows &sr, const float *q32p, const in
     return MIRX_OK;
 }
 
+// ---- the deep route (mirx_index_search_deep) -------------------------------------------------------------------
+// The sampled threshold is the j-th largest of `ngroups` group maxima of every stride-th row, ngroups * stride ~ size *
+// groups_per_tile / 256: it resolves candidate counts only up to about half the groups deep.  The deep route aims at
+// target = DEEP_TARGET_MUL * k_eff + DEEP_TARGET_ADD candidates per query (k_eff, the 2 eps band below the k-th score, room for
+// tau < lo) and is taken only where target <= ngroups * stride / 2, i.e. from target * DEEP_GROUP_ROWS / groups_per_tile(bn)
+// rows on; smaller galleries go to the exact scan, where it costs little.
+int64_t deep_target(int64_t k_eff) { return (int64_t)DEEP_TARGET_MUL * k_eff + DEEP_TARGET_ADD; }
+
+int64_t deep_min_rows(int64_t k_eff, int bn) {
+    return std::max<int64_t>(TIER1_MIN_ROWS, deep_target(k_eff) * DEEP_GROUP_ROWS / gemm_groups_per_tile(bn));
+}
+
+// The rank j whose group maximum leaves about `target` rows above it.  A fraction f of the groups has its maximum above tau when
+// each of a group's G sampled rows passes with probability p, 1 - f = (1 - p)^G; the rows expected above tau are p * G * ngroups *
+// stride = -ln(1 - f) * ngroups * stride for large G.  So f = 1 - exp(-target / (ngroups * stride)), at most one half.  (Speed
+// only: the guard decides what is answered.)
+int deep_sample_rank(int64_t k_eff, int ngroups, int64_t stride) {
+    const double f = 1.0 - std::exp(-(double)deep_target(k_eff) / ((double)ngroups * (double)stride));
+    const int64_t j = (int64_t)std::ceil(f * ngroups);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(j, ngroups / 2));
+}
+
 // The filter GEMM's workspace for a batch of nb_pad queries and the arguments every filter launch over the whole gallery shares
 // (thresholds in ix->tau, which the caller fills; the counters are the caller's to zero).
-int filter_args(mirx_index *ix, int64_t nb_pad, int bn, const float *bias_or_null, GemmArgs *out) {
+int filter_args(mirx_index *ix, int64_t nb_pad, int bn, const float *bias_or_null, GemmArgs *out, bool deep = false) {
     int regions = 0, slots = 0;
-    gemm_plan(ix->size, nb_pad, bn, &regions, &slots);
+    (deep ? gemm_plan_deep : gemm_plan)(ix->size, nb_pad, bn, &regions, &slots);
     MIRX_HIP(ix->tau.ensure((size_t)nb_pad * sizeof(float)));
     MIRX_HIP(ix->cnt.ensure((size_t)nb_pad * regions * sizeof(int)));
     MIRX_HIP(ix->cand.ensure((size_t)nb_pad * regions * slots * sizeof(Cand)));
@@ -339,7 +364,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     // ---- tier 1 ---------------------------------------------------------------------
     GemmArgs ga{};
     {
-        int rc = filter_args(ix, nb_pad, bn, sr.bias, &ga);
+        int rc = filter_args(ix, nb_pad, bn, sr.bias, &ga, sr.deep);
         if (rc) return rc;
     }
     const int regions = ga.regions, slots = ga.slots;
@@ -371,6 +396,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
         const int64_t k_eff = (int64_t)k + (exb ? 1 : 0);
         const int64_t rank_k = std::min<int64_t>((4 * k_eff + stride - 1) / stride, ngroups / 2);
         rank_j = (int)std::max<int64_t>(rank_j, rank_k);
+        if (sr.deep) rank_j = deep_sample_rank(k_eff, ngroups, stride);
         MIRX_HIP(ix->groupmax.ensure((size_t)nb_pad * ngroups * sizeof(float)));
         GemmArgs gs = ga;
         gs.n_rows = ms;
@@ -421,7 +447,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     fa.stats = ix->stats_dev;
     {
         StageTimer t(ix, st, MIRX_STAGE_FINALIZE);
-        MIRX_HIP(launch_finalize(fa, st));
+        MIRX_HIP((sr.deep ? launch_finalize_deep : launch_finalize)(fa, st));
     }
     MIRX_HIP(hipMemcpyAsync(ix->fail_count_host, ix->fail_count, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (!ix->pend_ev) MIRX_HIP(hipEventCreateWithFlags(&ix->pend_ev, hipEventDisableTiming));
@@ -457,7 +483,8 @@ int batch_back(mirx_index *ix) {
         const int bn2 = gemm_query_tile(nretry);
         const int64_t nr_pad = round_up(nretry, bn2);
         int regions2 = 0, slots2 = 0;
-        gemm_plan(ix->size, nr_pad, bn2, &regions2, &slots2);
+        const bool deep = ix->pend.rows.deep;
+        (deep ? gemm_plan_deep : gemm_plan)(ix->size, nr_pad, bn2, &regions2, &slots2);
         MIRX_HIP(ix->q16r.ensure((size_t)nr_pad * ix->dimp * sizeof(uint16_t)));
         MIRX_HIP(ix->taur.ensure((size_t)nr_pad * sizeof(float)));
         MIRX_HIP(ix->cnt.ensure((size_t)nr_pad * regions2 * sizeof(int)));
@@ -491,7 +518,7 @@ int batch_back(mirx_index *ix) {
         f2.qmap = ix->retry_list.as<int32_t>();
         {
             StageTimer t(ix, st, MIRX_STAGE_FINALIZE);
-            MIRX_HIP(launch_finalize(f2, st));
+            MIRX_HIP((deep ? launch_finalize_deep : launch_finalize)(f2, st));
         }
         MIRX_HIP(hipMemcpyAsync(ix->fail_count_host, ix->fail_count, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
         MIRX_HIP(hipEventRecord(ix->pend_ev, st));
@@ -1130,9 +1157,25 @@ int mirx_index_search_begin(mirx_index *ix, const float *q, int64_t nq, int k, c
     return rc;
 }
 
-int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
-                             const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
-                             int64_t *out_ids, void *stream) {
+// The plain search of mirx_index_search_deep: the deep route where it applies, else search_impl as mirx_index_search runs it.
+static int search_deep_plain(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude, float *out_val,
+                             double *out_f64, int64_t *out_ids, hipStream_t st) {
+    const int k_eff = k + (exclude ? 1 : 0);
+    const int bn = gemm_query_tile(std::min<int64_t>(std::max<int64_t>(nq, 1), QUERY_BATCH));   // the widest tile of the call's batches
+    if (ix->tiers != MIRX_TIER_AUTO || k_eff <= TIER1_MAX_K || ix->size < deep_min_rows(k_eff, bn))
+        return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st);
+    SearchRows sr;
+    sr.g32 = ix->g32;
+    sr.ids = ix->ids;
+    sr.n = ix->size;
+    sr.tier1 = sr.deep = true;
+    return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st, /*wait_last=*/true, &sr);
+}
+
+// mirx_index_search_masked (deep = false) and the masked form of mirx_index_search_deep: one mask pass, one count, then the route.
+static int search_masked_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                              const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
+                              int64_t *out_ids, void *stream, bool deep) {
     MIRX_ENTER_IDLE(ix, "search_masked");
     MIRX_CHECK(n_allow == ix->size, "search_masked: the mask needs one byte per row of the index (n_allow != size)");
     MIRX_CHECK(allow || n_allow == 0, "search_masked: null mask");
@@ -1146,14 +1189,23 @@ int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, 
     // allowed rows are ever gathered, else any number whose rows fit the limit
     const size_t row_bytes = (size_t)ix->dimp * sizeof(float) + sizeof(int64_t);
     const size_t gather_max = ix->mask_gather_bytes < 0 ? EXACT_WS_BYTES : (size_t)ix->mask_gather_bytes;
-    const int64_t most_rows = tier1_route(ix, TIER1_MIN_ROWS, k, exclude_ids_or_null) ? std::min(ix->size, TIER1_MIN_ROWS - 1) : ix->size;
+    // the deep route is open to the call when its k_eff is past the candidate lists' and the tiers are on auto; it is taken when
+    // the allowed rows reach deep_min_rows, with the same bias (route A of DESIGN 32)
+    const int k_eff = k + (exclude_ids_or_null ? 1 : 0);
+    deep = deep && ix->tiers == MIRX_TIER_AUTO && k_eff > TIER1_MAX_K;
+    const int64_t deep_rows = deep ? deep_min_rows(k_eff, gemm_query_tile(std::min<int64_t>(nq, QUERY_BATCH))) : 0;
+    const int64_t most_rows = deep ? std::min(ix->size, deep_rows - 1)
+                                   : (tier1_route(ix, TIER1_MIN_ROWS, k, exclude_ids_or_null) ? std::min(ix->size, TIER1_MIN_ROWS - 1) : ix->size);
     int64_t n_allowed = 0;
     int rc = mask_prepare(ix, allow, std::min((size_t)most_rows * row_bytes, gather_max), st, &n_allowed, "search_masked");
     if (rc) return rc;
-    if (n_allowed == ix->size)            // nothing masked: the plain search, bit for bit
+    if (n_allowed == ix->size) {          // nothing masked: the plain search, bit for bit
+        if (deep) return search_deep_plain(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
         return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
+    }
     SearchRows sr;
-    sr.tier1 = tier1_route(ix, n_allowed, k, exclude_ids_or_null);
+    sr.tier1 = deep ? n_allowed >= deep_rows : tier1_route(ix, n_allowed, k, exclude_ids_or_null);
+    sr.deep = deep && sr.tier1;
     const size_t gather_bytes = (size_t)n_allowed * row_bytes;
     if (sr.tier1 || (n_allowed > 0 && gather_bytes > gather_max)) {
         // all rows, the masked ones neutralised: tier 1 by the bias, the exact scan by -inf scores and the masked ids
@@ -1174,6 +1226,35 @@ int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, 
     }                                     // else nothing is allowed: n = 0, every slot reads (-1, -inf) and no row is scored
     return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
                        /*wait_last=*/true, &sr);
+}
+
+int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                             const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
+                             int64_t *out_ids, void *stream) {
+    return search_masked_impl(ix, q, nq, k, exclude_ids_or_null, allow, n_allow, out_scores_or_null, out_rank_scores_or_null, out_ids,
+                              stream, /*deep=*/false);
+}
+
+int mirx_index_search_deep(mirx_index *ix, const float *queries, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                           const uint8_t *allow_or_null, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids,
+                           void *stream) {
+    MIRX_CHECK(k >= 1 && k <= MAX_K, "search_deep: k must be in [1, 1024]");
+    MIRX_CHECK(ix, "search_deep: null index");
+    MIRX_CHECK(nq >= 0, "search_deep: nq < 0");
+    MIRX_CHECK(nq == 0 || (queries && out_ids && (out_values_or_null || out_f64_or_null)), "search_deep: null buffer");
+    if (allow_or_null)
+        return search_masked_impl(ix, queries, nq, k, exclude_ids_or_null, allow_or_null, ix->size, out_values_or_null, out_f64_or_null,
+                                  out_ids, stream, /*deep=*/true);
+    MIRX_ENTER_IDLE(ix, "search_deep");
+    return search_deep_plain(ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+int mirx_tier1_max_k(void) { return TIER1_MAX_K; }
+
+int64_t mirx_deep_min_rows(int k_eff, int64_t nq) {
+    if (k_eff < 1 || nq < 1) return -1;
+    return deep_min_rows(k_eff, gemm_query_tile(std::min<int64_t>(nq, QUERY_BATCH)));
 }
 
 int mirx_index_range_search(mirx_index *ix, const float *q, int64_t nq, double lo, double hi, const int64_t *exclude_ids_or_null,

@@ -319,6 +319,9 @@ struct GemmArgs {
 int gemm_query_tile(int64_t nq);                 // query-tile width chosen for nq (64/128/256)
 // Producer regions per query and slots per region of the filter GEMM for this problem.
 void gemm_plan(int64_t n_rows, int64_t nq_pad, int bn, int *regions, int *slots);
+// The deep route's plan: the same regions with about 2 * DEEP_CAP slots per query (at least DEEP_MIN_SLOTS per region).  The
+// launcher accepts either plan's (regions, slots) pair; the kernels read the slots at run time.
+void gemm_plan_deep(int64_t n_rows, int64_t nq_pad, int bn, int *regions, int *slots);
 size_t gemm_spill_bytes();                       // workspace the filter GEMM needs behind GemmArgs::spill
 int gemm_groups_per_tile(int bn);                // group-max groups per 256-row gallery tile
 hipError_t launch_gemm_filter(const GemmArgs &a, int bn, hipStream_t st);
@@ -359,6 +362,9 @@ hipError_t launch_gather_queries(const uint16_t *q16, const float *tau2, const i
 hipError_t launch_select_tau(const float *groupmax, int ngroups, int64_t nq, int64_t nq_pad,
                              int rank_j, float *tau, hipStream_t st);
 hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st);
+// k_finalize_deep.hip: the same contract for the deep route's candidate buffers (gemm_plan_deep): up to DEEP_CAP candidates per
+// query, regions <= DEEP_MAX_REGIONS
+hipError_t launch_finalize_deep(const FinalizeArgs &a, hipStream_t st);
 
 // ---- k_range.hip: range search (mirx_index_range_search): every row with lo < s <= hi, per query, best first -------------------
 constexpr int RANGE_CAP = CAND_CAP + CAND_OVF;   // most candidates the filter route re-scores per query; more -> exact route

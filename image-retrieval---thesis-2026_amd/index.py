@@ -82,6 +82,16 @@ def group_bounds(limit, group_size):
     return limit, group_size
 
 
+def tier1_max_k():
+    """the most k (+1 with excluded ids) FlatIndex.search answers on the filter route; past it search_deep is the faster call"""
+    return int(_lib.load().mirx_tier1_max_k())
+
+
+def deep_min_rows(k_eff, nq):
+    """rows (the index's, or a mask's allowed rows) from which search_deep's filter route answers nq queries at this k_eff"""
+    return int(_lib.load().mirx_deep_min_rows(int(k_eff), int(nq)))
+
+
 def _stream_ptr(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -236,6 +246,32 @@ class FlatIndex:
                                                  ctypes.c_void_p(sc.data_ptr()),
                                                  ctypes.c_void_p(ids.data_ptr()), st)
         _lib.check(rc, "mirx_index_search")
+        return sc, ids
+
+    def search_deep(self, q, k, exclude_ids=None, return_f64=False, allow=None):
+        """search()'s arguments and results, for 64 < k (+1 with exclude_ids) <= 1024 on galleries of at least
+        deep_min_rows(k_eff, nq) rows: the filter GEMM with candidate lists of 4096 rows per query (mirx_index_search_deep)
+        instead of search()'s scan of every row.  The answer is search()'s to the bit; every other call is handed to search()'s
+        own route inside the library, and k above 1024 goes to rank_top as in search().  last_stats() tells which route answered."""
+        if int(k) > _lib.MAX_SEARCH_K:
+            return self.rank_top(q, k, exclude_ids=exclude_ids, return_f64=return_f64, allow=allow)
+        q, ex = self._prep_queries(q, exclude_ids)
+        nq = q.shape[0]
+        am = None if allow is None else self._prep_allow(allow)
+        if am is not None and am.numel() != len(self):
+            raise ValueError(f"allow needs one entry per row of the index ({len(self)}), got {am.numel()}")
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+        scp = ctypes.c_void_p(sc.data_ptr())
+        if am is not None and am.numel() == 0:
+            am = None                                              # an empty index: nothing to mask
+        with torch.cuda.device(self.device):
+            rc = self._lib.mirx_index_search_deep(self._h, ctypes.c_void_p(q.data_ptr()), nq, int(k),
+                                                  ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
+                                                  ctypes.c_void_p(am.data_ptr()) if am is not None else None,
+                                                  None if return_f64 else scp, scp if return_f64 else None,
+                                                  ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
+        _lib.check(rc, "mirx_index_search_deep")
         return sc, ids
 
     def search_begin(self, q, k, exclude_ids=None):

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex, group_bounds, range_bounds
+from .index import FlatIndex, group_bounds, range_bounds, tier1_max_k
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -476,7 +476,7 @@ class Collection:
                                                                output_fields=output_fields)]
         lo = None if rng is None else range_bounds(self.metric_type, rng[0])[0]
         allow = None if expr is None else self._device_mask(expr)
-        find = self._ensure().rank_top if limit > 1024 else self._ensure().search
+        find = self._finder(limit, exclude_ids)
         if lo is None:
             sc, ids = find(q, limit, exclude_ids=exclude_ids, allow=allow)
             ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
@@ -488,6 +488,14 @@ class Collection:
             ids = np.where(s64 > lo, ids, -1)
             sc = (s64 if self.metric_type in ("COSINE", "IP") else -np.sqrt(np.maximum(-s64, 0.0))).astype(np.float32)
         return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
+
+    def _finder(self, limit, exclude_ids):
+        """the index call that answers `limit` hits per query: search up to the filter lists' k, search_deep up to 1024 (the
+        filter GEMM with deep candidate lists where the gallery is large enough), rank_top beyond"""
+        index = self._ensure()
+        if limit > 1024:
+            return index.rank_top
+        return index.search_deep if limit + (0 if exclude_ids is None else 1) > tier1_max_k() else index.search
 
     def _ranked(self, q, limit, exclude_ids=None, expr=None, param=None):
         """The lists of search(q, limit=limit, exclude_ids=.., expr=.., param=..) as tensors on the index's device, for a
@@ -506,7 +514,7 @@ class Collection:
                 dist[qi, :len(hits)] = [h.distance for h in hits]
             return torch.from_numpy(ids).to(index.device), torch.from_numpy(dist).to(index.device)
         allow = None if expr is None else self._device_mask(expr)
-        find = index.rank_top if limit > 1024 else index.search
+        find = self._finder(limit, exclude_ids)
         sc, ids = find(q, limit, exclude_ids=exclude_ids, allow=allow)
         return ids, (sc if self.metric_type in ("COSINE", "IP") else -sc)
 

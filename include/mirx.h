@@ -185,7 +185,7 @@ int mirx_index_search_f64(mirx_index *ix, const float *q, int64_t nq, int k,
  *       up to this call has finished; stats / timings refer to this search.
  * Between the two calls the index is busy and the query / output buffers must stay valid: the pending search holds pointers
  * into the index's workspace and rows, so every call that uses the workspace or moves rows -- mirx_index_search, _search_f64,
- * _search_begin, _search_masked, _range_search, _rank_all, _rank_top, _rank_top_masked, _group_fill, _add, _reserve,
+ * _search_begin, _search_masked, _search_deep, _range_search, _rank_all, _rank_top, _rank_top_masked, _group_fill, _add, _reserve,
  * _remove_ids -- returns MIRX_ESTATE and changes nothing.  mirx_index_search_end, _range_fetch, _range_last_stats, _last_stats,
  * _last_timings, _get_rows, _get_ids, _size, _dim and _set_option stay callable.
  * mirx_index_search == begin + end.  (No reference counterpart: MilvusRetriever.search is a blocking RPC,
@@ -224,6 +224,36 @@ int mirx_index_search_end(mirx_index *ix);
 int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                              const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,
                              double *out_rank_scores_or_null, int64_t *out_ids, void *stream);
+
+/*
+ * The search for 64 < k (+1 with exclude ids) <= 1024 on the filter GEMM ("deep route"): Milvus' collection.search(limit=100),
+ * recall@100-style evaluation, the per-request lists of a hybrid search.  mirx_index_search answers such a k by scoring every row.
+ *   queries, nq, k, exclude_ids, stream    as for mirx_index_search; 1 <= k <= 1024, else MIRX_EINVAL
+ *   allow            NULL, or one byte per row of the index (host or device, non-zero = eligible): mirx_index_search_masked's mask
+ *   out_values / out_f64 / out_ids          fp32 reported values and / or fp64 ranking scores (either may be NULL, not both), ids
+ * Result: exactly what mirx_index_search / _search_f64 / _search_masked return for the same arguments -- ids, fp64 scores and
+ * fp32 values bit for bit, (score desc, id asc), the excluded id skipped, (-1, -inf) in the slots past the eligible rows.
+ * A null index, null queries or null ids: MIRX_EINVAL before any device call.  Between mirx_index_search_begin and
+ * mirx_index_search_end: MIRX_ESTATE.
+ * Route, decided on the host: the deep route answers when the tiers are on auto, k_eff = k (+1 with exclude ids) > 64 and the
+ * rows that can rank (the index's, or the mask's allowed rows) number at least mirx_deep_min_rows(k_eff, nq) =
+ * max(32768, (2 k_eff + 512) * 512 / g), g = 8 / 4 / 2 threshold groups per gallery tile at up to 64 / 128 / more queries: below
+ * that the sampled threshold cannot resolve the 2 k_eff + 512 candidates per query the route aims at.  Every other call is handed
+ * to mirx_index_search / _search_masked unchanged (result, stats and stage timings are theirs).
+ * The deep route is the tier-1 sequence with its own capacities: candidate regions of about 8192 slots per query, a per-query
+ * finalize (k_finalize_deep.hip) that sorts up to 4096 candidates, applies the same completeness guard (tau < kth - 2 eps),
+ * re-scores the guard band in fp64 and writes k results; guard-rejected queries are filtered once more with the threshold the
+ * guard derived, and what still fails -- more than 4096 candidates, fewer than k_eff -- is scanned exactly.  No result comes
+ * from an approximate score.  mirx_index_last_stats: tier1_answered = queries the deep filter answered, exact_answered = the
+ * rest; candidates / reranked / overflowed / incomplete as for mirx_index_search.  Workspace at 8192 queries: 512 MiB of
+ * candidate regions (64 MiB for mirx_index_search), allocated on the first deep call and kept.
+ * mirx_tier1_max_k: the 64 above.  mirx_deep_min_rows: the bound (-1 for k_eff < 1 or nq < 1); neither touches a device.
+ */
+int mirx_index_search_deep(mirx_index *ix, const float *queries, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                           const uint8_t *allow_or_null, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids,
+                           void *stream);
+int mirx_tier1_max_k(void);
+int64_t mirx_deep_min_rows(int k_eff, int64_t nq);
 
 /* Counters of the most recent range search on an index. */
 typedef struct mirx_range_stats {
