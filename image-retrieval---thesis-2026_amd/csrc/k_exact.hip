@@ -16,8 +16,6 @@ namespace mirx {
 
 namespace {
 
-constexpr int64_t ID_LAST = INT64_MAX;   // sentinel id: sorts after every real id
-
 // ---- fp64 score tile ----------------------------------------------------------------------
 // Workgroup = 4 waves; QT queries live in registers as doubles; each wave walks 64 gallery
 // rows, one coalesced 16-B-per-lane load per chunk, and keeps row i's score in lane i so the

@@ -1,12 +1,14 @@
-// k_finalize.hip -- tier-1 tail: threshold selection from sampled group maxima, and the
-// per-query finalize (sort candidates, completeness guard, fp64 re-rank, final top-k).
+// k_finalize.hip -- the filter routes' tail: threshold selection from sampled group maxima, and the per-query finalize (gather
+// and sort the candidates, completeness guard, fp64 re-rank, final top-k), one kernel source at two capacities: CAND_CAP
+// candidates on 256 threads (mirx_index_search) and DEEP_CAP on 1024 (mirx_index_search_deep).
 //
-// Why the result is exact (DESIGN.md "Exactness"): the GEMM stores EVERY row whose
-// approximate score s~ exceeds tau.  With |s~ - s| <= eps for every row, the true top-k_eff
-// rows all have s~ >= kth(s~) - 2*eps, so if tau < kth(s~) - 2*eps and the list did not
-// overflow, re-scoring exactly the rows with s~ >= kth(s~) - 2*eps in fp64 and sorting them
-// (score desc, id asc) gives the oracle's answer.  Queries failing the guard go to the exact
-// scan; nothing is ever answered approximately.
+// Why the result is exact (DESIGN.md "Exactness"), whatever the capacity: the GEMM stores EVERY row whose approximate score s~
+// exceeds tau.  With |s~ - s| <= eps for every row (filter_eps), the true top-k_eff rows all have s~ >= kth(s~) - 2 eps.  So if
+// (a) the list did not overflow -- at most CAP candidates, no region's surplus lost to a full overflow list --, (b) it holds at
+// least k_eff rows and (c) tau < lo = kth(s~) - 2 eps (rounded down), then re-scoring exactly the rows with s~ >= lo in fp64, in
+// the oracle's summation order (lane_tree_score), and sorting them (score desc, id asc) gives the oracle's answer.  A query that
+// fails (c) alone is filtered once more with tau2 just below lo (retry list); every other failure, and a failure of the second
+// pass, goes to the exact scan (fail list).  Nothing is answered from approximate scores.
 #include "mirx_device.h"
 #include "mirx_kernels.h"
 
@@ -15,8 +17,6 @@
 namespace mirx {
 
 namespace {
-
-constexpr int64_t ID_LAST = INT64_MAX;
 
 // tau[q] = rank_j-th largest sampled group maximum of query q; +inf for padding queries.
 __global__ __launch_bounds__(256) void k_select_tau(const float *__restrict__ groupmax, int ngroups,
@@ -37,48 +37,35 @@ __global__ __launch_bounds__(256) void k_select_tau(const float *__restrict__ gr
     }
 }
 
-template <int METRIC>
-__global__ __launch_bounds__(256) void k_finalize(FinalizeArgs A) {
-    __shared__ unsigned long long keys[CAND_CAP];
-    __shared__ Hit hits[CAND_CAP];
+// One workgroup of THREADS threads per query.  Dynamic LDS: CAP keys (8 B) and CAP hits (16 B) -- 24 KiB at CAND_CAP, six
+// workgroups per CU; 96 KiB at DEEP_CAP, one workgroup of 16 waves per CU (160 KiB).  The hits' storage doubles as the region
+// offsets during the gather.  At run = CAP tied rows every candidate is re-scored, so the hits cannot be bounded below CAP.
+// Counters are integer atomics; no floating-point atomic is used.
+template <int METRIC, int CAP, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_finalize(FinalizeArgs A) {
+    static_assert((DEEP_MAX_REGIONS + 1) * sizeof(int) <= CAP * sizeof(Hit), "the region offsets live in the hits' storage");
+    constexpr int WAVES = THREADS / WAVE;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);                 // [CAP]
+    Hit *hits = reinterpret_cast<Hit *>(smem + (size_t)CAP * sizeof(unsigned long long));    // [CAP]
     __shared__ int sh_ok, sh_m;
     __shared__ float sh_lo;
     const int slot_q = blockIdx.x;                                  // index into tau / candidate buffers
     const int qi = A.qmap ? A.qmap[slot_q] : slot_q;                // original query number
     const int wave = threadIdx.x >> 6, lane = lane_id();
-    // gather the producer regions (+ the shared overflow list) of this query into `keys`
-    __shared__ int sh_cnt, sh_raw, sh_ovf;
-    if (threadIdx.x == 0) { sh_cnt = 0; sh_raw = 0; sh_ovf = 0; }
-    for (int i = threadIdx.x; i < CAND_CAP; i += 256) keys[i] = 0ull;
-    __syncthreads();
-    auto push = [&](const Cand cd) {
-        const int p = atomicAdd(&sh_cnt, 1);
-        if (p < CAND_CAP)
-            keys[p] = ((unsigned long long)f32_orderable(cd.s) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)cd.row);
-    };
-    for (int rg = threadIdx.x; rg < A.regions; rg += 256) {
-        const int cr = A.region_cnt[(int64_t)slot_q * A.regions + rg];
-        if (cr > 0) {
-            atomicAdd(&sh_raw, cr);
-            const int take = cr < A.slots ? cr : A.slots;
-            const Cand *src = A.cand + ((int64_t)slot_q * A.regions + rg) * A.slots;
-            for (int i = 0; i < take; ++i) push(src[i]);
-        }
-    }
-    {
-        const int oc = A.ovf_cnt[slot_q];
-        if (oc > CAND_OVF && threadIdx.x == 0) sh_ovf = 1;         // overflow list itself overflowed
-        const int take = oc < CAND_OVF ? oc : CAND_OVF;
-        for (int i = threadIdx.x; i < take; i += 256) push(A.ovf[(int64_t)slot_q * CAND_OVF + i]);
-    }
-    __syncthreads();
-    const int c_raw = sh_raw;
-    const bool overflow = sh_cnt > CAND_CAP || sh_ovf != 0;
-    const int c = sh_cnt > CAND_CAP ? CAND_CAP : sh_cnt;
+
+    // ---- gather and sort.  Where a candidate lands does not matter: the keys are distinct and sorted next.
+    const Gathered got = gather_cands<THREADS>(A.lists, slot_q, CAP, reinterpret_cast<int *>(hits),
+                                               [&](int p, const Cand cd) { keys[p] = cand_key(cd); });
+    const bool overflow = got.lost;
+    const int c = overflow ? 0 : got.taken;
+    const int m2 = pow2_ceil(c > 1 ? c : 1);
+    for (int i = c + threadIdx.x; i < m2; i += THREADS) keys[i] = 0ull;
     const int64_t ex = A.exclude ? A.exclude[qi] : -1;
     const int k_eff = A.k + (ex >= 0 ? 1 : 0);
-    const int m2 = pow2_ceil(c > 1 ? c : 1);
-    bitonic_lds(keys, m2, [](unsigned long long x, unsigned long long y) { return x > y; });
+    if (!overflow) bitonic_lds(keys, m2, [](unsigned long long x, unsigned long long y) { return x > y; });
+
+    // ---- guard
     if (threadIdx.x == 0) {
         int ok = (!overflow && c >= k_eff) ? 1 : 0, retry = 0;
         float lo = 0.0f;
@@ -117,16 +104,18 @@ __global__ __launch_bounds__(256) void k_finalize(FinalizeArgs A) {
     if (!sh_ok) return;
     const float lo = sh_lo;
     {
-        int mine = 0;
-        for (int i = threadIdx.x; i < c; i += 256)
-            mine += f32_from_orderable((uint32_t)(keys[i] >> 32)) >= lo ? 1 : 0;
-        if (mine) atomicAdd(&sh_m, mine);
+        int n = 0;
+        for (int i = threadIdx.x; i < c; i += THREADS) n += cand_key_score(keys[i]) >= lo ? 1 : 0;
+        n = wave_isum(n);
+        if (lane == 0 && n) atomicAdd(&sh_m, n);
     }
     __syncthreads();
     const int m = sh_m;                                   // sorted, so these are keys[0..m)
+
+    // ---- re-score in fp64, one row per wave and trip (the region offsets are dead: the hits take their storage)
     const float *qrow = A.q32p + (int64_t)qi * A.dimp;
-    for (int i = wave; i < m; i += 4) {
-        const uint32_t row = 0xFFFFFFFFu - (uint32_t)(keys[i] & 0xFFFFFFFFull);
+    for (int i = wave; i < m; i += WAVES) {
+        const uint32_t row = cand_key_row(keys[i]);
         const double s = lane_tree_score<METRIC>(qrow, A.g32 + (int64_t)row * A.dimp, A.dimp);
         if (lane == 0) {
             const int64_t id = A.ids[row];
@@ -137,26 +126,22 @@ __global__ __launch_bounds__(256) void k_finalize(FinalizeArgs A) {
         }
     }
     const int mp = pow2_ceil(m > 1 ? m : 1);
-    for (int i = m + threadIdx.x; i < mp; i += 256) { hits[i].s = -INFINITY; hits[i].id = ID_LAST; }
+    for (int i = m + threadIdx.x; i < mp; i += THREADS) { hits[i].s = -INFINITY; hits[i].id = ID_LAST; }
     bitonic_lds(hits, mp, [](const Hit &x, const Hit &y) { return hit_before(x.s, x.id, y.s, y.id); });
-    for (int r = threadIdx.x; r < A.k; r += 256) {
+    for (int r = threadIdx.x; r < A.k; r += THREADS) {
         Hit h;
         h.s = -INFINITY;
         h.id = ID_LAST;
         if (r < mp) h = hits[r];
-        const bool empty = h.id == ID_LAST;
+        const bool empty = h.id == ID_LAST;                // an empty slot's score is -inf, which reported_value keeps
         const int64_t o = (int64_t)qi * A.k + r;
         if (A.out_f64) A.out_f64[o] = empty ? -INFINITY : h.s;
         A.out_ids[o] = empty ? -1 : h.id;
-        if (A.out_val) {
-            float v = -INFINITY;
-            if (!empty) v = METRIC == 0 ? (float)h.s : (float)(-sqrt(fmax(-h.s, 0.0)));
-            A.out_val[o] = v;
-        }
+        if (A.out_val) A.out_val[o] = reported_value(h.s, A.metric);
     }
     if (threadIdx.x == 0) {
         atomicAdd((unsigned long long *)&A.stats->tier1_answered, 1ull);
-        atomicAdd((unsigned long long *)&A.stats->candidates, (unsigned long long)c_raw);
+        atomicAdd((unsigned long long *)&A.stats->candidates, (unsigned long long)got.raw);
         atomicAdd((unsigned long long *)&A.stats->reranked, (unsigned long long)m);
     }
 }
@@ -177,6 +162,18 @@ __global__ __launch_bounds__(256) void k_gather_queries(const uint16_t *__restri
         for (int c = threadIdx.x; c < chunks; c += 256) dst[c] = make_uint4(0, 0, 0, 0);
         if (threadIdx.x == 0) taur[i] = INFINITY;
     }
+}
+
+template <int METRIC, int CAP, int THREADS>
+hipError_t launch_finalize_as(const FinalizeArgs &a, hipStream_t st) {
+    constexpr size_t LDS_BYTES = (size_t)CAP * (sizeof(unsigned long long) + sizeof(Hit));
+    if constexpr (LDS_BYTES > 64 * 1024) {
+        static std::atomic<unsigned long long> attr_devs{0};
+        const hipError_t e = set_dynamic_lds(k_finalize<METRIC, CAP, THREADS>, LDS_BYTES, &attr_devs);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((k_finalize<METRIC, CAP, THREADS>), dim3(a.nq), dim3(THREADS), LDS_BYTES, st, a);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -203,13 +200,13 @@ hipError_t launch_select_tau(const float *groupmax, int ngroups, int64_t nq, int
     return hipGetLastError();
 }
 
-hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st) {
+hipError_t launch_finalize(const FinalizeArgs &a, bool deep, hipStream_t st) {
     if (a.nq <= 0) return hipSuccess;
-    if (a.metric == MIRX_METRIC_IP)
-        hipLaunchKernelGGL(k_finalize<0>, dim3(a.nq), dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL(k_finalize<1>, dim3(a.nq), dim3(256), 0, st, a);
-    return hipGetLastError();
+    if (a.lists.regions < 1 || a.lists.regions > DEEP_MAX_REGIONS || a.lists.slots < 1 || a.k < 1 || a.k > MAX_K)
+        return hipErrorInvalidValue;
+    const bool ip = a.metric == MIRX_METRIC_IP;
+    if (deep) return ip ? launch_finalize_as<0, DEEP_CAP, 1024>(a, st) : launch_finalize_as<1, DEEP_CAP, 1024>(a, st);
+    return ip ? launch_finalize_as<0, CAND_CAP, 256>(a, st) : launch_finalize_as<1, CAND_CAP, 256>(a, st);
 }
 
 }  // namespace mirx

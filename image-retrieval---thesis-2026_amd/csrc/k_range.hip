@@ -22,7 +22,6 @@ namespace mirx {
 
 namespace {
 
-constexpr int64_t ID_LAST = INT64_MAX;
 constexpr int RANGE_SORT = 2048;                 // power of two >= RANGE_CAP
 
 // One wave per query.  The GEMM scores s' = q.g (metric 0) or q.g - ||g||^2 / 2 (metric 1), for which s = s' resp.
@@ -59,33 +58,15 @@ template <int METRIC>
 __global__ __launch_bounds__(256) void k_range_finalize(RangeFinalizeArgs A) {
     __shared__ int32_t rows[RANGE_CAP];
     __shared__ Hit hits[RANGE_SORT];
-    __shared__ int sh_cnt, sh_raw, sh_ovf, sh_hits;
+    static_assert((DEEP_MAX_REGIONS + 1) * sizeof(int) <= sizeof(hits), "the region offsets live in the hits' storage");
+    __shared__ int sh_hits;
     const int qi = blockIdx.x;
     const int wave = threadIdx.x >> 6, lane = lane_id();
-    if (threadIdx.x == 0) { sh_cnt = 0; sh_raw = 0; sh_ovf = 0; sh_hits = 0; }
-    __syncthreads();
-    // gather the producer regions (+ the shared overflow list) of this query, as k_finalize does
-    auto push = [&](const Cand cd) {
-        const int p = atomicAdd(&sh_cnt, 1);
-        if (p < RANGE_CAP) rows[p] = cd.row;
-    };
-    for (int rg = threadIdx.x; rg < A.regions; rg += 256) {
-        const int cr = A.region_cnt[(int64_t)qi * A.regions + rg];
-        if (cr > 0) {
-            atomicAdd(&sh_raw, cr);
-            const int take = cr < A.slots ? cr : A.slots;
-            const Cand *src = A.cand + ((int64_t)qi * A.regions + rg) * A.slots;
-            for (int i = 0; i < take; ++i) push(src[i]);
-        }
-    }
-    {
-        const int oc = A.ovf_cnt[qi];
-        if (oc > CAND_OVF && threadIdx.x == 0) sh_ovf = 1;         // overflow list itself overflowed
-        const int take = oc < CAND_OVF ? oc : CAND_OVF;
-        for (int i = threadIdx.x; i < take; i += 256) push(A.ovf[(int64_t)qi * CAND_OVF + i]);
-    }
-    __syncthreads();
-    if (sh_cnt > RANGE_CAP || sh_ovf != 0) {                       // some candidate was lost: the exact route answers
+    if (threadIdx.x == 0) sh_hits = 0;
+    // the query's candidate rows; where a row lands does not matter, the hits are sorted by (score, id)
+    const Gathered got = gather_cands<256>(A.lists, qi, RANGE_CAP, reinterpret_cast<int *>(hits),
+                                           [&](int p, const Cand cd) { rows[p] = cd.row; });
+    if (got.lost) {                                                // some candidate was lost: the exact route answers
         if (threadIdx.x == 0) {
             const int p = atomicAdd(A.fail_count, 1);
             A.fail_list[p] = qi;
@@ -93,7 +74,7 @@ __global__ __launch_bounds__(256) void k_range_finalize(RangeFinalizeArgs A) {
         }
         return;
     }
-    const int c = sh_cnt;
+    const int c = got.taken;
     const bool has_ex = A.exclude != nullptr;
     const int64_t ex = has_ex ? A.exclude[qi] : 0;
     const float *qrow = A.q32p + (int64_t)qi * A.dimp;
@@ -125,7 +106,7 @@ __global__ __launch_bounds__(256) void k_range_finalize(RangeFinalizeArgs A) {
     if (threadIdx.x == 0) {
         A.count[qi] = m;
         atomicAdd(A.stats + 0, 1ull);
-        atomicAdd(A.stats + 1, (unsigned long long)sh_raw);
+        atomicAdd(A.stats + 1, (unsigned long long)got.raw);
     }
 }
 
@@ -256,6 +237,7 @@ hipError_t launch_range_tau(const float *q32p, const float *qnorm, const unsigne
 
 hipError_t launch_range_finalize(const RangeFinalizeArgs &a, hipStream_t st) {
     if (a.nq <= 0) return hipSuccess;
+    if (a.lists.regions < 1 || a.lists.regions > DEEP_MAX_REGIONS || a.lists.slots < 1) return hipErrorInvalidValue;
     if (a.metric == MIRX_METRIC_IP)
         hipLaunchKernelGGL(k_range_finalize<0>, dim3(a.nq), dim3(256), 0, st, a);
     else

@@ -48,9 +48,9 @@ constexpr int CAND_CAP = 1024;       // per-query candidate capacity of the thre
 constexpr int CAND_OVF = 256;        // per-query shared overflow list (global atomics, rare)
 constexpr int MAX_K = 1024;
 // The deep route (mirx_index_search_deep): the filter sequence for k_eff past TIER1_MAX_K, with its own capacities.
-constexpr int DEEP_CAP = 4096;          // per-query candidate capacity of k_finalize_deep (regions and overflow list together)
+constexpr int DEEP_CAP = 4096;          // per-query candidate capacity of k_finalize on the deep route (regions and overflow list together)
 constexpr int DEEP_MIN_SLOTS = 32;      // fewest slots of a deep candidate region: a wave row's rows of one gallery tile at the 64-query tile
-constexpr int DEEP_MAX_REGIONS = 2048;  // most producer regions per query the deep finalize scans (256 phases x 8 wave rows)
+constexpr int DEEP_MAX_REGIONS = 2048;  // most producer regions per query gather_cands scans, on every route (256 phases x 8 wave rows)
 constexpr int DEEP_TARGET_MUL = 2;      // the sampled threshold aims at DEEP_TARGET_MUL * k_eff + DEEP_TARGET_ADD candidates per query,
 constexpr int DEEP_TARGET_ADD = 512;    //   and the sample resolves that many only from
 constexpr int DEEP_GROUP_ROWS = 512;    //   deep_min_rows = target * DEEP_GROUP_ROWS / (groups per 256-row tile) gallery rows on

@@ -3,6 +3,7 @@
 // Device code only: every k_*.hip includes this header, host-only translation units include mirx_common.h.
 #pragma once
 #include "mirx_common.h"
+#include "mirx_kernels.h"      // CandLists, which gather_cands reads
 
 namespace mirx {
 
@@ -126,13 +127,101 @@ __device__ inline void bitonic_lds(T *a, int m, Before before) {
     __syncthreads();
 }
 
-// An unsigned image of an fp32 value that ascends with the value (the candidate sorts of k_finalize.hip / k_finalize_deep.hip).
+// An unsigned image of an fp32 value that ascends with the value (the candidate sort of k_finalize.hip).
 __device__ inline uint32_t f32_orderable(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ inline float f32_from_orderable(uint32_t e) {
     return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e);
+}
+
+// ---- the filter GEMM's candidate lists (CandLists, mirx_kernels.h) as their readers see them ---------------------------
+constexpr int64_t ID_LAST = INT64_MAX;   // sentinel id of an empty Hit: sorts after every real id
+
+// A candidate as one sortable word: the orderable s~ above the complemented row, so that descending keys rank the higher s~
+// first and, among equal s~, the lower row.  One key per row: the keys of a query are distinct.
+__device__ inline unsigned long long cand_key(const Cand cd) {
+    return ((unsigned long long)f32_orderable(cd.s) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)cd.row);
+}
+__device__ inline float cand_key_score(unsigned long long key) { return f32_from_orderable((uint32_t)(key >> 32)); }
+__device__ inline uint32_t cand_key_row(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull); }
+
+struct Gathered {
+    int raw;      // rows that passed the filter, counted by the regions (what the stats call candidates)
+    int taken;    // entries the lists hold for the query: every region's min(count, slots), then the overflow list's
+    bool lost;    // the overflow list overflowed, or `taken` exceeds the caller's capacity: nothing was put
+};
+
+// The candidates of query slot `slot_q`, by a workgroup of THREADS threads: put(p, cand) for every p in [0, taken), the regions'
+// entries in region order, then the overflow list's.  Deterministic: the regions' takes are scanned (thread t owns the regions
+// [t * per, (t + 1) * per)), then every thread copies flattened positions, finding a position's region by a binary search of
+// the offsets.  roff = LDS scratch of L.regions + 1 <= DEEP_MAX_REGIONS + 1 ints, free again on return.  Ends behind a barrier.
+template <int THREADS, typename Put>
+__device__ inline Gathered gather_cands(const CandLists &L, int slot_q, int cap, int *roff, Put put) {
+    constexpr int WAVES = THREADS / WAVE;
+    __shared__ int sh_wsum[WAVES], sh_wraw[WAVES];
+    const int wave = threadIdx.x >> 6, lane = lane_id();
+    const int per = (L.regions + THREADS - 1) / THREADS;
+    const int *rcnt = L.region_cnt + (int64_t)slot_q * L.regions;
+    const int oc = L.ovf_cnt[slot_q];                               // read beside the region counts, not behind a barrier
+    int mine = 0, raw = 0;
+    for (int j = 0; j < per; ++j) {
+        const int rg = threadIdx.x * per + j;
+        if (rg < L.regions) {
+            const int cr = rcnt[rg];
+            raw += cr;
+            mine += cr < L.slots ? cr : L.slots;
+        }
+    }
+    int incl = mine;                                                // inclusive scan inside the wave
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+        const int v = __shfl_up(incl, off, WAVE);
+        if (lane >= off) incl += v;
+    }
+    raw = wave_isum(raw);
+    if (lane == WAVE - 1) sh_wsum[wave] = incl;
+    if (lane == 0) sh_wraw[wave] = raw;
+    __syncthreads();
+    int base = 0, c_reg = 0;
+    Gathered g;
+    g.raw = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        if (w < wave) base += sh_wsum[w];
+        c_reg += sh_wsum[w];
+        g.raw += sh_wraw[w];
+    }
+    int at = base + incl - mine;                                    // exclusive offset of this thread's first region
+    for (int j = 0; j < per; ++j) {
+        const int rg = threadIdx.x * per + j;
+        if (rg < L.regions) {
+            roff[rg] = at;
+            const int cr = rcnt[rg];
+            at += cr < L.slots ? cr : L.slots;
+        }
+    }
+    if (threadIdx.x == 0) roff[L.regions] = c_reg;
+    const int otake = oc < CAND_OVF ? oc : CAND_OVF;
+    // (a full overflow list has lost rows; the candidates of the regions and of the list share the one capacity)
+    g.taken = c_reg + otake;
+    g.lost = oc > CAND_OVF || g.taken > cap;
+    __syncthreads();
+    if (!g.lost) {
+        const Cand *qcand = L.cand + (int64_t)slot_q * L.regions * L.slots;
+        for (int i = threadIdx.x; i < c_reg; i += THREADS) {
+            int lo_r = 0, hi_r = L.regions;                         // the last region with roff[rg] <= i (empty regions share offsets)
+            while (hi_r - lo_r > 1) {
+                const int mid = (lo_r + hi_r) >> 1;
+                if (roff[mid] <= i) lo_r = mid; else hi_r = mid;
+            }
+            put(i, qcand[(int64_t)lo_r * L.slots + (i - roff[lo_r])]);
+        }
+        for (int i = threadIdx.x; i < otake; i += THREADS) put(c_reg + i, L.ovf[(int64_t)slot_q * CAND_OVF + i]);
+    }
+    __syncthreads();
+    return g;
 }
 
 // fp32 -> bf16, round to nearest even (finite inputs).

@@ -8,7 +8,7 @@
 // The only host<->device synchronisation is one read of the rejected-query count.
 // A masked search (mirx_index_search_masked) runs the same sequence over a SearchRows that stands for the allowed rows.
 // The deep search (mirx_index_search_deep) runs it for k_eff past TIER1_MAX_K with SearchRows::deep set: gemm_plan_deep's candidate
-// regions, its own threshold rank and k_finalize_deep; where that route does not apply the call is handed to the two above.
+// regions, its own threshold rank and k_finalize at DEEP_CAP; where that route does not apply the call is handed to the two above.
 // A range search (mirx_index_range_search) runs prep -> threshold from the radius -> filter GEMM -> its own finalize, the radix
 // ranking for what that cannot answer, and a CSR assembly (k_range.hip).
 // The radix ranking (radix_plan / radix_sort_batch) serves mirx_index_rank_all / _rank_top / _rank_top_masked and the range
@@ -367,7 +367,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
         int rc = filter_args(ix, nb_pad, bn, sr.bias, &ga, sr.deep);
         if (rc) return rc;
     }
-    const int regions = ga.regions, slots = ga.slots;
+    const int regions = ga.regions;
     MIRX_HIP(ix->retry_list.ensure((size_t)nb_pad * sizeof(int32_t)));
     MIRX_HIP(ix->tau2.ensure((size_t)nb_pad * sizeof(float)));
     if (ix->force_tau_bits != 0x7fc00000u) {
@@ -424,12 +424,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     fa.ids = ix->ids;
     fa.gnorm_max_bits = ix->gnorm_max_bits;
     fa.tau = ix->tau.as<float>();
-    fa.regions = regions;
-    fa.slots = slots;
-    fa.region_cnt = ix->cnt.as<int>();
-    fa.cand = ix->cand.as<Cand>();
-    fa.ovf_cnt = ix->ovf_cnt.as<int>();
-    fa.ovf = ix->ovf.as<Cand>();
+    fa.lists = ga.lists();
     fa.exclude = exb;
     fa.n_rows = ix->size;
     fa.dimp = ix->dimp;
@@ -447,7 +442,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     fa.stats = ix->stats_dev;
     {
         StageTimer t(ix, st, MIRX_STAGE_FINALIZE);
-        MIRX_HIP((sr.deep ? launch_finalize_deep : launch_finalize)(fa, st));
+        MIRX_HIP(launch_finalize(fa, sr.deep, st));
     }
     MIRX_HIP(hipMemcpyAsync(ix->fail_count_host, ix->fail_count, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
     if (!ix->pend_ev) MIRX_HIP(hipEventCreateWithFlags(&ix->pend_ev, hipEventDisableTiming));
@@ -508,17 +503,14 @@ int batch_back(mirx_index *ix) {
         }
         FinalizeArgs f2 = fa;
         f2.tau = ix->taur.as<float>();
-        f2.regions = regions2;
-        f2.slots = slots2;
-        f2.region_cnt = ix->cnt.as<int>();
-        f2.cand = ix->cand.as<Cand>();
+        f2.lists = g2.lists();
         f2.nq = nretry;
         f2.retry_list = nullptr;          // no third chance: what fails now goes to the exact scan
         f2.tau2 = nullptr;
         f2.qmap = ix->retry_list.as<int32_t>();
         {
             StageTimer t(ix, st, MIRX_STAGE_FINALIZE);
-            MIRX_HIP((deep ? launch_finalize_deep : launch_finalize)(f2, st));
+            MIRX_HIP(launch_finalize(f2, deep, st));
         }
         MIRX_HIP(hipMemcpyAsync(ix->fail_count_host, ix->fail_count, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
         MIRX_HIP(hipEventRecord(ix->pend_ev, st));
@@ -832,7 +824,7 @@ int range_batch(mirx_index *ix, RangeCall &rc, const float *qb, int64_t nb, bool
             int r = filter_args(ix, nb_pad, bn, nullptr, &ga);
             if (r) return r;
         }
-        const int regions = ga.regions, slots = ga.slots;
+        const int regions = ga.regions;
         if (ix->rstage.ensure((size_t)nb * RANGE_CAP * sizeof(Hit)) != hipSuccess) {
             (void)hipGetLastError();
             return fail(MIRX_ENOMEM, "range_search: the staging rows (20 KiB per query of a batch) do not fit the device");
@@ -849,12 +841,7 @@ int range_batch(mirx_index *ix, RangeCall &rc, const float *qb, int64_t nb, bool
         fa.q32p = ix->q32p.as<float>();
         fa.g32 = ix->g32;
         fa.ids = ix->ids;
-        fa.regions = regions;
-        fa.slots = slots;
-        fa.region_cnt = ix->cnt.as<int>();
-        fa.cand = ix->cand.as<Cand>();
-        fa.ovf_cnt = ix->ovf_cnt.as<int>();
-        fa.ovf = ix->ovf.as<Cand>();
+        fa.lists = ga.lists();
         fa.exclude = rc.exclude;
         fa.allow = rc.allow;
         fa.n_rows = ix->size;

@@ -224,9 +224,6 @@ hipError_t launch_conv3x3_wino_s3(const float *x, const uint16_t *u3, int64_t n,
 hipError_t launch_conv3x3_d3(const float *x, const uint16_t *w3, int64_t n, int side, float *out, int64_t out_bs,
                              hipStream_t st);
 
-// ---- k_conv3x3_d2h.hip: the direct implicit GEMM on two fp16 terms per operand; ranges travel in range slots ------
-// w2 = [8 stages][9 taps][2 terms][32 oc][16 c] fp16 (scaled per output channel), oscale = [32] fp32
-
 // ---- k_dense_fused.hip: a whole dense layer of the 14 x 14 / 7 x 7 maps, bottleneck resident in LDS --------------------
 hipError_t launch_dense_fused(float *buf, int64_t bs, int cin, const float *scale, const float *shift, const uint16_t *w2,
                               const float *oscale, const float *bias, const uint16_t *w3, const float *c3osc, int64_t n,
@@ -294,6 +291,17 @@ struct RankMetricsArgs {
 hipError_t launch_rank_metrics(const RankMetricsArgs &a, int rel_kind, int ap_kind, hipStream_t st);
 
 // ---- k_gemm.hip -------------------------------------------------------------------------
+// The per-query candidate lists the filter GEMM fills and the finalize kernels (k_finalize.hip, k_range.hip) read through
+// gather_cands (mirx_device.h).  The readers' argument structs embed it and take it from GemmArgs::lists().
+struct CandLists {
+    int regions, slots;    // producer regions per query (<= DEEP_MAX_REGIONS) and slots per region (gemm_plan / gemm_plan_deep)
+    const int *region_cnt; // [nq_pad, regions]  rows that passed, per region
+    const Cand *cand;      // [nq_pad, regions, slots]
+    const int *ovf_cnt;    // [nq_pad]
+    const Cand *ovf;       // [nq_pad, CAND_OVF]
+};
+// The GEMM keeps the six fields as its own members, where they have always been: embedding CandLists moved them in the kernel
+// arguments, k_gemm16 was compiled to other registers and its filter pass measured 1.2 % slower (profiles/r31).
 struct GemmArgs {
     const uint16_t *g16;   // gallery bf16 [rows, dimp]
     const uint16_t *q16;   // queries bf16 [nq_pad, dimp]
@@ -302,7 +310,7 @@ struct GemmArgs {
     int64_t row_stride;    // gallery row step between consecutive tile rows (1 = dense)
     int64_t nq_pad;        // multiple of the query tile
     int dimp;
-    // filter mode: every (query, producer wave) owns a private region of CAND_SLOTS entries, so
+    // filter mode: every (query, producer wave) owns a private region of `slots` entries, so
     // the epilogue appends with plain stores; rows beyond a region go to a shared overflow list
     const float *tau;      // [nq_pad]
     int regions, slots;    // producer regions per query and slots per region (from gemm_plan)
@@ -315,6 +323,7 @@ struct GemmArgs {
     // group-max mode
     float *groupmax;       // [nq_pad, ngroups]
     int ngroups;
+    CandLists lists() const { return CandLists{regions, slots, region_cnt, cand, ovf_cnt, ovf}; }
 };
 int gemm_query_tile(int64_t nq);                 // query-tile width chosen for nq (64/128/256)
 // Producer regions per query and slots per region of the filter GEMM for this problem.
@@ -335,11 +344,7 @@ struct FinalizeArgs {
     const int64_t *ids;      // [rows]
     const unsigned *gnorm_max_bits;
     const float *tau;
-    int regions, slots;
-    const int *region_cnt;   // [nq, regions]
-    const Cand *cand;        // [nq, regions, slots]
-    const int *ovf_cnt;      // [nq]
-    const Cand *ovf;         // [nq, CAND_OVF]
+    CandLists lists;
     const int64_t *exclude;  // or null
     int64_t n_rows;
     int dimp, k, metric, nq;
@@ -361,10 +366,9 @@ hipError_t launch_gather_queries(const uint16_t *q16, const float *tau2, const i
                                  int64_t n_pad, int dimp, uint16_t *q16r, float *taur, hipStream_t st);
 hipError_t launch_select_tau(const float *groupmax, int ngroups, int64_t nq, int64_t nq_pad,
                              int rank_j, float *tau, hipStream_t st);
-hipError_t launch_finalize(const FinalizeArgs &a, hipStream_t st);
-// k_finalize_deep.hip: the same contract for the deep route's candidate buffers (gemm_plan_deep): up to DEEP_CAP candidates per
-// query, regions <= DEEP_MAX_REGIONS
-hipError_t launch_finalize_deep(const FinalizeArgs &a, hipStream_t st);
+// One kernel, two capacities: up to CAND_CAP candidates per query on 256 threads, or with `deep` (the deep route's candidate
+// buffers, gemm_plan_deep) up to DEEP_CAP on 1024.  1 <= regions <= DEEP_MAX_REGIONS, slots >= 1, 1 <= k <= MAX_K.
+hipError_t launch_finalize(const FinalizeArgs &a, bool deep, hipStream_t st);
 
 // ---- k_range.hip: range search (mirx_index_range_search): every row with lo < s <= hi, per query, best first -------------------
 constexpr int RANGE_CAP = CAND_CAP + CAND_OVF;   // most candidates the filter route re-scores per query; more -> exact route
@@ -375,11 +379,7 @@ struct RangeFinalizeArgs {
     const float *q32p;       // [nq, dimp]
     const float *g32;        // [rows, dimp]
     const int64_t *ids;      // [rows]
-    int regions, slots;      // the filter GEMM's candidate buffers, as in FinalizeArgs
-    const int *region_cnt;
-    const Cand *cand;
-    const int *ovf_cnt;
-    const Cand *ovf;
+    CandLists lists;         // the filter GEMM's candidate buffers, as in FinalizeArgs
     const int64_t *exclude;  // [nq] or null
     const uint8_t *allow;    // [rows] or null
     int64_t n_rows;

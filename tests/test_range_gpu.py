@@ -333,6 +333,45 @@ def test_overflow_falls_back_to_the_exact_route(metric):
     _same(_forced_exact(ix, lambda: _run(ix, q, lo)), _run(ix, q, lo))
 
 
+@pytest.mark.parametrize("over", [0, 1])
+@pytest.mark.parametrize("metric", METRICS)
+def test_range_cap_hits_and_one_past(metric, over):
+    """RANGE_CAP (+ 1) identical rows that equal query 0, lo between their score and every other row's, outside the filter's
+    band.  The rows are laid out on k_gemm.hip's plan for one 64-query tile (phase ph walks the gallery tiles ph, ph + nph, ..;
+    wave row wm of a tile's 256 rows feeds region ph * 8 + wm) so that no region receives more than its slots: the overflow
+    list stays empty and RANGE_CAP hits are exactly what the filter route holds; one more and the exact route answers the
+    query, with the full count.  The stats assert which route answered."""
+    g, ids = _big(metric)[0].clone(), _big(metric)[1]
+    run = RANGE_CAP + over
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nph = min(cus // 8 * 8, (BIG_N + 255) // 256)
+    slots = min(64, max(8, 2048 // (nph * 8)))                         # k_gemm.hip: region_slots()
+    r = np.arange(BIG_N)
+    region = ((r // 256) % nph) * 8 + (r % 256) // 32
+    rank_in_region = np.zeros(BIG_N, dtype=np.int64)
+    order = np.argsort(region, kind="stable")
+    starts = np.r_[0, np.cumsum(np.bincount(region))[:-1]]
+    rank_in_region[order] = np.arange(BIG_N) - starts[region[order]]
+    rows = np.nonzero(rank_in_region < slots)[0][:run]                 # at most `slots` rows of every region, lowest rows first
+    assert rows.shape[0] == run and np.bincount(region[rows]).max() <= slots
+    v = _unit(1, BIG_D, 36)
+    g[torch.as_tensor(rows)] = v
+    q = torch.cat([v, _big(metric)[2][:2]])
+    s = _scores(q, g, metric)
+    top = np.sort(s[0])[::-1]
+    assert top[run - 1] == top[0] and top[run] < top[0]
+    lo = _mid(top, run)
+    assert _most_candidates(q, g, s, np.full(3, lo), metric).tolist() == [run, 0, 0]      # nothing else inside the band
+    ix = _index(g, metric)
+    counts = _check(ix, q, s, ids, metric, lo)
+    assert counts.tolist() == [run, 0, 0]
+    st = ix.range_last_stats()
+    if over == 0:
+        assert st["filter_answered"] == 3 and st["exact_answered"] == 0 and st["hits"] == st["candidates"] == run, st
+    else:
+        assert st["filter_answered"] == 2 and st["exact_answered"] == 1 and st["hits"] == run, st
+
+
 # ---- 5. the eps margin -----------------------------------------------------------------------------------------------
 def _bf16(x):
     bits = OS.to_bf16_bits(x.numpy()).astype(np.uint32) << 16

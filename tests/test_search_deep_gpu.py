@@ -269,6 +269,65 @@ def test_capacity_at_and_one_past_deep_cap(over):
     assert (st["tier1_answered"] == nq) if over == 0 else (st["exact_answered"] == nq), st
 
 
+def _lay_out(region, pool, slots, total, surplus):
+    """`total` rows out of `pool` of which exactly `surplus` exceed their regions' `slots` and reach the overflow list
+    (tests/test_search_filter_edges_gpu.py's layout): regions are saturated one after the other, then filled"""
+    by_region = {}
+    for r in pool:
+        by_region.setdefault(int(region[r]), []).append(int(r))
+    rows, left = [], surplus
+    for rg in sorted(by_region):
+        have = by_region[rg]
+        if len(rows) == total:
+            break
+        if left > 0:
+            take = min(len(have), slots + left, total - len(rows))
+            left -= max(take - slots, 0)
+        else:
+            take = min(len(have), slots, total - len(rows))
+        rows += have[:take]
+    assert len(rows) == total and left == 0, (len(rows), left)
+    rows = np.sort(np.asarray(rows))
+    assert int(np.maximum(np.bincount(region[rows]) - slots, 0).sum()) == surplus
+    return rows
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_overflow_list_exactly_full_and_one_past(over):
+    """tau forced to 0.5 and runs of identical rows, laid out on k_gemm.hip's plan for one 64-query tile (phase ph walks the
+    gallery tiles ph, ph + nph, ..; wave row wm of a tile's 256 rows feeds region ph * 8 + wm) so that saturated regions send
+    exactly CAND_OVF (+ 1) rows of every query to the overflow list.  A deep region holds a whole wave row of one tile, so the
+    gallery has two tiles per phase.  The full list has lost nothing: the deep filter answers and counts every candidate; one
+    row more and the query is `overflowed` and scanned exactly.  The stats assert the premise."""
+    from mirx import _lib as L
+    ovf = _constexpr("mirx_common.h", "CAND_OVF")
+    min_slots = _constexpr("mirx_common.h", "DEEP_MIN_SLOTS")
+    nq, k, d, total = 8, 100, 256, 512 + 64 * over
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = max(2 * (cus // 8 * 8) * 256, deep_min_rows(k, nq)) + 257
+    nph = min(cus // 8 * 8, (n + 255) // 256)
+    r = np.arange(n)
+    region, slots = ((r // 256) % nph) * 8 + (r % 256) // 32, max(min_slots, 2 * DEEP_CAP // (nph * 8))   # region_slots_deep()
+    g, base, runs = _unit(n, d, 3721), _unit(nq, d, 3722), []
+    own = torch.zeros(nq, n, dtype=torch.bool)
+    for j in range(nq):
+        rows = _lay_out(region, np.nonzero((r % 256) // 32 == j)[0], slots, total, ovf + over)
+        g[torch.as_tensor(rows)] = base[j]
+        own[j, torch.as_tensor(rows)] = True
+        runs.append(rows)
+    dots = (base.double() @ g.double().t()).masked_fill_(own, -1.0)
+    assert float(dots.max()) < 0.5 - 4 * (2.0 ** -8 + 2.0 ** -18 + _dimp(d) * 2.0 ** -23)   # only the own run passes 0.5
+    ix = _index(d, "COSINE", g)
+    ix.set_option(L.OPT_FORCE_TAU, int(np.float32(0.5).view(np.uint32)))
+    st, _, o_i = _check(ix, base, k, 0, g)
+    np.testing.assert_array_equal(o_i, np.stack([rows[:k] for rows in runs]))
+    if over == 0:
+        assert st["candidates"] == nq * total and st["reranked"] == nq * total, st
+        assert st["overflowed"] == 0 and st["incomplete"] == 0 and st["tier1_answered"] == nq, st
+    else:
+        assert st["overflowed"] == nq and st["exact_answered"] == nq and st["tier1_answered"] == 0, st
+
+
 # ---- 5. guard and second chance ------------------------------------------------------------------------------------------------
 def test_first_threshold_too_high_is_retried():
     """Tight clusters of near-copies (tools/clustered_probe.py's recipe at small scale), larger than the route's candidate

@@ -486,3 +486,120 @@ def test_query_counts_around_the_query_tiles(nq, metric):
     st, _, o_i = _check(ix, q, k, mc, g, exclude=rows, filter_must_answer=True)
     assert not np.any(o_i == rows[:, None])
     _record("nq=%d excluded %s" % (nq, metric), st, worst, t0)
+
+
+# ---- the candidate lists at their capacities: CAND_CAP, and the overflow list's CAND_OVF ------------------------------------
+CAND_OVF = _constexpr("mirx_common.h", "CAND_OVF")
+
+
+def _region_of_rows(n):
+    """k_gemm.hip's plan for ONE 64-query tile over n rows (make_plan, the region index of the filter epilogue): a workgroup
+    per phase walks the gallery tiles ph, ph + nph, ..; its wave row wm owns rows 32 wm .. 32 wm + 31 of each 256-row tile and
+    the region ph * 8 + wm.  -> (region of every row, regions per query)"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    ngt = (n + 255) // 256
+    nph = max(1, min(cus // 8 * 8, ngt))
+    r = np.arange(n)
+    return ((r // 256) % nph) * 8 + (r % 256) // 32, nph * 8
+
+
+def _lay_out(region, pool, slots, total, surplus):
+    """`total` rows out of `pool` (row numbers) of which exactly `surplus` exceed their regions' `slots` -- those reach the
+    overflow list -- and the others fill regions to at most `slots`: regions are saturated one after the other until the
+    surplus is reached, then filled."""
+    by_region = {}
+    for r in pool:
+        by_region.setdefault(int(region[r]), []).append(int(r))
+    rows, left = [], surplus
+    for rg in sorted(by_region):
+        have = by_region[rg]
+        if len(rows) == total:
+            break
+        if left > 0:
+            take = min(len(have), slots + left, total - len(rows))
+            left -= max(take - slots, 0)
+        else:
+            take = min(len(have), slots, total - len(rows))
+        rows += have[:take]
+    assert len(rows) == total and left == 0, (len(rows), left)
+    rows = np.sort(np.asarray(rows))
+    per = np.bincount(region[rows])                                  # the model's own count of what it laid out
+    assert int(np.maximum(per - slots, 0).sum()) == surplus
+    return rows
+
+
+def _runs_laid_out(n, nq, slots_of, total, surplus, seed):
+    """-> (gallery, queries, rows of each query's run): query j is a unit vector, its run `total` copies of it among the rows
+    of wave row j, laid out by _lay_out; every other row is a unit vector that no query scores near 0.5"""
+    d = 256
+    region, regions = _region_of_rows(n)
+    slots = slots_of(regions)
+    g = _unit(n, d, seed)
+    base = _unit(nq, d, seed + 1)
+    runs = []
+    for j in range(nq):
+        rows = _lay_out(region, np.nonzero((np.arange(n) % 256) // 32 == j)[0], slots, total, surplus)
+        g[torch.as_tensor(rows)] = base[j]
+        runs.append(rows)
+    own = torch.zeros(nq, n, dtype=torch.bool)
+    for j in range(nq):
+        own[j, torch.as_tensor(runs[j])] = True
+    dots = (base.double() @ g.double().t()).masked_fill_(own, -1.0)
+    eps = 2.0 ** -8 + 2.0 ** -18 + _dimp(d) * 2.0 ** -23
+    assert float(dots.max()) < 0.5 - 4 * eps                          # nothing but the query's own run passes 0.5
+    return g, base, runs
+
+
+def _tier1_slots(regions):                                           # k_gemm.hip: region_slots()
+    return min(64, max(8, 2048 // max(regions, 1)))
+
+
+def _forced_half(g):
+    from mirx import _lib as L
+    ix = _index(g.shape[1], "COSINE", g)
+    ix.set_option(L.OPT_FORCE_TAU, int(np.float32(0.5).view(np.uint32)))
+    return ix
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_capacity_at_and_one_past_cand_cap(over):
+    """tau forced to 0.5: a query admits exactly its run of identical rows, which tie in the filter and in fp64, so the answer
+    is the run's lowest ids.  The run is laid out so that no region receives more than its slots (the overflow list stays
+    empty): run = CAND_CAP fills the candidate list to the last key and every one is re-scored; CAND_CAP + 1 is one past what
+    the list holds and goes to the exact scan.  The stats assert the premise: a lost candidate fails here, it does not pass
+    through the fallback."""
+    nq, k, run = 8, MAX_K, CAND_CAP + over
+    g, q, runs = _runs_laid_out(MIN_ROWS + 4 * 256 + 1, nq, _tier1_slots, run, 0, 811)
+    ix = _forced_half(g)
+    first = np.stack([r[:k] for r in runs])
+    st, _, o_i = _check(ix, q, k, 0, g)
+    np.testing.assert_array_equal(o_i, first)                         # all `run` rows tie: the k lowest ids
+    if over == 0:
+        assert st["candidates"] == nq * run and st["reranked"] == nq * run, st
+        assert st["overflowed"] == 0 and st["incomplete"] == 0 and st["tier1_answered"] == nq, st
+    else:
+        assert st["overflowed"] == nq and st["exact_answered"] == nq and st["tier1_answered"] == 0, st
+    # k = 63 with the run's first id excluded: k_eff = 64, the ids start one later
+    st, _, o_i = _check(ix, q, k - 1, 0, g, exclude=first[:, 0])
+    np.testing.assert_array_equal(o_i, np.stack([r[1:k] for r in runs]))
+    if over == 0:
+        assert st["candidates"] == nq * run and st["reranked"] == nq * run and st["tier1_answered"] == nq, st
+    else:
+        assert st["overflowed"] == nq and st["exact_answered"] == nq, st
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_overflow_list_exactly_full_and_one_past(over):
+    """The same runs, half of CAND_CAP long, laid out so that saturated regions send exactly CAND_OVF (+ 1) rows of every query
+    to the overflow list: a full list has lost nothing and tier 1 answers with every candidate counted; one row more and the
+    list has lost a row, the query is `overflowed` and the exact scan answers."""
+    nq, k, total = 8, MAX_K, CAND_CAP // 2 + over
+    g, q, runs = _runs_laid_out(MIN_ROWS + 4 * 256 + 1, nq, _tier1_slots, total, CAND_OVF + over, 821)
+    ix = _forced_half(g)
+    st, _, o_i = _check(ix, q, k, 0, g)
+    np.testing.assert_array_equal(o_i, np.stack([r[:k] for r in runs]))
+    if over == 0:
+        assert st["candidates"] == nq * total and st["reranked"] == nq * total, st
+        assert st["overflowed"] == 0 and st["incomplete"] == 0 and st["tier1_answered"] == nq, st
+    else:
+        assert st["overflowed"] == nq and st["exact_answered"] == nq and st["tier1_answered"] == 0, st
