@@ -62,7 +62,7 @@ class MirxError(RuntimeError):
 class SearchStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in
                 ("nq", "tier1_answered", "exact_answered", "candidates", "reranked",
-                 "overflowed", "incomplete")]
+                 "overflowed", "incomplete", "left_out")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -97,6 +97,7 @@ SYMBOLS = {
     "mirx_index_search_end": (_int, [_vp]),
     "mirx_index_search_masked": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mirx_index_search_deep": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_index_search_leave_out": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mirx_tier1_max_k": (_int, []),
     "mirx_deep_min_rows": (_i64, [_int, _i64]),
     "mirx_index_rank_top_masked": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),

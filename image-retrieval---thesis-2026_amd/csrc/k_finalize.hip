@@ -9,6 +9,14 @@
 // the oracle's summation order (lane_tree_score), and sorting them (score desc, id asc) gives the oracle's answer.  A query that
 // fails (c) alone is filtered once more with tau2 just below lo (retry list); every other failure, and a failure of the second
 // pass, goes to the exact scan (fail list).  Nothing is answered from approximate scores.
+//
+// Leave-group-out (CODES, mirx_index_search_leave_out): the same argument restricted to the eligible set E = the rows
+// whose code is not the query's.  A candidate outside E is dropped as it is gathered, before the sort: it never counts toward
+// c >= k_eff, never becomes the k_eff-th key and is never re-scored.  With no overflow the survivors are exactly E n {s~ > tau}
+// (overflow is still decided on the raw count: a lost candidate may have been eligible).  With at least k_eff survivors and
+// tau < lo = kth_surv(s~) - 2 eps, every eligible row with s~ >= lo is a survivor, and the true top k_eff of E all have
+// s~ >= kth_surv(s~) - 2 eps: they are among the re-scored rows.  The retry threshold tau2 is derived from kth_surv, so the second
+// pass is complete for E by construction.  The instantiations without CODES read neither code pointer.
 #include "mirx_device.h"
 #include "mirx_kernels.h"
 
@@ -41,26 +49,49 @@ __global__ __launch_bounds__(256) void k_select_tau(const float *__restrict__ gr
 // workgroups per CU; 96 KiB at DEEP_CAP, one workgroup of 16 waves per CU (160 KiB).  The hits' storage doubles as the region
 // offsets during the gather.  At run = CAP tied rows every candidate is re-scored, so the hits cannot be bounded below CAP.
 // Counters are integer atomics; no floating-point atomic is used.
-template <int METRIC, int CAP, int THREADS>
+template <int METRIC, int CAP, int THREADS, bool CODES>
 __global__ __launch_bounds__(THREADS) void k_finalize(FinalizeArgs A) {
     static_assert((DEEP_MAX_REGIONS + 1) * sizeof(int) <= CAP * sizeof(Hit), "the region offsets live in the hits' storage");
     constexpr int WAVES = THREADS / WAVE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);                 // [CAP]
     Hit *hits = reinterpret_cast<Hit *>(smem + (size_t)CAP * sizeof(unsigned long long));    // [CAP]
-    __shared__ int sh_ok, sh_m;
+    __shared__ int sh_ok, sh_m, sh_drop;
     __shared__ float sh_lo;
     const int slot_q = blockIdx.x;                                  // index into tau / candidate buffers
     const int qi = A.qmap ? A.qmap[slot_q] : slot_q;                // original query number
     const int wave = threadIdx.x >> 6, lane = lane_id();
 
     // ---- gather and sort.  Where a candidate lands does not matter: the keys are distinct and sorted next.
-    const Gathered got = gather_cands<THREADS>(A.lists, slot_q, CAP, reinterpret_cast<int *>(hits),
-                                               [&](int p, const Cand cd) { keys[p] = cand_key(cd); });
+    // CODES: a candidate that carries the query's code gets the padding key 0, below every real key (a real key's high word is
+    // 0 only for a NaN score, which passes no threshold), so the sort leaves the survivors in keys[0 .. c)
+    int32_t qcode = -1;
+    int dropped = 0;
+    if constexpr (CODES) {
+        qcode = A.query_codes[qi];
+        if (threadIdx.x == 0) sh_drop = 0;                          // (gather_cands' first barrier orders this before the adds)
+    }
+    const Gathered got = gather_cands<THREADS>(A.lists, slot_q, CAP, reinterpret_cast<int *>(hits), [&](int p, const Cand cd) {
+        if constexpr (CODES) {
+            const bool out = qcode >= 0 && A.row_codes[cd.row] == qcode;
+            dropped += out ? 1 : 0;
+            keys[p] = out ? 0ull : cand_key(cd);
+        } else {
+            keys[p] = cand_key(cd);
+        }
+    });
     const bool overflow = got.lost;
-    const int c = overflow ? 0 : got.taken;
-    const int m2 = pow2_ceil(c > 1 ? c : 1);
-    for (int i = c + threadIdx.x; i < m2; i += THREADS) keys[i] = 0ull;
+    const int taken = overflow ? 0 : got.taken;
+    int c = taken;                                                  // the candidates that can rank
+    if constexpr (CODES) {
+        dropped = wave_isum(dropped);
+        if (lane == 0 && dropped) atomicAdd(&sh_drop, dropped);
+        __syncthreads();
+        dropped = sh_drop;
+        c = taken - dropped;
+    }
+    const int m2 = pow2_ceil(taken > 1 ? taken : 1);
+    for (int i = taken + threadIdx.x; i < m2; i += THREADS) keys[i] = 0ull;
     const int64_t ex = A.exclude ? A.exclude[qi] : -1;
     const int k_eff = A.k + (ex >= 0 ? 1 : 0);
     if (!overflow) bitonic_lds(keys, m2, [](unsigned long long x, unsigned long long y) { return x > y; });
@@ -143,6 +174,7 @@ __global__ __launch_bounds__(THREADS) void k_finalize(FinalizeArgs A) {
         atomicAdd((unsigned long long *)&A.stats->tier1_answered, 1ull);
         atomicAdd((unsigned long long *)&A.stats->candidates, (unsigned long long)got.raw);
         atomicAdd((unsigned long long *)&A.stats->reranked, (unsigned long long)m);
+        if constexpr (CODES) atomicAdd((unsigned long long *)&A.stats->left_out, (unsigned long long)dropped);
     }
 }
 
@@ -164,15 +196,15 @@ __global__ __launch_bounds__(256) void k_gather_queries(const uint16_t *__restri
     }
 }
 
-template <int METRIC, int CAP, int THREADS>
+template <int METRIC, int CAP, int THREADS, bool CODES>
 hipError_t launch_finalize_as(const FinalizeArgs &a, hipStream_t st) {
     constexpr size_t LDS_BYTES = (size_t)CAP * (sizeof(unsigned long long) + sizeof(Hit));
     if constexpr (LDS_BYTES > 64 * 1024) {
         static std::atomic<unsigned long long> attr_devs{0};
-        const hipError_t e = set_dynamic_lds(k_finalize<METRIC, CAP, THREADS>, LDS_BYTES, &attr_devs);
+        const hipError_t e = set_dynamic_lds(k_finalize<METRIC, CAP, THREADS, CODES>, LDS_BYTES, &attr_devs);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_finalize<METRIC, CAP, THREADS>), dim3(a.nq), dim3(THREADS), LDS_BYTES, st, a);
+    hipLaunchKernelGGL((k_finalize<METRIC, CAP, THREADS, CODES>), dim3(a.nq), dim3(THREADS), LDS_BYTES, st, a);
     return hipGetLastError();
 }
 
@@ -205,8 +237,13 @@ hipError_t launch_finalize(const FinalizeArgs &a, bool deep, hipStream_t st) {
     if (a.lists.regions < 1 || a.lists.regions > DEEP_MAX_REGIONS || a.lists.slots < 1 || a.k < 1 || a.k > MAX_K)
         return hipErrorInvalidValue;
     const bool ip = a.metric == MIRX_METRIC_IP;
-    if (deep) return ip ? launch_finalize_as<0, DEEP_CAP, 1024>(a, st) : launch_finalize_as<1, DEEP_CAP, 1024>(a, st);
-    return ip ? launch_finalize_as<0, CAND_CAP, 256>(a, st) : launch_finalize_as<1, CAND_CAP, 256>(a, st);
+    if (a.row_codes) {                                              // leave-group-out: the CODES twins
+        if (!a.query_codes) return hipErrorInvalidValue;
+        if (deep) return ip ? launch_finalize_as<0, DEEP_CAP, 1024, true>(a, st) : launch_finalize_as<1, DEEP_CAP, 1024, true>(a, st);
+        return ip ? launch_finalize_as<0, CAND_CAP, 256, true>(a, st) : launch_finalize_as<1, CAND_CAP, 256, true>(a, st);
+    }
+    if (deep) return ip ? launch_finalize_as<0, DEEP_CAP, 1024, false>(a, st) : launch_finalize_as<1, DEEP_CAP, 1024, false>(a, st);
+    return ip ? launch_finalize_as<0, CAND_CAP, 256, false>(a, st) : launch_finalize_as<1, CAND_CAP, 256, false>(a, st);
 }
 
 }  // namespace mirx

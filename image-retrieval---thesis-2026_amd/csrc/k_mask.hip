@@ -75,6 +75,24 @@ __global__ __launch_bounds__(256) void mask_scores(double *__restrict__ scores, 
         if (row_masked(pos, r)) scores[qi * ld + r] = -INFINITY;
 }
 
+// leave-group-out: the entries of the rows that carry the query's code become NaN (see launch_leave_out_scores)
+__global__ __launch_bounds__(256) void leave_out_scores(double *__restrict__ scores, int64_t ld, int64_t n,
+                                                        const int32_t *__restrict__ row_codes,
+                                                        const int32_t *__restrict__ query_codes,
+                                                        const int32_t *__restrict__ qlist) {
+    const int64_t pos = blockIdx.y;
+    const int32_t qc = query_codes[qlist ? (int64_t)qlist[pos] : pos];
+    if (qc < 0) return;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256)
+        if (row_codes[r] == qc) scores[pos * ld + r] = __longlong_as_double(0x7FF8000000000000ll);
+}
+
+__global__ __launch_bounds__(256) void mask_gather_codes(const int32_t *__restrict__ row_codes, const int32_t *__restrict__ pos,
+                                                         int64_t n, int32_t *__restrict__ out) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256)
+        if (!row_masked(pos, r)) out[pos[r]] = row_codes[r];
+}
+
 __global__ __launch_bounds__(256) void mask_rank_keys(uint64_t *__restrict__ keys, const int32_t *__restrict__ pay, int64_t n,
                                                       const uint8_t *__restrict__ allow) {
     const int64_t qi = blockIdx.y;
@@ -115,6 +133,20 @@ hipError_t launch_mask_pass(const uint8_t *allow, int64_t n, int64_t cap, const 
 hipError_t launch_mask_scores(double *scores, int64_t ld, int64_t n, const int32_t *pos, int nq, hipStream_t st) {
     if (nq <= 0 || n <= 0) return hipSuccess;
     hipLaunchKernelGGL(mask_scores, dim3(grid_for(n), (unsigned)nq), dim3(256), 0, st, scores, ld, n, pos);
+    return hipGetLastError();
+}
+
+hipError_t launch_leave_out_scores(double *scores, int64_t ld, int64_t n, const int32_t *row_codes, const int32_t *query_codes,
+                                   const int32_t *qlist, int nq, hipStream_t st) {
+    if (nq <= 0 || n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(leave_out_scores, dim3(grid_for(n), (unsigned)nq), dim3(256), 0, st, scores, ld, n, row_codes, query_codes,
+                       qlist);
+    return hipGetLastError();
+}
+
+hipError_t launch_mask_gather_codes(const int32_t *row_codes, const int32_t *pos, int64_t n, int32_t *out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mask_gather_codes, dim3(grid_for(n)), dim3(256), 0, st, row_codes, pos, n, out);
     return hipGetLastError();
 }
 

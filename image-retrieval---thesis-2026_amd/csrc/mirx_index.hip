@@ -9,6 +9,8 @@
 // A masked search (mirx_index_search_masked) runs the same sequence over a SearchRows that stands for the allowed rows.
 // The deep search (mirx_index_search_deep) runs it for k_eff past TIER1_MAX_K with SearchRows::deep set: gemm_plan_deep's candidate
 // regions, its own threshold rank and k_finalize at DEEP_CAP; where that route does not apply the call is handed to the two above.
+// The leave-group-out search (mirx_index_search_leave_out) runs the masked / deep sequence with SearchRows::rcodes / qcodes set:
+// k_finalize's CODES twins drop the candidates that carry the query's code, and the exact scan turns their scores into NaN.
 // A range search (mirx_index_range_search) runs prep -> threshold from the radius -> filter GEMM -> its own finalize, the radix
 // ranking for what that cannot answer, and a CSR assembly (k_range.hip).
 // The radix ranking (radix_plan / radix_sort_batch) serves mirx_index_rank_all / _rank_top / _rank_top_masked and the range
@@ -71,6 +73,16 @@ struct SearchRows {
     const float *bias = nullptr;          // tier 1: the per-row bias of both GEMMs instead of the index's
     bool tier1 = false;
     bool deep = false;                    // tier 1 with the deep route's plan, threshold target and finalize (mirx_index_search_deep)
+    // leave-group-out (mirx_index_search_leave_out): row r is not eligible for query i when qcodes[i] >= 0 and rcodes[r] == qcodes[i]
+    const int32_t *rcodes = nullptr;      // one code per row of g32 (gathered with the rows where those are gathered), or null
+    const int32_t *qcodes = nullptr;      // one code per query of the batch
+    int64_t extra = 0;                    // rows a query may leave out (the caller's hint): sizes the sampled threshold only
+};
+
+// The leave-group-out arguments of a call, as its entry point received them.
+struct LeaveOut {
+    const int32_t *rcodes, *qcodes;       // by index row / by query of the call
+    int64_t extra;                        // max_left_out, at least 0
 };
 
 struct mirx_index {
@@ -109,7 +121,7 @@ struct mirx_index {
     size_t ev_used = 0;
     // workspace (each buffer frees itself with the index)
     DevBuf q32p, q16, qnorm, tau, cnt, cand, ovf_cnt, ovf, groupmax, fail_list, retry_list, tau2, q16r, taur,
-        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart, mallow, mbias, mids, mrows,
+        scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart, mallow, mbias, mids, mrows, mcodes,
         rstage, rcount, rxoff, rfirst, rexcl, rseg, rres;
     int *fail_count = nullptr;            // device
     mirx_search_stats *stats_dev = nullptr;
@@ -281,6 +293,9 @@ int exact_pass(mirx_index *ix, const SearchRows &sr, const float *q32p, const in
         MIRX_HIP(launch_scores_f64(qb, lst, cnt, sr.g32, sr.n, ix->dimp, ix->metric,
                                    ix->scores.as<double>(), ld, st));
         if (sr.mpos) MIRX_HIP(launch_mask_scores(ix->scores.as<double>(), ld, sr.n, sr.mpos, cnt, st));
+        if (sr.rcodes)
+            MIRX_HIP(launch_leave_out_scores(ix->scores.as<double>(), ld, sr.n, sr.rcodes, list_dev ? sr.qcodes : sr.qcodes + b, lst,
+                                             cnt, st));
         MIRX_HIP(launch_row_topk(ix->scores.as<double>(), ld, sr.n, sr.ids, lst, cnt, exb, k,
                                  ix->metric, of, oi, ov, st));
     }
@@ -393,7 +408,7 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
         // from: it goes to the exact scan.  At the smallest galleries (stride 8) j = 8 gives ~64, so from k_eff = 17 on
         // ask for 4 k_eff of them -- at most half the groups deep, where the j-th maximum still tracks the j-th score.
         // k_eff <= 16 keeps j at any stride, and so does every k at stride >= 32 (k_eff <= TIER1_MAX_K = 64).
-        const int64_t k_eff = (int64_t)k + (exb ? 1 : 0);
+        const int64_t k_eff = (int64_t)k + (exb ? 1 : 0) + sr.extra;
         const int64_t rank_k = std::min<int64_t>((4 * k_eff + stride - 1) / stride, ngroups / 2);
         rank_j = (int)std::max<int64_t>(rank_j, rank_k);
         if (sr.deep) rank_j = deep_sample_rank(k_eff, ngroups, stride);
@@ -440,6 +455,8 @@ int batch_front(mirx_index *ix, const float *qb, int64_t nb, int k, const int64_
     fa.tau2 = ix->tau2.as<float>();
     fa.qmap = nullptr;
     fa.stats = ix->stats_dev;
+    fa.row_codes = sr.rcodes;
+    fa.query_codes = sr.qcodes;
     {
         StageTimer t(ix, st, MIRX_STAGE_FINALIZE);
         MIRX_HIP(launch_finalize(fa, sr.deep, st));
@@ -528,16 +545,17 @@ int batch_back(mirx_index *ix) {
 }
 
 // The tier-1 sequence answers when the tiers are on auto, `rows` rows can rank (the gallery, or a masked call's allowed rows)
-// and the candidate lists hold k plus the excluded id; else the exact scan answers directly.
-bool tier1_route(const mirx_index *ix, int64_t rows, int k, const int64_t *exclude) {
-    return ix->tiers == MIRX_TIER_AUTO && rows >= TIER1_MIN_ROWS && k + (exclude ? 1 : 0) <= TIER1_MAX_K;
+// and the candidate lists hold k plus the excluded id (plus `extra`, the rows a leave-group-out query may drop); else the exact
+// scan answers directly.
+bool tier1_route(const mirx_index *ix, int64_t rows, int k, const int64_t *exclude, int64_t extra = 0) {
+    return ix->tiers == MIRX_TIER_AUTO && rows >= TIER1_MIN_ROWS && k + (exclude ? 1 : 0) + extra <= TIER1_MAX_K;
 }
 
 // The search of an index that enter_idle has let in.  wait_last = false: the last internal batch is left pending
 // (mirx_index_search_begin); batch_back completes it.
 int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude,
                 float *out_val, double *out_f64_user, int64_t *out_ids, hipStream_t st, bool wait_last = true,
-                const SearchRows *masked = nullptr) {
+                const SearchRows *masked = nullptr, const LeaveOut *lo = nullptr) {
     MIRX_CHECK(k >= 1 && k <= MAX_K, "search: k must be in [1, 1024]");
     MIRX_CHECK(nq >= 0, "search: nq < 0");
     MIRX_CHECK(nq == 0 || (q && out_ids && (out_val || out_f64_user)), "search: null buffer");
@@ -555,9 +573,16 @@ int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t
         sr.g32 = ix->g32;
         sr.ids = ix->ids;
         sr.n = ix->size;
-        sr.tier1 = tier1_route(ix, ix->size, k, exclude);
+        sr.tier1 = tier1_route(ix, ix->size, k, exclude, lo ? lo->extra : 0);
+        if (lo) {
+            sr.rcodes = lo->rcodes;
+            sr.qcodes = lo->qcodes;
+            sr.extra = lo->extra;
+        }
     }
+    const int32_t *qcodes = sr.qcodes;
     for (int64_t q0 = 0; q0 < nq; q0 += QUERY_BATCH) {
+        if (qcodes) sr.qcodes = qcodes + q0;
         const int64_t nb = std::min<int64_t>(QUERY_BATCH, nq - q0);
         const float *qb = q + q0 * ix->dim;
         const int64_t *exb = exclude ? exclude + q0 : nullptr;
@@ -1145,24 +1170,33 @@ int mirx_index_search_begin(mirx_index *ix, const float *q, int64_t nq, int k, c
 }
 
 // The plain search of mirx_index_search_deep: the deep route where it applies, else search_impl as mirx_index_search runs it.
+// With `lo` (mirx_index_search_leave_out) the route is picked as if k_eff were larger by lo->extra; with k + extra past MAX_K (the
+// excluded id rides on top, as it always has at k = MAX_K) neither list route is open and search_impl scans exactly.
 static int search_deep_plain(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude, float *out_val,
-                             double *out_f64, int64_t *out_ids, hipStream_t st) {
-    const int k_eff = k + (exclude ? 1 : 0);
+                             double *out_f64, int64_t *out_ids, hipStream_t st, const LeaveOut *lo = nullptr) {
+    const int64_t k_eff = (int64_t)k + (exclude ? 1 : 0) + (lo ? lo->extra : 0);
     const int bn = gemm_query_tile(std::min<int64_t>(std::max<int64_t>(nq, 1), QUERY_BATCH));   // the widest tile of the call's batches
-    if (ix->tiers != MIRX_TIER_AUTO || k_eff <= TIER1_MAX_K || ix->size < deep_min_rows(k_eff, bn))
-        return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st);
+    if (ix->tiers != MIRX_TIER_AUTO || k_eff <= TIER1_MAX_K || k + (lo ? lo->extra : 0) > MAX_K || ix->size < deep_min_rows(k_eff, bn))
+        return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st, /*wait_last=*/true, nullptr, lo);
     SearchRows sr;
     sr.g32 = ix->g32;
     sr.ids = ix->ids;
     sr.n = ix->size;
     sr.tier1 = sr.deep = true;
+    if (lo) {
+        sr.rcodes = lo->rcodes;
+        sr.qcodes = lo->qcodes;
+        sr.extra = lo->extra;
+    }
     return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st, /*wait_last=*/true, &sr);
 }
 
 // mirx_index_search_masked (deep = false) and the masked form of mirx_index_search_deep: one mask pass, one count, then the route.
+// With `lo` (the masked form of mirx_index_search_leave_out) the routes count lo->extra more rows per query, and where the allowed
+// rows are gathered their codes are gathered with them, into the order of the gathered ids.
 static int search_masked_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                               const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
-                              int64_t *out_ids, void *stream, bool deep) {
+                              int64_t *out_ids, void *stream, bool deep, const LeaveOut *lo = nullptr) {
     MIRX_ENTER_IDLE(ix, "search_masked");
     MIRX_CHECK(n_allow == ix->size, "search_masked: the mask needs one byte per row of the index (n_allow != size)");
     MIRX_CHECK(allow || n_allow == 0, "search_masked: null mask");
@@ -1171,27 +1205,39 @@ static int search_masked_impl(mirx_index *ix, const float *q, int64_t nq, int k,
     MIRX_CHECK(nq == 0 || (q && out_ids && (out_scores_or_null || out_rank_scores_or_null)), "search_masked: null buffer");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (nq == 0 || ix->size == 0)
-        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
+        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
+                           /*wait_last=*/true, nullptr, lo);
+    const int64_t extra = lo ? lo->extra : 0;
     // the gather's scratch is sized before the count is known: with the filter route open only fewer than TIER1_MIN_ROWS
     // allowed rows are ever gathered, else any number whose rows fit the limit
     const size_t row_bytes = (size_t)ix->dimp * sizeof(float) + sizeof(int64_t);
     const size_t gather_max = ix->mask_gather_bytes < 0 ? EXACT_WS_BYTES : (size_t)ix->mask_gather_bytes;
     // the deep route is open to the call when its k_eff is past the candidate lists' and the tiers are on auto; it is taken when
     // the allowed rows reach deep_min_rows, with the same bias (route A of DESIGN 32)
-    const int k_eff = k + (exclude_ids_or_null ? 1 : 0);
-    deep = deep && ix->tiers == MIRX_TIER_AUTO && k_eff > TIER1_MAX_K;
+    const int64_t k_eff = (int64_t)k + (exclude_ids_or_null ? 1 : 0) + extra;
+    deep = deep && ix->tiers == MIRX_TIER_AUTO && k_eff > TIER1_MAX_K && k + extra <= MAX_K;
     const int64_t deep_rows = deep ? deep_min_rows(k_eff, gemm_query_tile(std::min<int64_t>(nq, QUERY_BATCH))) : 0;
     const int64_t most_rows = deep ? std::min(ix->size, deep_rows - 1)
-                                   : (tier1_route(ix, TIER1_MIN_ROWS, k, exclude_ids_or_null) ? std::min(ix->size, TIER1_MIN_ROWS - 1) : ix->size);
+                                   : (tier1_route(ix, TIER1_MIN_ROWS, k, exclude_ids_or_null, extra) ? std::min(ix->size, TIER1_MIN_ROWS - 1) : ix->size);
+    if (lo && ix->mcodes.ensure((size_t)most_rows * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIRX_ENOMEM, "search_masked: the gathered codes do not fit the device");
+    }
     int64_t n_allowed = 0;
     int rc = mask_prepare(ix, allow, std::min((size_t)most_rows * row_bytes, gather_max), st, &n_allowed, "search_masked");
     if (rc) return rc;
     if (n_allowed == ix->size) {          // nothing masked: the plain search, bit for bit
-        if (deep) return search_deep_plain(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
-        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st);
+        if (deep) return search_deep_plain(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st, lo);
+        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
+                           /*wait_last=*/true, nullptr, lo);
     }
     SearchRows sr;
-    sr.tier1 = deep ? n_allowed >= deep_rows : tier1_route(ix, n_allowed, k, exclude_ids_or_null);
+    sr.tier1 = deep ? n_allowed >= deep_rows : tier1_route(ix, n_allowed, k, exclude_ids_or_null, extra);
+    if (lo) {
+        sr.rcodes = lo->rcodes;                                    // in row order: right wherever all rows are scanned
+        sr.qcodes = lo->qcodes;
+        sr.extra = extra;
+    }
     sr.deep = deep && sr.tier1;
     const size_t gather_bytes = (size_t)n_allowed * row_bytes;
     if (sr.tier1 || (n_allowed > 0 && gather_bytes > gather_max)) {
@@ -1210,6 +1256,12 @@ static int search_masked_impl(mirx_index *ix, const float *q, int64_t nq, int k,
         sr.g32 = s32;
         sr.ids = sid;
         sr.n = n_allowed;
+        if (lo) {
+            if ((size_t)n_allowed * sizeof(int32_t) > ix->mcodes.bytes)
+                return fail(MIRX_EHIP, "search_masked: the code scratch is smaller than the count needs");
+            MIRX_HIP(launch_mask_gather_codes(lo->rcodes, ix->cpos.as<int32_t>(), ix->size, ix->mcodes.as<int32_t>(), st));
+            sr.rcodes = ix->mcodes.as<int32_t>();
+        }
     }                                     // else nothing is allowed: n = 0, every slot reads (-1, -inf) and no row is scored
     return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
                        /*wait_last=*/true, &sr);
@@ -1235,6 +1287,25 @@ int mirx_index_search_deep(mirx_index *ix, const float *queries, int64_t nq, int
     MIRX_ENTER_IDLE(ix, "search_deep");
     return search_deep_plain(ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
                              reinterpret_cast<hipStream_t>(stream));
+}
+
+int mirx_index_search_leave_out(mirx_index *ix, const float *queries, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                                const uint8_t *allow_or_null, const int32_t *row_codes, const int32_t *query_codes,
+                                int64_t max_left_out, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids,
+                                void *stream) {
+    MIRX_CHECK(k >= 1 && k <= MAX_K, "search_leave_out: k must be in [1, 1024]");
+    MIRX_CHECK(nq >= 0, "search_leave_out: nq < 0");
+    MIRX_CHECK(row_codes && query_codes, "search_leave_out: null codes");
+    MIRX_CHECK(queries && out_ids && (out_values_or_null || out_f64_or_null), "search_leave_out: null buffer");
+    MIRX_CHECK(max_left_out >= -1, "search_leave_out: max_left_out must be -1 (unknown) or a row count");
+    MIRX_CHECK(ix, "search_leave_out: null index");
+    const LeaveOut lo{row_codes, query_codes, std::max<int64_t>(max_left_out, 0)};
+    if (allow_or_null)
+        return search_masked_impl(ix, queries, nq, k, exclude_ids_or_null, allow_or_null, ix->size, out_values_or_null, out_f64_or_null,
+                                  out_ids, stream, /*deep=*/true, &lo);
+    MIRX_ENTER_IDLE(ix, "search_leave_out");
+    return search_deep_plain(ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
+                             reinterpret_cast<hipStream_t>(stream), &lo);
 }
 
 int mirx_tier1_max_k(void) { return TIER1_MAX_K; }

@@ -132,6 +132,14 @@ hipError_t launch_mask_pass(const uint8_t *allow, int64_t n, int64_t cap, const 
 // scores [nq, ld]: the entries of masked rows -> -inf; pos = the scanned positions (n + 1 entries; row r is masked iff
 // pos[r + 1] == pos[r])
 hipError_t launch_mask_scores(double *scores, int64_t ld, int64_t n, const int32_t *pos, int nq, hipStream_t st);
+// leave-group-out (mirx_index_search_leave_out).  scores [nq, ld] of the queries qlist[0 .. nq) (or 0 .. nq-1 without a list): the
+// entry of row r becomes NaN where query_codes[q] >= 0 and row_codes[r] == query_codes[q].  A masked entry is (-inf, INT64_MAX)
+// because its id is masked with it; a left-out row keeps its id (the id vector serves every query), and (-inf, id) would rank
+// before an empty slot.  NaN ranks before nothing (hit_before compares with > and ==), so k_row_topk never takes the entry.
+hipError_t launch_leave_out_scores(double *scores, int64_t ld, int64_t n, const int32_t *row_codes, const int32_t *query_codes,
+                                   const int32_t *qlist, int nq, hipStream_t st);
+// codes of the kept rows in the gather's order: out[pos[r]] = row_codes[r] for every row r < n that the scanned positions keep
+hipError_t launch_mask_gather_codes(const int32_t *row_codes, const int32_t *pos, int64_t n, int32_t *out, hipStream_t st);
 // The radix ranking (rank_top under a mask, the range search's exact route) takes the allow bytes themselves: masked iff allow[r] == 0.
 // keys / pay [nq, n] as launch_rank_sort_build leaves them: a masked row's key -> RANK_KEY_LAST
 hipError_t launch_mask_rank_keys(uint64_t *keys, const int32_t *pay, int64_t n, const uint8_t *allow, int nq, hipStream_t st);
@@ -360,6 +368,10 @@ struct FinalizeArgs {
     // retry pass: slot i of the candidate buffers / tau belongs to original query qmap[i]
     const int32_t *qmap;     // or null (identity)
     mirx_search_stats *stats;  // device copy
+    // leave-group-out (mirx_index_search_leave_out): read by the CODES instantiations only, which launch_finalize picks when
+    // row_codes is set
+    const int32_t *row_codes;    // [rows], or null
+    const int32_t *query_codes;  // [nq] by original query number
 };
 // q16r[i] = q16[list[i]] for i < n, zero rows and tau = +inf up to n_pad (retry pass input).
 hipError_t launch_gather_queries(const uint16_t *q16, const float *tau2, const int32_t *list, int n,

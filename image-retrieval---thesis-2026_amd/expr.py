@@ -107,7 +107,9 @@ class ExprCache:
         self.text = None
         self.mask = None
         self.device_mask = None
-        self.device_codes = {}            # name -> the column's codes on the index's device (grouping search)
+        self.device_codes = {}            # name -> the column's codes on the index's device (grouping search); (name, "int32") ->
+                                          # the same as int32 (leave-group-out search)
+        self.tables = {}                  # name -> ({value: code}, rows per code) (leave-group-out search)
 
     def _coded(self, name):
         got = self.codes.get(name)
@@ -116,6 +118,14 @@ class ExprCache:
             values = self._column(name)
             codes = np.fromiter((table.setdefault(v, len(table)) for v in values), dtype=np.int64, count=len(values))
             got = self.codes[name] = (list(table), codes)
+        return got
+
+    def table(self, name):
+        """({value: code}, numpy int64 rows per code) of column `name`"""
+        got = self.tables.get(name)
+        if got is None:
+            distinct, codes = self._coded(name)
+            got = self.tables[name] = ({v: j for j, v in enumerate(distinct)}, np.bincount(codes, minlength=len(distinct)))
         return got
 
     def _compare(self, text, name, test, literals):

@@ -274,6 +274,54 @@ class FlatIndex:
         _lib.check(rc, "mirx_index_search_deep")
         return sc, ids
 
+    def search_leave_out(self, q, k, row_codes, query_codes, exclude_ids=None, allow=None, return_f64=False, max_left_out=-1):
+        """Leave-group-out search (mirx_index_search_leave_out): search_deep()'s results over the rows that do not share the
+        query's code -- row r is skipped for query i when query_codes[i] >= 0 and row_codes[r] == query_codes[i].  Negative
+        codes are nulls: such a query leaves nothing out, such a row is never left out.
+        row_codes: an int32 tensor on the index's device with one code per row, in the order of ids() (any other dtype, device
+        or length: ValueError).  query_codes: a tensor or sequence of nq ints.  exclude_ids / allow combine with it as in
+        search().  max_left_out: an upper bound on the rows one query leaves out, or -1 when unknown; it only picks the route
+        (speed), never the answer.  1 <= k <= 1024.  last_stats()["left_out"] counts the candidates the predicate dropped."""
+        k = int(k)
+        if not 1 <= k <= _lib.MAX_SEARCH_K:
+            raise ValueError(f"search_leave_out: k must be in [1, {_lib.MAX_SEARCH_K}], got {k}")
+        if not isinstance(row_codes, torch.Tensor) or row_codes.dtype != torch.int32:
+            raise ValueError("search_leave_out: row_codes must be an int32 tensor")
+        if row_codes.device != self.device:
+            raise ValueError(f"search_leave_out: row_codes must be on the index's device ({self.device}), got {row_codes.device}")
+        if row_codes.dim() != 1 or row_codes.numel() != len(self):
+            raise ValueError(f"search_leave_out: row_codes needs one code per row of the index ({len(self)}), "
+                             f"got shape {tuple(row_codes.shape)}")
+        q, ex = self._prep_queries(q, exclude_ids)
+        nq = q.shape[0]
+        qc = torch.as_tensor(query_codes).detach().reshape(-1)
+        if qc.numel() != nq:
+            raise ValueError(f"search_leave_out: query_codes needs one code per query ({nq}), got {qc.numel()}")
+        if qc.is_floating_point() or qc.dtype == torch.bool:
+            raise ValueError(f"search_leave_out: query_codes must be integers, got {qc.dtype}")
+        qc = qc.to(device=self.device, dtype=torch.int32).contiguous()
+        am = None if allow is None else self._prep_allow(allow)
+        if am is not None and am.numel() != len(self):
+            raise ValueError(f"allow needs one entry per row of the index ({len(self)}), got {am.numel()}")
+        rc_t = row_codes.detach().contiguous()
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+        if nq == 0:
+            return sc, ids
+        if len(self) == 0:
+            am = None                                              # an empty index: nothing to mask,
+            rc_t = torch.full((1,), -1, dtype=torch.int32, device=self.device)   # and no code to read (the ABI refuses a null)
+        scp = ctypes.c_void_p(sc.data_ptr())
+        with torch.cuda.device(self.device):
+            rc = self._lib.mirx_index_search_leave_out(self._h, ctypes.c_void_p(q.data_ptr()), nq, k,
+                                                       ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
+                                                       ctypes.c_void_p(am.data_ptr()) if am is not None else None,
+                                                       ctypes.c_void_p(rc_t.data_ptr()), ctypes.c_void_p(qc.data_ptr()),
+                                                       int(max_left_out), None if return_f64 else scp, scp if return_f64 else None,
+                                                       ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
+        _lib.check(rc, "mirx_index_search_leave_out")
+        return sc, ids
+
     def search_begin(self, q, k, exclude_ids=None):
         """First half of search(): enqueue the whole first pass on the current stream and return without waiting.
         -> a handle for search_end(); the index must not be used for anything else in between."""

@@ -432,6 +432,46 @@ class Collection:
             dev = cache.device_codes[name] = torch.from_numpy(codes).to(index.device)
         return distinct, dev
 
+    def _leave_out_check(self, field, values, nq, limit, group_by_field, param):
+        """The argument checks of search(leave_out_field=, leave_out_values=): host only, no device touched."""
+        from .expr import _kind
+        if field is None or values is None:
+            raise ValueError("leave_out_field and leave_out_values come together: the field, and one value (or None) per query")
+        if not isinstance(field, str) or not self.has_field(field):
+            raise ValueError(f"leave_out_field {field!r} is not a scalar field of {self.name} (fields: {', '.join(self._meta)})")
+        if group_by_field is not None:
+            raise ValueError("leave_out_field does not combine with group_by_field (grouping search has no leave-out form)")
+        if self._range_params(param) is not None:
+            raise ValueError("leave_out_field does not combine with a radius / range_filter (range search has no leave-out form)")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= int(limit) <= 1024:
+            raise ValueError(f"leave_out_field: limit must be an integer in [1, 1024], got {limit!r}")
+        if isinstance(values, (str, bytes)) or not hasattr(values, "__len__"):
+            raise ValueError("leave_out_values must be a sequence with one value (or None) per query")
+        if len(values) != nq:
+            raise ValueError(f"leave_out_values needs one value (or None) per query ({nq}), got {len(values)}")
+        column = self._meta[field]
+        want = "str" if field == "image_path" else (_kind(column[0]) if column else None)
+        for v in values:
+            if v is None:
+                continue
+            kind = _kind(v)
+            if kind is None or (want is not None and kind != want):
+                held = f"{type(column[0]).__name__} values such as {column[0]!r}" if column else "strings"
+                raise ValueError(f"leave_out_values: type mismatch: {field} holds {held}, got {v!r}")
+
+    def _leave_out_codes(self, field, values):
+        """-> (row codes: int32 on the index's device, cast once per collection state; one int32 code per query on the host, -1
+        for None and for a value no live row holds; the most rows one of the named values has)"""
+        _, codes = self._device_codes(field)
+        cache = self._expr
+        dev = cache.device_codes.get((field, "int32"))
+        if dev is None or dev.device != codes.device:
+            dev = cache.device_codes[(field, "int32")] = codes.to(torch.int32)
+        table, counts = cache.table(field)
+        qcodes = np.fromiter((-1 if v is None else table.get(v, -1) for v in values), dtype=np.int32, count=len(values))
+        named = qcodes[qcodes >= 0]
+        return dev, qcodes, int(counts[named].max()) if named.size else 0
+
     def _search_grouped(self, q, limit, group_by_field, group_size, fields, exclude_ids, expr):
         distinct, codes = self._device_codes(group_by_field)
         allow = None if expr is None else self._device_mask(expr)
@@ -441,7 +481,7 @@ class Collection:
         return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
 
     def search(self, data, anns_field="embedding", param=None, limit=10, output_fields=None, exclude_ids=None, expr=None,
-               group_by_field=None, group_size=1, strict_group_size=True):
+               group_by_field=None, group_size=1, strict_group_size=True, leave_out_field=None, leave_out_values=None):
         """-> list (one per query) of lists of Hit, best first.  `distance` follows Milvus:
         COSINE/IP -> similarity, L2 -> Euclidean distance (>= 0).  expr (pymilvus' scalar filter, mirx.expr) restricts the
         search to the rows it selects -- exactly, on the device (FlatIndex.search(allow=)) -- so there are fewer than `limit`
@@ -453,9 +493,26 @@ class Collection:
         group holding its best min(group_size, its eligible rows) rows (group_size <= 64, limit * group_size <= 16384); a
         hit's entity always carries the group field.  Exact (FlatIndex.search_grouped): strict_group_size=True is the only
         deterministic reading, so False is accepted and returns the same.  expr and exclude_ids work as without grouping; a
-        radius does not combine with grouping (ValueError: range_search is the other call)."""
+        radius does not combine with grouping (ValueError: range_search is the other call).
+        leave_out_field (a scalar field of the schema) with leave_out_values (one literal per query, or None) makes it the
+        leave-group-out search: query i skips every row whose field equals leave_out_values[i] -- the reference's
+        `r.image_path != query.image_path` (fusion_eval/metrics.py:65, milvus_adapter.py:204-207) for any field, e.g. the patient
+        of a study -- exactly, on the device (FlatIndex.search_leave_out), as one `expr='field != value'` search per query would.
+        None, or a value no row holds, leaves nothing out.  expr and exclude_ids combine with it; limit <= 1024; grouping and a
+        radius do not combine with it (ValueError, like an unknown field, a wrong length or a literal of the wrong type)."""
         q = self._queries(data)
         fields = output_fields or []
+        if leave_out_field is not None or leave_out_values is not None:
+            self._leave_out_check(leave_out_field, leave_out_values, q.shape[0], limit, group_by_field, param)
+            if self.num_entities == 0:
+                return [[] for _ in range(q.shape[0])]
+            limit = min(int(limit), self.num_entities)
+            codes, qcodes, most = self._leave_out_codes(leave_out_field, leave_out_values)
+            allow = None if expr is None else self._device_mask(expr)
+            sc, ids = self._ensure().search_leave_out(q, limit, codes, qcodes, exclude_ids=exclude_ids, allow=allow,
+                                                      max_left_out=most)
+            ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
+            return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
         if group_by_field is not None:
             if not self.has_field(group_by_field):
                 raise ValueError(f"group_by_field {group_by_field!r} is not a scalar field of {self.name} "
@@ -1004,11 +1061,14 @@ class MilvusRetriever:
             norms = torch.cat([out[i:i + 1].norm(2, 1, True) for i in range(out.shape[0])])
             return out / norms.clamp_min(1e-12).expand_as(out)
 
-    def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE", expr=None, group_by=None, group_size=1):
+    def search(self, query_image_path, top_k=10, search_params=None, metric_type="COSINE", expr=None, group_by=None, group_size=1,
+               leave_out=None):
         """-> (results, query_embedding).  results: best-first dicts {id, image_path, label,
         distance, similarity}; similarity = distance for COSINE/IP, 1 - d^2/2 for L2.  expr: Collection.search's filter.
         group_by (a scalar field) / group_size: Collection.search's grouping search -- top_k counts groups, the dicts come group
-        after group and gain a "group" key with the field's value (without group_by the dicts keep the reference's keys)."""
+        after group and gain a "group" key with the field's value (without group_by the dicts keep the reference's keys).
+        leave_out: (field, value) -- Collection.search's leave-group-out search: rows whose field equals value are skipped (the
+        dicts are unchanged)."""
         if isinstance(query_image_path, str):
             from PIL import Image
             img = Image.open(query_image_path).convert("RGB")
@@ -1024,13 +1084,23 @@ class MilvusRetriever:
             raise ValueError(f"metric type not match: index has {self.collection.metric_type}, search asked {metric_type}")
         hits = self.collection.search(data=query_embedding, anns_field="embedding", param=search_params,
                                       limit=top_k, output_fields=["image_path", "label"], expr=expr,
-                                      **self._grouping(group_by, group_size))[0]
+                                      **self._grouping(group_by, group_size), **self._leaving_out(leave_out, 1))[0]
         return [self._format(h, metric_type, group_by) for h in hits], query_embedding
 
     @staticmethod
     def _grouping(group_by, group_size):
         """Collection.search's grouping keywords, none when no grouping is asked for"""
         return {} if group_by is None else {"group_by_field": group_by, "group_size": group_size}
+
+    @staticmethod
+    def _leaving_out(leave_out, nq):
+        """Collection.search's leave-out keywords from search()'s (field, value) (nq = 1) or batch_search()'s (field, [values])"""
+        if leave_out is None:
+            return {}
+        if not isinstance(leave_out, (tuple, list)) or len(leave_out) != 2:
+            raise ValueError("leave_out is a pair: (field, value) for search, (field, [one value per query]) for batch_search")
+        field, values = leave_out
+        return {"leave_out_field": field, "leave_out_values": [values] if nq == 1 else values}
 
     @staticmethod
     def _format(hit, metric_type, group_by=None):
@@ -1042,9 +1112,10 @@ class MilvusRetriever:
             out["group"] = hit.entity.get(group_by)
         return out
 
-    def batch_search(self, query_image_paths, top_k=10, search_params=None, expr=None, group_by=None, group_size=1):
+    def batch_search(self, query_image_paths, top_k=10, search_params=None, expr=None, group_by=None, group_size=1, leave_out=None):
         """One batched embed + one batched search (the reference loops search(); results equal, to the bit: _embed_rows).
-        expr: Collection.search's filter, one for the whole batch.  group_by / group_size: as in search()."""
+        expr: Collection.search's filter, one for the whole batch.  group_by / group_size: as in search().  leave_out:
+        (field, [one value or None per query]) -- search()'s leave-group-out, each query with its own value."""
         if len(query_image_paths) == 0:
             return []
         from PIL import Image
@@ -1056,7 +1127,8 @@ class MilvusRetriever:
         if self.collection is None:
             self.load_collection()
         all_hits = self.collection.search(data=emb, param=search_params, limit=top_k, output_fields=["image_path", "label"],
-                                          expr=expr, **self._grouping(group_by, group_size))
+                                          expr=expr, **self._grouping(group_by, group_size),
+                                          **self._leaving_out(leave_out, None))
         return [[self._format(h, self.collection.metric_type, group_by) for h in hits] for hits in all_hits]
 
     def adapter(self, name=None):

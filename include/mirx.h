@@ -84,6 +84,8 @@ typedef struct mirx_search_stats {
     int64_t reranked;         /* rows re-scored in fp64 by tier 1, summed over queries      */
     int64_t overflowed;       /* queries whose candidate list overflowed its capacity       */
     int64_t incomplete;       /* queries whose completeness guard failed                    */
+    int64_t left_out;         /* candidates dropped by mirx_index_search_leave_out's predicate on the filter routes,
+                                 summed over the queries those routes answered              */
 } mirx_search_stats;
 
 const char *mirx_last_error(void);
@@ -185,7 +187,7 @@ int mirx_index_search_f64(mirx_index *ix, const float *q, int64_t nq, int k,
  *       up to this call has finished; stats / timings refer to this search.
  * Between the two calls the index is busy and the query / output buffers must stay valid: the pending search holds pointers
  * into the index's workspace and rows, so every call that uses the workspace or moves rows -- mirx_index_search, _search_f64,
- * _search_begin, _search_masked, _search_deep, _range_search, _rank_all, _rank_top, _rank_top_masked, _group_fill, _add, _reserve,
+ * _search_begin, _search_masked, _search_deep, _search_leave_out, _range_search, _rank_all, _rank_top, _rank_top_masked, _group_fill, _add, _reserve,
  * _remove_ids -- returns MIRX_ESTATE and changes nothing.  mirx_index_search_end, _range_fetch, _range_last_stats, _last_stats,
  * _last_timings, _get_rows, _get_ids, _size, _dim and _set_option stay callable.
  * mirx_index_search == begin + end.  (No reference counterpart: MilvusRetriever.search is a blocking RPC,
@@ -254,6 +256,39 @@ int mirx_index_search_deep(mirx_index *ix, const float *queries, int64_t nq, int
                            void *stream);
 int mirx_tier1_max_k(void);
 int64_t mirx_deep_min_rows(int k_eff, int64_t nq);
+
+/*
+ * Leave-group-out search: the top k of the rows that do NOT share the query's key.  Replaces the host-side filters
+ * `r.image_path != query.image_path` of fusion_eval/metrics.py:65 and retrieval_analysis/milvus_adapter.py:204-207 (every row
+ * whose field value equals the query's is dropped, not only the query's own row), which pymilvus cannot express for a batch:
+ * one `expr` serves all its queries.  Patient-wise evaluation of NIH ChestX-ray14 / VinDr / COVIDx galleries is the use.
+ *   row_codes    device, [mirx_index_size] int32, one code per row in row order (as an allow mask); a negative code is the
+ *                field's null and is never left out
+ *   query_codes  device, [nq] int32; a negative code leaves nothing out for that query
+ *   max_left_out a speed hint only: an upper bound on the rows any query of the call leaves out, or -1 = unknown (routes as 0)
+ *   queries, nq, k, exclude_ids, allow, the three outputs, stream: as for mirx_index_search_deep; 1 <= k <= 1024
+ * Row r is eligible for query i  <=>  r is live, allow[r] != 0 (when a mask is given), id[r] != exclude_ids[i] (when given)
+ * and !(query_codes[i] >= 0 && row_codes[r] == query_codes[i]).
+ * Result: the top k of the eligible rows, (score desc, id asc), (-1, -inf) in the slots past them -- ids, fp64 ranking scores
+ * and fp32 values bit for bit what mirx_index_search_masked returns for that one query under allow[r] = (row_codes[r] !=
+ * query_codes[i]) ANDed with the caller's mask, hence what a fresh index of the eligible rows returns.
+ * A null index, queries, ids, row_codes or query_codes, both score outputs null, or k out of range: MIRX_EINVAL before any
+ * device call.  Between mirx_index_search_begin and mirx_index_search_end: MIRX_ESTATE.
+ * Route, decided on the host as if k_eff were k (+1 with exclude ids) + max_left_out: the candidate lists of
+ * mirx_index_search while that is <= mirx_tier1_max_k(); the deep route while k + max_left_out <= 1024 and the rows that can rank number
+ * at least mirx_deep_min_rows of it; else the exact scan.  The sampled threshold is sized for that count.  The hint never
+ * changes the answer: on the filter routes the finalize kernel drops a candidate that shares the query's code BEFORE the
+ * completeness guard counts the list (it asks for k_eff eligible candidates and takes the k_eff-th eligible score), so a
+ * hint that is too small only sends more queries to the retry pass or the exact scan.  The exact scan turns the left-out
+ * entries of its fp64 score tile into NaN, which ranks before nothing, not even an empty slot.  Under a mask the routes are
+ * those of mirx_index_search_masked; where the allowed rows are gathered their codes are gathered with them.
+ * mirx_index_last_stats / _last_timings describe the call; left_out counts the dropped candidates.  No host wait beyond the
+ * routes' own, no floating-point atomics; the result does not depend on scheduling.
+ */
+int mirx_index_search_leave_out(mirx_index *ix, const float *queries, int64_t nq, int k, const int64_t *exclude_ids_or_null,
+                                const uint8_t *allow_or_null, const int32_t *row_codes, const int32_t *query_codes,
+                                int64_t max_left_out, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids,
+                                void *stream);
 
 /* Counters of the most recent range search on an index. */
 typedef struct mirx_range_stats {
