@@ -114,6 +114,10 @@ SYMBOLS = {
     "mirx_topk_merge": (_int, [_vp, _vp, _int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "mirx_rank_metrics": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _int, _int, ctypes.c_double, _int,
                                  ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_rank_metrics_grouped": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _int, _int, ctypes.c_double, _int,
+                                         ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_index_rank_metrics": (_int, [_vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _vp, _int, ctypes.c_double, _int,
+                                       ctypes.POINTER(ctypes.c_int32), _int, _vp, _vp, _vp, _vp, _vp]),
     "mirx_group_walk": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp,
                                _vp]),
     "mirx_group_count": (_int, [_vp, _vp, _i64, _i64, _vp, _vp]),

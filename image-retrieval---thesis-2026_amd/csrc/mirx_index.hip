@@ -122,7 +122,7 @@ struct mirx_index {
     // workspace (each buffer frees itself with the index)
     DevBuf q32p, q16, qnorm, tau, cnt, cand, ovf_cnt, ovf, groupmax, fail_list, retry_list, tau2, q16r, taur,
         scores, stage, rankwork, spill, rkeys, rpay, rhist, idperm, creq, cpos, cpart, mallow, mbias, mids, mrows, mcodes,
-        rstage, rcount, rxoff, rfirst, rexcl, rseg, rres;
+        rstage, rcount, rxoff, rfirst, rexcl, rseg, rres, mwalk;
     int *fail_count = nullptr;            // device
     mirx_search_stats *stats_dev = nullptr;
     int *fail_count_host = nullptr;       // pinned
@@ -1489,6 +1489,61 @@ int mirx_index_rank_top_masked(mirx_index *ix, const float *q, int64_t nq, int64
     if (rc) return rc;
     return rank_radix(ix, q, nq, k, exclude_ids_or_null, /*drop_excluded=*/true, out_ids, out_scores_or_null,
                       out_rank_scores_or_null, st, am);
+}
+
+int mirx_index_rank_metrics(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null, int self_kind,
+                            const int64_t *row_labels, const int64_t *query_labels, const int32_t *row_codes_or_null,
+                            const int32_t *query_codes_or_null, int rel_kind, double jaccard_threshold, int ap_kind,
+                            const int32_t *kappas, int nk, double *out_ap, int64_t *out_cnt, int64_t *out_nrel, int64_t *out_maxpos,
+                            void *stream) {
+    MIRX_CHECK(nq >= 0, "rank_metrics: nq < 0");
+    MIRX_CHECK(self_kind >= 0 && self_kind <= 2, "rank_metrics: self_kind must be 0, 1 or 2");
+    MIRX_CHECK(self_kind == 0 || exclude_ids_or_null, "rank_metrics: self_kind 1 and 2 need exclude_ids");
+    MIRX_CHECK((row_codes_or_null == nullptr) == (query_codes_or_null == nullptr),
+               "rank_metrics: row_codes and query_codes go together (both or neither)");
+    MIRX_CHECK(nk >= 0 && nk <= MIRX_MAX_KAPPAS && (nk == 0 || (kappas && out_cnt)), "rank_metrics: 0 <= nk <= 8");
+    MIRX_CHECK((rel_kind == 0 || rel_kind == 1) && (ap_kind == 0 || ap_kind == 1), "rank_metrics: bad kind");
+    MIRX_CHECK(nq == 0 || (q && query_labels && out_ap && out_nrel && out_maxpos), "rank_metrics: null buffer");
+    RankWalkArgs a{};
+    for (int j = 0; j < nk; ++j) {
+        MIRX_CHECK(kappas[j] >= 1, "rank_metrics: kappa must be >= 1");
+        a.kappas[j] = kappas[j];
+    }
+    MIRX_CHECK(ix, "rank_metrics: null index");
+    MIRX_ENTER_IDLE(ix, "rank_metrics");
+    MIRX_CHECK(nq == 0 || ix->size == 0 || row_labels, "rank_metrics: null row_labels");
+    if (nq == 0) return MIRX_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t n = ix->size;
+    RadixBatch rb{};
+    rb.per = std::min<int64_t>(1024, nq);
+    if (n > 0) {
+        int rc = radix_plan(ix, nq, "rank_metrics", st, &rb);
+        if (rc) return rc;
+    }
+    if (ix->mwalk.ensure(std::max<size_t>(256, rank_walk_workspace_bytes(rb.per, n))) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MIRX_ENOMEM, "rank_metrics: the walk's partials do not fit the device");
+    }
+    a.n = n; a.ids = ix->ids; a.self_kind = self_kind; a.row_labels = row_labels; a.row_codes = row_codes_or_null;
+    a.jaccard_threshold = jaccard_threshold; a.nk = nk; a.pay = rb.pa;
+    rank_walk_carve(a, ix->mwalk.p, rb.per);
+    for (int64_t b = 0; b < nq; b += rb.per) {
+        const int cnt = (int)std::min<int64_t>(rb.per, nq - b);
+        const int64_t *exb = exclude_ids_or_null ? exclude_ids_or_null + b : nullptr;
+        if (n > 0) {
+            int rc = prep_queries(ix, q + b * ix->dim, cnt, cnt, st);
+            if (rc) return rc;
+            // rank_all's order: the excluded row keeps its place behind every score
+            if ((rc = radix_sort_batch(ix, rb, ix->q32p.as<float>(), nullptr, cnt, exb, /*drop_excluded=*/false, nullptr, st))) return rc;
+        }
+        a.nq = cnt; a.exclude = exb; a.query_labels = query_labels + b;
+        a.query_codes = query_codes_or_null ? query_codes_or_null + b : nullptr;
+        a.out_ap = out_ap + b; a.out_cnt = reinterpret_cast<unsigned long long *>(out_cnt) + b * nk;
+        a.out_nrel = out_nrel + b; a.out_maxpos = out_maxpos + b;
+        MIRX_HIP(launch_rank_walk(a, rel_kind, ap_kind, st));
+    }
+    return MIRX_OK;
 }
 
 int mirx_index_group_fill(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null, int limit, int group_size,

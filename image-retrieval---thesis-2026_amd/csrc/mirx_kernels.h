@@ -295,8 +295,48 @@ struct RankMetricsArgs {
     double *out_ap;                // [nq]
     int64_t *out_cnt;              // [nq, nk]
     int64_t *out_nrel, *out_maxpos;
+    // leave-group-out (mirx_rank_metrics_grouped): read by the CODES instantiations only, which launch_rank_metrics picks when
+    // gallery_codes is set.  An entry whose id carries the query's code leaves the list like a dropped self entry.
+    const int32_t *gallery_codes;  // [n_labels] by id, or null
+    const int32_t *query_codes;    // [nq]; negative = the query leaves nothing out
 };
 hipError_t launch_rank_metrics(const RankMetricsArgs &a, int rel_kind, int ap_kind, hipStream_t st);
+
+// The same walk over the radix ranking's row payload (mirx_index_rank_metrics), parallel along the list: every query's list of
+// n rows is cut into segments of rank_walk_segment(n) entries, a multiple of 4096 that keeps the segments at or below 1024.
+// launch_rank_walk runs three passes:
+//   count    per (query, segment): entries taken out and relevant entries                                -> seg_cnt
+//   terms    per (query, segment): the AP terms, the per-kappa hits and the last relevant position of the segment, from the
+//            counts of the segments before it                                                            -> seg_ap, seg_max, out_cnt
+//   finish   one wavefront per query adds the segments' partials in a fixed order                        -> out_ap, out_nrel, out_maxpos
+// Every floating-point sum's order depends on n alone; out_cnt is zeroed first and added to with integer atomics.
+struct RankWalkArgs {
+    const int32_t *pay;            // [nq, n] rows, best first (RadixBatch::pa)
+    int64_t n;                     // rows per list
+    int nq;                        // lists of this batch
+    const int64_t *ids;            // [n] id of a row
+    const int64_t *exclude;        // [nq] or null
+    int self_kind;                 // 0: the excluded row is an ordinary entry, 1: never relevant, 2: also taken out
+    const int64_t *row_labels;     // [n] by row
+    const int64_t *query_labels;   // [nq]
+    const int32_t *row_codes;      // [n] by row, or null
+    const int32_t *query_codes;    // [nq], or null
+    double jaccard_threshold;
+    int32_t kappas[MIRX_MAX_KAPPAS];
+    int nk;
+    int64_t seg_len;               // rank_walk_segment(n)
+    int nseg;                      // ceil(n / seg_len)
+    int32_t *seg_cnt;              // [nq, nseg, 2] taken out, relevant
+    double *seg_ap;                // [nq, nseg]
+    int64_t *seg_max;              // [nq, nseg] largest 1-based relevant position of the segment, 0 = none
+    double *out_ap;                // [nq]
+    unsigned long long *out_cnt;   // [nq, nk]
+    int64_t *out_nrel, *out_maxpos;
+};
+int64_t rank_walk_segment(int64_t n);
+size_t rank_walk_workspace_bytes(int64_t per, int64_t n);   // seg_cnt, seg_ap, seg_max of `per` lists, each 256-byte aligned
+void rank_walk_carve(RankWalkArgs &a, void *workspace, int64_t per);   // fills seg_len, nseg and the three pointers from a.n
+hipError_t launch_rank_walk(const RankWalkArgs &a, int rel_kind, int ap_kind, hipStream_t st);
 
 // ---- k_gemm.hip -------------------------------------------------------------------------
 // The per-query candidate lists the filter GEMM fills and the finalize kernels (k_finalize.hip, k_range.hip) read through

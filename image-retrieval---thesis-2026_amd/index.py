@@ -388,6 +388,72 @@ class FlatIndex:
         _lib.check(rc, "mirx_index_rank_all")
         return (ids, sc) if with_scores else ids
 
+    def rank_metrics(self, q, row_labels, query_labels, kappas=(), exclude_ids=None, self_kind=0, row_codes=None,
+                     query_codes=None, jaccard_threshold=None, standard_ap=False):
+        """The metric tail of the FULL ranking of every query without the ranking (mirx_index_rank_metrics): what
+        metrics.rank_metrics_device returns for rank_all(q, exclude_ids) -- the same dict: ap [nq] f64 (NaN = no relevant
+        row), cnt [nq, len(kappas)], nrel, maxpos int64, on the index's device -- evaluated batch by batch out of the sort's
+        workspace, so no [nq, ntotal] tensor exists and the gallery size is bounded by the sort alone.
+        row_labels: int64 tensor on the index's device, one label (class id, or multi-hot bit mask with jaccard_threshold)
+        per row in the order of ids(); query_labels: nq ints.  self_kind says what the excluded id is: 0 an ordinary last
+        entry (compute_map's quirk), 1 never relevant (compute_map_multilabel), 2 also taken out of the list
+        (fusion_eval/metrics.py); 1 and 2 need exclude_ids.  row_codes (int32 tensor on the device, one per row) with
+        query_codes (nq ints): query i's list loses every row r with query_codes[i] >= 0 and row_codes[r] ==
+        query_codes[i] before anything is counted -- leave-group-out; negative codes are nulls.  Wrong dtypes, devices or
+        lengths: ValueError before any device work."""
+        who = "rank_metrics"
+        if self_kind not in (0, 1, 2):
+            raise ValueError(f"{who}: self_kind must be 0, 1 or 2, got {self_kind!r}")
+        if self_kind != 0 and exclude_ids is None:
+            raise ValueError(f"{who}: self_kind {self_kind} needs exclude_ids")
+        if (row_codes is None) != (query_codes is None):
+            raise ValueError(f"{who}: row_codes and query_codes come together")
+        ks = [int(k) for k in kappas]
+        if len(ks) > 8 or any(k < 1 for k in ks):
+            raise ValueError(f"{who}: at most 8 kappas, each at least 1, got {ks}")
+        size = len(self)
+        for name, t, dt in (("row_labels", row_labels, torch.int64), ("row_codes", row_codes, torch.int32)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt:
+                raise ValueError(f"{who}: {name} must be an {str(dt).split('.')[-1]} tensor")
+            if t.device != self.device:
+                raise ValueError(f"{who}: {name} must be on the index's device ({self.device}), got {t.device}")
+            if t.dim() != 1 or t.numel() != size:
+                raise ValueError(f"{who}: {name} needs one entry per row of the index ({size}), got shape {tuple(t.shape)}")
+        q, ex = self._prep_queries(q, exclude_ids)
+        nq = q.shape[0]
+
+        def per_query(name, v, dt):
+            t = torch.as_tensor(v).detach().reshape(-1)
+            if t.numel() != nq:
+                raise ValueError(f"{who}: {name} needs one entry per query ({nq}), got {t.numel()}")
+            if t.is_floating_point() or t.dtype == torch.bool:
+                raise ValueError(f"{who}: {name} must be integers, got {t.dtype}")
+            return t.to(device=self.device, dtype=dt).contiguous()
+        ql = per_query("query_labels", query_labels, torch.int64)
+        qc = None if query_codes is None else per_query("query_codes", query_codes, torch.int32)
+        rl = row_labels.detach().contiguous()
+        rc_t = None if row_codes is None else row_codes.detach().contiguous()
+        ap = torch.empty(nq, dtype=torch.float64, device=self.device)
+        cnt = torch.empty((nq, len(ks)), dtype=torch.int64, device=self.device)
+        nrel = torch.empty(nq, dtype=torch.int64, device=self.device)
+        maxpos = torch.empty(nq, dtype=torch.int64, device=self.device)
+        out = {"ap": ap, "cnt": cnt, "nrel": nrel, "maxpos": maxpos}
+        if nq == 0:
+            return out
+        if size == 0 and rc_t is not None:
+            rc_t = torch.full((1,), -1, dtype=torch.int32, device=self.device)   # no code to read, and codes come in pairs
+        karr = (ctypes.c_int32 * max(1, len(ks)))(*ks)
+        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+        with torch.cuda.device(self.device):
+            rc = self._lib.mirx_index_rank_metrics(
+                self._h, vp(q), nq, vp(ex), int(self_kind), vp(rl), vp(ql), vp(rc_t), vp(qc),
+                0 if jaccard_threshold is None else 1, float(jaccard_threshold or 0.0), 1 if standard_ap else 0, karr, len(ks),
+                vp(ap), vp(cnt), vp(nrel), vp(maxpos), _stream_ptr(self.device))
+        _lib.check(rc, "mirx_index_rank_metrics")
+        return out
+
     def range_search(self, q, lo, hi=float("inf"), exclude_ids=None, allow=None, return_f64=False):
         """Every row whose fp64 ranking score s (dot product; NEGATIVE SQUARED distance for L2) has lo < s <= hi -- not the
         best k.  -> (lims int64 [nq + 1], scores [total], ids int64 [total]) on the index device: the hits of query i are

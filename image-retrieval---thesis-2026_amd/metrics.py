@@ -35,13 +35,16 @@ def _is_cuda(x):
 
 
 def rank_metrics_device(ranks, gallery_labels, query_labels, kappas=(), query_ids=None, drop_self=False,
-                        jaccard_threshold=None, standard_ap=False):
+                        jaccard_threshold=None, standard_ap=False, gallery_codes=None, query_codes=None):
     """One device pass over ranked lists (include/mirx.h: mirx_rank_metrics).
 
     ranks: CUDA int64 [nq, n] (row per query, best first; a transposed view of a contiguous
     [n, nq] tensor is copied).  labels: class ids, or multi-hot bit masks when `jaccard_threshold`
     is given.  -> dict of CUDA tensors: ap [nq] f64 (NaN = no relevant id), cnt [nq, len(kappas)]
-    i64, nrel [nq] i64, maxpos [nq] i64."""
+    i64, nrel [nq] i64, maxpos [nq] i64.
+    gallery_codes (one int per gallery id, aligned with gallery_labels) with query_codes (one per list): every entry that
+    carries its query's code is taken out of the list before anything is counted (mirx_rank_metrics_grouped: leave-group-out;
+    negative codes are nulls).  Both or neither."""
     import ctypes
     from . import _lib
     lib = _lib.load()
@@ -56,6 +59,13 @@ def rank_metrics_device(ranks, gallery_labels, query_labels, kappas=(), query_id
     if ql.numel() != nq:
         raise ValueError("rank_metrics_device: one query label per ranked list")
     qi = None if query_ids is None else torch.as_tensor(query_ids).to(device=dev, dtype=torch.int64).contiguous()
+    if (gallery_codes is None) != (query_codes is None):
+        raise ValueError("rank_metrics_device: gallery_codes and query_codes come together")
+    if gallery_codes is not None:
+        gc = torch.as_tensor(gallery_codes).to(device=dev, dtype=torch.int32).contiguous()
+        qc = torch.as_tensor(query_codes).to(device=dev, dtype=torch.int32).contiguous()
+        if gc.numel() != gl.numel() or qc.numel() != nq:
+            raise ValueError("rank_metrics_device: one gallery code per gallery label and one query code per ranked list")
     ks = [int(k) for k in kappas]
     karr = (ctypes.c_int32 * max(1, len(ks)))(*ks)
     ap = torch.empty(nq, dtype=torch.float64, device=dev)
@@ -65,16 +75,42 @@ def rank_metrics_device(ranks, gallery_labels, query_labels, kappas=(), query_id
     vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
     with torch.cuda.device(dev):
         st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.mirx_rank_metrics(vp(ranks), nq, n, ranks.stride(0) if nq else n, vp(gl), gl.numel(), vp(ql),
+        if gallery_codes is not None:
+            one = torch.full((1,), -1, dtype=torch.int32, device=dev)     # the ABI refuses null codes, also for empty inputs
+            _lib.check(lib.mirx_rank_metrics_grouped(
+                vp(ranks), nq, n, ranks.stride(0) if nq > 1 else n, vp(gl), gl.numel(), vp(ql), vp(qi), 1 if drop_self else 0,
+                0 if jaccard_threshold is None else 1, float(jaccard_threshold or 0.0), 1 if standard_ap else 0, karr, len(ks),
+                vp(gc) or vp(one), vp(qc) or vp(one), vp(ap), vp(cnt), vp(nrel), vp(maxpos), st), "mirx_rank_metrics_grouped")
+            return {"ap": ap, "cnt": cnt, "nrel": nrel, "maxpos": maxpos}
+        _lib.check(lib.mirx_rank_metrics(vp(ranks), nq, n, ranks.stride(0) if nq > 1 else n, vp(gl), gl.numel(), vp(ql),
                                          vp(qi), 1 if drop_self else 0, 0 if jaccard_threshold is None else 1,
                                          float(jaccard_threshold or 0.0), 1 if standard_ap else 0, karr, len(ks),
                                          vp(ap), vp(cnt), vp(nrel), vp(maxpos), st), "mirx_rank_metrics")
     return {"ap": ap, "cnt": cnt, "nrel": nrel, "maxpos": maxpos}
 
 
-def _compute_map_device(ranks, gnd, kappas):
+def group_codes(groups, n=None):
+    """One value per image (strings or ints; equal values are one group) -> int32 dictionary codes, all >= 0."""
+    g = _np(groups)
+    if g.ndim != 1 or (n is not None and g.shape[0] != n):
+        raise ValueError(f"groups needs one value per image{'' if n is None else f' ({n})'}, got shape {tuple(g.shape)}")
+    return np.unique(g, return_inverse=True)[1].reshape(-1).astype(np.int32)
+
+
+def _kept(order, codes, qi):
+    """A ranked list with the entries of query qi's group (and empty slots, id -1) taken out."""
+    order = order[order >= 0]
+    return order[codes[order] != codes[qi]]
+
+
+def _compute_map_device(ranks, gnd, kappas, codes=None):
     gnd_t = torch.as_tensor(_np(gnd)).to(ranks.device)
-    res = rank_metrics_device(ranks.t(), gnd_t, gnd_t, kappas)
+    res = rank_metrics_device(ranks.t(), gnd_t, gnd_t, kappas, gallery_codes=codes, query_codes=codes)
+    return map_from_device_result(res, kappas)
+
+
+def map_from_device_result(res, kappas):
+    """compute_map's four results from one rank_metrics_device / FlatIndex.rank_metrics result (trapezoidal AP)."""
     aps = res["ap"].cpu().numpy()
     nq, nk = aps.shape[0], len(kappas)
     nrel = res["nrel"].cpu().numpy().astype(np.float64)
@@ -100,13 +136,30 @@ def _label_bitmasks(labels):
 
 
 # ---- test.py:38-54 ---------------------------------------------------------------------------
-def retrieval_accuracy(output, target, topk=(1,), topk_ids=None):
+def retrieval_accuracy(output, target, topk=(1,), topk_ids=None, groups=None):
     """R@k in percent (list of 0-d float32 values, like the reference's tensors).
 
     `output` is the [N,N] score matrix of the reference call; pass ``topk_ids=[N,>=max k]``
-    (ranked ids with self already excluded, e.g. from FlatIndex.search) to skip the matrix."""
+    (ranked ids with self already excluded, e.g. from FlatIndex.search) to skip the matrix.
+    groups (one value per image): query i's list loses every image of i's group, itself included, before the first k
+    are looked at; with topk_ids pass lists long enough to keep k entries (FlatIndex.search_leave_out's already are; id
+    -1 is an empty slot)."""
     target_np = _np(target)
     maxk = max(topk)
+    if groups is not None:
+        n = target_np.shape[0]
+        codes = group_codes(groups, n)
+        full = np.argsort(-_np(output), axis=1, kind="stable") if topk_ids is None else _np(topk_ids)
+        hit_at = np.full(n, np.iinfo(np.int64).max)                  # 0-based position of the first hit in the kept list
+        for i in range(n):
+            hits = np.flatnonzero(target_np[_kept(full[i], codes, i)[:maxk]] == target_np[i])
+            if hits.size:
+                hit_at[i] = hits[0]
+        res = []
+        for k in topk:
+            val = np.float32(np.float32(np.count_nonzero(hit_at < k)) * np.float32(100.0 / n))
+            res.append(torch.tensor(val) if torch is not None else val)
+        return res
     if topk_ids is None:
         scores = _np(output)
         order = np.argsort(-scores, axis=1, kind="stable")[:, :maxk]
@@ -135,13 +188,21 @@ def compute_ap(ranks, nres):
 
 
 # ---- test.py:95-146 --------------------------------------------------------------------------
-def compute_map(ranks, gnd, kappas=[]):
+def compute_map(ranks, gnd, kappas=[], groups=None):
     """mAP, per-query AP, mean precision@kappas, per-query precision@kappas.
 
     `ranks` is [db_size, n_queries] (column i = ranking of query i).  Quirks of the
     reference kept: the query itself counts as a positive (it sits at the last rank because
     its score was -inf, test.py:119,1081); precision@kappa divides by
-    min(largest 1-based positive rank, kappa) (test.py:139)."""
+    min(largest 1-based positive rank, kappa) (test.py:139).
+    groups (one value per image, e.g. the patient): column i loses every image of i's group -- the query itself with
+    them, so it is no longer that last positive -- and the same formulas apply to what is left; nres is the number of
+    positives left, and a query with none has AP NaN and is skipped in both means (test.py:122-126)."""
+    if groups is not None:
+        codes = group_codes(groups, len(gnd))
+        if _is_cuda(ranks) and len(kappas) <= 8 and len(gnd):
+            return _compute_map_device(ranks, gnd, list(kappas), codes)
+        return _compute_map_grouped(_np(ranks), _np(gnd), list(kappas), codes)
     if _is_cuda(ranks) and len(kappas) <= 8 and len(gnd):
         return _compute_map_device(ranks, gnd, list(kappas))
     ranks = _np(ranks)
@@ -168,6 +229,25 @@ def compute_map(ranks, gnd, kappas=[]):
             prs[:, jk] = np.sum(rel & (r + 1.0 <= kq[None, :]), axis=0) / kq
     # every query has at least itself as a positive, so the reference's "nempty" is 0
     return float(np.sum(aps) / nq), aps, np.sum(prs, axis=0) / nq, prs
+
+
+def _compute_map_grouped(ranks, gnd, kappas, codes):
+    nq, nk = len(gnd), len(kappas)
+    aps = np.full(nq, np.nan)
+    prs = np.zeros((nq, nk))
+    for i in range(nq):
+        pos = np.flatnonzero(gnd[_kept(ranks[:, i], codes, i)] == gnd[i])   # 0-based positions of the positives left
+        if pos.size == 0:
+            prs[i] = np.nan
+            continue
+        aps[i] = compute_ap(pos, pos.size)
+        for jk, kap in enumerate(kappas):
+            kq = min(float(pos[-1] + 1), float(kap))
+            prs[i, jk] = np.count_nonzero(pos + 1 <= kq) / kq
+    ok = ~np.isnan(aps)
+    if not ok.any():
+        return float("nan"), aps, np.full(nk, np.nan), prs
+    return float(np.sum(aps[ok]) / ok.sum()), aps, np.sum(prs[ok], axis=0) / ok.sum(), prs
 
 
 # ---- test.py:149-162 -------------------------------------------------------------------------
@@ -198,22 +278,33 @@ def _prf(true, pred):
 
 
 # ---- test.py:165-223 -------------------------------------------------------------------------
-def compute_classification_metrics(labels, dists, k_values=[1, 5, 10, 15, 20], ranks=None):
+def compute_classification_metrics(labels, dists, k_values=[1, 5, 10, 15, 20], ranks=None, groups=None):
     """Majority-vote classification metrics per k (percent), keys as in the reference.
 
     `dists` is the reference's [N,N] score matrix (higher = more similar); pass
     ``ranks=[db, N]`` (column per query, as torch.argsort(dists, dim=0, descending=True)) to
     reuse a ranking.  sklearn's macro/weighted precision/recall/F1 (zero_division=0) and
-    accuracy are computed directly."""
+    accuracy are computed directly.
+    groups (one value per image): column i loses every image of i's group before its first k entries vote; an id of -1
+    (an empty slot of FlatIndex.search_leave_out) is not a vote, and a query left without votes predicts no class."""
     labels_np = _np(labels)
     if ranks is None:
         ranks = np.argsort(-_np(dists), axis=0, kind="stable")
     ranks = _np(ranks)
     n = labels_np.shape[0]
+    kept = None
+    if groups is not None:
+        codes = group_codes(groups, n)
+        kept = [_kept(ranks[:, i], codes, i) for i in range(n)]
+        none = labels_np.min() - 1 if n else 0                        # stands for "no prediction": equals no label
     results = {}
     for k in k_values:
-        top = labels_np[ranks[:k, :]]                                 # [k, N]
-        pred = np.array([majority_vote(top[:, i]) for i in range(n)])
+        if kept is None:
+            top = labels_np[ranks[:k, :]]                             # [k, N]
+            pred = np.array([majority_vote(top[:, i]) for i in range(n)])
+        else:
+            votes = [majority_vote(labels_np[kept[i][:k]]) for i in range(n)]
+            pred = np.array([none if v is None else v for v in votes])
         p, r, f, w = _prf(labels_np, pred)
         results[k] = {
             "precision_macro": float(p.mean() * 100.0),
@@ -228,15 +319,19 @@ def compute_classification_metrics(labels, dists, k_values=[1, 5, 10, 15, 20], r
 
 
 # ---- test.py:941-985 -------------------------------------------------------------------------
-def compute_map_multilabel(dists, labels, threshold=0.5, ranks=None):
+def compute_map_multilabel(dists, labels, threshold=0.5, ranks=None, groups=None):
     """Jaccard-thresholded mAP over the full ranking (query itself never relevant).
-    `ranks` (optional) is [db, N] column-per-query like np.argsort(-dists, axis=0)."""
+    `ranks` (optional) is [db, N] column-per-query like np.argsort(-dists, axis=0).
+    groups (one value per image): column i loses every image of i's group before the AP is taken; queries left without
+    a relevant image are skipped, as those without one are today."""
+    codes = None if groups is None else group_codes(groups, _np(labels).shape[0])
     if _is_cuda(ranks):
         masks = _label_bitmasks(labels)
         if masks is not None:
             n = masks.shape[0]
             res = rank_metrics_device(ranks.t(), masks, masks, (), query_ids=np.arange(n),
-                                      jaccard_threshold=float(threshold), standard_ap=True)
+                                      jaccard_threshold=float(threshold), standard_ap=True,
+                                      gallery_codes=codes, query_codes=codes)
             aps = res["ap"].cpu().numpy()
             aps = aps[~np.isnan(aps)]
             return np.mean(aps) if aps.size else 0
@@ -253,6 +348,11 @@ def compute_map_multilabel(dists, labels, threshold=0.5, ranks=None):
     aps = []
     pos = np.arange(1, n + 1, dtype=np.float64)
     for i in range(n):
+        if codes is not None:
+            sr = rel[i][_kept(ranks[:, i], codes, i)]
+            if sr.any():
+                aps.append(float(np.sum(np.cumsum(sr)[sr] / pos[:sr.size][sr]) / np.count_nonzero(sr)))
+            continue
         tot = np.count_nonzero(rel[i])
         if tot > 0:
             sr = rel[i][ranks[:, i]]

@@ -279,12 +279,15 @@ def query_gallery(collection, query_rows, top_k=0, nprobe=10, batch_size=4096):
     return out
 
 
-def evaluate_map(model, data_loader, device, jaccard_threshold=0.4):
+def evaluate_map(model, data_loader, device, jaccard_threshold=0.4, groups=None):
     """nih_multilabel_training.evaluate_map: mAP (percent) over all pairs of the loader's images, relevance =
     Jaccard(labels) > threshold.  Quirks kept: the query itself stays in its list with similarity -1 and counts as a
     relevant item whenever its own Jaccard (1 for any labelled image) passes the threshold; queries without a relevant
-    item are skipped.  On a GPU the ranking and the AP run on the device (FlatIndex.rank_all + mirx_rank_metrics)."""
-    from .metrics import _average_precision, _label_bitmasks, rank_metrics_device
+    item are skipped.  On a GPU the ranking and the AP run on the device, the ranking never leaving the sort's workspace
+    (FlatIndex.rank_metrics), so the NIH set's 112 120 images need no [N, N] array.
+    groups (one value per image of the loader, in its order, e.g. the patient id): every query's list loses the images of
+    its own group, itself included, before the AP is taken -- leave-one-patient-out."""
+    from .metrics import _average_precision, _label_bitmasks, group_codes
     model.eval()
     embs, labs = [], []
     with torch.no_grad():
@@ -299,9 +302,11 @@ def evaluate_map(model, data_loader, device, jaccard_threshold=0.4):
         from .index import FlatIndex
         ix = FlatIndex(emb.shape[1], "IP", emb.device.index)
         ix.add(emb)
-        ranks = ix.rank_all(emb, exclude_ids=torch.arange(n))          # self last, like its score of -1
-        ap = rank_metrics_device(ranks, masks, masks, (), jaccard_threshold=float(jaccard_threshold),
-                                 standard_ap=True)["ap"].cpu().numpy()
+        mt = torch.from_numpy(masks).to(emb.device)
+        codes = None if groups is None else torch.from_numpy(group_codes(groups, n)).to(emb.device)
+        ap = ix.rank_metrics(emb, mt, mt, (), exclude_ids=torch.arange(n), self_kind=0,   # self last, like its score of -1
+                             row_codes=codes, query_codes=codes, jaccard_threshold=float(jaccard_threshold),
+                             standard_ap=True)["ap"].cpu().numpy()
         ap = ap[~np.isnan(ap)]
         return float(np.mean(ap) * 100.0) if ap.size else 0.0
     emb = emb.cpu()
@@ -309,10 +314,14 @@ def evaluate_map(model, data_loader, device, jaccard_threshold=0.4):
     sim.fill_diagonal_(-1)
     lab = labels.float()
     aps = []
+    keep = None if groups is None else group_codes(groups, n)
     for i in range(n):
         inter = (lab[i] * lab).sum(dim=1)
         union = (lab[i] + lab).clamp(max=1).sum(dim=1)
         rel = ((inter / (union + 1e-8)) > jaccard_threshold).float().numpy()
+        row = sim[i].numpy()
+        if keep is not None:
+            rel, row = rel[keep != keep[i]], row[keep != keep[i]]
         if rel.sum() > 0:
-            aps.append(_average_precision(rel, sim[i].numpy()))
+            aps.append(_average_precision(rel, row))
     return float(np.mean(aps) * 100.0) if aps else 0.0

@@ -472,6 +472,54 @@ class Collection:
         named = qcodes[qcodes >= 0]
         return dev, qcodes, int(counts[named].max()) if named.size else 0
 
+    def self_metrics(self, label_field="label", kappas=(1, 5, 10), leave_out_field=None, standard_ap=False, chunk_rows=4096):
+        """Self-retrieval metrics of the collection's live rows from field names, without re-embedding anything: every row
+        queries the collection with its own vector and is excluded from its own list; relevance is equality of
+        `label_field`.  The full rankings are walked on the device (FlatIndex.rank_metrics), `chunk_rows` queries per call, and
+        never exist as arrays.  leave_out_field (e.g. the patient of a study): a row's list also loses every row that shares
+        its value of that field -- leave-group-out.
+        Default: evaluate()'s numbers (mirx.evaluate.evaluate_embeddings) -- the trapezoidal AP, precision@kappa over
+        min(largest positive rank, kappa), and without leave_out_field the row itself as the positive at the last rank.
+        standard_ap=True: the mean of precision at each relevant rank with the row itself taken out of its list and
+        precision@kappa = hits / kappa (fusion_eval/metrics.py).
+        -> {"mAP", "pr": mean precision@kappa [len(kappas)], "acc": R@kappa in percent float32 [len(kappas)], "n_queries",
+        "n_skipped": rows without a relevant row left (skipped in mAP and pr)}.  Unknown fields: ValueError."""
+        from .metrics import map_from_device_result
+        for what, f in (("label_field", label_field), ("leave_out_field", leave_out_field)):
+            if f is not None and (not isinstance(f, str) or not self.has_field(f)):
+                raise ValueError(f"{what} {f!r} is not a scalar field of {self.name} (fields: {', '.join(self._meta)})")
+        if label_field is None:
+            raise ValueError("self_metrics: label_field names the field that decides relevance")
+        ks = [int(k) for k in kappas]
+        if len(ks) > 8 or any(k < 1 for k in ks):
+            raise ValueError(f"self_metrics: at most 8 kappas, each at least 1, got {list(kappas)}")
+        n = self.num_entities
+        if n == 0:
+            return {"mAP": float("nan"), "pr": np.full(len(ks), np.nan), "acc": np.zeros(len(ks), dtype=np.float32),
+                    "n_queries": 0, "n_skipped": 0}
+        index = self._ensure()
+        _, labels = self._device_codes(label_field)
+        codes = None if leave_out_field is None else self._leave_out_codes(leave_out_field, [])[0]
+        parts = []
+        for s in range(0, n, int(chunk_rows)):
+            q, ids = index.rows(s, min(int(chunk_rows), n - s))
+            e = s + q.shape[0]
+            parts.append(index.rank_metrics(q, labels, labels[s:e], ks, exclude_ids=ids, self_kind=2 if standard_ap else 0,
+                                            row_codes=codes, query_codes=None if codes is None else codes[s:e],
+                                            standard_ap=standard_ap))
+        res = {k: torch.cat([p[k] for p in parts], dim=0) for k in parts[0]}
+        hit = (res["cnt"] > 0).sum(dim=0).cpu().numpy()
+        acc = np.array([np.float32(np.float32(h) * np.float32(100.0 / n)) for h in hit], dtype=np.float32)
+        if standard_ap:
+            aps = res["ap"].cpu().numpy()
+            ok = ~np.isnan(aps)
+            cnt = res["cnt"].cpu().numpy().astype(np.float64)
+            m_ap = float(aps[ok].mean()) if ok.any() else float("nan")
+            pr = (cnt[ok] / np.asarray(ks, dtype=np.float64)[None, :]).mean(axis=0) if ok.any() else np.full(len(ks), np.nan)
+        else:
+            m_ap, aps, pr, _ = map_from_device_result(res, ks)
+        return {"mAP": m_ap, "pr": pr, "acc": acc, "n_queries": n, "n_skipped": int(np.isnan(aps).sum())}
+
     def _search_grouped(self, q, limit, group_by_field, group_size, fields, exclude_ids, expr):
         distinct, codes = self._device_codes(group_by_field)
         allow = None if expr is None else self._device_mask(expr)

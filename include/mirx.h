@@ -765,6 +765,42 @@ int mirx_rank_metrics(const int64_t *ranks, int64_t nq, int64_t n, int64_t row_s
                       void *stream);
 
 /*
+ * mirx_rank_metrics with a group taken out of every list (leave-group-out evaluation: a patient's other studies are neither
+ * hits nor misses).  gallery_codes[id] (device [n_labels], indexed like gallery_labels) and query_codes[q] (device [nq]): entry
+ * `id` is taken out of query q's list iff query_codes[q] >= 0 && 0 <= id < n_labels && gallery_codes[id] == query_codes[q].
+ * Such an entry is treated exactly like the dropped self entry of drop_self: it has no position (later ranks move up), is never
+ * relevant and counts in none of out_cnt, out_nrel, out_maxpos; the trapezoidal AP and the caller's kq = min(max(pos), kappa)
+ * rule therefore apply to the list AFTER removal.  A negative query code leaves nothing out (all negative: mirx_rank_metrics'
+ * outputs bit for bit); a negative gallery code is the field's null and is never left out.  out_ap is NaN when no relevant entry
+ * remains.  Everything else, the MIRX_EINVAL cases included (null codes among them), is mirx_rank_metrics'.
+ */
+int mirx_rank_metrics_grouped(const int64_t *ranks, int64_t nq, int64_t n, int64_t row_stride,
+                              const int64_t *gallery_labels, int64_t n_labels, const int64_t *query_labels,
+                              const int64_t *query_ids_or_null, int drop_self, int rel_kind,
+                              double jaccard_threshold, int ap_kind, const int32_t *kappas, int nk,
+                              const int32_t *gallery_codes, const int32_t *query_codes,
+                              double *out_ap, int64_t *out_cnt, int64_t *out_nrel, int64_t *out_maxpos,
+                              void *stream);
+
+/*
+ * The full ranking of every query, evaluated without ever leaving the sort's workspace: per query the outputs are those of
+ * mirx_index_rank_all(q, exclude_ids_or_null) followed by mirx_rank_metrics_grouped over that ranking (labels and codes mapped
+ * from row order to ids) -- integer outputs equal, out_ap within 1e-12, NaN in the same places -- and no [nq, size] array exists
+ * on either side of the call.  row_labels / row_codes_or_null: device [size] in ROW order (the order of the index's ids);
+ * query_labels / query_codes_or_null: device [nq].  Both codes pointers or neither (MIRX_EINVAL).  self_kind says what the
+ * excluded id is: 0 = an ordinary last entry (mirx_rank_metrics with query_ids = NULL), 1 = never relevant (query_ids = exclude,
+ * drop_self = 0), 2 = also taken out of the list (drop_self = 1); 1 and 2 need exclude_ids.  rel_kind, jaccard_threshold,
+ * ap_kind, kappas (host), nk <= 8 as in mirx_rank_metrics.  Batches, workspace (32 bytes per row and query of a batch, plus 20
+ * bytes per 4096 rows) and the sort are mirx_index_rank_top's; there is no host wait.  A query's out_ap bits depend on the
+ * gallery and the query alone, not on nq or its place in the call.  MIRX_ESTATE between mirx_index_search_begin and _end.
+ */
+int mirx_index_rank_metrics(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null, int self_kind,
+                            const int64_t *row_labels, const int64_t *query_labels,
+                            const int32_t *row_codes_or_null, const int32_t *query_codes_or_null,
+                            int rel_kind, double jaccard_threshold, int ap_kind, const int32_t *kappas, int nk,
+                            double *out_ap, int64_t *out_cnt, int64_t *out_nrel, int64_t *out_maxpos, void *stream);
+
+/*
  * Grouping search: the best hits PER GROUP instead of the best rows -- pymilvus' collection.search(..., group_by_field=..,
  * group_size=.., strict_group_size=True), which the reference's callers get from their Milvus service and its own scripts never
  * exercise ("the nearest case of every diagnosis", "ten different patients, not ten follow-ups of one").  The contract, per
