@@ -6,11 +6,13 @@
 //   -> finalize (sort candidates, completeness guard, fp64 re-rank, top-k)
 //   -> exact scan (fp64 score tiles + row top-k) for the queries the guard rejected.
 // The only host<->device synchronisation is one read of the rejected-query count.
-// A masked search (mirx_index_search_masked) runs the same sequence over a SearchRows that stands for the allowed rows.
-// The deep search (mirx_index_search_deep) runs it for k_eff past TIER1_MAX_K with SearchRows::deep set: gemm_plan_deep's candidate
-// regions, its own threshold rank and k_finalize at DEEP_CAP; where that route does not apply the call is handed to the two above.
-// The leave-group-out search (mirx_index_search_leave_out) runs the masked / deep sequence with SearchRows::rcodes / qcodes set:
-// k_finalize's CODES twins drop the candidates that carry the query's code, and the exact scan turns their scores into NaN.
+// The six top-k entry points (mirx_index_search, _f64, _begin, _masked, _deep, _leave_out) each fill a SearchCall; search_call
+// checks it, asks mirx_route.h which route answers and builds the one SearchRows the sequence runs over:
+//   a mask           a SearchRows that stands for the allowed rows (neutralised in place, or gathered);
+//   the deep route   k_eff past TIER1_MAX_K with SearchRows::deep set: gemm_plan_deep's candidate regions, its own threshold rank
+//                    and k_finalize at DEEP_CAP;
+//   leave-group-out  SearchRows::rcodes / qcodes set: k_finalize's CODES twins drop the candidates that carry the query's code,
+//                    and the exact scan turns their scores into NaN.
 // A range search (mirx_index_range_search) runs prep -> threshold from the radius -> filter GEMM -> its own finalize, the radix
 // ranking for what that cannot answer, and a CSR assembly (k_range.hip).
 // The radix ranking (radix_plan / radix_sort_batch) serves mirx_index_rank_all / _rank_top / _rank_top_masked and the range
@@ -24,6 +26,7 @@
 #include <vector>
 
 #include "mirx_kernels.h"
+#include "mirx_route.h"
 
 using namespace mirx;
 
@@ -61,7 +64,7 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-// What a search scans.  The index itself for the plain calls; a masked call passes a stand-in for its allowed rows:
+// What a search scans (built by search_call alone).  The index itself without a mask; under one, a stand-in for the allowed rows:
 //   tier 1    the index's rows with `bias` (-inf on masked rows) in the sample and filter GEMMs, and for the queries the guard
 //             rejects the exact scan over all rows with the masked ones neutralised (mpos, ids = the masked ids)
 //   exact     either that neutralised scan, or g32 / ids = the allowed rows gathered into scratch, n of them
@@ -77,12 +80,6 @@ struct SearchRows {
     const int32_t *rcodes = nullptr;      // one code per row of g32 (gathered with the rows where those are gathered), or null
     const int32_t *qcodes = nullptr;      // one code per query of the batch
     int64_t extra = 0;                    // rows a query may leave out (the caller's hint): sizes the sampled threshold only
-};
-
-// The leave-group-out arguments of a call, as its entry point received them.
-struct LeaveOut {
-    const int32_t *rcodes, *qcodes;       // by index row / by query of the call
-    int64_t extra;                        // max_left_out, at least 0
 };
 
 struct mirx_index {
@@ -166,7 +163,7 @@ struct DeviceGuard {
 // The index's device stays selected until the entry point returns (declares the DeviceGuard `dg`).
 #define MIRX_SELECT_DEVICE(ix, who)  \
     DeviceGuard dg((ix)->device);    \
-    if (!dg.ok) return fail(MIRX_EHIP, who ": cannot select the index device")
+    if (!dg.ok) return fail(MIRX_EHIP, std::string(who) + ": cannot select the index device")
 
 // The first step of every entry point that uses the workspace or moves rows (searches, rankings, add, reserve, remove): a search
 // that is begun holds GemmArgs / FinalizeArgs that point into both, so until mirx_index_search_end the index is busy.
@@ -181,6 +178,8 @@ int enter_idle(mirx_index *ix, const char *who) {
 #define MIRX_ENTER_IDLE(ix, who)                    \
     if (int rc_ = enter_idle(ix, who)) return rc_;  \
     MIRX_SELECT_DEVICE(ix, who)
+// MIRX_CHECK for the bodies several entry points share: `who` (a C string) goes in front of the message.
+#define MIRX_WHO_CHECK(who, cond, msg) MIRX_CHECK(cond, std::string(who) + ": " msg)
 
 bool is_device_pointer(const void *p) {
     hipPointerAttribute_t attr;
@@ -302,24 +301,16 @@ int exact_pass(mirx_index *ix, const SearchRows &sr, const float *q32p, const in
     return MIRX_OK;
 }
 
-// ---- the deep route (mirx_index_search_deep) -------------------------------------------------------------------
-// The sampled threshold is the j-th largest of `ngroups` group maxima of every stride-th row, ngroups * stride ~ size *
-// groups_per_tile / 256: it resolves candidate counts only up to about half the groups deep.  The deep route aims at
-// target = DEEP_TARGET_MUL * k_eff + DEEP_TARGET_ADD candidates per query (k_eff, the 2 eps band below the k-th score, room for
-// tau < lo) and is taken only where target <= ngroups * stride / 2, i.e. from target * DEEP_GROUP_ROWS / groups_per_tile(bn)
-// rows on; smaller galleries go to the exact scan, where it costs little.
-int64_t deep_target(int64_t k_eff) { return (int64_t)DEEP_TARGET_MUL * k_eff + DEEP_TARGET_ADD; }
+// ---- the deep route (mirx_index_search_deep; where it is taken: mirx_route.h) ------------------------------------
+// The constants the route decision reads.
+RouteLimits route_limits() { return {TIER1_MIN_ROWS, TIER1_MAX_K, MAX_K, DEEP_TARGET_MUL, DEEP_TARGET_ADD, DEEP_GROUP_ROWS}; }
 
-int64_t deep_min_rows(int64_t k_eff, int bn) {
-    return std::max<int64_t>(TIER1_MIN_ROWS, deep_target(k_eff) * DEEP_GROUP_ROWS / gemm_groups_per_tile(bn));
-}
-
-// The rank j whose group maximum leaves about `target` rows above it.  A fraction f of the groups has its maximum above tau when
-// each of a group's G sampled rows passes with probability p, 1 - f = (1 - p)^G; the rows expected above tau are p * G * ngroups *
+// The rank j whose group maximum leaves about target = deep_target(k_eff) (mirx_route.h) rows above it.  A fraction f of the groups
+// has its maximum above tau when each of a group's G sampled rows passes with probability p, 1 - f = (1 - p)^G; the rows expected above tau are p * G * ngroups *
 // stride = -ln(1 - f) * ngroups * stride for large G.  So f = 1 - exp(-target / (ngroups * stride)), at most one half.  (Speed
 // only: the guard decides what is answered.)
 int deep_sample_rank(int64_t k_eff, int ngroups, int64_t stride) {
-    const double f = 1.0 - std::exp(-(double)deep_target(k_eff) / ((double)ngroups * (double)stride));
+    const double f = 1.0 - std::exp(-(double)deep_target(route_limits(), k_eff) / ((double)ngroups * (double)stride));
     const int64_t j = (int64_t)std::ceil(f * ngroups);
     return (int)std::max<int64_t>(1, std::min<int64_t>(j, ngroups / 2));
 }
@@ -544,75 +535,6 @@ int batch_back(mirx_index *ix) {
     return MIRX_OK;
 }
 
-// The tier-1 sequence answers when the tiers are on auto, `rows` rows can rank (the gallery, or a masked call's allowed rows)
-// and the candidate lists hold k plus the excluded id (plus `extra`, the rows a leave-group-out query may drop); else the exact
-// scan answers directly.
-bool tier1_route(const mirx_index *ix, int64_t rows, int k, const int64_t *exclude, int64_t extra = 0) {
-    return ix->tiers == MIRX_TIER_AUTO && rows >= TIER1_MIN_ROWS && k + (exclude ? 1 : 0) + extra <= TIER1_MAX_K;
-}
-
-// The search of an index that enter_idle has let in.  wait_last = false: the last internal batch is left pending
-// (mirx_index_search_begin); batch_back completes it.
-int search_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude,
-                float *out_val, double *out_f64_user, int64_t *out_ids, hipStream_t st, bool wait_last = true,
-                const SearchRows *masked = nullptr, const LeaveOut *lo = nullptr) {
-    MIRX_CHECK(k >= 1 && k <= MAX_K, "search: k must be in [1, 1024]");
-    MIRX_CHECK(nq >= 0, "search: nq < 0");
-    MIRX_CHECK(nq == 0 || (q && out_ids && (out_val || out_f64_user)), "search: null buffer");
-    MIRX_HIP(hipMemsetAsync(ix->stats_dev, 0, sizeof(mirx_search_stats), st));
-    ix->stats_host = mirx_search_stats{};
-    ix->stats_host.nq = nq;
-    ix->spans.clear();
-    ix->ev_used = 0;
-    if (nq == 0) return MIRX_OK;
-
-    SearchRows sr;
-    if (masked) {
-        sr = *masked;
-    } else {
-        sr.g32 = ix->g32;
-        sr.ids = ix->ids;
-        sr.n = ix->size;
-        sr.tier1 = tier1_route(ix, ix->size, k, exclude, lo ? lo->extra : 0);
-        if (lo) {
-            sr.rcodes = lo->rcodes;
-            sr.qcodes = lo->qcodes;
-            sr.extra = lo->extra;
-        }
-    }
-    const int32_t *qcodes = sr.qcodes;
-    for (int64_t q0 = 0; q0 < nq; q0 += QUERY_BATCH) {
-        if (qcodes) sr.qcodes = qcodes + q0;
-        const int64_t nb = std::min<int64_t>(QUERY_BATCH, nq - q0);
-        const float *qb = q + q0 * ix->dim;
-        const int64_t *exb = exclude ? exclude + q0 : nullptr;
-        float *ovb = out_val ? out_val + q0 * k : nullptr;
-        int64_t *oib = out_ids + q0 * k;
-        // fp64 ranking scores are always produced (user buffer or workspace)
-        double *ofb;
-        if (out_f64_user) {
-            ofb = out_f64_user + q0 * k;
-        } else {
-            MIRX_HIP(ix->stage.ensure((size_t)nb * k * sizeof(double)));
-            ofb = ix->stage.as<double>();
-        }
-        int rc = batch_front(ix, qb, nb, k, exb, ovb, ofb, oib, sr, st);
-        if (rc) return rc;
-        if (wait_last || q0 + QUERY_BATCH < nq) {
-            rc = batch_back(ix);
-            if (rc) return rc;
-        }
-    }
-    return MIRX_OK;
-}
-
-// mirx_index_search / _search_f64 / _search_begin
-int search_plain(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude, float *out_val, double *out_f64,
-                 int64_t *out_ids, void *stream, bool wait_last) {
-    MIRX_ENTER_IDLE(ix, "search");
-    return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, reinterpret_cast<hipStream_t>(stream), wait_last);
-}
-
 // A call's row mask on the device: a device pointer as it is, a host mask through ix->mallow (enqueued on st).
 int device_allow(mirx_index *ix, const uint8_t *allow, hipStream_t st, const char *who, const uint8_t **out) {
     *out = allow;
@@ -745,6 +667,171 @@ int mask_prepare(mirx_index *ix, const uint8_t *allow, size_t gather_bytes, hipS
     if (total < 0 || total > size) return fail(MIRX_EHIP, std::string(who) + ": the scan returned an impossible count");
     *n_allowed = total;
     return MIRX_OK;
+}
+
+// ---- the top-k search call ------------------------------------------------------------------------------------------------
+// Every argument a top-k entry point can receive: each of the six fills one and hands it to search_call.
+struct SearchCall {
+    const char *who;                      // the entry point, in front of every message
+    mirx_index *ix;
+    const float *q;
+    int64_t nq;
+    int k;
+    const int64_t *exclude;               // one id per query, or null
+    float *out_val;                       // fp32 reported values and / or
+    double *out_f64;                      //   fp64 ranking scores
+    int64_t *out_ids;
+    void *stream;
+    bool wait_last = true;                // false: the last internal batch is left pending (mirx_index_search_begin); batch_back completes it
+    bool allow_deep = false;              // the deep route is open to the call (mirx_index_search_deep / _leave_out)
+    const uint8_t *allow = nullptr;       // the row mask, host or device, or null
+    bool has_n_allow = false;             // the entry point takes the mask's length from its caller (mirx_index_search_masked):
+    int64_t n_allow = 0;                  //   it must be the index's size
+    bool leave_out = false;               // mirx_index_search_leave_out: codes, queries and outputs are required, even at nq == 0
+    const int32_t *rcodes = nullptr;      // one code per index row
+    const int32_t *qcodes = nullptr;      // one code per query
+    int64_t max_left_out = 0;             // the caller's bound on the rows a query leaves out, -1 = unknown: picks the route only
+};
+
+// The one top-k search: checks the call, enters idle, counts the mask, asks mirx_route.h for the route, builds the SearchRows it
+// names and runs the internal batches over it.
+int search_call(const SearchCall &c) {
+    MIRX_WHO_CHECK(c.who, c.k >= 1 && c.k <= MAX_K, "k must be in [1, 1024]");
+    MIRX_WHO_CHECK(c.who, c.nq >= 0, "nq < 0");
+    MIRX_WHO_CHECK(c.who, !c.leave_out || (c.rcodes && c.qcodes), "null codes");
+    MIRX_WHO_CHECK(c.who, (c.nq == 0 && !c.leave_out) || (c.q && c.out_ids && (c.out_val || c.out_f64)), "null buffer");
+    MIRX_WHO_CHECK(c.who, c.max_left_out >= -1, "max_left_out must be -1 (unknown) or a row count");
+    mirx_index *ix = c.ix;
+    MIRX_ENTER_IDLE(ix, c.who);
+    if (c.has_n_allow) {
+        MIRX_WHO_CHECK(c.who, c.n_allow == ix->size, "the mask needs one byte per row of the index (n_allow != size)");
+        MIRX_WHO_CHECK(c.who, c.allow || c.n_allow == 0, "null mask");
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+    MIRX_HIP(hipMemsetAsync(ix->stats_dev, 0, sizeof(mirx_search_stats), st));
+    ix->stats_host = mirx_search_stats{};
+    ix->stats_host.nq = c.nq;
+    ix->spans.clear();
+    ix->ev_used = 0;
+    if (c.nq == 0) return MIRX_OK;
+
+    // ---- the route (an empty index has nothing to mask: the plain call, where every slot becomes (-1, -inf)) -------------------
+    const int64_t size = ix->size;
+    const bool masked = c.allow && size > 0;
+    const RouteLimits lim = route_limits();
+    RouteCall rc{};
+    rc.tiers_auto = ix->tiers == MIRX_TIER_AUTO;
+    rc.size = size;
+    rc.k = c.k;
+    rc.has_exclude = c.exclude != nullptr;
+    rc.extra = std::max<int64_t>(c.max_left_out, 0);
+    rc.allow_deep = c.allow_deep;
+    rc.tile_groups = gemm_groups_per_tile(gemm_query_tile(std::min<int64_t>(c.nq, QUERY_BATCH)));   // the widest tile of the call's batches
+    rc.row_bytes = (int64_t)ix->dimp * sizeof(float) + sizeof(int64_t);
+    rc.gather_max = ix->mask_gather_bytes < 0 ? (int64_t)EXACT_WS_BYTES : ix->mask_gather_bytes;
+    int64_t n_allowed = size;
+    if (masked) {
+        // one mask pass, one count; the gather's scratch is sized before the count is known
+        const int64_t most_rows = route_most_rows(lim, rc);
+        if (c.rcodes && ix->mcodes.ensure((size_t)most_rows * sizeof(int32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MIRX_ENOMEM, std::string(c.who) + ": the gathered codes do not fit the device");
+        }
+        int r = mask_prepare(ix, c.allow, (size_t)std::min(most_rows * rc.row_bytes, rc.gather_max), st, &n_allowed, c.who);
+        if (r) return r;
+    }
+    const Route route = route_pick(lim, rc, masked, n_allowed);
+
+    SearchRows sr;
+    sr.tier1 = route.list != RouteList::EXACT;
+    sr.deep = route.list == RouteList::DEEP;
+    sr.rcodes = c.rcodes;                 // in row order: right wherever all rows are scanned
+    sr.qcodes = c.qcodes;
+    sr.extra = rc.extra;
+    switch (route.rows) {
+        case RouteRows::INDEX:
+            sr.g32 = ix->g32;
+            sr.ids = ix->ids;
+            sr.n = size;
+            break;
+        case RouteRows::NEUTRALISED:
+            // all rows, the masked ones neutralised: tier 1 by the bias, the exact scan by -inf scores and the masked ids
+            sr.g32 = ix->g32;
+            sr.ids = ix->mids.as<int64_t>();
+            sr.n = size;
+            sr.mpos = ix->cpos.as<int32_t>();
+            sr.bias = sr.tier1 ? ix->mbias.as<float>() : nullptr;
+            break;
+        case RouteRows::GATHERED: {
+            // few allowed rows: gather them (ascending, so ids keep their order) and scan only those; their codes go with them
+            if ((size_t)(n_allowed * rc.row_bytes) > ix->mrows.bytes)
+                return fail(MIRX_EHIP, std::string(c.who) + ": the gather scratch is smaller than the count needs");
+            float *s32 = ix->mrows.as<float>();
+            int64_t *sid = reinterpret_cast<int64_t *>(s32 + n_allowed * ix->dimp);
+            MIRX_HIP(launch_compact_gather(ix->g32, ix->ids, ix->cpos.as<int32_t>(), size, ix->dimp, s32, sid, st));
+            sr.g32 = s32;
+            sr.ids = sid;
+            sr.n = n_allowed;
+            if (c.rcodes) {
+                if ((size_t)n_allowed * sizeof(int32_t) > ix->mcodes.bytes)
+                    return fail(MIRX_EHIP, std::string(c.who) + ": the code scratch is smaller than the count needs");
+                MIRX_HIP(launch_mask_gather_codes(c.rcodes, ix->cpos.as<int32_t>(), size, ix->mcodes.as<int32_t>(), st));
+                sr.rcodes = ix->mcodes.as<int32_t>();
+            }
+            break;
+        }
+        case RouteRows::NONE:             // nothing is allowed: n = 0, every slot reads (-1, -inf) and no row is scored
+            break;
+    }
+
+    // ---- the internal batches -----------------------------------------------------------------------------------------------
+    for (int64_t q0 = 0; q0 < c.nq; q0 += QUERY_BATCH) {
+        if (c.qcodes) sr.qcodes = c.qcodes + q0;
+        const int64_t nb = std::min<int64_t>(QUERY_BATCH, c.nq - q0);
+        const float *qb = c.q + q0 * ix->dim;
+        const int64_t *exb = c.exclude ? c.exclude + q0 : nullptr;
+        float *ovb = c.out_val ? c.out_val + q0 * c.k : nullptr;
+        int64_t *oib = c.out_ids + q0 * c.k;
+        // fp64 ranking scores are always produced (user buffer or workspace)
+        double *ofb;
+        if (c.out_f64) {
+            ofb = c.out_f64 + q0 * c.k;
+        } else {
+            MIRX_HIP(ix->stage.ensure((size_t)nb * c.k * sizeof(double)));
+            ofb = ix->stage.as<double>();
+        }
+        int r = batch_front(ix, qb, nb, c.k, exb, ovb, ofb, oib, sr, st);
+        if (r) return r;
+        if (c.wait_last || q0 + QUERY_BATCH < c.nq) {
+            r = batch_back(ix);
+            if (r) return r;
+        }
+    }
+    return MIRX_OK;
+}
+
+// mirx_index_rank_top and _rank_top_masked (masked: allow / n_allow are the caller's, and n_allow must be the index's size).
+int rank_top_call(const char *who, mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude, bool masked,
+                  const uint8_t *allow, int64_t n_allow, float *out_val, double *out_f64, int64_t *out_ids, void *stream) {
+    MIRX_WHO_CHECK(who, k >= 1, "k must be at least 1");
+    MIRX_WHO_CHECK(who, nq >= 0, "nq < 0");
+    MIRX_WHO_CHECK(who, out_ids, "out_ids is null");
+    MIRX_WHO_CHECK(who, out_val || out_f64, "both score outputs are null");
+    MIRX_ENTER_IDLE(ix, who);
+    if (masked) {
+        MIRX_WHO_CHECK(who, n_allow == ix->size, "the mask needs one byte per row of the index (n_allow != size)");
+        MIRX_WHO_CHECK(who, allow || n_allow == 0, "null mask");
+    }
+    MIRX_WHO_CHECK(who, q || nq == 0, "null queries");
+    MIRX_WHO_CHECK(who, k <= ix->size, "k is larger than the index");
+    if (nq == 0) return MIRX_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uint8_t *am = nullptr;          // (masked and past the checks: the index has rows, so the mask is not null)
+    if (masked) {
+        int rc = device_allow(ix, allow, st, who, &am);
+        if (rc) return rc;
+    }
+    return rank_radix(ix, q, nq, k, exclude, /*drop_excluded=*/true, out_ids, out_val, out_f64, st, am);
 }
 
 // ---- range search (k_range.hip) -----------------------------------------------------------------------------------------
@@ -1150,169 +1237,66 @@ int mirx_index_get_ids(const mirx_index *ix, int64_t first, int64_t n, int64_t *
     return MIRX_OK;
 }
 
+// The top-k entry points: each fills a SearchCall (who, the index, queries, nq, k, exclude ids, the three outputs, the stream, then
+// what only it has) for search_call.
 int mirx_index_search(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                       float *out_scores, int64_t *out_ids, void *stream) {
-    return search_plain(ix, q, nq, k, exclude_ids_or_null, out_scores, nullptr, out_ids, stream, /*wait_last=*/true);
+    return search_call({"search", ix, q, nq, k, exclude_ids_or_null, out_scores, nullptr, out_ids, stream});
 }
 
 int mirx_index_search_f64(mirx_index *ix, const float *q, int64_t nq, int k,
                           const int64_t *exclude_ids_or_null, double *out_rank_scores, int64_t *out_ids,
                           void *stream) {
-    return search_plain(ix, q, nq, k, exclude_ids_or_null, nullptr, out_rank_scores, out_ids, stream, /*wait_last=*/true);
+    return search_call({"search_f64", ix, q, nq, k, exclude_ids_or_null, nullptr, out_rank_scores, out_ids, stream});
 }
 
 int mirx_index_search_begin(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                             float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream) {
-    const int rc = search_plain(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, stream,
-                                /*wait_last=*/false);
+    SearchCall c{"search_begin", ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, stream};
+    c.wait_last = false;
+    const int rc = search_call(c);
     if (rc == MIRX_OK) ix->begun = true;
     return rc;
-}
-
-// The plain search of mirx_index_search_deep: the deep route where it applies, else search_impl as mirx_index_search runs it.
-// With `lo` (mirx_index_search_leave_out) the route is picked as if k_eff were larger by lo->extra; with k + extra past MAX_K (the
-// excluded id rides on top, as it always has at k = MAX_K) neither list route is open and search_impl scans exactly.
-static int search_deep_plain(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude, float *out_val,
-                             double *out_f64, int64_t *out_ids, hipStream_t st, const LeaveOut *lo = nullptr) {
-    const int64_t k_eff = (int64_t)k + (exclude ? 1 : 0) + (lo ? lo->extra : 0);
-    const int bn = gemm_query_tile(std::min<int64_t>(std::max<int64_t>(nq, 1), QUERY_BATCH));   // the widest tile of the call's batches
-    if (ix->tiers != MIRX_TIER_AUTO || k_eff <= TIER1_MAX_K || k + (lo ? lo->extra : 0) > MAX_K || ix->size < deep_min_rows(k_eff, bn))
-        return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st, /*wait_last=*/true, nullptr, lo);
-    SearchRows sr;
-    sr.g32 = ix->g32;
-    sr.ids = ix->ids;
-    sr.n = ix->size;
-    sr.tier1 = sr.deep = true;
-    if (lo) {
-        sr.rcodes = lo->rcodes;
-        sr.qcodes = lo->qcodes;
-        sr.extra = lo->extra;
-    }
-    return search_impl(ix, q, nq, k, exclude, out_val, out_f64, out_ids, st, /*wait_last=*/true, &sr);
-}
-
-// mirx_index_search_masked (deep = false) and the masked form of mirx_index_search_deep: one mask pass, one count, then the route.
-// With `lo` (the masked form of mirx_index_search_leave_out) the routes count lo->extra more rows per query, and where the allowed
-// rows are gathered their codes are gathered with them, into the order of the gathered ids.
-static int search_masked_impl(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
-                              const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
-                              int64_t *out_ids, void *stream, bool deep, const LeaveOut *lo = nullptr) {
-    MIRX_ENTER_IDLE(ix, "search_masked");
-    MIRX_CHECK(n_allow == ix->size, "search_masked: the mask needs one byte per row of the index (n_allow != size)");
-    MIRX_CHECK(allow || n_allow == 0, "search_masked: null mask");
-    MIRX_CHECK(k >= 1 && k <= MAX_K, "search_masked: k must be in [1, 1024]");
-    MIRX_CHECK(nq >= 0, "search_masked: nq < 0");
-    MIRX_CHECK(nq == 0 || (q && out_ids && (out_scores_or_null || out_rank_scores_or_null)), "search_masked: null buffer");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (nq == 0 || ix->size == 0)
-        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
-                           /*wait_last=*/true, nullptr, lo);
-    const int64_t extra = lo ? lo->extra : 0;
-    // the gather's scratch is sized before the count is known: with the filter route open only fewer than TIER1_MIN_ROWS
-    // allowed rows are ever gathered, else any number whose rows fit the limit
-    const size_t row_bytes = (size_t)ix->dimp * sizeof(float) + sizeof(int64_t);
-    const size_t gather_max = ix->mask_gather_bytes < 0 ? EXACT_WS_BYTES : (size_t)ix->mask_gather_bytes;
-    // the deep route is open to the call when its k_eff is past the candidate lists' and the tiers are on auto; it is taken when
-    // the allowed rows reach deep_min_rows, with the same bias (route A of DESIGN 32)
-    const int64_t k_eff = (int64_t)k + (exclude_ids_or_null ? 1 : 0) + extra;
-    deep = deep && ix->tiers == MIRX_TIER_AUTO && k_eff > TIER1_MAX_K && k + extra <= MAX_K;
-    const int64_t deep_rows = deep ? deep_min_rows(k_eff, gemm_query_tile(std::min<int64_t>(nq, QUERY_BATCH))) : 0;
-    const int64_t most_rows = deep ? std::min(ix->size, deep_rows - 1)
-                                   : (tier1_route(ix, TIER1_MIN_ROWS, k, exclude_ids_or_null, extra) ? std::min(ix->size, TIER1_MIN_ROWS - 1) : ix->size);
-    if (lo && ix->mcodes.ensure((size_t)most_rows * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MIRX_ENOMEM, "search_masked: the gathered codes do not fit the device");
-    }
-    int64_t n_allowed = 0;
-    int rc = mask_prepare(ix, allow, std::min((size_t)most_rows * row_bytes, gather_max), st, &n_allowed, "search_masked");
-    if (rc) return rc;
-    if (n_allowed == ix->size) {          // nothing masked: the plain search, bit for bit
-        if (deep) return search_deep_plain(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st, lo);
-        return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
-                           /*wait_last=*/true, nullptr, lo);
-    }
-    SearchRows sr;
-    sr.tier1 = deep ? n_allowed >= deep_rows : tier1_route(ix, n_allowed, k, exclude_ids_or_null, extra);
-    if (lo) {
-        sr.rcodes = lo->rcodes;                                    // in row order: right wherever all rows are scanned
-        sr.qcodes = lo->qcodes;
-        sr.extra = extra;
-    }
-    sr.deep = deep && sr.tier1;
-    const size_t gather_bytes = (size_t)n_allowed * row_bytes;
-    if (sr.tier1 || (n_allowed > 0 && gather_bytes > gather_max)) {
-        // all rows, the masked ones neutralised: tier 1 by the bias, the exact scan by -inf scores and the masked ids
-        sr.g32 = ix->g32;
-        sr.ids = ix->mids.as<int64_t>();
-        sr.n = ix->size;
-        sr.mpos = ix->cpos.as<int32_t>();
-        sr.bias = sr.tier1 ? ix->mbias.as<float>() : nullptr;
-    } else if (n_allowed > 0) {
-        // few allowed rows: gather them (ascending, so ids keep their order) and scan only those
-        if (gather_bytes > ix->mrows.bytes) return fail(MIRX_EHIP, "search_masked: the gather scratch is smaller than the count needs");
-        float *s32 = ix->mrows.as<float>();
-        int64_t *sid = reinterpret_cast<int64_t *>(s32 + n_allowed * ix->dimp);
-        MIRX_HIP(launch_compact_gather(ix->g32, ix->ids, ix->cpos.as<int32_t>(), ix->size, ix->dimp, s32, sid, st));
-        sr.g32 = s32;
-        sr.ids = sid;
-        sr.n = n_allowed;
-        if (lo) {
-            if ((size_t)n_allowed * sizeof(int32_t) > ix->mcodes.bytes)
-                return fail(MIRX_EHIP, "search_masked: the code scratch is smaller than the count needs");
-            MIRX_HIP(launch_mask_gather_codes(lo->rcodes, ix->cpos.as<int32_t>(), ix->size, ix->mcodes.as<int32_t>(), st));
-            sr.rcodes = ix->mcodes.as<int32_t>();
-        }
-    }                                     // else nothing is allowed: n = 0, every slot reads (-1, -inf) and no row is scored
-    return search_impl(ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, st,
-                       /*wait_last=*/true, &sr);
 }
 
 int mirx_index_search_masked(mirx_index *ix, const float *q, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                              const uint8_t *allow, int64_t n_allow, float *out_scores_or_null, double *out_rank_scores_or_null,
                              int64_t *out_ids, void *stream) {
-    return search_masked_impl(ix, q, nq, k, exclude_ids_or_null, allow, n_allow, out_scores_or_null, out_rank_scores_or_null, out_ids,
-                              stream, /*deep=*/false);
+    SearchCall c{"search_masked", ix, q, nq, k, exclude_ids_or_null, out_scores_or_null, out_rank_scores_or_null, out_ids, stream};
+    c.allow = allow;
+    c.has_n_allow = true;
+    c.n_allow = n_allow;
+    return search_call(c);
 }
 
 int mirx_index_search_deep(mirx_index *ix, const float *queries, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                            const uint8_t *allow_or_null, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids,
                            void *stream) {
-    MIRX_CHECK(k >= 1 && k <= MAX_K, "search_deep: k must be in [1, 1024]");
-    MIRX_CHECK(ix, "search_deep: null index");
-    MIRX_CHECK(nq >= 0, "search_deep: nq < 0");
-    MIRX_CHECK(nq == 0 || (queries && out_ids && (out_values_or_null || out_f64_or_null)), "search_deep: null buffer");
-    if (allow_or_null)
-        return search_masked_impl(ix, queries, nq, k, exclude_ids_or_null, allow_or_null, ix->size, out_values_or_null, out_f64_or_null,
-                                  out_ids, stream, /*deep=*/true);
-    MIRX_ENTER_IDLE(ix, "search_deep");
-    return search_deep_plain(ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
-                             reinterpret_cast<hipStream_t>(stream));
+    SearchCall c{"search_deep", ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids, stream};
+    c.allow_deep = true;
+    c.allow = allow_or_null;
+    return search_call(c);
 }
 
 int mirx_index_search_leave_out(mirx_index *ix, const float *queries, int64_t nq, int k, const int64_t *exclude_ids_or_null,
                                 const uint8_t *allow_or_null, const int32_t *row_codes, const int32_t *query_codes,
                                 int64_t max_left_out, float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids,
                                 void *stream) {
-    MIRX_CHECK(k >= 1 && k <= MAX_K, "search_leave_out: k must be in [1, 1024]");
-    MIRX_CHECK(nq >= 0, "search_leave_out: nq < 0");
-    MIRX_CHECK(row_codes && query_codes, "search_leave_out: null codes");
-    MIRX_CHECK(queries && out_ids && (out_values_or_null || out_f64_or_null), "search_leave_out: null buffer");
-    MIRX_CHECK(max_left_out >= -1, "search_leave_out: max_left_out must be -1 (unknown) or a row count");
-    MIRX_CHECK(ix, "search_leave_out: null index");
-    const LeaveOut lo{row_codes, query_codes, std::max<int64_t>(max_left_out, 0)};
-    if (allow_or_null)
-        return search_masked_impl(ix, queries, nq, k, exclude_ids_or_null, allow_or_null, ix->size, out_values_or_null, out_f64_or_null,
-                                  out_ids, stream, /*deep=*/true, &lo);
-    MIRX_ENTER_IDLE(ix, "search_leave_out");
-    return search_deep_plain(ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
-                             reinterpret_cast<hipStream_t>(stream), &lo);
+    SearchCall c{"search_leave_out", ix, queries, nq, k, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids, stream};
+    c.allow_deep = true;
+    c.allow = allow_or_null;
+    c.leave_out = true;
+    c.rcodes = row_codes;
+    c.qcodes = query_codes;
+    c.max_left_out = max_left_out;
+    return search_call(c);
 }
 
 int mirx_tier1_max_k(void) { return TIER1_MAX_K; }
 
 int64_t mirx_deep_min_rows(int k_eff, int64_t nq) {
     if (k_eff < 1 || nq < 1) return -1;
-    return deep_min_rows(k_eff, gemm_query_tile(std::min<int64_t>(nq, QUERY_BATCH)));
+    return deep_min_rows(route_limits(), k_eff, gemm_groups_per_tile(gemm_query_tile(std::min<int64_t>(nq, QUERY_BATCH))));
 }
 
 int mirx_index_range_search(mirx_index *ix, const float *q, int64_t nq, double lo, double hi, const int64_t *exclude_ids_or_null,
@@ -1458,37 +1442,15 @@ int mirx_index_rank_all(mirx_index *ix, const float *q, int64_t nq, const int64_
 
 int mirx_index_rank_top(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
                         float *out_scores_or_null, double *out_rank_scores_or_null, int64_t *out_ids, void *stream) {
-    MIRX_CHECK(k >= 1, "rank_top: k must be at least 1");
-    MIRX_CHECK(nq >= 0, "rank_top: nq < 0");
-    MIRX_CHECK(out_ids, "rank_top: out_ids is null");
-    MIRX_CHECK(out_scores_or_null || out_rank_scores_or_null, "rank_top: both score outputs are null");
-    MIRX_ENTER_IDLE(ix, "rank_top");
-    MIRX_CHECK(q || nq == 0, "rank_top: null queries");
-    MIRX_CHECK(k <= ix->size, "rank_top: k is larger than the index");
-    if (nq == 0) return MIRX_OK;
-    return rank_radix(ix, q, nq, k, exclude_ids_or_null, /*drop_excluded=*/true, out_ids, out_scores_or_null,
-                      out_rank_scores_or_null, reinterpret_cast<hipStream_t>(stream));
+    return rank_top_call("rank_top", ix, q, nq, k, exclude_ids_or_null, /*masked=*/false, nullptr, 0, out_scores_or_null,
+                         out_rank_scores_or_null, out_ids, stream);
 }
 
 int mirx_index_rank_top_masked(mirx_index *ix, const float *q, int64_t nq, int64_t k, const int64_t *exclude_ids_or_null,
                                const uint8_t *allow, int64_t n_allow, float *out_scores_or_null,
                                double *out_rank_scores_or_null, int64_t *out_ids, void *stream) {
-    MIRX_ENTER_IDLE(ix, "rank_top_masked");
-    MIRX_CHECK(n_allow == ix->size, "rank_top_masked: the mask needs one byte per row of the index (n_allow != size)");
-    MIRX_CHECK(allow || n_allow == 0, "rank_top_masked: null mask");
-    MIRX_CHECK(k >= 1, "rank_top_masked: k must be at least 1");
-    MIRX_CHECK(nq >= 0, "rank_top_masked: nq < 0");
-    MIRX_CHECK(out_ids, "rank_top_masked: out_ids is null");
-    MIRX_CHECK(out_scores_or_null || out_rank_scores_or_null, "rank_top_masked: both score outputs are null");
-    MIRX_CHECK(q || nq == 0, "rank_top_masked: null queries");
-    MIRX_CHECK(k <= ix->size, "rank_top_masked: k is larger than the index");
-    if (nq == 0) return MIRX_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const uint8_t *am = nullptr;
-    int rc = device_allow(ix, allow, st, "rank_top_masked", &am);
-    if (rc) return rc;
-    return rank_radix(ix, q, nq, k, exclude_ids_or_null, /*drop_excluded=*/true, out_ids, out_scores_or_null,
-                      out_rank_scores_or_null, st, am);
+    return rank_top_call("rank_top_masked", ix, q, nq, k, exclude_ids_or_null, /*masked=*/true, allow, n_allow, out_scores_or_null,
+                         out_rank_scores_or_null, out_ids, stream);
 }
 
 int mirx_index_rank_metrics(mirx_index *ix, const float *q, int64_t nq, const int64_t *exclude_ids_or_null, int self_kind,

@@ -5,6 +5,7 @@ milvus/milvus_retrieval.py:80-86) or the inline torch brute force (test.py:1080-
 Torch is plumbing only: tensors own the query/result memory, `data_ptr()` crosses the ABI.
 """
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -98,6 +99,16 @@ def _stream_ptr(device):
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _ptr_or_null(t):
+    """_ptr, with a null for an empty tensor too"""
+    return None if t is None or not t.numel() else ctypes.c_void_p(t.data_ptr())
+
+
+def _score_ptrs(sc, return_f64):
+    """(fp32 reported values, fp64 ranking scores): the score outputs of a call that fills `sc` as one of the two"""
+    return (None, _ptr_or_null(sc)) if return_f64 else (_ptr_or_null(sc), None)
 
 
 class FlatIndex:
@@ -208,6 +219,52 @@ class FlatIndex:
             a = a.to(self.device)
         return a
 
+    def _topk_call(self, q, k, exclude_ids, allow, return_f64, mask_who=None):
+        """What search / search_deep / search_leave_out / rank_top / range_search hand the library: the queries and exclude ids
+        on the device, the row mask as bytes (None without one) and, unless k is None (range_search), the [nq, k] outputs with
+        the arguments every top-k entry point shares -- `head` = queries, nq, k, exclude ids; `outs` = the fp32 values or the
+        fp64 ranking scores (the other one null), ids.  mask_who: the method's name where a mask of the wrong length is its ValueError,
+        before any device work (an empty index's empty mask then counts as none); None leaves the length to the library."""
+        c = types.SimpleNamespace()
+        c.q, c.ex = self._prep_queries(q, exclude_ids)
+        c.am = None if allow is None else self._prep_allow(allow)
+        if mask_who is not None and c.am is not None:
+            if c.am.numel() != len(self):
+                raise ValueError(f"{mask_who}: allow needs one entry per row of the index ({len(self)}), got {c.am.numel()}")
+            if c.am.numel() == 0:
+                c.am = None
+        c.nq = c.q.shape[0]
+        if k is not None:
+            c.head = (_ptr(c.q), c.nq, int(k), _ptr(c.ex))
+            c.ids = torch.empty((c.nq, max(k, 0)), dtype=torch.int64, device=self.device)
+            c.sc = torch.empty((c.nq, max(k, 0)), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+            c.outs = _score_ptrs(c.sc, return_f64) + (_ptr(c.ids),)
+        return c
+
+    def _call(self, name, *args):
+        """the library's index entry point `name` on this index, its device current, the current stream as the last argument"""
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self._lib, name)(self._h, *args, _stream_ptr(self.device)), name)
+
+    def _per_row(self, t, dtype, who, name):
+        """`t` checked as a tensor of `dtype` on the index's device with one entry per row (in the order of ids()), contiguous"""
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise ValueError(f"{who}: {name} must be an {str(dtype).split('.')[-1]} tensor")
+        if t.device != self.device:
+            raise ValueError(f"{who}: {name} must be on the index's device ({self.device}), got {t.device}")
+        if t.dim() != 1 or t.numel() != len(self):
+            raise ValueError(f"{who}: {name} needs one entry per row of the index ({len(self)}), got shape {tuple(t.shape)}")
+        return t.detach().contiguous()
+
+    def _per_query(self, v, nq, dtype, who, name):
+        """`v` (tensor or sequence of nq integers) as a contiguous `dtype` tensor on the index's device"""
+        t = torch.as_tensor(v).detach().reshape(-1)
+        if t.numel() != nq:
+            raise ValueError(f"{who}: {name} needs one entry per query ({nq}), got {t.numel()}")
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise ValueError(f"{who}: {name} must be integers, got {t.dtype}")
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
     def search(self, q, k, exclude_ids=None, return_f64=False, allow=None):
         """-> (scores [nq,k] float32 reported values, ids [nq,k] int64) on the index device.
 
@@ -218,35 +275,14 @@ class FlatIndex:
         bit); slots past the eligible rows read (-inf, -1).  The mask belongs to this call alone."""
         if int(k) > _lib.MAX_SEARCH_K:
             return self.rank_top(q, k, exclude_ids=exclude_ids, return_f64=return_f64, allow=allow)
-        q, ex = self._prep_queries(q, exclude_ids)
-        nq = q.shape[0]
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        exp = ctypes.c_void_p(ex.data_ptr()) if ex is not None else None
-        if allow is not None:
-            am = self._prep_allow(allow)
-            sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
-            scp = ctypes.c_void_p(sc.data_ptr())
-            with torch.cuda.device(self.device):
-                rc = self._lib.mirx_index_search_masked(self._h, ctypes.c_void_p(q.data_ptr()), nq, int(k), exp,
-                                                        ctypes.c_void_p(am.data_ptr()) if am.numel() else None, am.numel(),
-                                                        None if return_f64 else scp, scp if return_f64 else None,
-                                                        ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
-            _lib.check(rc, "mirx_index_search_masked")
-            return sc, ids
-        with torch.cuda.device(self.device):
-            st = _stream_ptr(self.device)
-            if return_f64:
-                sc = torch.empty((nq, k), dtype=torch.float64, device=self.device)
-                rc = self._lib.mirx_index_search_f64(self._h, ctypes.c_void_p(q.data_ptr()), nq, int(k), exp,
-                                                     ctypes.c_void_p(sc.data_ptr()),
-                                                     ctypes.c_void_p(ids.data_ptr()), st)
-            else:
-                sc = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-                rc = self._lib.mirx_index_search(self._h, ctypes.c_void_p(q.data_ptr()), nq, int(k), exp,
-                                                 ctypes.c_void_p(sc.data_ptr()),
-                                                 ctypes.c_void_p(ids.data_ptr()), st)
-        _lib.check(rc, "mirx_index_search")
-        return sc, ids
+        c = self._topk_call(q, k, exclude_ids, allow, return_f64)
+        if c.am is not None:
+            self._call("mirx_index_search_masked", *c.head, _ptr_or_null(c.am), c.am.numel(), *c.outs)
+        elif return_f64:
+            self._call("mirx_index_search_f64", *c.head, *c.outs[1:])
+        else:
+            self._call("mirx_index_search", *c.head, c.outs[0], c.outs[2])
+        return c.sc, c.ids
 
     def search_deep(self, q, k, exclude_ids=None, return_f64=False, allow=None):
         """search()'s arguments and results, for 64 < k (+1 with exclude_ids) <= 1024 on galleries of at least
@@ -255,24 +291,9 @@ class FlatIndex:
         own route inside the library, and k above 1024 goes to rank_top as in search().  last_stats() tells which route answered."""
         if int(k) > _lib.MAX_SEARCH_K:
             return self.rank_top(q, k, exclude_ids=exclude_ids, return_f64=return_f64, allow=allow)
-        q, ex = self._prep_queries(q, exclude_ids)
-        nq = q.shape[0]
-        am = None if allow is None else self._prep_allow(allow)
-        if am is not None and am.numel() != len(self):
-            raise ValueError(f"allow needs one entry per row of the index ({len(self)}), got {am.numel()}")
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
-        scp = ctypes.c_void_p(sc.data_ptr())
-        if am is not None and am.numel() == 0:
-            am = None                                              # an empty index: nothing to mask
-        with torch.cuda.device(self.device):
-            rc = self._lib.mirx_index_search_deep(self._h, ctypes.c_void_p(q.data_ptr()), nq, int(k),
-                                                  ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
-                                                  ctypes.c_void_p(am.data_ptr()) if am is not None else None,
-                                                  None if return_f64 else scp, scp if return_f64 else None,
-                                                  ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
-        _lib.check(rc, "mirx_index_search_deep")
-        return sc, ids
+        c = self._topk_call(q, k, exclude_ids, allow, return_f64, mask_who="search_deep")
+        self._call("mirx_index_search_deep", *c.head, _ptr(c.am), *c.outs)
+        return c.sc, c.ids
 
     def search_leave_out(self, q, k, row_codes, query_codes, exclude_ids=None, allow=None, return_f64=False, max_left_out=-1):
         """Leave-group-out search (mirx_index_search_leave_out): search_deep()'s results over the rows that do not share the
@@ -285,42 +306,15 @@ class FlatIndex:
         k = int(k)
         if not 1 <= k <= _lib.MAX_SEARCH_K:
             raise ValueError(f"search_leave_out: k must be in [1, {_lib.MAX_SEARCH_K}], got {k}")
-        if not isinstance(row_codes, torch.Tensor) or row_codes.dtype != torch.int32:
-            raise ValueError("search_leave_out: row_codes must be an int32 tensor")
-        if row_codes.device != self.device:
-            raise ValueError(f"search_leave_out: row_codes must be on the index's device ({self.device}), got {row_codes.device}")
-        if row_codes.dim() != 1 or row_codes.numel() != len(self):
-            raise ValueError(f"search_leave_out: row_codes needs one code per row of the index ({len(self)}), "
-                             f"got shape {tuple(row_codes.shape)}")
-        q, ex = self._prep_queries(q, exclude_ids)
-        nq = q.shape[0]
-        qc = torch.as_tensor(query_codes).detach().reshape(-1)
-        if qc.numel() != nq:
-            raise ValueError(f"search_leave_out: query_codes needs one code per query ({nq}), got {qc.numel()}")
-        if qc.is_floating_point() or qc.dtype == torch.bool:
-            raise ValueError(f"search_leave_out: query_codes must be integers, got {qc.dtype}")
-        qc = qc.to(device=self.device, dtype=torch.int32).contiguous()
-        am = None if allow is None else self._prep_allow(allow)
-        if am is not None and am.numel() != len(self):
-            raise ValueError(f"allow needs one entry per row of the index ({len(self)}), got {am.numel()}")
-        rc_t = row_codes.detach().contiguous()
-        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
-        if nq == 0:
-            return sc, ids
+        rc_t = self._per_row(row_codes, torch.int32, "search_leave_out", "row_codes")
+        c = self._topk_call(q, k, exclude_ids, allow, return_f64, mask_who="search_leave_out")
+        qc = self._per_query(query_codes, c.nq, torch.int32, "search_leave_out", "query_codes")
+        if c.nq == 0:
+            return c.sc, c.ids
         if len(self) == 0:
-            am = None                                              # an empty index: nothing to mask,
-            rc_t = torch.full((1,), -1, dtype=torch.int32, device=self.device)   # and no code to read (the ABI refuses a null)
-        scp = ctypes.c_void_p(sc.data_ptr())
-        with torch.cuda.device(self.device):
-            rc = self._lib.mirx_index_search_leave_out(self._h, ctypes.c_void_p(q.data_ptr()), nq, k,
-                                                       ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
-                                                       ctypes.c_void_p(am.data_ptr()) if am is not None else None,
-                                                       ctypes.c_void_p(rc_t.data_ptr()), ctypes.c_void_p(qc.data_ptr()),
-                                                       int(max_left_out), None if return_f64 else scp, scp if return_f64 else None,
-                                                       ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
-        _lib.check(rc, "mirx_index_search_leave_out")
-        return sc, ids
+            rc_t = torch.full((1,), -1, dtype=torch.int32, device=self.device)   # no code to read (the ABI refuses a null)
+        self._call("mirx_index_search_leave_out", *c.head, _ptr(c.am), _ptr(rc_t), _ptr(qc), int(max_left_out), *c.outs)
+        return c.sc, c.ids
 
     def search_begin(self, q, k, exclude_ids=None):
         """First half of search(): enqueue the whole first pass on the current stream and return without waiting.
@@ -350,27 +344,12 @@ class FlatIndex:
         ids [nq,k]); the excluded id is left out and slots past the eligible rows read (-inf, -1).  Sorts the whole gallery per
         query (a radix sort, 32 bytes of workspace per row and query): for k <= 1024 search() is the faster call.  allow: search()'s
         row mask; the cost stays that of the unmasked call (every row is scored and sorted, masked rows end behind the rest)."""
-        q, ex = self._prep_queries(q, exclude_ids)
-        am = None if allow is None else self._prep_allow(allow)
-        nq, k = q.shape[0], int(k)
-        ids = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=self.device)
-        sc = torch.empty((nq, max(k, 0)), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
-        scp = ctypes.c_void_p(sc.data_ptr())
-        exp = ctypes.c_void_p(ex.data_ptr()) if ex is not None else None
-        with torch.cuda.device(self.device):
-            if am is None:
-                rc = self._lib.mirx_index_rank_top(
-                    self._h, ctypes.c_void_p(q.data_ptr()), nq, k, exp,
-                    None if return_f64 else scp, scp if return_f64 else None,
-                    ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
-            else:
-                rc = self._lib.mirx_index_rank_top_masked(
-                    self._h, ctypes.c_void_p(q.data_ptr()), nq, k, exp,
-                    ctypes.c_void_p(am.data_ptr()) if am.numel() else None, am.numel(),
-                    None if return_f64 else scp, scp if return_f64 else None,
-                    ctypes.c_void_p(ids.data_ptr()), _stream_ptr(self.device))
-        _lib.check(rc, "mirx_index_rank_top" if am is None else "mirx_index_rank_top_masked")
-        return sc, ids
+        c = self._topk_call(q, int(k), exclude_ids, allow, return_f64)
+        if c.am is None:
+            self._call("mirx_index_rank_top", *c.head, *c.outs)
+        else:
+            self._call("mirx_index_rank_top_masked", *c.head, _ptr_or_null(c.am), c.am.numel(), *c.outs)
+        return c.sc, c.ids
 
     def rank_all(self, q, exclude_ids=None, with_scores=False):
         """Full ranking [nq, ntotal] (row = query, excluded id last): score descending, equal scores by ascending id.  Any
@@ -412,29 +391,12 @@ class FlatIndex:
         if len(ks) > 8 or any(k < 1 for k in ks):
             raise ValueError(f"{who}: at most 8 kappas, each at least 1, got {ks}")
         size = len(self)
-        for name, t, dt in (("row_labels", row_labels, torch.int64), ("row_codes", row_codes, torch.int32)):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor) or t.dtype != dt:
-                raise ValueError(f"{who}: {name} must be an {str(dt).split('.')[-1]} tensor")
-            if t.device != self.device:
-                raise ValueError(f"{who}: {name} must be on the index's device ({self.device}), got {t.device}")
-            if t.dim() != 1 or t.numel() != size:
-                raise ValueError(f"{who}: {name} needs one entry per row of the index ({size}), got shape {tuple(t.shape)}")
+        rl = self._per_row(row_labels, torch.int64, who, "row_labels")
+        rc_t = None if row_codes is None else self._per_row(row_codes, torch.int32, who, "row_codes")
         q, ex = self._prep_queries(q, exclude_ids)
         nq = q.shape[0]
-
-        def per_query(name, v, dt):
-            t = torch.as_tensor(v).detach().reshape(-1)
-            if t.numel() != nq:
-                raise ValueError(f"{who}: {name} needs one entry per query ({nq}), got {t.numel()}")
-            if t.is_floating_point() or t.dtype == torch.bool:
-                raise ValueError(f"{who}: {name} must be integers, got {t.dtype}")
-            return t.to(device=self.device, dtype=dt).contiguous()
-        ql = per_query("query_labels", query_labels, torch.int64)
-        qc = None if query_codes is None else per_query("query_codes", query_codes, torch.int32)
-        rl = row_labels.detach().contiguous()
-        rc_t = None if row_codes is None else row_codes.detach().contiguous()
+        ql = self._per_query(query_labels, nq, torch.int64, who, "query_labels")
+        qc = None if query_codes is None else self._per_query(query_codes, nq, torch.int32, who, "query_codes")
         ap = torch.empty(nq, dtype=torch.float64, device=self.device)
         cnt = torch.empty((nq, len(ks)), dtype=torch.int64, device=self.device)
         nrel = torch.empty(nq, dtype=torch.int64, device=self.device)
@@ -445,13 +407,10 @@ class FlatIndex:
         if size == 0 and rc_t is not None:
             rc_t = torch.full((1,), -1, dtype=torch.int32, device=self.device)   # no code to read, and codes come in pairs
         karr = (ctypes.c_int32 * max(1, len(ks)))(*ks)
-        vp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
-        with torch.cuda.device(self.device):
-            rc = self._lib.mirx_index_rank_metrics(
-                self._h, vp(q), nq, vp(ex), int(self_kind), vp(rl), vp(ql), vp(rc_t), vp(qc),
-                0 if jaccard_threshold is None else 1, float(jaccard_threshold or 0.0), 1 if standard_ap else 0, karr, len(ks),
-                vp(ap), vp(cnt), vp(nrel), vp(maxpos), _stream_ptr(self.device))
-        _lib.check(rc, "mirx_index_rank_metrics")
+        vp = _ptr_or_null
+        self._call("mirx_index_rank_metrics", vp(q), nq, vp(ex), int(self_kind), vp(rl), vp(ql), vp(rc_t), vp(qc),
+                   0 if jaccard_threshold is None else 1, float(jaccard_threshold or 0.0), 1 if standard_ap else 0, karr, len(ks),
+                   vp(ap), vp(cnt), vp(nrel), vp(maxpos))
         return out
 
     def range_search(self, q, lo, hi=float("inf"), exclude_ids=None, allow=None, return_f64=False):
@@ -463,27 +422,15 @@ class FlatIndex:
         row, hi <= lo nothing; a NaN bound raises ValueError.  range_bounds() maps pymilvus' radius / range_filter onto lo, hi.
         The answer does not depend on the route (filter GEMM + fp64 re-score of every candidate, or the exact scan)."""
         lo, hi = _bound(lo, "lo"), _bound(hi, "hi")
-        q, ex = self._prep_queries(q, exclude_ids)
-        am = None if allow is None else self._prep_allow(allow)
-        if am is not None and am.numel() != len(self):
-            raise ValueError(f"allow needs one entry per row of the index ({len(self)}), got {am.numel()}")
-        nq = q.shape[0]
-        lims = torch.empty((nq + 1,), dtype=torch.int64, device=self.device)
+        c = self._topk_call(q, None, exclude_ids, allow, return_f64, mask_who="range_search")
+        lims = torch.empty((c.nq + 1,), dtype=torch.int64, device=self.device)
         total = ctypes.c_int64(0)
-        with torch.cuda.device(self.device):
-            st = _stream_ptr(self.device)
-            _lib.check(self._lib.mirx_index_range_search(
-                self._h, ctypes.c_void_p(q.data_ptr()), nq, lo, hi,
-                ctypes.c_void_p(ex.data_ptr()) if ex is not None else None,
-                ctypes.c_void_p(am.data_ptr()) if am is not None and am.numel() else None, am.numel() if am is not None else 0,
-                ctypes.c_void_p(lims.data_ptr()), ctypes.byref(total), st), "mirx_index_range_search")
-            n = int(total.value)
-            sc = torch.empty((n,), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
-            ids = torch.empty((n,), dtype=torch.int64, device=self.device)
-            scp = ctypes.c_void_p(sc.data_ptr()) if n else None
-            _lib.check(self._lib.mirx_index_range_fetch(self._h, None if return_f64 else scp, scp if return_f64 else None,
-                                                        ctypes.c_void_p(ids.data_ptr()) if n else None, st),
-                       "mirx_index_range_fetch")
+        self._call("mirx_index_range_search", _ptr(c.q), c.nq, lo, hi, _ptr(c.ex), _ptr(c.am), 0 if c.am is None else c.am.numel(),
+                   _ptr(lims), ctypes.byref(total))
+        n = int(total.value)
+        sc = torch.empty((n,), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_index_range_fetch", *_score_ptrs(sc, return_f64), _ptr_or_null(ids))
         return lims, sc, ids
 
     # -- grouping search (DESIGN 34) -------------------------------------------------------------------------------------
