@@ -50,6 +50,8 @@ RESAMPLE_TILE_W, RESAMPLE_TILE_H = 32, 16
 RESAMPLE_DESC_WORDS = 8
 RESAMPLE_OUT_U8, RESAMPLE_OUT_F32 = 0, 1
 RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 0, 1
+IVF_MAX_NLIST, IVF_MAX_DIM = 65536, 2048   # mirx_ivf_create's limits (include/mirx.h)
+IVF_OPT_SCORE_BYTES = 1            # test hook: the score workspace budget of mirx_ivf_search in bytes (0 = default, 1 GiB)
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
 FORCE_TAU_OFF = 0x7FC00000
@@ -70,6 +72,13 @@ class SearchStats(ctypes.Structure):
 
 class RangeStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int64) for n in ("nq", "filter_answered", "exact_answered", "candidates", "hits")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class IvfStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("nq", "rows_scored", "pairs", "work_items", "batches")]
 
     def as_dict(self):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
@@ -234,6 +243,21 @@ SYMBOLS = {
     "mirx_resample_batch": (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "mirx_resample_taps_filter": (_int, [_int, _int, _int]),
     "mirx_resample_plan_filter": (_int, [_int, _int, _int, _int, _int, _vp, _i64]),
+    "mirx_ivf_create": (_int, [_int, _int, _int, _int, ctypes.POINTER(_vp)]),
+    "mirx_ivf_destroy": (None, [_vp]),
+    "mirx_ivf_train": (_int, [_vp, _vp, _i64, _vp, _int, _vp]),
+    "mirx_ivf_set_centroids": (_int, [_vp, _vp]),
+    "mirx_ivf_get_centroids": (_int, [_vp, _vp]),
+    "mirx_ivf_add": (_int, [_vp, _vp, _i64, _vp]),
+    "mirx_ivf_remove_ids": (_int, [_vp, _vp, _i64, ctypes.POINTER(_i64), _vp]),
+    "mirx_ivf_size": (_i64, [_vp]),
+    "mirx_ivf_list_sizes": (_int, [_vp, _vp]),
+    "mirx_ivf_assign": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "mirx_ivf_search": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mirx_ivf_last_stats": (_int, [_vp, _vp, ctypes.POINTER(IvfStats)]),
+    "mirx_ivf_set_option": (_int, [_vp, _int, _i64]),
+    "mirx_ivf_query_tile": (_int, [_int]),
+    "mirx_ivf_row_block": (_int, []),
 }
 
 _lib = None

@@ -30,40 +30,6 @@
 
 using namespace mirx;
 
-static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }                          // on the device that is current: mirx_index_destroy selects the index's
-    hipError_t ensure(size_t need) {
-        if (need <= bytes) return hipSuccess;
-        if (p) {
-            hipError_t e = hipFree(p);
-            p = nullptr;
-            bytes = 0;
-            if (e != hipSuccess) return e;
-        }
-        size_t want = need + need / 4;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            e = hipMalloc(&p, need);
-            want = need;
-        }
-        if (e == hipSuccess) bytes = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // What a search scans (built by search_call alone).  The index itself without a mask; under one, a stand-in for the allowed rows:
 //   tier 1    the index's rows with `bias` (-inf on masked rows) in the sample and filter GEMMs, and for the queries the guard
 //             rejects the exact scan over all rows with the masked ones neutralised (mpos, ids = the masked ids)
@@ -148,18 +114,6 @@ namespace {
 constexpr size_t EXACT_WS_BYTES = (size_t)1 << 30;   // fp64 score tile workspace per pass
 constexpr size_t COMPACT_SCRATCH_BYTES = (size_t)256 << 20;   // most a removal's chunk scratch takes by default
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 // The index's device stays selected until the entry point returns (declares the DeviceGuard `dg`).
 #define MIRX_SELECT_DEVICE(ix, who)  \
     DeviceGuard dg((ix)->device);    \
@@ -180,15 +134,6 @@ int enter_idle(mirx_index *ix, const char *who) {
     MIRX_SELECT_DEVICE(ix, who)
 // MIRX_CHECK for the bodies several entry points share: `who` (a C string) goes in front of the message.
 #define MIRX_WHO_CHECK(who, cond, msg) MIRX_CHECK(cond, std::string(who) + ": " msg)
-
-bool is_device_pointer(const void *p) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();   // unregistered host memory reports an error: treat as host
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
 
 int grow(mirx_index *ix, int64_t want_rows) {
     if (want_rows <= ix->cap) return MIRX_OK;

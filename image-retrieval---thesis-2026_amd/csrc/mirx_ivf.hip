@@ -1,0 +1,450 @@
+// mirx_ivf.hip -- the IVF_FLAT index of the C ABI (include/mirx.h, mirx_ivf_*): k-means lists over a flat index of the centroids,
+// the list-major fp32 master, and the search of the probed lists (kernels: k_ivf.hip).
+//
+// "Nearest centroid" is never restated here: assignments and probes are mirx_index_search / mirx_index_rank_top over `cent`, a
+// mirx_index that holds the centroids with ids 0 .. nlist-1, so the rule (fp64 lane-tree score, ties to the lowest list) is the
+// one oracle/search_ref.c pins.  The layout is planned on the host -- list numbers and ids travel there (8 bytes per row), a
+// counting sort gives every row its destination, the device moves the rows -- which keeps add / remove / re-assign free of
+// order-dependent atomics at a cost that is stated in the header.
+#include <algorithm>
+#include <new>
+#include <numeric>
+#include <unordered_set>
+#include <vector>
+
+#include "mirx_kernels.h"
+
+using namespace mirx;
+
+struct mirx_ivf {
+    int dim = 0, dimp = 0, metric = 0, device = 0, nlist = 0;
+    mirx_index *cent = nullptr;           // flat index over the centroids; null until they are fixed
+    DevBuf centroids;                     // [nlist, dim] fp32
+    int64_t size = 0;
+    DevBuf rows, ids, offsets;            // [size, dimp] list-major, [size], [nlist + 1] int64
+    std::vector<int64_t> off_h, ids_h, seq_h;   // host mirrors of offsets / ids, and each row's insertion number (list-major)
+    int64_t next_seq = 0, next_auto = 0;
+    int64_t score_bytes = 0;              // MIRX_IVF_OPT_SCORE_BYTES; 0 = SCORE_WS_BYTES
+    // scratch
+    DevBuf stage, lists, fval, a_order, a_loff, upd, pos, newids, q32p, pids, probes, qoff, cntcur, pairoff, itemoff, pair_q,
+        pair_off, scores;
+    unsigned long long *stats_dev = nullptr;   // [3] rows scored, pairs, work items
+    int64_t last_nq = 0, last_batches = 0;
+};
+
+namespace {
+
+constexpr size_t SCORE_WS_BYTES = (size_t)1 << 30;
+constexpr int64_t MAX_BATCH_PAIRS = (int64_t)1 << 26;   // (query, probe) pairs of one internal batch
+
+#define MIRX_IVF_ENTER(ivf, who)                                                        \
+    MIRX_CHECK(ivf, std::string(who) + ": null ivf");                                   \
+    DeviceGuard dg((ivf)->device);                                                      \
+    if (!dg.ok) return fail(MIRX_EHIP, std::string(who) + ": cannot select the ivf's device")
+
+// rows as a device pointer: the caller's, or a copy in `buf`
+int device_rows(mirx_ivf *ivf, const float *rows, int64_t n, DevBuf &buf, const float **out) {
+    *out = rows;
+    if (is_device_pointer(rows)) return MIRX_OK;
+    const size_t bytes = (size_t)n * ivf->dim * sizeof(float);
+    if (buf.ensure(bytes) != hipSuccess) return fail(MIRX_ENOMEM, "ivf: no memory to stage the rows");
+    MIRX_HIP(hipMemcpy(buf.p, rows, bytes, hipMemcpyHostToDevice));
+    *out = buf.as<float>();
+    return MIRX_OK;
+}
+
+// the flat index over the current centroids (ids = list numbers)
+int rebuild_centroid_index(mirx_ivf *ivf) {
+    if (ivf->cent) mirx_index_destroy(ivf->cent);
+    ivf->cent = nullptr;
+    if (int rc = mirx_index_create(ivf->dim, ivf->metric, ivf->device, &ivf->cent)) return rc;
+    return mirx_index_add(ivf->cent, ivf->centroids.as<float>(), ivf->nlist, nullptr);
+}
+
+// out_lists[i] (device) = the list of rows[i] (device, [n, dim]); the work is enqueued on st, mirx_index_search waits as it does
+int assign_rows(mirx_ivf *ivf, const float *rows, int64_t n, int64_t *out_lists, hipStream_t st) {
+    if (n == 0) return MIRX_OK;
+    MIRX_HIP(ivf->fval.ensure((size_t)n * sizeof(float)));
+    return mirx_index_search(ivf->cent, rows, n, 1, nullptr, ivf->fval.as<float>(), out_lists, st);
+}
+
+// the same, to the host
+int assign_to_host(mirx_ivf *ivf, const float *rows, int64_t n, std::vector<int64_t> &out, hipStream_t st) {
+    out.resize((size_t)n);
+    if (n == 0) return MIRX_OK;
+    MIRX_HIP(ivf->lists.ensure((size_t)n * sizeof(int64_t)));
+    if (int rc = assign_rows(ivf, rows, n, ivf->lists.as<int64_t>(), st)) return rc;
+    MIRX_HIP(hipMemcpyAsync(out.data(), ivf->lists.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    for (int64_t v : out)
+        if (v < 0 || v >= ivf->nlist) return fail(MIRX_EHIP, "ivf: the centroid search returned no list for a row");
+    return MIRX_OK;
+}
+
+// The one layout change behind add / remove / re-assign.  old_dst[p] = where resident row p goes (-1: dropped); the n_new rows of
+// new_rows (device, [n_new, dim]) with new_ids go to new_dst.  total = the rows afterwards, new_off their offsets; seq / ids
+// mirrors follow.  Everything is allocated before a row moves: MIRX_ENOMEM leaves the ivf untouched.
+int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *new_rows, int64_t n_new,
+             const std::vector<int64_t> &new_ids, const std::vector<int64_t> &new_dst, int64_t total,
+             const std::vector<int64_t> &new_off, hipStream_t st) {
+    const int64_t n_old = ivf->size;
+    DevBuf rows2, ids2;
+    const size_t pos_bytes = (size_t)std::max<int64_t>(n_old, n_new) * sizeof(int64_t);
+    if (rows2.ensure((size_t)std::max<int64_t>(total, 1) * ivf->dimp * sizeof(float)) != hipSuccess ||
+        ids2.ensure((size_t)std::max<int64_t>(total, 1) * sizeof(int64_t)) != hipSuccess ||
+        ivf->pos.ensure(std::max<size_t>(pos_bytes, 8)) != hipSuccess ||
+        ivf->newids.ensure((size_t)std::max<int64_t>(n_new, 1) * sizeof(int64_t)) != hipSuccess ||
+        ivf->offsets.ensure((size_t)(ivf->nlist + 1) * sizeof(int64_t)) != hipSuccess)
+        return fail(MIRX_ENOMEM, "ivf: no memory for the new layout");
+    std::vector<int64_t> ids_h((size_t)total), seq_h((size_t)total);
+    if (n_old) {
+        MIRX_HIP(hipMemcpyAsync(ivf->pos.p, old_dst.data(), (size_t)n_old * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(launch_ivf_place(ivf->rows.as<float>(), n_old, ivf->dimp, ivf->dimp, nullptr, ivf->pos.as<int64_t>(),
+                                  rows2.as<float>(), ivf->dimp, st));
+        MIRX_HIP(launch_ivf_place_ids(ivf->ids.as<int64_t>(), n_old, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
+        MIRX_HIP(hipStreamSynchronize(st));                     // pos is reused below
+        for (int64_t p = 0; p < n_old; ++p)
+            if (old_dst[(size_t)p] >= 0) {
+                ids_h[(size_t)old_dst[(size_t)p]] = ivf->ids_h[(size_t)p];
+                seq_h[(size_t)old_dst[(size_t)p]] = ivf->seq_h[(size_t)p];
+            }
+    }
+    if (n_new) {
+        MIRX_HIP(hipMemcpyAsync(ivf->pos.p, new_dst.data(), (size_t)n_new * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(hipMemcpyAsync(ivf->newids.p, new_ids.data(), (size_t)n_new * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(launch_ivf_place(new_rows, n_new, ivf->dim, ivf->dim, nullptr, ivf->pos.as<int64_t>(), rows2.as<float>(),
+                                  ivf->dimp, st));
+        MIRX_HIP(launch_ivf_place_ids(ivf->newids.as<int64_t>(), n_new, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
+        for (int64_t j = 0; j < n_new; ++j) {
+            ids_h[(size_t)new_dst[(size_t)j]] = new_ids[(size_t)j];
+            seq_h[(size_t)new_dst[(size_t)j]] = ivf->next_seq + j;
+        }
+        ivf->next_seq += n_new;
+    }
+    MIRX_HIP(hipMemcpyAsync(ivf->offsets.p, new_off.data(), (size_t)(ivf->nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    std::swap(ivf->rows.p, rows2.p);
+    std::swap(ivf->rows.bytes, rows2.bytes);
+    std::swap(ivf->ids.p, ids2.p);
+    std::swap(ivf->ids.bytes, ids2.bytes);
+    ivf->ids_h.swap(ids_h);
+    ivf->seq_h.swap(seq_h);
+    ivf->off_h = new_off;
+    ivf->size = total;
+    return MIRX_OK;
+}
+
+// the resident rows to the lists of the current centroids, insertion order kept inside each list
+int reassign_resident(mirx_ivf *ivf, hipStream_t st) {
+    const int64_t n = ivf->size;
+    if (n == 0) return MIRX_OK;
+    const float *flat = ivf->rows.as<float>();
+    if (ivf->dimp != ivf->dim) {                                 // the centroid search reads rows of `dim` floats
+        MIRX_HIP(ivf->stage.ensure((size_t)n * ivf->dim * sizeof(float)));
+        MIRX_HIP(launch_ivf_place(ivf->rows.as<float>(), n, ivf->dimp, ivf->dim, nullptr, nullptr, ivf->stage.as<float>(), ivf->dim, st));
+        flat = ivf->stage.as<float>();
+    }
+    std::vector<int64_t> lists;
+    if (int rc = assign_to_host(ivf, flat, n, lists, st)) return rc;
+    std::vector<int64_t> by_seq((size_t)n);
+    std::iota(by_seq.begin(), by_seq.end(), (int64_t)0);
+    std::sort(by_seq.begin(), by_seq.end(), [&](int64_t a, int64_t b) { return ivf->seq_h[(size_t)a] < ivf->seq_h[(size_t)b]; });
+    std::vector<int64_t> off((size_t)ivf->nlist + 1, 0), dst((size_t)n);
+    for (int64_t v : lists) ++off[(size_t)v + 1];
+    for (int l = 0; l < ivf->nlist; ++l) off[(size_t)l + 1] += off[(size_t)l];
+    std::vector<int64_t> cur(off.begin(), off.end() - 1);
+    for (int64_t p : by_seq) dst[(size_t)p] = cur[(size_t)lists[(size_t)p]]++;
+    const int64_t keep_seq = ivf->next_seq;
+    const int rc = relayout(ivf, dst, nullptr, 0, {}, {}, n, off, st);
+    ivf->next_seq = keep_seq;
+    return rc;
+}
+
+int fix_centroids(mirx_ivf *ivf, hipStream_t st) {
+    if (int rc = rebuild_centroid_index(ivf)) return rc;
+    return reassign_resident(ivf, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mirx_ivf_query_tile(int dim) {
+    if (dim < 1 || dim > MIRX_IVF_MAX_DIM) return -1;
+    return ivf_query_tile((int)round_up(dim, DIM_ALIGN));
+}
+int mirx_ivf_row_block(void) { return IVF_ROWS; }
+
+int mirx_ivf_create(int dim, int metric, int nlist, int device, mirx_ivf **out) {
+    MIRX_CHECK(out, "ivf_create: out is null");
+    *out = nullptr;
+    MIRX_CHECK(dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "ivf_create: dim out of range (1 .. 2048)");
+    MIRX_CHECK(metric == MIRX_METRIC_IP || metric == MIRX_METRIC_NEG_L2, "ivf_create: unknown metric");
+    MIRX_CHECK(nlist >= 1 && nlist <= MIRX_IVF_MAX_NLIST, "ivf_create: nlist out of range (1 .. 65536)");
+    int ndev = 0;
+    MIRX_HIP(hipGetDeviceCount(&ndev));
+    MIRX_CHECK(device >= 0 && device < ndev, "ivf_create: no such device");
+    DeviceGuard dg(device);
+    if (!dg.ok) return fail(MIRX_EHIP, "ivf_create: cannot select device");
+    mirx_ivf *ivf = new (std::nothrow) mirx_ivf();
+    if (!ivf) return fail(MIRX_ENOMEM, "ivf_create: host allocation failed");
+    ivf->dim = dim;
+    ivf->dimp = (int)round_up(dim, DIM_ALIGN);
+    ivf->metric = metric;
+    ivf->nlist = nlist;
+    ivf->device = device;
+    ivf->off_h.assign((size_t)nlist + 1, 0);
+    hipError_t e;
+    if ((e = ivf->centroids.ensure((size_t)nlist * dim * sizeof(float))) != hipSuccess ||
+        (e = ivf->offsets.ensure((size_t)(nlist + 1) * sizeof(int64_t))) != hipSuccess ||
+        (e = hipMemset(ivf->offsets.p, 0, (size_t)(nlist + 1) * sizeof(int64_t))) != hipSuccess ||
+        (e = hipMalloc(&ivf->stats_dev, 3 * sizeof(unsigned long long))) != hipSuccess ||
+        (e = hipMemset(ivf->stats_dev, 0, 3 * sizeof(unsigned long long))) != hipSuccess) {
+        mirx_ivf_destroy(ivf);
+        return fail(MIRX_ENOMEM, std::string("ivf_create: ") + hipGetErrorString(e));
+    }
+    *out = ivf;
+    return MIRX_OK;
+}
+
+void mirx_ivf_destroy(mirx_ivf *ivf) {
+    if (!ivf) return;
+    DeviceGuard dg(ivf->device);
+    if (ivf->cent) mirx_index_destroy(ivf->cent);
+    if (ivf->stats_dev) (void)hipFree(ivf->stats_dev);
+    delete ivf;                           // every DevBuf releases itself, inside dg's scope
+}
+
+int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *init_positions_or_null, int iters, void *stream) {
+    MIRX_CHECK(ivf && rows, "ivf_train: null argument");
+    MIRX_CHECK(n >= ivf->nlist, "ivf_train: fewer rows than lists");
+    MIRX_CHECK(n <= 0x7FFFFF00ll, "ivf_train: more than 2^31 rows");
+    MIRX_CHECK(iters >= 0, "ivf_train: iters must not be negative");
+    const int nlist = ivf->nlist, dim = ivf->dim;
+    std::vector<int64_t> start((size_t)nlist);
+    for (int j = 0; j < nlist; ++j) {
+        start[(size_t)j] = init_positions_or_null ? init_positions_or_null[j] : (int64_t)j * n / nlist;
+        MIRX_CHECK(start[(size_t)j] >= 0 && start[(size_t)j] < n, "ivf_train: an initial position is not a row");
+    }
+    MIRX_IVF_ENTER(ivf, "ivf_train");
+    hipStream_t st = (hipStream_t)stream;
+    const float *drows = nullptr;
+    DevBuf trows;                                      // a host caller's rows for the length of the call (the stage serves the re-assignment)
+    if (int rc = device_rows(ivf, rows, n, trows, &drows)) return rc;
+    MIRX_HIP(ivf->pos.ensure((size_t)nlist * sizeof(int64_t)));
+    MIRX_HIP(ivf->upd.ensure((size_t)nlist * dim * sizeof(float)));
+    MIRX_HIP(ivf->a_order.ensure((size_t)n * sizeof(int32_t)));
+    MIRX_HIP(ivf->a_loff.ensure((size_t)(nlist + 1) * sizeof(int64_t)));
+    MIRX_HIP(hipMemcpyAsync(ivf->pos.p, start.data(), (size_t)nlist * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    MIRX_HIP(launch_ivf_place(drows, nlist, dim, dim, ivf->pos.as<int64_t>(), nullptr, ivf->centroids.as<float>(), dim, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    std::vector<int64_t> cur, prev, loff((size_t)nlist + 1);
+    std::vector<int32_t> order((size_t)n);
+    for (int it = 0; it < iters; ++it) {
+        if (int rc = rebuild_centroid_index(ivf)) return rc;
+        if (int rc = assign_to_host(ivf, drows, n, cur, st)) return rc;
+        if (it > 0 && cur == prev) break;
+        std::fill(loff.begin(), loff.end(), 0);
+        for (int64_t v : cur) ++loff[(size_t)v + 1];
+        for (int l = 0; l < nlist; ++l) loff[(size_t)l + 1] += loff[(size_t)l];
+        std::vector<int64_t> at(loff.begin(), loff.end() - 1);
+        for (int64_t r = 0; r < n; ++r) order[(size_t)at[(size_t)cur[(size_t)r]]++] = (int32_t)r;
+        MIRX_HIP(hipMemcpyAsync(ivf->a_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(hipMemcpyAsync(ivf->a_loff.p, loff.data(), (size_t)(nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(launch_ivf_update(drows, dim, ivf->a_order.as<int32_t>(), ivf->a_loff.as<int64_t>(), nlist,
+                                   ivf->centroids.as<float>(), ivf->upd.as<float>(), ivf->metric == MIRX_METRIC_IP, st));
+        MIRX_HIP(hipStreamSynchronize(st));
+        prev.swap(cur);
+    }
+    return fix_centroids(ivf, st);
+}
+
+int mirx_ivf_set_centroids(mirx_ivf *ivf, const float *centroids) {
+    MIRX_CHECK(ivf && centroids, "ivf_set_centroids: null argument");
+    MIRX_IVF_ENTER(ivf, "ivf_set_centroids");
+    MIRX_HIP(hipMemcpy(ivf->centroids.p, centroids, (size_t)ivf->nlist * ivf->dim * sizeof(float), hipMemcpyDefault));
+    return fix_centroids(ivf, nullptr);
+}
+
+int mirx_ivf_get_centroids(const mirx_ivf *ivf, float *out_centroids) {
+    MIRX_CHECK(ivf && out_centroids, "ivf_get_centroids: null argument");
+    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_get_centroids: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    MIRX_IVF_ENTER(ivf, "ivf_get_centroids");
+    MIRX_HIP(hipMemcpy(out_centroids, ivf->centroids.p, (size_t)ivf->nlist * ivf->dim * sizeof(float), hipMemcpyDefault));
+    return MIRX_OK;
+}
+
+int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids_or_null) {
+    MIRX_CHECK(ivf && n >= 0 && (rows || n == 0), "ivf_add: bad argument");
+    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_add: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    MIRX_CHECK(ivf->size + n <= 0x7FFFFF00ll, "ivf_add: more than 2^31 rows per index");
+    MIRX_IVF_ENTER(ivf, "ivf_add");
+    if (n == 0) return MIRX_OK;
+    const float *drows = nullptr;
+    if (int rc = device_rows(ivf, rows, n, ivf->stage, &drows)) return rc;
+    std::vector<int64_t> lists, new_ids((size_t)n);
+    if (int rc = assign_to_host(ivf, drows, n, lists, nullptr)) return rc;
+    if (ids_or_null) {
+        MIRX_HIP(hipMemcpy(new_ids.data(), ids_or_null, (size_t)n * sizeof(int64_t), hipMemcpyDefault));
+    } else {
+        const int64_t first = std::max(ivf->next_auto, ivf->size);
+        for (int64_t i = 0; i < n; ++i) new_ids[(size_t)i] = first + i;
+        ivf->next_auto = first + n;
+    }
+    const int nlist = ivf->nlist;
+    std::vector<int64_t> add((size_t)nlist + 1, 0), off((size_t)nlist + 1, 0);
+    for (int64_t v : lists) ++add[(size_t)v + 1];
+    for (int l = 0; l < nlist; ++l) add[(size_t)l + 1] += add[(size_t)l];          // new rows in front of list l
+    for (int l = 0; l <= nlist; ++l) off[(size_t)l] = ivf->off_h[(size_t)l] + add[(size_t)l];
+    std::vector<int64_t> old_dst((size_t)ivf->size), new_dst((size_t)n), at((size_t)nlist);
+    for (int l = 0; l < nlist; ++l) {
+        for (int64_t p = ivf->off_h[(size_t)l]; p < ivf->off_h[(size_t)l + 1]; ++p) old_dst[(size_t)p] = p + add[(size_t)l];
+        at[(size_t)l] = ivf->off_h[(size_t)l + 1] + add[(size_t)l];                // behind the list's resident rows
+    }
+    for (int64_t j = 0; j < n; ++j) new_dst[(size_t)j] = at[(size_t)lists[(size_t)j]]++;
+    return relayout(ivf, old_dst, drows, n, new_ids, new_dst, ivf->size + n, off, nullptr);
+}
+
+int mirx_ivf_remove_ids(mirx_ivf *ivf, const int64_t *ids, int64_t n, int64_t *out_removed_or_null, void *stream) {
+    MIRX_CHECK(ivf && n >= 0 && (ids || n == 0), "ivf_remove_ids: bad argument");
+    MIRX_IVF_ENTER(ivf, "ivf_remove_ids");
+    if (out_removed_or_null) *out_removed_or_null = 0;
+    if (n == 0 || ivf->size == 0) return MIRX_OK;
+    std::vector<int64_t> req((size_t)n);
+    MIRX_HIP(hipMemcpy(req.data(), ids, (size_t)n * sizeof(int64_t), hipMemcpyDefault));
+    const std::unordered_set<int64_t> gone(req.begin(), req.end());
+    const int nlist = ivf->nlist;
+    std::vector<int64_t> dst((size_t)ivf->size), off((size_t)nlist + 1, 0);
+    int64_t kept = 0;
+    for (int l = 0; l < nlist; ++l) {
+        off[(size_t)l] = kept;
+        for (int64_t p = ivf->off_h[(size_t)l]; p < ivf->off_h[(size_t)l + 1]; ++p)
+            dst[(size_t)p] = gone.count(ivf->ids_h[(size_t)p]) ? -1 : kept++;
+    }
+    off[(size_t)nlist] = kept;
+    const int64_t removed = ivf->size - kept;
+    if (removed) {
+        if (int rc = relayout(ivf, dst, nullptr, 0, {}, {}, kept, off, (hipStream_t)stream)) return rc;
+    }
+    if (out_removed_or_null) *out_removed_or_null = removed;
+    return MIRX_OK;
+}
+
+int64_t mirx_ivf_size(const mirx_ivf *ivf) { return ivf ? ivf->size : -1; }
+
+int mirx_ivf_list_sizes(const mirx_ivf *ivf, int64_t *out_sizes) {
+    MIRX_CHECK(ivf && out_sizes, "ivf_list_sizes: null argument");
+    for (int l = 0; l < ivf->nlist; ++l) out_sizes[l] = ivf->off_h[(size_t)l + 1] - ivf->off_h[(size_t)l];
+    return MIRX_OK;
+}
+
+int mirx_ivf_assign(mirx_ivf *ivf, const float *rows, int64_t n, int64_t *out_lists, void *stream) {
+    MIRX_CHECK(ivf && n >= 0 && ((rows && out_lists) || n == 0), "ivf_assign: bad argument");
+    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_assign: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    MIRX_IVF_ENTER(ivf, "ivf_assign");
+    return assign_rows(ivf, rows, n, out_lists, (hipStream_t)stream);
+}
+
+int mirx_ivf_set_option(mirx_ivf *ivf, int option, int64_t value) {
+    MIRX_CHECK(ivf, "ivf_set_option: null ivf");
+    MIRX_CHECK(option == MIRX_IVF_OPT_SCORE_BYTES, "ivf_set_option: unknown option");
+    MIRX_CHECK(value >= 0, "ivf_set_option: score bytes must be 0 (default) or a byte count");
+    ivf->score_bytes = value;
+    return MIRX_OK;
+}
+
+int mirx_ivf_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int nprobe, const int64_t *exclude_ids_or_null,
+                    float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids, int32_t *out_probes_or_null,
+                    void *stream) {
+    MIRX_CHECK(ivf && nq >= 0 && ((q && out_ids) || nq == 0), "ivf_search: null argument");
+    MIRX_CHECK(out_values_or_null || out_f64_or_null || nq == 0, "ivf_search: both score outputs are null");
+    MIRX_CHECK(k >= 1 && k <= MAX_K, "ivf_search: k out of range (1 .. 1024)");
+    MIRX_CHECK(nprobe >= 1, "ivf_search: nprobe must be at least 1");
+    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_search: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    MIRX_IVF_ENTER(ivf, "ivf_search");
+    hipStream_t st = (hipStream_t)stream;
+    const int nlist = ivf->nlist, np = std::min(nprobe, nlist), dimp = ivf->dimp;
+    const int qt = ivf_query_tile(dimp);
+    ivf->last_nq = nq;
+    ivf->last_batches = 0;
+    MIRX_HIP(hipMemsetAsync(ivf->stats_dev, 0, 3 * sizeof(unsigned long long), st));
+    if (nq == 0) return MIRX_OK;
+    // a compact row is never longer than the np largest lists together
+    std::vector<int64_t> sizes((size_t)nlist);
+    int64_t blocks = 0;
+    for (int l = 0; l < nlist; ++l) {
+        sizes[(size_t)l] = ivf->off_h[(size_t)l + 1] - ivf->off_h[(size_t)l];
+        blocks += (sizes[(size_t)l] + IVF_ROWS - 1) / IVF_ROWS;
+    }
+    std::partial_sort(sizes.begin(), sizes.begin() + np, sizes.end(), std::greater<int64_t>());
+    const int64_t ld = std::max<int64_t>(1, std::accumulate(sizes.begin(), sizes.begin() + np, (int64_t)0));
+    const int64_t budget = ivf->score_bytes > 0 ? ivf->score_bytes : (int64_t)SCORE_WS_BYTES;
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8)));
+    per = std::min(per, std::max<int64_t>(1, MAX_BATCH_PAIRS / np));
+    while (per > 1 && (per / qt + 1) * std::max<int64_t>(blocks, 1) > 0x7FFFFFFFll) per /= 2;   // work items fit an int
+    MIRX_CHECK((per / qt + 1) * std::max<int64_t>(blocks, 1) <= 0x7FFFFFFFll, "ivf_search: too many row blocks for one query");
+    hipError_t e;
+    if ((e = ivf->scores.ensure((size_t)per * ld * sizeof(double))) != hipSuccess ||
+        (e = ivf->q32p.ensure((size_t)per * dimp * sizeof(float))) != hipSuccess ||
+        (e = ivf->pids.ensure((size_t)per * np * sizeof(int64_t))) != hipSuccess ||
+        (e = ivf->fval.ensure((size_t)per * np * sizeof(float))) != hipSuccess ||
+        (e = ivf->probes.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->qoff.ensure((size_t)per * (np + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->cntcur.ensure((size_t)2 * nlist * sizeof(int))) != hipSuccess ||
+        (e = ivf->pairoff.ensure((size_t)(nlist + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->itemoff.ensure((size_t)(nlist + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->pair_q.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->pair_off.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess)
+        return fail(MIRX_ENOMEM, std::string("ivf_search: workspace: ") + hipGetErrorString(e));
+    for (int64_t q0 = 0; q0 < nq; q0 += per) {
+        const int nb = (int)std::min(per, nq - q0);
+        const float *qb = q + q0 * ivf->dim;
+        // the probes: the centroid index's own top-np (past mirx_index_search's k limit, its radix ranking: the same ranking)
+        int rc = np <= MAX_K ? mirx_index_search(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), ivf->pids.as<int64_t>(), st)
+                             : mirx_index_rank_top(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), nullptr,
+                                                   ivf->pids.as<int64_t>(), st);
+        if (rc) return rc;
+        MIRX_HIP(launch_ivf_place(qb, nb, ivf->dim, ivf->dim, nullptr, nullptr, ivf->q32p.as<float>(), dimp, st));
+        MIRX_HIP(launch_ivf_invert(ivf->pids.as<int64_t>(), nb, np, ivf->offsets.as<int64_t>(), nlist, qt, ivf->probes.as<int32_t>(),
+                                   out_probes_or_null ? out_probes_or_null + q0 * np : nullptr, ivf->qoff.as<int32_t>(),
+                                   ivf->cntcur.as<int>(), ivf->pairoff.as<int32_t>(), ivf->itemoff.as<int32_t>(),
+                                   ivf->pair_q.as<int32_t>(), ivf->pair_off.as<int32_t>(), ivf->stats_dev, st));
+        IvfScoreArgs sa{};
+        sa.q32p = ivf->q32p.as<float>();
+        sa.rows = ivf->rows.as<float>();
+        sa.dimp = dimp;
+        sa.nlist = nlist;
+        sa.qt = qt;
+        sa.offsets = ivf->offsets.as<int64_t>();
+        sa.pairoff = ivf->pairoff.as<int32_t>();
+        sa.itemoff = ivf->itemoff.as<int32_t>();
+        sa.pair_q = ivf->pair_q.as<int32_t>();
+        sa.pair_off = ivf->pair_off.as<int32_t>();
+        sa.out = ivf->scores.as<double>();
+        sa.ld = ld;
+        MIRX_HIP(launch_ivf_scores(sa, ivf->metric, st));
+        MIRX_HIP(launch_ivf_topk(ivf->scores.as<double>(), ld, ivf->probes.as<int32_t>(), ivf->qoff.as<int32_t>(), nb, np,
+                                 ivf->offsets.as<int64_t>(), ivf->ids.as<int64_t>(),
+                                 exclude_ids_or_null ? exclude_ids_or_null + q0 : nullptr, k, ivf->metric,
+                                 out_f64_or_null ? out_f64_or_null + q0 * k : nullptr, out_ids + q0 * k,
+                                 out_values_or_null ? out_values_or_null + q0 * k : nullptr, st));
+        ++ivf->last_batches;
+    }
+    return MIRX_OK;
+}
+
+int mirx_ivf_last_stats(mirx_ivf *ivf, void *stream, mirx_ivf_stats *out) {
+    MIRX_CHECK(ivf && out, "ivf_last_stats: null argument");
+    MIRX_IVF_ENTER(ivf, "ivf_last_stats");
+    unsigned long long v[3] = {0, 0, 0};
+    MIRX_HIP(hipStreamSynchronize((hipStream_t)stream));
+    MIRX_HIP(hipMemcpy(v, ivf->stats_dev, sizeof(v), hipMemcpyDeviceToHost));
+    out->nq = ivf->last_nq;
+    out->rows_scored = (int64_t)v[0];
+    out->pairs = (int64_t)v[1];
+    out->work_items = (int64_t)v[2];
+    out->batches = ivf->last_batches;
+    return MIRX_OK;
+}
+
+}  // extern "C"

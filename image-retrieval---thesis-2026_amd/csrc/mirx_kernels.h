@@ -511,6 +511,42 @@ struct GroupFillArgs {
 };
 hipError_t launch_group_fill(const GroupFillArgs &a, int metric, hipStream_t st);
 
+// ---- k_ivf.hip: the IVF_FLAT index (mirx_ivf_*): layout moves, the k-means update, the inverted probe table, the list scan --------
+constexpr int IVF_ROWS = 256;                    // rows of a list per work item of the list scan (64 per wave, 4 waves)
+constexpr int IVF_LDS_BYTES = 64 * 1024;         // the item's queries as doubles: two workgroups fit a CU's 160 KiB
+int ivf_query_tile(int dimp);                    // queries per work item: min(16, IVF_LDS_BYTES / (8 dimp))
+// dst row (dst_pos ? dst_pos[i] : i) = the first `cols` floats of src row (src_pos ? src_pos[i] : i), zeros up to dst_ld; a negative
+// dst_pos drops the row.  src and dst must not overlap.
+hipError_t launch_ivf_place(const float *src, int64_t n, int src_ld, int cols, const int64_t *src_pos, const int64_t *dst_pos,
+                            float *dst, int dst_ld, hipStream_t st);
+hipError_t launch_ivf_place_ids(const int64_t *src, int64_t n, const int64_t *dst_pos, int64_t *dst, hipStream_t st);
+// One Lloyd update.  order = the training rows sorted by list (stable), loff[nlist + 1] = where each list starts in it.  cent[l] =
+// fp32(sum in fp64, ascending row order / count), then normalised as launch_l2_normalize does when `normalize`; an empty list keeps
+// its centroid.  upd = scratch [nlist, dim].
+hipError_t launch_ivf_update(const float *rows, int dim, const int32_t *order, const int64_t *loff, int nlist, float *cent,
+                             float *upd, bool normalize, hipStream_t st);
+// pids [nq, nprobe] (the centroid index's search result) -> probes (int32, also to out_probes when set), qoff [nq, nprobe + 1] =
+// each probed list's offset in the query's compact score row, and the table in list order: list l's pairs are the slots
+// pairoff[l] .. pairoff[l + 1] of pair_q (the query) / pair_off (its qoff entry), its work items itemoff[l] .. itemoff[l + 1].
+// cnt_cursor = 2 nlist ints of scratch; stats[0..2] += rows scored, pairs, work items.
+hipError_t launch_ivf_invert(const int64_t *pids, int nq, int nprobe, const int64_t *offsets, int nlist, int qt, int32_t *probes,
+                             int32_t *out_probes, int32_t *qoff, int *cnt_cursor, int32_t *pairoff, int32_t *itemoff,
+                             int32_t *pair_q, int32_t *pair_off, unsigned long long *stats, hipStream_t st);
+struct IvfScoreArgs {
+    const float *q32p;           // [nq, dimp] the batch's queries, zero padded
+    const float *rows;           // [size, dimp] list-major
+    int dimp, nlist, qt;
+    const int64_t *offsets;      // [nlist + 1]
+    const int32_t *pairoff, *itemoff, *pair_q, *pair_off;   // launch_ivf_invert's
+    double *out;                 // [nq, ld] compact score rows
+    int64_t ld;
+};
+hipError_t launch_ivf_scores(const IvfScoreArgs &a, int metric, hipStream_t st);
+// per query: the best k of its compact row by (score desc, id asc), ids taken from the probed lists, exclude[i] skipped
+hipError_t launch_ivf_topk(const double *scores, int64_t ld, const int32_t *probes, const int32_t *qoff, int nq, int nprobe,
+                           const int64_t *offsets, const int64_t *ids, const int64_t *exclude, int k, int metric, double *out_f64,
+                           int64_t *out_ids, float *out_val, hipStream_t st);
+
 // ---- k_fuse.hip: hybrid search's rank / score fusion (mirx_fuse_ranked) ------------------------------------------------------
 struct FuseArgs {
     const int64_t *codes;        // [nq, row_stride >= m] document codes of the concatenated lists, -1 = empty slot

@@ -695,6 +695,174 @@ class FlatIndex:
         return out, ids
 
 
+IVF_TRAIN_ROWS_PER_LIST = 256              # IvfFlatIndex.train(max_rows=None) trains on at most this many rows per list
+
+
+def ivf_search_bounds(k, nprobe):
+    """k / nprobe of an IVF search as ints, ValueError outside mirx_ivf_search's contract"""
+    for name, v in (("k", k), ("nprobe", nprobe)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {type(v).__name__}")
+    k, nprobe = int(k), int(nprobe)
+    if not 1 <= k <= _lib.MAX_SEARCH_K:
+        raise ValueError(f"IVF search: k must be in [1, {_lib.MAX_SEARCH_K}], got {k}")
+    if nprobe < 1:
+        raise ValueError(f"IVF search: nprobe must be at least 1, got {nprobe}")
+    return k, nprobe
+
+
+class IvfFlatIndex:
+    """IVF_FLAT over fp32 rows resident on one GPU (mirx_ivf_*, include/mirx.h): the reference's own index type
+    (milvus/milvus_setup.py:191-213) and search parameters (nprobe, milvus/milvus_retrieval.py:69-86).
+
+    The rows live in `nlist` lists, each row in the list of its nearest centroid; search() scans the lists of the query's
+    `nprobe` nearest centroids and returns THE EXACT TOP-K OF THOSE ROWS: fp64 lane-tree scores, ties to the lowest id, bit for
+    bit what FlatIndex.search(allow=rows whose list is probed) returns.  Only the choice of lists is approximate; nprobe >= nlist
+    is FlatIndex.search's answer.  "Nearest" is FlatIndex's own ranking over the centroids (ties to the lowest list)."""
+
+    def __init__(self, dim, metric="COSINE", nlist=1024, device=None):
+        if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= _lib.IVF_MAX_NLIST:
+            raise ValueError(f"nlist must be an integer in [1, {_lib.IVF_MAX_NLIST}], got {nlist!r}")
+        if not 1 <= int(dim) <= _lib.IVF_MAX_DIM:
+            raise ValueError(f"IvfFlatIndex: dim must be in [1, {_lib.IVF_MAX_DIM}], got {dim}")
+        self.metric = metric_code(metric)
+        if not torch.cuda.is_available():
+            raise MirxError("IvfFlatIndex needs a GPU: libmirx has no CPU path")
+        self._lib = _lib.load()
+        if device is None:
+            device = torch.cuda.current_device()
+        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+        self.dim, self.nlist = int(dim), int(nlist)
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.mirx_ivf_create(self.dim, self.metric, self.nlist, self.device.index, ctypes.byref(h)),
+                   "mirx_ivf_create")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._lib.mirx_ivf_destroy(h)
+            self._h = None
+
+    def __len__(self):
+        return int(self._lib.mirx_ivf_size(self._h))
+
+    def _rows(self, rows, who):
+        rows = torch.as_tensor(rows)
+        if rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"{who}: expected [n, {self.dim}] rows, got {tuple(rows.shape)}")
+        rows = rows.detach().to(torch.float32).contiguous()
+        if rows.is_cuda and rows.device != self.device:
+            rows = rows.to(self.device)
+        if rows.is_cuda:
+            torch.cuda.current_stream(self.device).synchronize()
+        return rows
+
+    def _call(self, name, *args):
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self._lib, name)(self._h, *args), name)
+
+    def train(self, rows, iters=10, init_positions=None, max_rows=None):
+        """Lloyd's k-means (mirx_ivf_train) and fix the centroids: start from rows[init_positions] (default: the rows at
+        floor(j n / nlist)), `iters` updates at most, stop early when no row changes its list.  It trains on at most max_rows
+        rows taken at an even stride (row floor(i n / max_rows)); max_rows=None means 256 * nlist.  Deterministic: two calls
+        give equal bits."""
+        rows = self._rows(rows, "train")
+        limit = IVF_TRAIN_ROWS_PER_LIST * self.nlist if max_rows is None else int(max_rows)
+        if limit < self.nlist:
+            raise ValueError(f"train: max_rows ({limit}) is below nlist ({self.nlist})")
+        if rows.shape[0] < self.nlist:
+            raise ValueError(f"train: {rows.shape[0]} rows cannot seed {self.nlist} lists")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"train: iters must be a non-negative integer, got {iters!r}")
+        n = rows.shape[0]
+        if n > limit:
+            pick = (torch.arange(limit, dtype=torch.int64) * n) // limit
+            rows = rows[pick.to(rows.device)].contiguous()
+            if rows.is_cuda:
+                torch.cuda.current_stream(self.device).synchronize()
+        pos = None
+        if init_positions is not None:
+            pos = np.ascontiguousarray(np.asarray(init_positions).reshape(-1), dtype=np.int64)
+            if pos.size != self.nlist or (pos < 0).any() or (pos >= rows.shape[0]).any():
+                raise ValueError(f"train: init_positions needs {self.nlist} row numbers in [0, {rows.shape[0]})")
+        self._call("mirx_ivf_train", _ptr(rows), rows.shape[0], None if pos is None else ctypes.c_void_p(pos.ctypes.data),
+                   int(iters), _stream_ptr(self.device))
+
+    def set_centroids(self, centroids):
+        """Fix the centroids to a caller's [nlist, dim] array; rows already added are re-assigned."""
+        c = self._rows(centroids, "set_centroids")
+        if c.shape[0] != self.nlist:
+            raise ValueError(f"set_centroids: expected {self.nlist} centroids, got {c.shape[0]}")
+        self._call("mirx_ivf_set_centroids", _ptr(c))
+
+    @property
+    def centroids(self):
+        out = torch.empty((self.nlist, self.dim), dtype=torch.float32, device=self.device)
+        self._call("mirx_ivf_get_centroids", _ptr(out))
+        return out
+
+    def add(self, rows, ids=None):
+        """Append rows (cpu or this GPU) to their lists; ids as FlatIndex.add.  Every call rebuilds the list-major layout: the
+        resident rows move once, so add in large batches."""
+        rows = self._rows(rows, "add")
+        idp = None
+        if ids is not None:
+            ids = torch.as_tensor(ids).detach().to(torch.int64).contiguous()
+            if ids.numel() != rows.shape[0]:
+                raise ValueError("ids and rows disagree in length")
+            if ids.is_cuda:
+                ids = ids.to(self.device)
+                torch.cuda.current_stream(self.device).synchronize()
+            idp = _ptr(ids)
+        self._call("mirx_ivf_add", _ptr(rows), rows.shape[0], idp)
+
+    def remove(self, ids):
+        """FlatIndex.remove's contract -> the number of rows removed."""
+        ids = torch.as_tensor(ids).detach().to(torch.int64).reshape(-1).contiguous()
+        if ids.is_cuda:
+            ids = ids.to(self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+        removed = ctypes.c_int64(0)
+        self._call("mirx_ivf_remove_ids", _ptr_or_null(ids), ids.numel(), ctypes.byref(removed), _stream_ptr(self.device))
+        return int(removed.value)
+
+    def assign(self, rows):
+        """-> int64 [n] on the index device: the list each row would be added to"""
+        rows = self._rows(rows, "assign").to(self.device)
+        out = torch.empty((rows.shape[0],), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_assign", _ptr_or_null(rows), rows.shape[0], _ptr_or_null(out), _stream_ptr(self.device))
+        return out
+
+    def list_sizes(self):
+        out = np.empty((self.nlist,), dtype=np.int64)
+        _lib.check(self._lib.mirx_ivf_list_sizes(self._h, ctypes.c_void_p(out.ctypes.data)), "mirx_ivf_list_sizes")
+        return out
+
+    def set_option(self, option, value):
+        _lib.check(self._lib.mirx_ivf_set_option(self._h, option, int(value)), "mirx_ivf_set_option")
+
+    def search(self, q, k, nprobe=10, exclude_ids=None, return_f64=False, return_probes=False):
+        """-> (scores [nq, k], ids [nq, k]) as FlatIndex.search (fp32 reported values, or the fp64 ranking scores with
+        return_f64), over the rows of the `nprobe` lists nearest to each query (nprobe is clamped to nlist); with
+        return_probes a third tensor [nq, min(nprobe, nlist)] int32 names those lists, nearest first.  1 <= k <= 1024."""
+        k, nprobe = ivf_search_bounds(k, nprobe)
+        q, ex = FlatIndex._prep_queries(self, q, exclude_ids)
+        nq, npc = q.shape[0], min(nprobe, self.nlist)
+        ids = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        sc = torch.empty((nq, k), dtype=torch.float64 if return_f64 else torch.float32, device=self.device)
+        probes = torch.empty((nq, npc), dtype=torch.int32, device=self.device) if return_probes else None
+        self._call("mirx_ivf_search", _ptr_or_null(q), nq, k, nprobe, _ptr(ex), *_score_ptrs(sc, return_f64), _ptr_or_null(ids),
+                   _ptr_or_null(probes), _stream_ptr(self.device))
+        return (sc, ids, probes) if return_probes else (sc, ids)
+
+    def last_stats(self):
+        """nq, rows_scored ((query, row) pairs scored), pairs ((query, list) pairs), work_items and batches of the last search"""
+        s = _lib.IvfStats()
+        self._call("mirx_ivf_last_stats", _stream_ptr(self.device), ctypes.byref(s))
+        return s.as_dict()
+
+
 def l2_normalize_(x):
     """In-place F.normalize(x, dim=1) on a CUDA fp32 tensor (model.py:83)."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2):

@@ -151,10 +151,15 @@ def _as_store(store):
     return store if isinstance(store, Store) else Store(store)
 
 
+def _nih_index_params(metric_type, index_type, nlist):
+    return {"metric_type": metric_type, "index_type": index_type, "params": {"nlist": nlist}}
+
+
 def create_nih_collection(collection_name, drop_old=False, metric_type="COSINE", index_type="IVF_FLAT", nlist=1024,
-                          device=None, store=None):
+                          device=None, store=None, approximate=False):
     """Schema id / image_path / image_name / label_text / label_vector_json / embedding[256]; index_type and nlist are
-    accepted for compatibility (the search is exhaustive).  store: a mirx.store.Store or a directory -- the collection
+    accepted for compatibility (the search is exhaustive) unless approximate=True turns the reference's IVF_FLAT index on
+    (Collection.create_index(..., approximate=True): process state, searches that carry nprobe probe that many lists).  store: a mirx.store.Store or a directory -- the collection
     persists there (flush() commits; another process finds it with get_nih_collection(name, store=...)); None keeps it in
     this process."""
     if store is None:
@@ -165,6 +170,8 @@ def create_nih_collection(collection_name, drop_old=False, metric_type="COSINE",
             col = Collection(collection_name, EMBEDDING_DIM, "NIH multi-label gallery embeddings", metric_type=metric_type,
                              device=device, extra_fields=_NIH_FIELDS, has_label=False)
             _COLLECTIONS[collection_name] = col
+        if approximate:
+            col.create_index("embedding", _nih_index_params(metric_type, index_type, nlist), approximate=True)
         col.load()
         return col
     store = _as_store(store)
@@ -180,6 +187,8 @@ def create_nih_collection(collection_name, drop_old=False, metric_type="COSINE",
         else:
             stored = store.create(collection_name, EMBEDDING_DIM, metric_type, schema, "NIH multi-label gallery embeddings")
         col = _STORED[key] = Collection.from_stored(stored, device=device)
+    if approximate:
+        col.create_index("embedding", _nih_index_params(col.metric_type, index_type, nlist), approximate=True)
     col.load()
     return col
 

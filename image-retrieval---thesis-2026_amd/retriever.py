@@ -11,7 +11,9 @@ Mirrors (paths into /root/reference):
                                                     on image_path (fusion_eval/, retrieval_analysis/); DESIGN 35
 The "server" is a device-resident FlatIndex (libmirx); searches are EXACT (the reference's
 IVF_FLAT nlist=1024 / nprobe=10 index is approximate, milvus_setup.py:191-213) and
-`search_params` / `nprobe` are accepted and ignored, except `radius` / `range_filter` (a range search).  Metadata (image_path, label) stays on
+`search_params` / `nprobe` are accepted and ignored, except `radius` / `range_filter` (a range search) and, on a collection
+whose index was created with `create_index(..., approximate=True)`, `nprobe`: the opt-in IVF_FLAT index (mirx.index.IvfFlatIndex,
+DESIGN 41) that reproduces the reference's own search.  Metadata (image_path, label) stays on
 the host, keyed by the int64 ids the index returns.
 
 Errors follow the reference: unknown model type -> ValueError; connect() swallows failures
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex, group_bounds, range_bounds, tier1_max_k
+from .index import FlatIndex, IvfFlatIndex, group_bounds, range_bounds, tier1_max_k
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -144,6 +146,10 @@ class Collection:
         self._joins = {}                                    # cache: the join tables of hybrid searches this collection leads
         self._stored = stored
         self._resident = stored is None                     # whether _index mirrors the live rows
+        # the opt-in approximate index (create_index(..., approximate=True)): process state, never stored
+        self._approx_nlist = None                           # nlist while the approximate index is on
+        self._ivf = None                                    # the IvfFlatIndex over the live rows; None = to be (re)built
+        self._ivf_centroids = None                          # its centroids, trained once and kept across rebuilds
 
     @classmethod
     def from_stored(cls, stored, device=None):
@@ -209,6 +215,7 @@ class Collection:
         self._expr = None
         self._version += 1
         self._joins = {}
+        self._ivf = None                                    # rebuilt lazily, with the kept centroids
 
     def expr_mask(self, expr):
         """The rows a filter expression (mirx.expr: comparisons of id and the scalar fields with literals, in / not in,
@@ -268,14 +275,63 @@ class Collection:
     def is_persistent(self):
         return self._stored is not None
 
-    def create_index(self, field_name="embedding", index_params=None):
-        metric = (index_params or {}).get("metric_type", self.metric_type)
+    def create_index(self, field_name="embedding", index_params=None, approximate=False):
+        """pymilvus' create_index.  Without `approximate` only the metric is kept: index_type and nlist are accepted and
+        ignored, every search is exact.  approximate=True with index_params["index_type"] == "IVF_FLAT" (any other type:
+        ValueError) turns the collection's approximate index on: an IvfFlatIndex of index_params["params"]["nlist"] lists
+        (default 1024) beside the flat index, built from the resident rows at load() or at the first approximate search and
+        trained once; after insert / delete / compact the lists are rebuilt lazily with the kept centroids.  It is process
+        state: a stored collection opened again is exact until this call is made again.  See search() for the calls it serves."""
+        params = index_params or {}
+        nlist = None
+        if approximate:
+            if params.get("index_type") != "IVF_FLAT":
+                raise ValueError(f"approximate=True needs index_type 'IVF_FLAT', got {params.get('index_type')!r}")
+            inner = params.get("params") if isinstance(params.get("params"), dict) else {}
+            nlist = inner.get("nlist", 1024)
+            if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= 65536:
+                raise ValueError(f"nlist must be an integer in [1, 65536], got {nlist!r}")
+            nlist = int(nlist)
+        metric = params.get("metric_type", self.metric_type)
         if self._ids and metric != self.metric_type:
             raise ValueError("metric_type cannot change after rows were inserted")
         self.metric_type = metric
         if self._stored is not None:
             self._stored.set_metric(metric)
+        if nlist != self._approx_nlist:
+            self._approx_nlist, self._ivf, self._ivf_centroids = nlist, None, None
         return True
+
+    def _ensure_ivf(self):
+        """The approximate index over the live rows, or None while there are fewer rows than lists (nothing to train on: the
+        exact routes answer).  A build copies the flat index's rows on the device (both indexes stay resident), trains on the
+        first build and re-uses those centroids afterwards."""
+        if self._approx_nlist is None or self.num_entities < self._approx_nlist:
+            return None
+        if self._ivf is None:
+            index = self._ensure()
+            rows, ids = index.rows()
+            ivf = IvfFlatIndex(self.dim, self.metric_type, self._approx_nlist, index.device)
+            if self._ivf_centroids is None:
+                ivf.train(rows)
+                self._ivf_centroids = ivf.centroids
+            else:
+                ivf.set_centroids(self._ivf_centroids)
+            ivf.add(rows, ids)
+            self._ivf = ivf
+        return self._ivf
+
+    @staticmethod
+    def _nprobe(param):
+        """nprobe of pymilvus' search `param` -- under param["params"] or at its top level, as _range_params reads its keys --
+        when it is an integer >= 1, else None"""
+        if not isinstance(param, dict):
+            return None
+        inner = param.get("params") if isinstance(param.get("params"), dict) else {}
+        v = inner["nprobe"] if "nprobe" in inner else param.get("nprobe")
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            return None
+        return int(v)
 
     def load(self):
         """Make the rows resident.  A collection opened from disk streams its file in bounded pieces (mirx.store.
@@ -283,6 +339,7 @@ class Collection:
         if self._resident:
             if self._index is None:
                 self._index = FlatIndex(self.dim, self.metric_type, self._device)
+            self._ensure_ivf()
             return
         index = FlatIndex(self.dim, self.metric_type, self._device)
         index.reserve(self.num_entities)
@@ -299,12 +356,13 @@ class Collection:
         if self._expr is not None:
             self._expr.device_mask = None
             self._expr.device_codes = {}
+        self._ensure_ivf()
 
     def release(self):
         """pymilvus' collection.release(): a persistent collection gives its device memory back (load() reads it again);
         in memory the index is the only copy and stays."""
         if self._stored is not None:
-            self._index, self._resident = None, False
+            self._index, self._resident, self._ivf = None, False, None
             if self._expr is not None:
                 self._expr.device_mask = None
                 self._expr.device_codes = {}
@@ -535,7 +593,12 @@ class Collection:
         search to the rows it selects -- exactly, on the device (FlatIndex.search(allow=)) -- so there are fewer than `limit`
         hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes.
         param: {"params": {"radius": r, "range_filter": f}} (or the two keys at the top level) makes it pymilvus' range search:
-        the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored.
+        the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored,
+        with one exception: on a collection whose index was created with approximate=True (IVF_FLAT), a plain top-k call --
+        no expr, no grouping, no leave-out, no radius, limit <= 1024; exclude_ids allowed -- whose param carries an integer
+        nprobe >= 1 (under "params" or at the top level) is answered by the IVF_FLAT index: the exact top `limit` of the rows
+        in the nprobe lists nearest to the query (IvfFlatIndex.search).  Every other call stays on the exact routes below, and
+        so do hybrid_search's lists and self_metrics; so does every call while the collection holds fewer rows than nlist.
         group_by_field (a scalar field of the schema) makes it pymilvus' grouping search: `limit` counts GROUPS (at most 1024),
         the result per query is one flat list of Hit, group after group, best group first and rank order inside a group, each
         group holding its best min(group_size, its eligible rows) rows (group_size <= 64, limit * group_size <= 16384); a
@@ -580,6 +643,12 @@ class Collection:
             return [hits[:limit] for hits in self.range_search(q, rng[0], rng[1], expr=expr, exclude_ids=exclude_ids,
                                                                output_fields=output_fields)]
         lo = None if rng is None else range_bounds(self.metric_type, rng[0])[0]
+        nprobe = self._nprobe(param) if self._approx_nlist is not None and rng is None and expr is None and limit <= 1024 else None
+        ivf = None if nprobe is None else self._ensure_ivf()
+        if ivf is not None:
+            sc, ids = ivf.search(q, limit, nprobe, exclude_ids=exclude_ids)
+            ids, sc = ids.cpu().numpy(), sc.cpu().numpy()
+            return [self._hits(ids[qi], sc[qi], fields) for qi in range(q.shape[0])]
         allow = None if expr is None else self._device_mask(expr)
         find = self._finder(limit, exclude_ids)
         if lo is None:
@@ -943,11 +1012,13 @@ class MilvusManager:
         self.collections[model_type] = col
         return col
 
-    def create_index(self, model_type, index_type="IVF_FLAT", metric_type="COSINE", nlist=1024):
+    def create_index(self, model_type, index_type="IVF_FLAT", metric_type="COSINE", nlist=1024, approximate=False):
         if model_type not in self.collections:
             raise ValueError(f"Collection for {model_type} not loaded")
-        # index_type / nlist are accepted for compatibility: the search is always exhaustive
-        self.collections[model_type].create_index("embedding", {"metric_type": metric_type})
+        # index_type / nlist are accepted for compatibility: the search is exhaustive unless approximate=True asks for the
+        # reference's IVF_FLAT (Collection.create_index)
+        self.collections[model_type].create_index(
+            "embedding", {"metric_type": metric_type, "index_type": index_type, "params": {"nlist": nlist}}, approximate=approximate)
         return True
 
     def load_collection(self, model_type):

@@ -1538,6 +1538,84 @@ int mirx_resample_plan_filter(int in_size, int out_size, int first, int n, int f
 int mirx_resample_batch(const void *blob_host, const void *blob_dev, int64_t blob_bytes, int64_t b, int s, int out_kind,
                         const float *mean3, const float *std3, void *out, void *stream);
 
+/*
+ * The IVF_FLAT index: the reference's own index type -- every driver creates its collection with index_params = {"index_type":
+ * "IVF_FLAT", "params": {"nlist": 1024}} (milvus/milvus_setup.py:191-213, nih_zilliz_utils.py) and searches it with
+ * {"metric_type": "COSINE", "params": {"nprobe": 10}} (milvus/milvus_retrieval.py:69-86, query_nih_zilliz.py:56-63).  The rows are
+ * partitioned into nlist lists by their nearest of nlist centroids; a search scans the lists of the query's nprobe nearest
+ * centroids only.  The project's rule holds: no hit is decided from an approximate score.  An answer is THE EXACT TOP-K OF THE ROWS
+ * IN THE PROBED LISTS -- fp64 lane-tree scores, ties to the lowest id, bit for bit what mirx_index_search_masked returns under
+ * the mask "the row's list is probed" -- and the only approximation is which lists are probed: nprobe >= nlist is
+ * mirx_index_search's answer to the bit.  "Nearest" is the metric's own ranking (fp64 lane-tree score, ties to the lowest list
+ * number): mirx_index_search over an internal flat index of the centroids, k = 1 for an assignment, k = nprobe for the probes.
+ * An ivf is not re-entrant; every call below is synchronous in the host sense unless stated.
+ *
+ * mirx_ivf_create   1 <= nlist <= 65536; 1 <= dim <= 2048; the metrics of mirx_index_create; MIRX_EINVAL before any device call.
+ * mirx_ivf_train    Lloyd's k-means over rows [n, dim] (host or device), n >= nlist (else MIRX_EINVAL); fixes the centroids.
+ *     start       centroid j = rows[init_positions[j]] (host, nlist int64 in [0, n)); NULL: init_positions[j] = floor(j n / nlist)
+ *     assignment  every row to its nearest centroid, as above
+ *     update      per list and column ONE fp64 accumulator over the list's rows in ascending row order, divided by the count and
+ *                 rounded once to fp32; with MIRX_METRIC_IP the fp32 mean is then normalised as mirx_l2_normalize does it
+ *                 (spherical k-means); an empty list keeps its centroid.  No floating atomics: two calls give equal bits.
+ *     stopping    after `iters` (>= 0) updates, or earlier when an assignment pass changes no row's list
+ *   One assignment per iteration travels to the host (8 bytes per row), which orders the rows by list for the update.  An ivf that
+ *   already holds rows re-assigns them to the new centroids (as mirx_ivf_set_centroids).
+ * mirx_ivf_set_centroids / _get_centroids   [nlist, dim] fp32, host or device: a caller's own quantiser, and the tests' way to
+ *   force list sizes.  Set on an ivf that holds rows re-assigns them (insertion order inside each list is kept).
+ * mirx_ivf_add      rows [n, dim] (host or device), ids as for mirx_index_add (NULL = auto ids, which go on past the largest auto
+ *   id handed out).  Before the centroids are fixed: MIRX_ESTATE.  The fp32 master is kept LIST-MAJOR (a list's rows contiguous, in
+ *   insertion order) with offsets[nlist + 1] and the ids.  Cost: the new rows' assignment (n x nlist fp64 scores) and a rebuild of
+ *   the whole layout into a second allocation -- every resident row moves once per call, so add in large batches.
+ * mirx_ivf_remove_ids   the semantics of mirx_index_remove_ids (duplicates count once, absent ids are ignored, every row of a
+ *   repeated id goes, auto ids are not reused); the lists stay contiguous and ordered.  The request and the ids meet on the host;
+ *   the survivors move once.
+ * mirx_ivf_size / _list_sizes (host, nlist int64) / _assign (rows device [n, dim] -> out_lists device [n] int64, the list each
+ *   row would be added to; enqueued on `stream`).
+ * mirx_ivf_search   the exact top-k of the probed lists.
+ *     q              device [nq, dim] fp32;  1 <= k <= 1024;  nprobe >= 1, clamped to nlist
+ *     exclude_ids    device, nq int64 or NULL, as for mirx_index_search
+ *     out_values / out_f64 / out_ids   device [nq, k]: fp32 reported values and / or fp64 ranking scores (either may be NULL, not
+ *                    both), ids; ordered (score desc, id asc), the excluded id skipped, (-1, -inf) past the eligible rows
+ *     out_probes     device [nq, nprobe (clamped)] int32 or NULL: the lists probed, nearest first
+ *   Work per internal batch of queries: the centroid search; the [nq, nprobe] table inverted into list order on the device
+ *   (histogram, scan, scatter: integer atomics hand out slots, each pair owns its slot and no result depends on their order); ONE
+ *   launch that scores every (query, probed list) pair -- a work item is (a list, mirx_ivf_row_block() of its rows, up to
+ *   mirx_ivf_query_tile(dim) of the queries probing it), the queries in LDS as doubles, the rows streamed once per query group,
+ *   scores from the transposed lane tree of the exact tier -- into a compact row per query (its probed lists concatenated in probe
+ *   order); then the exact tier's selection over that row with the ids of the lists.  A batch is as many queries as a 1 GiB score
+ *   workspace holds rows of `the nprobe largest lists` doubles (MIRX_IVF_OPT_SCORE_BYTES lowers it for tests).  No floating atomics.
+ * mirx_ivf_last_stats   waits for `stream`, then copies the counters of the last search.
+ * mirx_ivf_query_tile / _row_block   the list scan's block sizes (tests reach their edges); no device touched.
+ */
+typedef struct mirx_ivf mirx_ivf;
+typedef struct mirx_ivf_stats {
+    int64_t nq;            /* queries in the call                                   */
+    int64_t rows_scored;   /* (query, row) pairs scored in fp64                     */
+    int64_t pairs;         /* (query, probed list) pairs                            */
+    int64_t work_items;    /* work items of the list scan, summed over its batches  */
+    int64_t batches;       /* internal batches                                      */
+} mirx_ivf_stats;
+#define MIRX_IVF_MAX_NLIST 65536
+#define MIRX_IVF_MAX_DIM 2048
+#define MIRX_IVF_OPT_SCORE_BYTES 1   /* test hook: the score workspace's budget in bytes; 0 = default (1 GiB) */
+int mirx_ivf_create(int dim, int metric, int nlist, int device, mirx_ivf **out);
+void mirx_ivf_destroy(mirx_ivf *ivf);
+int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *init_positions_or_null, int iters, void *stream);
+int mirx_ivf_set_centroids(mirx_ivf *ivf, const float *centroids);
+int mirx_ivf_get_centroids(const mirx_ivf *ivf, float *out_centroids);
+int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids_or_null);
+int mirx_ivf_remove_ids(mirx_ivf *ivf, const int64_t *ids, int64_t n, int64_t *out_removed_or_null, void *stream);
+int64_t mirx_ivf_size(const mirx_ivf *ivf);
+int mirx_ivf_list_sizes(const mirx_ivf *ivf, int64_t *out_sizes);
+int mirx_ivf_assign(mirx_ivf *ivf, const float *rows, int64_t n, int64_t *out_lists, void *stream);
+int mirx_ivf_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int nprobe, const int64_t *exclude_ids_or_null,
+                    float *out_values_or_null, double *out_f64_or_null, int64_t *out_ids, int32_t *out_probes_or_null,
+                    void *stream);
+int mirx_ivf_last_stats(mirx_ivf *ivf, void *stream, mirx_ivf_stats *out);
+int mirx_ivf_set_option(mirx_ivf *ivf, int option, int64_t value);
+int mirx_ivf_query_tile(int dim);
+int mirx_ivf_row_block(void);
+
 #ifdef __cplusplus
 }
 #endif
