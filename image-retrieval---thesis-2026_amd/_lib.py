@@ -51,6 +51,7 @@ RESAMPLE_DESC_WORDS = 8
 RESAMPLE_OUT_U8, RESAMPLE_OUT_F32 = 0, 1
 RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 0, 1
 IVF_MAX_NLIST, IVF_MAX_DIM = 65536, 2048   # mirx_ivf_create's limits (include/mirx.h)
+IVF_FLAT, IVF_SQ8 = 0, 1           # mirx_ivf_create_typed's kinds
 IVF_OPT_SCORE_BYTES = 1            # test hook: the score workspace budget of mirx_ivf_search in bytes (0 = default, 1 GiB)
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
@@ -258,6 +259,15 @@ SYMBOLS = {
     "mirx_ivf_set_option": (_int, [_vp, _int, _i64]),
     "mirx_ivf_query_tile": (_int, [_int]),
     "mirx_ivf_row_block": (_int, []),
+    "mirx_ivf_create_typed": (_int, [_int, _int, _int, _int, _int, ctypes.POINTER(_vp)]),
+    "mirx_ivf_kind": (_int, [_vp]),
+    "mirx_ivf_sq8_train": (_int, [_vp, _vp, _i64, _vp]),
+    "mirx_ivf_sq8_set_range": (_int, [_vp, _vp, _vp]),
+    "mirx_ivf_sq8_get_range": (_int, [_vp, _vp, _vp]),
+    "mirx_ivf_get_codes": (_int, [_vp, _vp, _vp, _vp]),
+    "mirx_ivf_reconstruct": (_int, [_vp, _vp, _vp]),
+    "mirx_sq8_encode": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mirx_sq8_decode": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,11 +1,13 @@
-// k_ivf.hip -- the kernels of the IVF_FLAT index (mirx_ivf.hip, include/mirx.h): the probe table inverted into list order, one
-// launch that scores every (query, probed list) pair in fp64, the top-k of a query's compact score row, and the k-means update.
+// k_ivf.hip -- the kernels of the IVF indexes (mirx_ivf.hip, include/mirx.h): the probe table inverted into list order, one
+// launch that scores every (query, probed list) pair in fp64, the top-k of a query's compact score row, the k-means update, and
+// IVF_SQ8's quantiser (per-column range, encode, decode); the list scan reads fp32 rows or 8-bit code rows from one source.
 // Every score comes from the transposed lane tree of k_scores_f64_lds (k_exact.hip), so it has the bits of oracle/search_ref.c;
 // the integer atomics below only hand out slots that their owners alone write, so no result depends on their order.
 //
 // Reference behaviour replaced (paths into /root/reference):
 //   index_params = {"index_type": "IVF_FLAT", "params": {"nlist": 1024}}        milvus/milvus_setup.py:191-213
 //   collection.search(..., param={"params": {"nprobe": 10}})                    milvus/milvus_retrieval.py:69-86
+//   index_type: 'IVF_FLAT', 'IVF_SQ8', 'IVF_PQ', 'HNSW', 'FLAT'                  milvus/milvus_setup.py:191-213
 #include "mirx_device.h"
 #include "mirx_kernels.h"
 
@@ -16,17 +18,19 @@ namespace mirx {
 namespace {
 
 // ---- row moves ------------------------------------------------------------------------------------------------------------------
-// dst row (dst_pos ? dst_pos[i] : i) = src row (src_pos ? src_pos[i] : i), `cols` floats, the rest of the dst row zeroed; a
+// dst row (dst_pos ? dst_pos[i] : i) = src row (src_pos ? src_pos[i] : i), `cols` elements, the rest of the dst row zeroed; a
 // negative dst_pos drops the row.  One workgroup walks rows, a thread a column: the layout changes of add / remove / re-assign.
-__global__ __launch_bounds__(256) void k_ivf_place(const float *__restrict__ src, int64_t n, int src_ld, int cols,
+// T = float for fp32 rows, uint32_t for code rows (four codes a word).
+template <typename T>
+__global__ __launch_bounds__(256) void k_ivf_place(const T *__restrict__ src, int64_t n, int src_ld, int cols,
                                                    const int64_t *__restrict__ src_pos, const int64_t *__restrict__ dst_pos,
-                                                   float *__restrict__ dst, int dst_ld) {
+                                                   T *__restrict__ dst, int dst_ld) {
     for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
         const int64_t d = dst_pos ? dst_pos[i] : i;
         if (d < 0) continue;
-        const float *s = src + (src_pos ? src_pos[i] : i) * src_ld;
-        float *o = dst + d * dst_ld;
-        for (int c = threadIdx.x; c < dst_ld; c += 256) o[c] = c < cols ? s[c] : 0.f;
+        const T *s = src + (src_pos ? src_pos[i] : i) * src_ld;
+        T *o = dst + d * dst_ld;
+        for (int c = threadIdx.x; c < dst_ld; c += 256) o[c] = c < cols ? s[c] : T(0);
     }
 }
 
@@ -36,6 +40,85 @@ __global__ __launch_bounds__(256) void k_ivf_place_ids(const int64_t *__restrict
         const int64_t d = dst_pos[i];
         if (d >= 0) dst[d] = src[i];
     }
+}
+
+// ---- the SQ8 quantiser ------------------------------------------------------------------------------------------------------------
+// code = min(255, max(0, floor(((double)x - vmin) / scale + 0.5))), NaN and a zero scale -> 0; xhat = (float)(vmin + code * scale)
+// with the product exact in double (8 x 24 bits), so the fma below rounds once to double as the sum does, then once to float.
+__device__ __forceinline__ uint32_t sq8_encode(float x, float vmin, float scale) {
+    if (scale == 0.f) return 0u;
+    const double t = ((double)x - (double)vmin) / (double)scale;
+    const double r = floor(t + 0.5);
+    if (!(r >= 0.0)) return 0u;                                                    // NaN too
+    return r > 255.0 ? 255u : (uint32_t)r;
+}
+__device__ __forceinline__ float sq8_decode(uint32_t code, double vmin, double scale) {
+    return (float)fma((double)code, scale, vmin);
+}
+
+// Per-column min / max over rows [n, dim], NaN ignored (every comparison with it is false).  Workgroup b folds rows b, b + grid,
+// ... into part[b] = [2][dim]; k_sq8_range folds the partials in workgroup order: no atomics, every call the same bits.
+__global__ __launch_bounds__(256) void k_sq8_minmax(const float *__restrict__ rows, int64_t n, int dim, float *__restrict__ part) {
+    for (int c = threadIdx.x; c < dim; c += 256) {
+        float mn = INFINITY, mx = -INFINITY;
+        for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+            const float v = rows[i * dim + c];
+            if (v < mn) mn = v;
+            if (v > mx) mx = v;
+        }
+        part[((int64_t)blockIdx.x * 2 + 0) * dim + c] = mn;
+        part[((int64_t)blockIdx.x * 2 + 1) * dim + c] = mx;
+    }
+}
+
+// vmin[c], scale[c] = (float)(((double)vmax - (double)vmin) / 255) from nparts partials; columns dim .. dimp-1 and a column
+// without a number get vmin = scale = 0; a zero minimum is stored as +0 (min does not order the two zeros).
+__global__ __launch_bounds__(256) void k_sq8_range(const float *__restrict__ part, int nparts, int dim, int dimp,
+                                                   float *__restrict__ vmin, float *__restrict__ scale) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= dimp) return;
+    float mn = INFINITY, mx = -INFINITY;
+    if (c < dim)
+        for (int b = 0; b < nparts; ++b) {
+            const float a = part[((int64_t)b * 2 + 0) * dim + c], z = part[((int64_t)b * 2 + 1) * dim + c];
+            if (a < mn) mn = a;
+            if (z > mx) mx = z;
+        }
+    const bool any = mn <= mx;
+    vmin[c] = any ? mn + 0.f : 0.f;
+    scale[c] = any ? (float)(((double)mx - (double)mn) / 255.0) : 0.f;
+}
+
+// rows [n, cols] fp32 -> code rows of dst_ld bytes (a multiple of 4) at dst row (dst_pos ? dst_pos[i] : i), a thread four columns
+// and one 4-byte store; columns cols .. dst_ld-1 hold code 0.  k_ivf_place of the code master.
+__global__ __launch_bounds__(256) void k_sq8_encode_place(const float *__restrict__ src, int64_t n, int cols,
+                                                          const float *__restrict__ vmin, const float *__restrict__ scale,
+                                                          const int64_t *__restrict__ dst_pos, uint8_t *__restrict__ dst,
+                                                          int dst_ld) {
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int64_t d = dst_pos ? dst_pos[i] : i;
+        if (d < 0) continue;
+        const float *s = src + i * cols;
+        uint32_t *o = reinterpret_cast<uint32_t *>(dst + d * dst_ld);
+        for (int w = threadIdx.x; w < (dst_ld >> 2); w += 256) {
+            uint32_t word = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = 4 * w + e;
+                if (c < cols) word |= sq8_encode(s[c], vmin[c], scale[c]) << (8 * e);
+            }
+            o[w] = word;
+        }
+    }
+}
+
+// code rows of src_ld bytes -> fp32 rows [n, cols]
+__global__ __launch_bounds__(256) void k_sq8_decode(const uint8_t *__restrict__ src, int64_t n, int src_ld, int cols,
+                                                    const float *__restrict__ vmin, const float *__restrict__ scale,
+                                                    float *__restrict__ dst) {
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x)
+        for (int c = threadIdx.x; c < cols; c += 256)
+            dst[i * cols + c] = sq8_decode(src[i * src_ld + c], (double)vmin[c], (double)scale[c]);
 }
 
 // ---- k-means update -------------------------------------------------------------------------------------------------------------
@@ -162,8 +245,12 @@ __global__ __launch_bounds__(256) void k_ivf_scatter(const int32_t *__restrict__
 // takes items b, b + gridDim.x, ...; consecutive items of a list share its rows (the query group is the fast index), so
 // workgroups that run side by side read the same lines.  The score of (query, row) goes to the query's compact row at the pair's
 // offset + the row's position in its list: every entry has one writer.
-template <int METRIC, int CPL>
-__global__ __launch_bounds__(256, 2) void k_ivf_scores(const float *__restrict__ q32p, const float *__restrict__ rows, int dimp,
+// SQ8: `rows` are code rows of dimp bytes.  A lane's chunk is one 4-byte load of four codes (the fp32 rows' lane-to-column map),
+// decoded once per row group to the fp32 values k_sq8_decode gives, with the lane's (double) vmin and scale held in registers for
+// the whole launch; from there on the two forms are the same instructions, so a score has the bits of the decoded row's.
+template <int METRIC, int CPL, bool SQ8>
+__global__ __launch_bounds__(256, 2) void k_ivf_scores(const float *__restrict__ q32p, const void *__restrict__ rows,
+                                                       const float *__restrict__ vmin, const float *__restrict__ scale, int dimp,
                                                        const int64_t *__restrict__ offsets, int nlist, int qt,
                                                        const int32_t *__restrict__ pairoff, const int32_t *__restrict__ itemoff,
                                                        const int32_t *__restrict__ pair_q, const int32_t *__restrict__ pair_off,
@@ -177,6 +264,18 @@ __global__ __launch_bounds__(256, 2) void k_ivf_scores(const float *__restrict__
     const int sel_hi = lane >> 5, sel_16 = (lane >> 4) & 1;
     const int my_row_in4 = sel_hi + 2 * sel_16;
     const int total = itemoff[nlist];
+    double dmin[SQ8 ? 4 * CPL : 1], dscale[SQ8 ? 4 * CPL : 1];
+    if (SQ8) {
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+            const int chunk = lane + WAVE * c;
+            const bool in = chunk < nchunk;
+            const float4 a = in ? *reinterpret_cast<const float4 *>(vmin + 4 * chunk) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 b = in ? *reinterpret_cast<const float4 *>(scale + 4 * chunk) : make_float4(0.f, 0.f, 0.f, 0.f);
+            dmin[4 * c] = (double)a.x; dmin[4 * c + 1] = (double)a.y; dmin[4 * c + 2] = (double)a.z; dmin[4 * c + 3] = (double)a.w;
+            dscale[4 * c] = (double)b.x; dscale[4 * c + 1] = (double)b.y; dscale[4 * c + 2] = (double)b.z; dscale[4 * c + 3] = (double)b.w;
+        }
+    }
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
         int lo = 0, hi = nlist;                                                    // itemoff[lo] <= item < itemoff[hi]
         while (hi - lo > 1) {
@@ -203,7 +302,8 @@ __global__ __launch_bounds__(256, 2) void k_ivf_scores(const float *__restrict__
         __syncthreads();
         const int r0 = rb * IVF_ROWS + wave * 64;                                  // this wave's 64 rows, counted inside the list
         if (r0 >= n) continue;                                                     // (no barrier is skipped: both are behind us)
-        const float *g32 = rows + first * dimp;
+        const float *g32 = static_cast<const float *>(rows) + (SQ8 ? 0 : first * dimp);
+        const uint8_t *g8 = static_cast<const uint8_t *>(rows) + (SQ8 ? first * dimp : 0);
         double keep[16];
 #pragma unroll
         for (int t = 0; t < 16; ++t) keep[t] = 0.0;
@@ -211,15 +311,31 @@ __global__ __launch_bounds__(256, 2) void k_ivf_scores(const float *__restrict__
             const int rg = r0 + grp * 4;
             if (rg >= n) break;
             float4 gv[4][CPL];
+            uint32_t gw[SQ8 ? 4 : 1][CPL];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int64_t row = rg + r < n ? rg + r : n - 1;                   // clamp: results of rows >= n are not stored
 #pragma unroll
                 for (int c = 0; c < CPL; ++c) {
                     const int chunk = lane + WAVE * c;
-                    gv[r][c] = chunk < nchunk ? *reinterpret_cast<const float4 *>(g32 + row * dimp + 4 * chunk)
-                                              : make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (SQ8)
+                        gw[r][c] = chunk < nchunk ? *reinterpret_cast<const uint32_t *>(g8 + row * dimp + 4 * chunk) : 0u;
+                    else
+                        gv[r][c] = chunk < nchunk ? *reinterpret_cast<const float4 *>(g32 + row * dimp + 4 * chunk)
+                                                  : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
+            }
+            if (SQ8) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int c = 0; c < CPL; ++c) {
+                        const uint32_t w = gw[r][c];
+                        gv[r][c] = make_float4(sq8_decode(w & 255u, dmin[4 * c], dscale[4 * c]),
+                                               sq8_decode((w >> 8) & 255u, dmin[4 * c + 1], dscale[4 * c + 1]),
+                                               sq8_decode((w >> 16) & 255u, dmin[4 * c + 2], dscale[4 * c + 2]),
+                                               sq8_decode(w >> 24, dmin[4 * c + 3], dscale[4 * c + 3]));
+                    }
             }
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
@@ -330,16 +446,16 @@ __global__ __launch_bounds__(256) void k_ivf_topk(const double *__restrict__ sco
     }
 }
 
-template <int METRIC>
+template <int METRIC, bool SQ8>
 hipError_t launch_ivf_scores_t(const IvfScoreArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.qt * a.dimp * sizeof(double) + 32 * sizeof(int32_t);
     const unsigned grid = (unsigned)current_device_cus() * 4;
 #define MIRX_IVF_LAUNCH(CPL)                                                                                                   \
     {                                                                                                                          \
-        hipError_t e = set_dynamic_lds(k_ivf_scores<METRIC, CPL>, lds);                                                        \
+        hipError_t e = set_dynamic_lds(k_ivf_scores<METRIC, CPL, SQ8>, lds);                                                   \
         if (e != hipSuccess) return e;                                                                                         \
-        hipLaunchKernelGGL((k_ivf_scores<METRIC, CPL>), dim3(grid), dim3(256), lds, st, a.q32p, a.rows, a.dimp, a.offsets,     \
-                           a.nlist, a.qt, a.pairoff, a.itemoff, a.pair_q, a.pair_off, a.out, a.ld);                            \
+        hipLaunchKernelGGL((k_ivf_scores<METRIC, CPL, SQ8>), dim3(grid), dim3(256), lds, st, a.q32p, a.rows, a.vmin, a.scale,  \
+                           a.dimp, a.offsets, a.nlist, a.qt, a.pairoff, a.itemoff, a.pair_q, a.pair_off, a.out, a.ld);         \
     }
     if (a.dimp <= 256) MIRX_IVF_LAUNCH(1)
     else if (a.dimp <= 512) MIRX_IVF_LAUNCH(2)
@@ -360,7 +476,41 @@ hipError_t launch_ivf_place(const float *src, int64_t n, int src_ld, int cols, c
                             float *dst, int dst_ld, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
-    hipLaunchKernelGGL(k_ivf_place, dim3(grid), dim3(256), 0, st, src, n, src_ld, cols, src_pos, dst_pos, dst, dst_ld);
+    hipLaunchKernelGGL(k_ivf_place<float>, dim3(grid), dim3(256), 0, st, src, n, src_ld, cols, src_pos, dst_pos, dst, dst_ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_ivf_place_codes(const uint8_t *src, int64_t n, int ld, const int64_t *dst_pos, uint8_t *dst, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
+    hipLaunchKernelGGL(k_ivf_place<uint32_t>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint32_t *>(src), n, ld >> 2,
+                       ld >> 2, nullptr, dst_pos, reinterpret_cast<uint32_t *>(dst), ld >> 2);
+    return hipGetLastError();
+}
+
+int sq8_minmax_parts(int64_t n) { return (int)(n < 1024 ? n : 1024); }
+
+hipError_t launch_sq8_range(const float *rows, int64_t n, int dim, int dimp, float *part, float *vmin, float *scale,
+                            hipStream_t st) {
+    const int parts = sq8_minmax_parts(n);
+    hipLaunchKernelGGL(k_sq8_minmax, dim3(parts), dim3(256), 0, st, rows, n, dim, part);
+    hipLaunchKernelGGL(k_sq8_range, dim3((dimp + 255) / 256), dim3(256), 0, st, part, parts, dim, dimp, vmin, scale);
+    return hipGetLastError();
+}
+
+hipError_t launch_sq8_encode_place(const float *src, int64_t n, int cols, const float *vmin, const float *scale,
+                                   const int64_t *dst_pos, uint8_t *dst, int dst_ld, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
+    hipLaunchKernelGGL(k_sq8_encode_place, dim3(grid), dim3(256), 0, st, src, n, cols, vmin, scale, dst_pos, dst, dst_ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_sq8_decode(const uint8_t *src, int64_t n, int src_ld, int cols, const float *vmin, const float *scale,
+                             float *dst, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
+    hipLaunchKernelGGL(k_sq8_decode, dim3(grid), dim3(256), 0, st, src, n, src_ld, cols, vmin, scale, dst);
     return hipGetLastError();
 }
 
@@ -397,7 +547,8 @@ hipError_t launch_ivf_invert(const int64_t *pids, int nq, int nprobe, const int6
 }
 
 hipError_t launch_ivf_scores(const IvfScoreArgs &a, int metric, hipStream_t st) {
-    return metric == MIRX_METRIC_IP ? launch_ivf_scores_t<0>(a, st) : launch_ivf_scores_t<1>(a, st);
+    if (a.vmin) return metric == MIRX_METRIC_IP ? launch_ivf_scores_t<0, true>(a, st) : launch_ivf_scores_t<1, true>(a, st);
+    return metric == MIRX_METRIC_IP ? launch_ivf_scores_t<0, false>(a, st) : launch_ivf_scores_t<1, false>(a, st);
 }
 
 hipError_t launch_ivf_topk(const double *scores, int64_t ld, const int32_t *probes, const int32_t *qoff, int nq, int nprobe,

@@ -1,5 +1,5 @@
-// mirx_ivf.hip -- the IVF_FLAT index of the C ABI (include/mirx.h, mirx_ivf_*): k-means lists over a flat index of the centroids,
-// the list-major fp32 master, and the search of the probed lists (kernels: k_ivf.hip).
+// mirx_ivf.hip -- the IVF indexes of the C ABI (include/mirx.h, mirx_ivf_*): k-means lists over a flat index of the centroids,
+// the list-major master (fp32 rows for IVF_FLAT, 8-bit codes for IVF_SQ8), and the search of the probed lists (kernels: k_ivf.hip).
 //
 // "Nearest centroid" is never restated here: assignments and probes are mirx_index_search / mirx_index_rank_top over `cent`, a
 // mirx_index that holds the centroids with ids 0 .. nlist-1, so the rule (fp64 lane-tree score, ties to the lowest list) is the
@@ -17,11 +17,13 @@
 using namespace mirx;
 
 struct mirx_ivf {
-    int dim = 0, dimp = 0, metric = 0, device = 0, nlist = 0;
+    int dim = 0, dimp = 0, metric = 0, device = 0, nlist = 0, kind = MIRX_IVF_FLAT;
     mirx_index *cent = nullptr;           // flat index over the centroids; null until they are fixed
     DevBuf centroids;                     // [nlist, dim] fp32
     int64_t size = 0;
-    DevBuf rows, ids, offsets;            // [size, dimp] list-major, [size], [nlist + 1] int64
+    DevBuf rows, ids, offsets;            // [size, dimp] list-major (fp32, or uint8 codes for SQ8), [size], [nlist + 1] int64
+    DevBuf range;                         // SQ8: vmin [dimp] then scale [dimp] fp32, zero in the padding
+    bool range_fixed = false;
     std::vector<int64_t> off_h, ids_h, seq_h;   // host mirrors of offsets / ids, and each row's insertion number (list-major)
     int64_t next_seq = 0, next_auto = 0;
     int64_t score_bytes = 0;              // MIRX_IVF_OPT_SCORE_BYTES; 0 = SCORE_WS_BYTES
@@ -30,6 +32,11 @@ struct mirx_ivf {
         pair_off, scores;
     unsigned long long *stats_dev = nullptr;   // [3] rows scored, pairs, work items
     int64_t last_nq = 0, last_batches = 0;
+
+    bool sq8() const { return kind == MIRX_IVF_SQ8; }
+    size_t row_bytes() const { return (size_t)dimp * (sq8() ? 1 : sizeof(float)); }
+    const float *vmin() const { return range.as<float>(); }
+    const float *scale() const { return range.as<float>() + dimp; }
 };
 
 namespace {
@@ -41,6 +48,15 @@ constexpr int64_t MAX_BATCH_PAIRS = (int64_t)1 << 26;   // (query, probe) pairs 
     MIRX_CHECK(ivf, std::string(who) + ": null ivf");                                   \
     DeviceGuard dg((ivf)->device);                                                      \
     if (!dg.ok) return fail(MIRX_EHIP, std::string(who) + ": cannot select the ivf's device")
+
+#define MIRX_IVF_SQ8_ONLY(ivf, who) MIRX_CHECK((ivf)->sq8(), std::string(who) + ": the ivf is not MIRX_IVF_SQ8")
+
+// SQ8 keeps no originals: what would re-assign or re-encode the resident rows is refused
+int sq8_resident(const mirx_ivf *ivf, const char *who) {
+    if (ivf->sq8() && ivf->size > 0)
+        return fail(MIRX_ESTATE, std::string(who) + ": an IVF_SQ8 index that holds rows keeps its centroids and range (the original rows are gone)");
+    return MIRX_OK;
+}
 
 // rows as a device pointer: the caller's, or a copy in `buf`
 int device_rows(mirx_ivf *ivf, const float *rows, int64_t n, DevBuf &buf, const float **out) {
@@ -90,7 +106,7 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *ne
     const int64_t n_old = ivf->size;
     DevBuf rows2, ids2;
     const size_t pos_bytes = (size_t)std::max<int64_t>(n_old, n_new) * sizeof(int64_t);
-    if (rows2.ensure((size_t)std::max<int64_t>(total, 1) * ivf->dimp * sizeof(float)) != hipSuccess ||
+    if (rows2.ensure((size_t)std::max<int64_t>(total, 1) * ivf->row_bytes()) != hipSuccess ||
         ids2.ensure((size_t)std::max<int64_t>(total, 1) * sizeof(int64_t)) != hipSuccess ||
         ivf->pos.ensure(std::max<size_t>(pos_bytes, 8)) != hipSuccess ||
         ivf->newids.ensure((size_t)std::max<int64_t>(n_new, 1) * sizeof(int64_t)) != hipSuccess ||
@@ -99,8 +115,11 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *ne
     std::vector<int64_t> ids_h((size_t)total), seq_h((size_t)total);
     if (n_old) {
         MIRX_HIP(hipMemcpyAsync(ivf->pos.p, old_dst.data(), (size_t)n_old * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        MIRX_HIP(launch_ivf_place(ivf->rows.as<float>(), n_old, ivf->dimp, ivf->dimp, nullptr, ivf->pos.as<int64_t>(),
-                                  rows2.as<float>(), ivf->dimp, st));
+        if (ivf->sq8())
+            MIRX_HIP(launch_ivf_place_codes(ivf->rows.as<uint8_t>(), n_old, ivf->dimp, ivf->pos.as<int64_t>(), rows2.as<uint8_t>(), st));
+        else
+            MIRX_HIP(launch_ivf_place(ivf->rows.as<float>(), n_old, ivf->dimp, ivf->dimp, nullptr, ivf->pos.as<int64_t>(),
+                                      rows2.as<float>(), ivf->dimp, st));
         MIRX_HIP(launch_ivf_place_ids(ivf->ids.as<int64_t>(), n_old, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
         MIRX_HIP(hipStreamSynchronize(st));                     // pos is reused below
         for (int64_t p = 0; p < n_old; ++p)
@@ -112,8 +131,12 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *ne
     if (n_new) {
         MIRX_HIP(hipMemcpyAsync(ivf->pos.p, new_dst.data(), (size_t)n_new * sizeof(int64_t), hipMemcpyHostToDevice, st));
         MIRX_HIP(hipMemcpyAsync(ivf->newids.p, new_ids.data(), (size_t)n_new * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        MIRX_HIP(launch_ivf_place(new_rows, n_new, ivf->dim, ivf->dim, nullptr, ivf->pos.as<int64_t>(), rows2.as<float>(),
-                                  ivf->dimp, st));
+        if (ivf->sq8())
+            MIRX_HIP(launch_sq8_encode_place(new_rows, n_new, ivf->dim, ivf->vmin(), ivf->scale(), ivf->pos.as<int64_t>(),
+                                             rows2.as<uint8_t>(), ivf->dimp, st));
+        else
+            MIRX_HIP(launch_ivf_place(new_rows, n_new, ivf->dim, ivf->dim, nullptr, ivf->pos.as<int64_t>(), rows2.as<float>(),
+                                      ivf->dimp, st));
         MIRX_HIP(launch_ivf_place_ids(ivf->newids.as<int64_t>(), n_new, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
         for (int64_t j = 0; j < n_new; ++j) {
             ids_h[(size_t)new_dst[(size_t)j]] = new_ids[(size_t)j];
@@ -134,7 +157,7 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *ne
     return MIRX_OK;
 }
 
-// the resident rows to the lists of the current centroids, insertion order kept inside each list
+// the resident rows to the lists of the current centroids, insertion order kept inside each list (fp32 rows only: sq8_resident)
 int reassign_resident(mirx_ivf *ivf, hipStream_t st) {
     const int64_t n = ivf->size;
     if (n == 0) return MIRX_OK;
@@ -176,8 +199,13 @@ int mirx_ivf_query_tile(int dim) {
 int mirx_ivf_row_block(void) { return IVF_ROWS; }
 
 int mirx_ivf_create(int dim, int metric, int nlist, int device, mirx_ivf **out) {
+    return mirx_ivf_create_typed(dim, metric, nlist, MIRX_IVF_FLAT, device, out);
+}
+
+int mirx_ivf_create_typed(int dim, int metric, int nlist, int kind, int device, mirx_ivf **out) {
     MIRX_CHECK(out, "ivf_create: out is null");
     *out = nullptr;
+    MIRX_CHECK(kind == MIRX_IVF_FLAT || kind == MIRX_IVF_SQ8, "ivf_create: unknown kind (MIRX_IVF_FLAT, MIRX_IVF_SQ8)");
     MIRX_CHECK(dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "ivf_create: dim out of range (1 .. 2048)");
     MIRX_CHECK(metric == MIRX_METRIC_IP || metric == MIRX_METRIC_NEG_L2, "ivf_create: unknown metric");
     MIRX_CHECK(nlist >= 1 && nlist <= MIRX_IVF_MAX_NLIST, "ivf_create: nlist out of range (1 .. 65536)");
@@ -193,11 +221,13 @@ int mirx_ivf_create(int dim, int metric, int nlist, int device, mirx_ivf **out) 
     ivf->metric = metric;
     ivf->nlist = nlist;
     ivf->device = device;
+    ivf->kind = kind;
     ivf->off_h.assign((size_t)nlist + 1, 0);
     hipError_t e;
     if ((e = ivf->centroids.ensure((size_t)nlist * dim * sizeof(float))) != hipSuccess ||
         (e = ivf->offsets.ensure((size_t)(nlist + 1) * sizeof(int64_t))) != hipSuccess ||
         (e = hipMemset(ivf->offsets.p, 0, (size_t)(nlist + 1) * sizeof(int64_t))) != hipSuccess ||
+        (kind == MIRX_IVF_SQ8 && (e = ivf->range.ensure((size_t)2 * ivf->dimp * sizeof(float))) != hipSuccess) ||
         (e = hipMalloc(&ivf->stats_dev, 3 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipMemset(ivf->stats_dev, 0, 3 * sizeof(unsigned long long))) != hipSuccess) {
         mirx_ivf_destroy(ivf);
@@ -206,6 +236,8 @@ int mirx_ivf_create(int dim, int metric, int nlist, int device, mirx_ivf **out) 
     *out = ivf;
     return MIRX_OK;
 }
+
+int mirx_ivf_kind(const mirx_ivf *ivf) { return ivf ? ivf->kind : -1; }
 
 void mirx_ivf_destroy(mirx_ivf *ivf) {
     if (!ivf) return;
@@ -220,6 +252,7 @@ int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *i
     MIRX_CHECK(n >= ivf->nlist, "ivf_train: fewer rows than lists");
     MIRX_CHECK(n <= 0x7FFFFF00ll, "ivf_train: more than 2^31 rows");
     MIRX_CHECK(iters >= 0, "ivf_train: iters must not be negative");
+    if (int rc = sq8_resident(ivf, "ivf_train")) return rc;
     const int nlist = ivf->nlist, dim = ivf->dim;
     std::vector<int64_t> start((size_t)nlist);
     for (int j = 0; j < nlist; ++j) {
@@ -261,6 +294,7 @@ int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *i
 
 int mirx_ivf_set_centroids(mirx_ivf *ivf, const float *centroids) {
     MIRX_CHECK(ivf && centroids, "ivf_set_centroids: null argument");
+    if (int rc = sq8_resident(ivf, "ivf_set_centroids")) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_set_centroids");
     MIRX_HIP(hipMemcpy(ivf->centroids.p, centroids, (size_t)ivf->nlist * ivf->dim * sizeof(float), hipMemcpyDefault));
     return fix_centroids(ivf, nullptr);
@@ -277,6 +311,8 @@ int mirx_ivf_get_centroids(const mirx_ivf *ivf, float *out_centroids) {
 int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids_or_null) {
     MIRX_CHECK(ivf && n >= 0 && (rows || n == 0), "ivf_add: bad argument");
     if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_add: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    if (ivf->sq8() && !ivf->range_fixed)
+        return fail(MIRX_ESTATE, "ivf_add: the range is not fixed yet (mirx_ivf_sq8_train / _sq8_set_range)");
     MIRX_CHECK(ivf->size + n <= 0x7FFFFF00ll, "ivf_add: more than 2^31 rows per index");
     MIRX_IVF_ENTER(ivf, "ivf_add");
     if (n == 0) return MIRX_OK;
@@ -331,6 +367,99 @@ int mirx_ivf_remove_ids(mirx_ivf *ivf, const int64_t *ids, int64_t n, int64_t *o
 }
 
 int64_t mirx_ivf_size(const mirx_ivf *ivf) { return ivf ? ivf->size : -1; }
+
+int mirx_ivf_sq8_train(mirx_ivf *ivf, const float *rows, int64_t n, void *stream) {
+    MIRX_CHECK(ivf && rows, "ivf_sq8_train: null argument");
+    MIRX_IVF_SQ8_ONLY(ivf, "ivf_sq8_train");
+    MIRX_CHECK(n >= 1, "ivf_sq8_train: no rows");
+    if (int rc = sq8_resident(ivf, "ivf_sq8_train")) return rc;
+    MIRX_IVF_ENTER(ivf, "ivf_sq8_train");
+    hipStream_t st = (hipStream_t)stream;
+    const float *drows = nullptr;
+    DevBuf trows;
+    if (int rc = device_rows(ivf, rows, n, trows, &drows)) return rc;
+    MIRX_HIP(ivf->upd.ensure((size_t)sq8_minmax_parts(n) * 2 * ivf->dim * sizeof(float)));
+    MIRX_HIP(launch_sq8_range(drows, n, ivf->dim, ivf->dimp, ivf->upd.as<float>(), ivf->range.as<float>(),
+                              ivf->range.as<float>() + ivf->dimp, st));
+    MIRX_HIP(hipStreamSynchronize(st));                      // trows may be a copy that ends with the call
+    ivf->range_fixed = true;
+    return MIRX_OK;
+}
+
+int mirx_ivf_sq8_set_range(mirx_ivf *ivf, const float *vmin, const float *scale) {
+    MIRX_CHECK(ivf && vmin && scale, "ivf_sq8_set_range: null argument");
+    MIRX_IVF_SQ8_ONLY(ivf, "ivf_sq8_set_range");
+    if (int rc = sq8_resident(ivf, "ivf_sq8_set_range")) return rc;
+    MIRX_IVF_ENTER(ivf, "ivf_sq8_set_range");
+    MIRX_HIP(hipMemset(ivf->range.p, 0, (size_t)2 * ivf->dimp * sizeof(float)));
+    MIRX_HIP(hipMemcpy(ivf->range.p, vmin, (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
+    MIRX_HIP(hipMemcpy(ivf->range.as<float>() + ivf->dimp, scale, (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
+    ivf->range_fixed = true;
+    return MIRX_OK;
+}
+
+int mirx_ivf_sq8_get_range(const mirx_ivf *ivf, float *out_vmin, float *out_scale) {
+    MIRX_CHECK(ivf && out_vmin && out_scale, "ivf_sq8_get_range: null argument");
+    MIRX_IVF_SQ8_ONLY(ivf, "ivf_sq8_get_range");
+    if (!ivf->range_fixed) return fail(MIRX_ESTATE, "ivf_sq8_get_range: the range is not fixed yet (mirx_ivf_sq8_train / _sq8_set_range)");
+    MIRX_IVF_ENTER(ivf, "ivf_sq8_get_range");
+    MIRX_HIP(hipMemcpy(out_vmin, ivf->vmin(), (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
+    MIRX_HIP(hipMemcpy(out_scale, ivf->scale(), (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
+    return MIRX_OK;
+}
+
+// ids and list numbers of the resident rows in list-major order, to device arrays (either may be null)
+static int resident_ids_lists(const mirx_ivf *ivf, int64_t *out_ids, int64_t *out_lists) {
+    if (out_ids) MIRX_HIP(hipMemcpy(out_ids, ivf->ids.p, (size_t)ivf->size * sizeof(int64_t), hipMemcpyDeviceToDevice));
+    if (out_lists) {
+        std::vector<int64_t> lists((size_t)ivf->size);
+        for (int l = 0; l < ivf->nlist; ++l)
+            std::fill(lists.begin() + ivf->off_h[(size_t)l], lists.begin() + ivf->off_h[(size_t)l + 1], (int64_t)l);
+        MIRX_HIP(hipMemcpy(out_lists, lists.data(), (size_t)ivf->size * sizeof(int64_t), hipMemcpyHostToDevice));
+    }
+    return MIRX_OK;
+}
+
+int mirx_ivf_get_codes(const mirx_ivf *ivf, uint8_t *out_codes, int64_t *out_ids_or_null, int64_t *out_lists_or_null) {
+    MIRX_CHECK(ivf && (out_codes || ivf->size == 0), "ivf_get_codes: null argument");
+    MIRX_IVF_SQ8_ONLY(ivf, "ivf_get_codes");
+    MIRX_IVF_ENTER(ivf, "ivf_get_codes");
+    if (ivf->size == 0) return MIRX_OK;
+    MIRX_HIP(hipMemcpy2D(out_codes, (size_t)ivf->dim, ivf->rows.p, (size_t)ivf->dimp, (size_t)ivf->dim, (size_t)ivf->size,
+                         hipMemcpyDeviceToDevice));
+    return resident_ids_lists(ivf, out_ids_or_null, out_lists_or_null);
+}
+
+int mirx_ivf_reconstruct(const mirx_ivf *ivf, float *out_rows, int64_t *out_ids_or_null) {
+    MIRX_CHECK(ivf && (out_rows || ivf->size == 0), "ivf_reconstruct: null argument");
+    MIRX_IVF_SQ8_ONLY(ivf, "ivf_reconstruct");
+    MIRX_IVF_ENTER(ivf, "ivf_reconstruct");
+    if (ivf->size == 0) return MIRX_OK;
+    MIRX_HIP(launch_sq8_decode(ivf->rows.as<uint8_t>(), ivf->size, ivf->dimp, ivf->dim, ivf->vmin(), ivf->scale(), out_rows, nullptr));
+    MIRX_HIP(hipStreamSynchronize(nullptr));
+    return resident_ids_lists(ivf, out_ids_or_null, nullptr);
+}
+
+int mirx_sq8_encode(const float *rows, int64_t n, int dim, const float *vmin, const float *scale, uint8_t *out_codes, void *stream) {
+    MIRX_CHECK(n >= 0 && dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "sq8_encode: n or dim out of range");
+    MIRX_CHECK((rows && out_codes && vmin && scale) || n == 0, "sq8_encode: null argument");
+    if (n == 0) return MIRX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int dimp = (int)round_up(dim, DIM_ALIGN);
+    DevBuf padded;                                           // the kernel stores whole words: rows of dimp bytes, copied out below
+    if (padded.ensure((size_t)n * dimp) != hipSuccess) return fail(MIRX_ENOMEM, "sq8_encode: no memory for the padded codes");
+    MIRX_HIP(launch_sq8_encode_place(rows, n, dim, vmin, scale, nullptr, padded.as<uint8_t>(), dimp, st));
+    MIRX_HIP(hipMemcpy2DAsync(out_codes, (size_t)dim, padded.p, (size_t)dimp, (size_t)dim, (size_t)n, hipMemcpyDeviceToDevice, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    return MIRX_OK;
+}
+
+int mirx_sq8_decode(const uint8_t *codes, int64_t n, int dim, const float *vmin, const float *scale, float *out_rows, void *stream) {
+    MIRX_CHECK(n >= 0 && dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "sq8_decode: n or dim out of range");
+    MIRX_CHECK((codes && out_rows && vmin && scale) || n == 0, "sq8_decode: null argument");
+    MIRX_HIP(launch_sq8_decode(codes, n, dim, dim, vmin, scale, out_rows, (hipStream_t)stream));
+    return MIRX_OK;
+}
 
 int mirx_ivf_list_sizes(const mirx_ivf *ivf, int64_t *out_sizes) {
     MIRX_CHECK(ivf && out_sizes, "ivf_list_sizes: null argument");
@@ -411,7 +540,9 @@ int mirx_ivf_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int nprobe
                                    ivf->pair_q.as<int32_t>(), ivf->pair_off.as<int32_t>(), ivf->stats_dev, st));
         IvfScoreArgs sa{};
         sa.q32p = ivf->q32p.as<float>();
-        sa.rows = ivf->rows.as<float>();
+        sa.rows = ivf->rows.p;
+        sa.vmin = ivf->sq8() ? ivf->vmin() : nullptr;
+        sa.scale = ivf->sq8() ? ivf->scale() : nullptr;
         sa.dimp = dimp;
         sa.nlist = nlist;
         sa.qt = qt;

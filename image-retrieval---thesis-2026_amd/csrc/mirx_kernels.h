@@ -520,6 +520,18 @@ int ivf_query_tile(int dimp);                    // queries per work item: min(1
 hipError_t launch_ivf_place(const float *src, int64_t n, int src_ld, int cols, const int64_t *src_pos, const int64_t *dst_pos,
                             float *dst, int dst_ld, hipStream_t st);
 hipError_t launch_ivf_place_ids(const int64_t *src, int64_t n, const int64_t *dst_pos, int64_t *dst, hipStream_t st);
+// the same move for IVF_SQ8's code rows of ld bytes (a multiple of 4): dst row dst_pos[i] = src row i, a negative dst_pos drops it
+hipError_t launch_ivf_place_codes(const uint8_t *src, int64_t n, int ld, const int64_t *dst_pos, uint8_t *dst, hipStream_t st);
+// IVF_SQ8's quantiser (include/mirx.h).  range: vmin / scale [dimp] from rows [n, dim], n >= 1, part = scratch of
+// sq8_minmax_parts(n) * 2 * dim floats; encode_place: rows [n, cols] -> code rows of dst_ld bytes (a multiple of 4, zero codes
+// past cols) at dst row (dst_pos ? dst_pos[i] : i); decode: code rows of src_ld bytes -> fp32 [n, cols].
+int sq8_minmax_parts(int64_t n);
+hipError_t launch_sq8_range(const float *rows, int64_t n, int dim, int dimp, float *part, float *vmin, float *scale,
+                            hipStream_t st);
+hipError_t launch_sq8_encode_place(const float *src, int64_t n, int cols, const float *vmin, const float *scale,
+                                   const int64_t *dst_pos, uint8_t *dst, int dst_ld, hipStream_t st);
+hipError_t launch_sq8_decode(const uint8_t *src, int64_t n, int src_ld, int cols, const float *vmin, const float *scale,
+                             float *dst, hipStream_t st);
 // One Lloyd update.  order = the training rows sorted by list (stable), loff[nlist + 1] = where each list starts in it.  cent[l] =
 // fp32(sum in fp64, ascending row order / count), then normalised as launch_l2_normalize does when `normalize`; an empty list keeps
 // its centroid.  upd = scratch [nlist, dim].
@@ -534,7 +546,8 @@ hipError_t launch_ivf_invert(const int64_t *pids, int nq, int nprobe, const int6
                              int32_t *pair_q, int32_t *pair_off, unsigned long long *stats, hipStream_t st);
 struct IvfScoreArgs {
     const float *q32p;           // [nq, dimp] the batch's queries, zero padded
-    const float *rows;           // [size, dimp] list-major
+    const void *rows;            // [size, dimp] list-major: fp32, or 8-bit codes when vmin is set
+    const float *vmin, *scale;   // [dimp] IVF_SQ8's range, zero in the padding; both null for fp32 rows
     int dimp, nlist, qt;
     const int64_t *offsets;      // [nlist + 1]
     const int32_t *pairoff, *itemoff, *pair_q, *pair_off;   // launch_ivf_invert's

@@ -720,22 +720,24 @@ class IvfFlatIndex:
     bit what FlatIndex.search(allow=rows whose list is probed) returns.  Only the choice of lists is approximate; nprobe >= nlist
     is FlatIndex.search's answer.  "Nearest" is FlatIndex's own ranking over the centroids (ties to the lowest list)."""
 
+    KIND = _lib.IVF_FLAT
+
     def __init__(self, dim, metric="COSINE", nlist=1024, device=None):
         if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= _lib.IVF_MAX_NLIST:
             raise ValueError(f"nlist must be an integer in [1, {_lib.IVF_MAX_NLIST}], got {nlist!r}")
         if not 1 <= int(dim) <= _lib.IVF_MAX_DIM:
-            raise ValueError(f"IvfFlatIndex: dim must be in [1, {_lib.IVF_MAX_DIM}], got {dim}")
+            raise ValueError(f"{type(self).__name__}: dim must be in [1, {_lib.IVF_MAX_DIM}], got {dim}")
         self.metric = metric_code(metric)
         if not torch.cuda.is_available():
-            raise MirxError("IvfFlatIndex needs a GPU: libmirx has no CPU path")
+            raise MirxError(f"{type(self).__name__} needs a GPU: libmirx has no CPU path")
         self._lib = _lib.load()
         if device is None:
             device = torch.cuda.current_device()
         self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         self.dim, self.nlist = int(dim), int(nlist)
         h = ctypes.c_void_p()
-        _lib.check(self._lib.mirx_ivf_create(self.dim, self.metric, self.nlist, self.device.index, ctypes.byref(h)),
-                   "mirx_ivf_create")
+        _lib.check(self._lib.mirx_ivf_create_typed(self.dim, self.metric, self.nlist, self.KIND, self.device.index,
+                                                   ctypes.byref(h)), "mirx_ivf_create_typed")
         self._h = h
 
     def __del__(self):
@@ -762,11 +764,8 @@ class IvfFlatIndex:
         with torch.cuda.device(self.device):
             _lib.check(getattr(self._lib, name)(self._h, *args), name)
 
-    def train(self, rows, iters=10, init_positions=None, max_rows=None):
-        """Lloyd's k-means (mirx_ivf_train) and fix the centroids: start from rows[init_positions] (default: the rows at
-        floor(j n / nlist)), `iters` updates at most, stop early when no row changes its list.  It trains on at most max_rows
-        rows taken at an even stride (row floor(i n / max_rows)); max_rows=None means 256 * nlist.  Deterministic: two calls
-        give equal bits."""
+    def _train_sample(self, rows, iters, init_positions, max_rows):
+        """train()'s argument checks -> (the rows to train on: at most max_rows at an even stride, init positions or None)"""
         rows = self._rows(rows, "train")
         limit = IVF_TRAIN_ROWS_PER_LIST * self.nlist if max_rows is None else int(max_rows)
         if limit < self.nlist:
@@ -786,6 +785,14 @@ class IvfFlatIndex:
             pos = np.ascontiguousarray(np.asarray(init_positions).reshape(-1), dtype=np.int64)
             if pos.size != self.nlist or (pos < 0).any() or (pos >= rows.shape[0]).any():
                 raise ValueError(f"train: init_positions needs {self.nlist} row numbers in [0, {rows.shape[0]})")
+        return rows, pos
+
+    def train(self, rows, iters=10, init_positions=None, max_rows=None):
+        """Lloyd's k-means (mirx_ivf_train) and fix the centroids: start from rows[init_positions] (default: the rows at
+        floor(j n / nlist)), `iters` updates at most, stop early when no row changes its list.  It trains on at most max_rows
+        rows taken at an even stride (row floor(i n / max_rows)); max_rows=None means 256 * nlist.  Deterministic: two calls
+        give equal bits."""
+        rows, pos = self._train_sample(rows, iters, init_positions, max_rows)
         self._call("mirx_ivf_train", _ptr(rows), rows.shape[0], None if pos is None else ctypes.c_void_p(pos.ctypes.data),
                    int(iters), _stream_ptr(self.device))
 
@@ -861,6 +868,97 @@ class IvfFlatIndex:
         s = _lib.IvfStats()
         self._call("mirx_ivf_last_stats", _stream_ptr(self.device), ctypes.byref(s))
         return s.as_dict()
+
+
+class IvfSq8Index(IvfFlatIndex):
+    """IVF_SQ8 (mirx_ivf_create_typed(MIRX_IVF_SQ8), include/mirx.h): IvfFlatIndex with the rows kept as 8-bit codes, a quarter
+    of the fp32 master.  The quantiser is per column and global: code = round((x - vmin[d]) / scale[d]) clamped to 0 .. 255, the
+    decoded value (float)(vmin[d] + code * scale[d]) in double arithmetic.  A row's list comes from its original values; then the
+    row is encoded and the original is gone.  search() returns THE EXACT TOP-K OVER THE DECODED ROWS of the probed lists: bit for
+    bit FlatIndex.search(allow=rows whose list is probed) on a FlatIndex over reconstruct()'s rows.  An index that holds rows
+    keeps its centroids and its range (MirxError from train / set_centroids / train_range / set_range): remove the rows first."""
+
+    KIND = _lib.IVF_SQ8
+
+    def train(self, rows, iters=10, init_positions=None, max_rows=None):
+        """IvfFlatIndex.train, and the range (train_range) from the same strided sample"""
+        rows, pos = self._train_sample(rows, iters, init_positions, max_rows)
+        self._call("mirx_ivf_train", _ptr(rows), rows.shape[0], None if pos is None else ctypes.c_void_p(pos.ctypes.data),
+                   int(iters), _stream_ptr(self.device))
+        self._call("mirx_ivf_sq8_train", _ptr(rows), rows.shape[0], _stream_ptr(self.device))
+
+    def train_range(self, rows):
+        """Fix the range to the rows' per-column minimum and (maximum - minimum) / 255 (NaN ignored); every row is read."""
+        rows = self._rows(rows, "train_range")
+        if rows.shape[0] < 1:
+            raise ValueError("train_range: no rows")
+        self._call("mirx_ivf_sq8_train", _ptr(rows), rows.shape[0], _stream_ptr(self.device))
+
+    def set_range(self, vmin, scale):
+        """Fix the range to a caller's vmin [dim] and scale [dim]."""
+        arrs = []
+        for name, v in (("vmin", vmin), ("scale", scale)):
+            v = torch.as_tensor(v).detach().to(torch.float32).reshape(-1).contiguous()
+            if v.numel() != self.dim:
+                raise ValueError(f"set_range: {name} needs {self.dim} values, got {v.numel()}")
+            arrs.append(v.to(self.device) if v.is_cuda else v)
+        torch.cuda.current_stream(self.device).synchronize()
+        self._call("mirx_ivf_sq8_set_range", _ptr(arrs[0]), _ptr(arrs[1]))
+
+    @property
+    def range(self):
+        """(vmin [dim], scale [dim]) fp32 on the index device"""
+        vmin = torch.empty((self.dim,), dtype=torch.float32, device=self.device)
+        scale = torch.empty((self.dim,), dtype=torch.float32, device=self.device)
+        self._call("mirx_ivf_sq8_get_range", _ptr(vmin), _ptr(scale))
+        return vmin, scale
+
+    def codes(self):
+        """-> (codes uint8 [n, dim], ids int64 [n], lists int64 [n]) on the index device, in list-major order"""
+        n = len(self)
+        codes = torch.empty((n, self.dim), dtype=torch.uint8, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        lists = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_get_codes", _ptr_or_null(codes), _ptr_or_null(ids), _ptr_or_null(lists))
+        return codes, ids, lists
+
+    def reconstruct(self):
+        """-> (decoded rows fp32 [n, dim], ids int64 [n]) on the index device, in list-major order: the rows search() scores"""
+        n = len(self)
+        rows = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_reconstruct", _ptr_or_null(rows), _ptr_or_null(ids))
+        return rows, ids
+
+
+def sq8_encode(rows, vmin, scale):
+    """mirx_sq8_encode: CUDA fp32 rows [n, dim] -> uint8 codes [n, dim] under vmin / scale [dim]"""
+    rows, vmin, scale = (torch.as_tensor(t).to(torch.float32).contiguous() for t in (rows, vmin, scale))
+    if not rows.is_cuda or rows.dim() != 2 or vmin.shape != (rows.shape[1],) or scale.shape != (rows.shape[1],):
+        raise ValueError("sq8_encode expects CUDA rows [n, dim] and vmin / scale [dim]")
+    vmin, scale = vmin.to(rows.device), scale.to(rows.device)
+    out = torch.empty(rows.shape, dtype=torch.uint8, device=rows.device)
+    with torch.cuda.device(rows.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_sq8_encode(_ptr_or_null(rows), rows.shape[0], rows.shape[1], _ptr(vmin), _ptr(scale),
+                                               _ptr_or_null(out), _stream_ptr(rows.device)), "mirx_sq8_encode")
+    return out
+
+
+def sq8_decode(codes, vmin, scale):
+    """mirx_sq8_decode: CUDA uint8 codes [n, dim] -> fp32 rows [n, dim], (float)(vmin + code * scale) in double arithmetic"""
+    codes = torch.as_tensor(codes).contiguous()
+    vmin, scale = (torch.as_tensor(t).to(torch.float32).contiguous() for t in (vmin, scale))
+    if not codes.is_cuda or codes.dtype != torch.uint8 or codes.dim() != 2 or vmin.shape != (codes.shape[1],) or \
+            scale.shape != (codes.shape[1],):
+        raise ValueError("sq8_decode expects CUDA uint8 codes [n, dim] and vmin / scale [dim]")
+    vmin, scale = vmin.to(codes.device), scale.to(codes.device)
+    out = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
+    with torch.cuda.device(codes.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_sq8_decode(_ptr_or_null(codes), codes.shape[0], codes.shape[1], _ptr(vmin), _ptr(scale),
+                                               _ptr_or_null(out), _stream_ptr(codes.device)), "mirx_sq8_decode")
+    return out
 
 
 def l2_normalize_(x):

@@ -13,7 +13,7 @@ The "server" is a device-resident FlatIndex (libmirx); searches are EXACT (the r
 IVF_FLAT nlist=1024 / nprobe=10 index is approximate, milvus_setup.py:191-213) and
 `search_params` / `nprobe` are accepted and ignored, except `radius` / `range_filter` (a range search) and, on a collection
 whose index was created with `create_index(..., approximate=True)`, `nprobe`: the opt-in IVF_FLAT index (mirx.index.IvfFlatIndex,
-DESIGN 41) that reproduces the reference's own search.  Metadata (image_path, label) stays on
+DESIGN 41) that reproduces the reference's own search, or IVF_SQ8 (mirx.index.IvfSq8Index), the same over 8-bit codes.  Metadata (image_path, label) stays on
 the host, keyed by the int64 ids the index returns.
 
 Errors follow the reference: unknown model type -> ValueError; connect() swallows failures
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex, IvfFlatIndex, group_bounds, range_bounds, tier1_max_k
+from .index import FlatIndex, IvfFlatIndex, IvfSq8Index, group_bounds, range_bounds, tier1_max_k
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -148,8 +148,10 @@ class Collection:
         self._resident = stored is None                     # whether _index mirrors the live rows
         # the opt-in approximate index (create_index(..., approximate=True)): process state, never stored
         self._approx_nlist = None                           # nlist while the approximate index is on
-        self._ivf = None                                    # the IvfFlatIndex over the live rows; None = to be (re)built
+        self._approx_type = None                            # "IVF_FLAT" or "IVF_SQ8" while it is on
+        self._ivf = None                                    # the IvfFlatIndex / IvfSq8Index over the live rows; None = to be (re)built
         self._ivf_centroids = None                          # its centroids, trained once and kept across rebuilds
+        self._ivf_range = None                              # IVF_SQ8: its (vmin, scale), trained once and kept likewise
 
     @classmethod
     def from_stored(cls, stored, device=None):
@@ -277,16 +279,18 @@ class Collection:
 
     def create_index(self, field_name="embedding", index_params=None, approximate=False):
         """pymilvus' create_index.  Without `approximate` only the metric is kept: index_type and nlist are accepted and
-        ignored, every search is exact.  approximate=True with index_params["index_type"] == "IVF_FLAT" (any other type:
-        ValueError) turns the collection's approximate index on: an IvfFlatIndex of index_params["params"]["nlist"] lists
-        (default 1024) beside the flat index, built from the resident rows at load() or at the first approximate search and
-        trained once; after insert / delete / compact the lists are rebuilt lazily with the kept centroids.  It is process
-        state: a stored collection opened again is exact until this call is made again.  See search() for the calls it serves."""
+        ignored, every search is exact.  approximate=True with index_params["index_type"] "IVF_FLAT" or "IVF_SQ8" (any other
+        type: ValueError) turns the collection's approximate index on: an IvfFlatIndex / IvfSq8Index of
+        index_params["params"]["nlist"] lists (default 1024) beside the flat index, built from the resident rows at load() or at
+        the first approximate search and trained once; after insert / delete / compact the lists are rebuilt lazily with the
+        kept centroids (IVF_SQ8: and the kept range, so rows inserted later clamp to the trained range).  It is process state: a
+        stored collection opened again is exact until this call is made again.  See search() for the calls it serves."""
         params = index_params or {}
-        nlist = None
+        nlist, kind = None, None
         if approximate:
-            if params.get("index_type") != "IVF_FLAT":
-                raise ValueError(f"approximate=True needs index_type 'IVF_FLAT', got {params.get('index_type')!r}")
+            kind = params.get("index_type")
+            if kind not in ("IVF_FLAT", "IVF_SQ8"):
+                raise ValueError(f"approximate=True needs index_type 'IVF_FLAT' or 'IVF_SQ8', got {kind!r}")
             inner = params.get("params") if isinstance(params.get("params"), dict) else {}
             nlist = inner.get("nlist", 1024)
             if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= 65536:
@@ -298,8 +302,9 @@ class Collection:
         self.metric_type = metric
         if self._stored is not None:
             self._stored.set_metric(metric)
-        if nlist != self._approx_nlist:
-            self._approx_nlist, self._ivf, self._ivf_centroids = nlist, None, None
+        if (nlist, kind) != (self._approx_nlist, self._approx_type):
+            self._approx_nlist, self._approx_type = nlist, kind
+            self._ivf, self._ivf_centroids, self._ivf_range = None, None, None
         return True
 
     def _ensure_ivf(self):
@@ -311,12 +316,16 @@ class Collection:
         if self._ivf is None:
             index = self._ensure()
             rows, ids = index.rows()
-            ivf = IvfFlatIndex(self.dim, self.metric_type, self._approx_nlist, index.device)
+            sq8 = self._approx_type == "IVF_SQ8"
+            ivf = (IvfSq8Index if sq8 else IvfFlatIndex)(self.dim, self.metric_type, self._approx_nlist, index.device)
             if self._ivf_centroids is None:
                 ivf.train(rows)
                 self._ivf_centroids = ivf.centroids
+                self._ivf_range = ivf.range if sq8 else None
             else:
                 ivf.set_centroids(self._ivf_centroids)
+                if sq8:
+                    ivf.set_range(*self._ivf_range)
             ivf.add(rows, ids)
             self._ivf = ivf
         return self._ivf
@@ -594,10 +603,10 @@ class Collection:
         hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes.
         param: {"params": {"radius": r, "range_filter": f}} (or the two keys at the top level) makes it pymilvus' range search:
         the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored,
-        with one exception: on a collection whose index was created with approximate=True (IVF_FLAT), a plain top-k call --
+        with one exception: on a collection whose index was created with approximate=True (IVF_FLAT or IVF_SQ8), a plain top-k call --
         no expr, no grouping, no leave-out, no radius, limit <= 1024; exclude_ids allowed -- whose param carries an integer
-        nprobe >= 1 (under "params" or at the top level) is answered by the IVF_FLAT index: the exact top `limit` of the rows
-        in the nprobe lists nearest to the query (IvfFlatIndex.search).  Every other call stays on the exact routes below, and
+        nprobe >= 1 (under "params" or at the top level) is answered by that index: the exact top `limit` of the rows
+        in the nprobe lists nearest to the query (IvfFlatIndex.search; IVF_SQ8: of their decoded rows, IvfSq8Index.search).  Every other call stays on the exact routes below, and
         so do hybrid_search's lists and self_metrics; so does every call while the collection holds fewer rows than nlist.
         group_by_field (a scalar field of the schema) makes it pymilvus' grouping search: `limit` counts GROUPS (at most 1024),
         the result per query is one flat list of Hit, group after group, best group first and rank order inside a group, each

@@ -1616,6 +1616,50 @@ int mirx_ivf_set_option(mirx_ivf *ivf, int option, int64_t value);
 int mirx_ivf_query_tile(int dim);
 int mirx_ivf_row_block(void);
 
+/*
+ * IVF_SQ8: the same lists, probes, work items and top-k with the master kept as 8-bit codes, a quarter of the fp32 master (the
+ * reference's create_index documents the type: 'IVF_FLAT', 'IVF_SQ8', 'IVF_PQ', 'HNSW', 'FLAT', milvus/milvus_setup.py:191-213).
+ * The rule is bent in one declared place: AN IVF_SQ8 ANSWER IS THE IVF_FLAT ANSWER OVER THE DECODED ROWS -- per query the exact
+ * fp64 top-k over the decoded rows of its probed lists, bit for bit what mirx_index_search_masked returns on a flat index that
+ * holds the decoded fp32 rows under the same ids; nprobe >= nlist is mirx_index_search over the decoded rows.  The approximations
+ * are the choice of lists and the quantiser, and both are defined exactly.
+ *
+ * Quantiser: per column, global (not per list, not residual); vmin[dim], scale[dim] fp32.
+ *     train    vmin[d] / vmax[d] = min / max of column d over the training rows (NaN ignored; a zero minimum is stored as +0; a
+ *              column without a number gets vmin = scale = 0), scale[d] = (float)(((double)vmax[d] - (double)vmin[d]) / 255.0).
+ *              Partials per workgroup folded in a fixed order, no floating atomics: two calls give equal bits.
+ *     encode   t = ((double)x - (double)vmin[d]) / (double)scale[d]; code = (uint8)min(255.0, max(0.0, floor(t + 0.5))), t + 0.5
+ *              one IEEE double addition; scale[d] == 0 -> 0; NaN, -inf -> 0; +inf -> 255; rows outside the range clamp.
+ *     decode   xhat = (float)((double)vmin[d] + (double)code * (double)scale[d]): the product is exact in double, one rounding to
+ *              double, one to float.
+ *   A row's list is chosen from its ORIGINAL fp32 values, then the row is encoded; the originals are not kept.
+ *
+ * mirx_ivf_create_typed   mirx_ivf_create with kind = MIRX_IVF_FLAT (what mirx_ivf_create means) or MIRX_IVF_SQ8; any other kind:
+ *   MIRX_EINVAL before any device call.  mirx_ivf_kind: the kind, -1 for NULL.
+ * mirx_ivf_sq8_train (rows [n, dim], n >= 1, host or device) / _sq8_set_range / _sq8_get_range (vmin, scale: dim fp32 each, host or
+ *   device) fix or read the range.  mirx_ivf_get_codes (out_codes [size, dim] uint8, ids, list numbers) and mirx_ivf_reconstruct
+ *   (out_rows [size, dim] fp32 decoded, ids): device arrays in list-major order, the order of the master; the _or_null ones may be
+ *   NULL.  All of these on a MIRX_IVF_FLAT handle: MIRX_EINVAL.
+ * State, MIRX_IVF_SQ8 (MIRX_ESTATE, nothing changed): mirx_ivf_add before both the centroids and the range are fixed;
+ *   mirx_ivf_sq8_train / _sq8_set_range while rows are resident (they were encoded with the old range); mirx_ivf_train /
+ *   _set_centroids while rows are resident (IVF_FLAT re-assigns its rows; there are no originals to re-assign here).  Every other
+ *   mirx_ivf_* call keeps its contract; mirx_ivf_search reads the codes: a lane loads four codes where it loaded four floats,
+ *   decodes them once per row group with its columns' (double) vmin and scale held in registers, and goes on as for fp32 rows.
+ * mirx_sq8_encode / mirx_sq8_decode   the quantiser over device arrays (rows [n, dim] fp32, codes [n, dim] uint8, vmin / scale
+ *   [dim]), without an index; encode waits for its work, decode is enqueued on `stream`.
+ */
+#define MIRX_IVF_FLAT 0
+#define MIRX_IVF_SQ8 1
+int mirx_ivf_create_typed(int dim, int metric, int nlist, int kind, int device, mirx_ivf **out);
+int mirx_ivf_kind(const mirx_ivf *ivf);
+int mirx_ivf_sq8_train(mirx_ivf *ivf, const float *rows, int64_t n, void *stream);
+int mirx_ivf_sq8_set_range(mirx_ivf *ivf, const float *vmin, const float *scale);
+int mirx_ivf_sq8_get_range(const mirx_ivf *ivf, float *out_vmin, float *out_scale);
+int mirx_ivf_get_codes(const mirx_ivf *ivf, uint8_t *out_codes, int64_t *out_ids_or_null, int64_t *out_lists_or_null);
+int mirx_ivf_reconstruct(const mirx_ivf *ivf, float *out_rows, int64_t *out_ids_or_null);
+int mirx_sq8_encode(const float *rows, int64_t n, int dim, const float *vmin, const float *scale, uint8_t *out_codes, void *stream);
+int mirx_sq8_decode(const uint8_t *codes, int64_t n, int dim, const float *vmin, const float *scale, float *out_rows, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

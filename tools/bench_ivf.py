@@ -4,18 +4,23 @@
 The gallery is clustered -- unit rows around `--centres` random unit centres -- because IVF recall on uniform random rows
 says nothing.  For every query count and nprobe the two arms alternate in one process after a warm-up of each; a call is timed
 with the host clock around a device synchronise; medians with the range of the repeats are reported, with recall@k of the IVF
-ids against the flat index's exact ids, and the train and add times of the IVF index."""
+ids against the flat index's exact ids, and the train and add times of the IVF index.
+
+--index-type IVF_SQ8 adds an IvfSq8Index with the IVF_FLAT index's centroids and a range trained on the same strided
+sample as a third alternating arm, its recall against the exact ids and against IVF_FLAT's at equal nprobe, and for both index
+types the device memory held after the build and the peak during add (torch.cuda.mem_get_info, polled from a thread)."""
 import argparse
 import json
 import os
 import statistics
 import sys
+import threading
 import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mirx.index import FlatIndex, IvfFlatIndex  # noqa: E402
+from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, IvfFlatIndex, IvfSq8Index  # noqa: E402
 
 
 def clustered(n, d, centres, spread, dev, seed):
@@ -37,6 +42,39 @@ def timed(fn):
     return (time.perf_counter() - t0) * 1e3, r
 
 
+def free_bytes(settle=False):
+    """free device memory; settle: after a synchronise and with torch's cached blocks returned, so that a difference of two
+    readings is what libmirx holds (masters and scratch), not what torch keeps for reuse"""
+    if settle:
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    return torch.cuda.mem_get_info()[0]
+
+
+def peak_during(fn):
+    """(ms, the most device memory in use during fn() above what was in use before it, polled every 0.2 ms)"""
+    torch.cuda.synchronize()
+    start, low, done = free_bytes(True), [free_bytes()], threading.Event()
+
+    def poll():
+        while not done.is_set():
+            low[0] = min(low[0], free_bytes())
+            time.sleep(2e-4)
+
+    th = threading.Thread(target=poll)
+    th.start()
+    try:
+        ms = timed(fn)[0]
+    finally:
+        done.set()
+        th.join()
+    return ms, start - min(low[0], free_bytes())
+
+
+def recall(ids, want):
+    return (ids[:, :, None] == want[:, None, :]).any(dim=2).float().mean().item()
+
+
 def stat(ms):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "repeats": len(ms)}
 
@@ -54,6 +92,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--heavy-repeats", type=int, default=3, help="repeats of a call that scores more than 2^33 (query, row) pairs")
     ap.add_argument("--train-iters", type=int, default=10)
+    ap.add_argument("--index-type", default="IVF_FLAT", choices=["IVF_FLAT", "IVF_SQ8"])
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -62,13 +101,28 @@ def main():
     flat.reserve(a.n)
     t_flat_add, _ = timed(lambda: flat.add(rows))
     ivf = IvfFlatIndex(a.d, "COSINE", a.nlist, 0)
+    held0 = free_bytes(True)
     t_train, _ = timed(lambda: ivf.train(rows, iters=a.train_iters))
-    t_add, _ = timed(lambda: ivf.add(rows))
+    t_add, peak_add = peak_during(lambda: ivf.add(rows))
+    held = held0 - free_bytes(True)
     sizes = ivf.list_sizes()
     out = {"rows": a.n, "dim": a.d, "nlist": a.nlist, "centres": a.centres, "spread": a.spread, "k": a.k,
            "train_ms": t_train, "train_rows": min(a.n, 256 * a.nlist), "train_iters": a.train_iters, "ivf_add_ms": t_add,
            "flat_add_ms": t_flat_add, "list_sizes": {"min": int(sizes.min()), "median": float(statistics.median(sizes.tolist())),
-                                                      "max": int(sizes.max()), "empty": int((sizes == 0).sum())}, "cases": []}
+                                                      "max": int(sizes.max()), "empty": int((sizes == 0).sum())},
+           "index_type": a.index_type, "ivf_held_bytes": held, "ivf_add_peak_bytes": peak_add, "cases": []}
+    sq8 = None
+    if a.index_type == "IVF_SQ8":                                            # the same centroids, the range from train()'s sample
+        held0 = free_bytes(True)
+        sq8 = IvfSq8Index(a.d, "COSINE", a.nlist, 0)
+        sq8.set_centroids(ivf.centroids)
+        limit = IVF_TRAIN_ROWS_PER_LIST * a.nlist
+        sample = rows if a.n <= limit else rows[(torch.arange(limit, dtype=torch.int64, device=dev) * a.n) // limit].contiguous()
+        t_range, _ = timed(lambda: sq8.train_range(sample))
+        del sample
+        t_add8, peak_add8 = peak_during(lambda: sq8.add(rows))
+        out.update({"sq8_train_range_ms": t_range, "sq8_add_ms": t_add8, "sq8_held_bytes": held0 - free_bytes(True),
+                    "sq8_add_peak_bytes": peak_add8, "rows_bytes_fp32": a.n * a.d * 4})
     print({k: v for k, v in out.items() if k != "cases"}, flush=True)
     g = torch.Generator(device=dev).manual_seed(4321)
     for nq in [int(v) for v in a.queries.split(",")]:
@@ -78,14 +132,19 @@ def main():
         for nprobe in [int(v) for v in a.nprobe.split(",")]:
             ids = ivf.search(q, a.k, nprobe)[1]                              # warm-up of this shape (flat: above)
             st = ivf.last_stats()
-            hit = (ids[:, :, None] == exact[:, None, :]).any(dim=2).float().mean().item()
+            hit = recall(ids, exact)
+            ids8 = None if sq8 is None else sq8.search(q, a.k, nprobe)[1]   # warm-up of the third arm
             reps = a.heavy_repeats if st["rows_scored"] > 1 << 33 else a.repeats
-            t_ivf, t_flat = [], []
+            t_ivf, t_flat, t_sq8 = [], [], []
             for _ in range(reps):                                            # alternating arms
                 t_ivf.append(timed(lambda: ivf.search(q, a.k, nprobe))[0])
+                if sq8 is not None:
+                    t_sq8.append(timed(lambda: sq8.search(q, a.k, nprobe))[0])
                 t_flat.append(timed(lambda: flat.search(q, a.k))[0])
             case = {"queries": nq, "nprobe": nprobe, "recall_at_k": hit, "ivf": stat(t_ivf), "flat": stat(t_flat),
                     "rows_scored_per_query": st["rows_scored"] / nq, "work_items": st["work_items"], "batches": st["batches"]}
+            if sq8 is not None:
+                case.update({"sq8": stat(t_sq8), "sq8_recall_at_k": recall(ids8, exact), "sq8_recall_vs_ivf_flat": recall(ids8, ids)})
             out["cases"].append(case)
             print(case, flush=True)
     if a.json:
