@@ -52,6 +52,8 @@ RESAMPLE_OUT_U8, RESAMPLE_OUT_F32 = 0, 1
 RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 0, 1
 IVF_MAX_NLIST, IVF_MAX_DIM = 65536, 2048   # mirx_ivf_create's limits (include/mirx.h)
 IVF_FLAT, IVF_SQ8 = 0, 1           # mirx_ivf_create_typed's kinds
+IVF_PQ = 2                         # mirx_ivf_create_pq's kind
+PQ_MAX_M = 64                      # mirx_ivf_create_pq: m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0
 IVF_OPT_SCORE_BYTES = 1            # test hook: the score workspace budget of mirx_ivf_search in bytes (0 = default, 1 GiB)
 ROLLOUT_FUSE = {"mean": 0, "max": 1, "min": 2}   # mirx_rollout_layer `fusion`
 STAGES = ("prep", "sample", "gemm", "finalize", "exact")
@@ -268,6 +270,15 @@ SYMBOLS = {
     "mirx_ivf_reconstruct": (_int, [_vp, _vp, _vp]),
     "mirx_sq8_encode": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "mirx_sq8_decode": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "mirx_ivf_create_pq": (_int, [_int, _int, _int, _int, _int, _int, ctypes.POINTER(_vp)]),
+    "mirx_ivf_pq_train": (_int, [_vp, _vp, _i64, _int, _vp]),
+    "mirx_ivf_pq_set_codebooks": (_int, [_vp, _vp]),
+    "mirx_ivf_pq_get_codebooks": (_int, [_vp, _vp]),
+    "mirx_ivf_pq_m": (_int, [_vp]),
+    "mirx_ivf_pq_item_rows": (_int, []),
+    "mirx_pq_encode": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "mirx_pq_decode": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "mirx_pq_tables": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp]),
 }
 
 _lib = None

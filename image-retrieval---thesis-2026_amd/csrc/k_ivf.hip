@@ -531,6 +531,14 @@ hipError_t launch_ivf_update(const float *rows, int dim, const int32_t *order, c
     return hipGetLastError();
 }
 
+hipError_t launch_ivf_probes(const int64_t *pids, int nq, int nprobe, const int64_t *offsets, int nlist, int32_t *probes,
+                             int32_t *out_probes, int32_t *qoff, int *cnt, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nlist * sizeof(int), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ivf_probes, dim3(nq), dim3(64), 0, st, pids, nq, nprobe, offsets, nlist, probes, out_probes, qoff, cnt);
+    return hipGetLastError();
+}
+
 hipError_t launch_ivf_invert(const int64_t *pids, int nq, int nprobe, const int64_t *offsets, int nlist, int qt, int32_t *probes,
                              int32_t *out_probes, int32_t *qoff, int *cnt_cursor, int32_t *pairoff, int32_t *itemoff,
                              int32_t *pair_q, int32_t *pair_off, unsigned long long *stats, hipStream_t st) {

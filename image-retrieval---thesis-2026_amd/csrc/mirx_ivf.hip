@@ -1,5 +1,6 @@
 // mirx_ivf.hip -- the IVF indexes of the C ABI (include/mirx.h, mirx_ivf_*): k-means lists over a flat index of the centroids,
-// the list-major master (fp32 rows for IVF_FLAT, 8-bit codes for IVF_SQ8), and the search of the probed lists (kernels: k_ivf.hip).
+// the list-major master (fp32 rows for IVF_FLAT, 8-bit codes for IVF_SQ8, m codeword numbers for IVF_PQ), and the search of the
+// probed lists (kernels: k_ivf.hip, k_ivf_pq.hip).
 //
 // "Nearest centroid" is never restated here: assignments and probes are mirx_index_search / mirx_index_rank_top over `cent`, a
 // mirx_index that holds the centroids with ids 0 .. nlist-1, so the rule (fp64 lane-tree score, ties to the lowest list) is the
@@ -24,17 +25,22 @@ struct mirx_ivf {
     DevBuf rows, ids, offsets;            // [size, dimp] list-major (fp32, or uint8 codes for SQ8), [size], [nlist + 1] int64
     DevBuf range;                         // SQ8: vmin [dimp] then scale [dimp] fp32, zero in the padding
     bool range_fixed = false;
+    int pq_m = 0;                         // PQ: sub-quantisers; a code row is pq_m bytes
+    DevBuf codebooks;                     // PQ: [pq_m][256][dim / pq_m] fp32
+    bool cb_fixed = false;
     std::vector<int64_t> off_h, ids_h, seq_h;   // host mirrors of offsets / ids, and each row's insertion number (list-major)
     int64_t next_seq = 0, next_auto = 0;
     int64_t score_bytes = 0;              // MIRX_IVF_OPT_SCORE_BYTES; 0 = SCORE_WS_BYTES
     // scratch
     DevBuf stage, lists, fval, a_order, a_loff, upd, pos, newids, q32p, pids, probes, qoff, cntcur, pairoff, itemoff, pair_q,
-        pair_off, scores;
+        pair_off, scores, tables, pq_sub, pq_found, pq_codes;
     unsigned long long *stats_dev = nullptr;   // [3] rows scored, pairs, work items
     int64_t last_nq = 0, last_batches = 0;
 
     bool sq8() const { return kind == MIRX_IVF_SQ8; }
-    size_t row_bytes() const { return (size_t)dimp * (sq8() ? 1 : sizeof(float)); }
+    bool pq() const { return kind == MIRX_IVF_PQ; }
+    int code_ld() const { return pq() ? pq_m : dimp; }                             // bytes of a code row (SQ8, PQ)
+    size_t row_bytes() const { return pq() ? (size_t)pq_m : (size_t)dimp * (sq8() ? 1 : sizeof(float)); }
     const float *vmin() const { return range.as<float>(); }
     const float *scale() const { return range.as<float>() + dimp; }
 };
@@ -50,11 +56,15 @@ constexpr int64_t MAX_BATCH_PAIRS = (int64_t)1 << 26;   // (query, probe) pairs 
     if (!dg.ok) return fail(MIRX_EHIP, std::string(who) + ": cannot select the ivf's device")
 
 #define MIRX_IVF_SQ8_ONLY(ivf, who) MIRX_CHECK((ivf)->sq8(), std::string(who) + ": the ivf is not MIRX_IVF_SQ8")
+#define MIRX_IVF_PQ_ONLY(ivf, who) MIRX_CHECK((ivf)->pq(), std::string(who) + ": the ivf is not MIRX_IVF_PQ")
+#define MIRX_IVF_CODED_ONLY(ivf, who) MIRX_CHECK((ivf)->sq8() || (ivf)->pq(), std::string(who) + ": the ivf is not MIRX_IVF_SQ8 or MIRX_IVF_PQ")
 
-// SQ8 keeps no originals: what would re-assign or re-encode the resident rows is refused
+// SQ8 and PQ keep no originals: what would re-assign or re-encode the resident rows is refused
 int sq8_resident(const mirx_ivf *ivf, const char *who) {
     if (ivf->sq8() && ivf->size > 0)
         return fail(MIRX_ESTATE, std::string(who) + ": an IVF_SQ8 index that holds rows keeps its centroids and range (the original rows are gone)");
+    if (ivf->pq() && ivf->size > 0)
+        return fail(MIRX_ESTATE, std::string(who) + ": an IVF_PQ index that holds rows keeps its centroids and codebooks (the original rows are gone)");
     return MIRX_OK;
 }
 
@@ -84,23 +94,141 @@ int assign_rows(mirx_ivf *ivf, const float *rows, int64_t n, int64_t *out_lists,
     return mirx_index_search(ivf->cent, rows, n, 1, nullptr, ivf->fval.as<float>(), out_lists, st);
 }
 
-// the same, to the host
-int assign_to_host(mirx_ivf *ivf, const float *rows, int64_t n, std::vector<int64_t> &out, hipStream_t st) {
+// to the host: for every row the nearest of `ix`'s nlist rows (ids 0 .. nlist-1), by ix's own search
+int nearest_to_host(mirx_ivf *ivf, mirx_index *ix, int nlist, const float *rows, int64_t n, std::vector<int64_t> &out,
+                    hipStream_t st) {
     out.resize((size_t)n);
     if (n == 0) return MIRX_OK;
     MIRX_HIP(ivf->lists.ensure((size_t)n * sizeof(int64_t)));
-    if (int rc = assign_rows(ivf, rows, n, ivf->lists.as<int64_t>(), st)) return rc;
+    MIRX_HIP(ivf->fval.ensure((size_t)n * sizeof(float)));
+    if (int rc = mirx_index_search(ix, rows, n, 1, nullptr, ivf->fval.as<float>(), ivf->lists.as<int64_t>(), st)) return rc;
     MIRX_HIP(hipMemcpyAsync(out.data(), ivf->lists.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     MIRX_HIP(hipStreamSynchronize(st));
     for (int64_t v : out)
-        if (v < 0 || v >= ivf->nlist) return fail(MIRX_EHIP, "ivf: the centroid search returned no list for a row");
+        if (v < 0 || v >= nlist) return fail(MIRX_EHIP, "ivf: the centroid search returned no list for a row");
+    return MIRX_OK;
+}
+
+// the list of every row, to the host
+int assign_to_host(mirx_ivf *ivf, const float *rows, int64_t n, std::vector<int64_t> &out, hipStream_t st) {
+    return nearest_to_host(ivf, ivf->cent, ivf->nlist, rows, n, out, st);
+}
+
+// a flat index over rows [n, dim] (device) with ids 0 .. n-1
+int flat_over(int dim, int metric, int device, const float *rows, int n, mirx_index **out) {
+    *out = nullptr;
+    if (int rc = mirx_index_create(dim, metric, device, out)) return rc;
+    if (int rc = mirx_index_add(*out, rows, n, nullptr)) {
+        mirx_index_destroy(*out);
+        *out = nullptr;
+        return rc;
+    }
+    return MIRX_OK;
+}
+
+// Lloyd's loop of mirx_ivf_train over rows [n, dim] (device): cent [nlist, dim] (device) starts at rows[start[.]], then at most
+// `iters` updates, stopping when an assignment pass changes no row's list.  "Nearest" is a flat index over the current centroids.
+int lloyd(mirx_ivf *ivf, const float *drows, int64_t n, int dim, int metric, int nlist, const std::vector<int64_t> &start,
+          int iters, float *cent, hipStream_t st) {
+    MIRX_HIP(ivf->pos.ensure((size_t)nlist * sizeof(int64_t)));
+    MIRX_HIP(ivf->upd.ensure((size_t)nlist * dim * sizeof(float)));
+    MIRX_HIP(ivf->a_order.ensure((size_t)n * sizeof(int32_t)));
+    MIRX_HIP(ivf->a_loff.ensure((size_t)(nlist + 1) * sizeof(int64_t)));
+    MIRX_HIP(hipMemcpyAsync(ivf->pos.p, start.data(), (size_t)nlist * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    MIRX_HIP(launch_ivf_place(drows, nlist, dim, dim, ivf->pos.as<int64_t>(), nullptr, cent, dim, st));
+    MIRX_HIP(hipStreamSynchronize(st));
+    std::vector<int64_t> cur, prev, loff((size_t)nlist + 1);
+    std::vector<int32_t> order((size_t)n);
+    for (int it = 0; it < iters; ++it) {
+        mirx_index *ix = nullptr;
+        if (int rc = flat_over(dim, metric, ivf->device, cent, nlist, &ix)) return rc;
+        const int rc = nearest_to_host(ivf, ix, nlist, drows, n, cur, st);
+        mirx_index_destroy(ix);
+        if (rc) return rc;
+        if (it > 0 && cur == prev) break;
+        std::fill(loff.begin(), loff.end(), 0);
+        for (int64_t v : cur) ++loff[(size_t)v + 1];
+        for (int l = 0; l < nlist; ++l) loff[(size_t)l + 1] += loff[(size_t)l];
+        std::vector<int64_t> at(loff.begin(), loff.end() - 1);
+        for (int64_t r = 0; r < n; ++r) order[(size_t)at[(size_t)cur[(size_t)r]]++] = (int32_t)r;
+        MIRX_HIP(hipMemcpyAsync(ivf->a_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(hipMemcpyAsync(ivf->a_loff.p, loff.data(), (size_t)(nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        MIRX_HIP(launch_ivf_update(drows, dim, ivf->a_order.as<int32_t>(), ivf->a_loff.as<int64_t>(), nlist, cent,
+                                   ivf->upd.as<float>(), metric == MIRX_METRIC_IP, st));
+        MIRX_HIP(hipStreamSynchronize(st));
+        prev.swap(cur);
+    }
+    return MIRX_OK;
+}
+
+// ---- IVF_PQ's quantiser: "nearest codeword" is mirx_index_search(k = 1) over a sub-space's 256 codewords, never restated --------
+bool pq_shape_ok(int dim, int m) {
+    return m >= 4 && m <= PQ_MAX_M && m % 4 == 0 && dim >= 1 && dim <= MIRX_IVF_MAX_DIM && dim % (4 * m) == 0;
+}
+
+void free_codeword_indexes(std::vector<mirx_index *> &v) {
+    for (mirx_index *ix : v)
+        if (ix) mirx_index_destroy(ix);
+    v.clear();
+}
+
+// per sub-space a flat L2 index over its codewords; cb = device [m][256][dim / m]
+int build_codeword_indexes(int dim, int m, int device, const float *cb, std::vector<mirx_index *> &out) {
+    free_codeword_indexes(out);
+    const int dsub = dim / m;
+    for (int j = 0; j < m; ++j) {
+        mirx_index *ix = nullptr;
+        if (int rc = flat_over(dsub, MIRX_METRIC_NEG_L2, device, cb + (size_t)j * 256 * dsub, 256, &ix)) {
+            free_codeword_indexes(out);
+            return rc;
+        }
+        out.push_back(ix);
+    }
+    return MIRX_OK;
+}
+
+constexpr int64_t PQ_ENCODE_CHUNK = (int64_t)1 << 16;   // rows per pass of the encoder: bounds its scratch and the m indexes' workspaces
+
+// the encoder's passes over rows [n, dim] with the m codeword indexes given; enqueued on st
+int pq_encode_chunks(const std::vector<mirx_index *> &cbidx, int dim, int m, const float *drows, int64_t n, uint8_t *codes,
+                     DevBuf &sub, DevBuf &found, DevBuf &fval, hipStream_t st) {
+    const int dsub = dim / m;
+    const int64_t chunk = std::min<int64_t>(n, PQ_ENCODE_CHUNK);
+    if (sub.ensure((size_t)chunk * dsub * sizeof(float)) != hipSuccess || found.ensure((size_t)chunk * sizeof(int64_t)) != hipSuccess ||
+        fval.ensure((size_t)chunk * sizeof(float)) != hipSuccess)
+        return fail(MIRX_ENOMEM, "pq_encode: no memory for the encoder's scratch");
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t nc = std::min(chunk, n - c0);
+        for (int j = 0; j < m; ++j) {
+            MIRX_HIP(launch_ivf_place(drows + c0 * dim + (int64_t)j * dsub, nc, dim, dsub, nullptr, nullptr, sub.as<float>(), dsub, st));
+            if (int rc = mirx_index_search(cbidx[(size_t)j], sub.as<float>(), nc, 1, nullptr, fval.as<float>(), found.as<int64_t>(), st))
+                return rc;
+            MIRX_HIP(launch_pq_pack(found.as<int64_t>(), nc, m, j, codes + c0 * m, st));
+        }
+    }
+    return MIRX_OK;
+}
+
+// codes [n, m] (device) of rows [n, dim] (device) under cb (device [m][256][dim / m]): sub-vector j of every row searched in a flat
+// index over sub-space j's codewords.  The m indexes live for the call only -- their search workspaces (tens of MB each) would
+// outweigh the codes if the handle kept them.  Waits for its work, on failure too: the indexes are freed behind it.
+int pq_encode_rows(int device, int dim, int m, const float *cb, const float *drows, int64_t n, uint8_t *codes, DevBuf &sub,
+                   DevBuf &found, DevBuf &fval, hipStream_t st) {
+    if (n == 0) return MIRX_OK;
+    std::vector<mirx_index *> cbidx;
+    if (int rc = build_codeword_indexes(dim, m, device, cb, cbidx)) return rc;
+    const int rc = pq_encode_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    free_codeword_indexes(cbidx);
+    if (rc) return rc;
+    MIRX_HIP(e);
     return MIRX_OK;
 }
 
 // The one layout change behind add / remove / re-assign.  old_dst[p] = where resident row p goes (-1: dropped); the n_new rows of
 // new_rows (device, [n_new, dim]) with new_ids go to new_dst.  total = the rows afterwards, new_off their offsets; seq / ids
 // mirrors follow.  Everything is allocated before a row moves: MIRX_ENOMEM leaves the ivf untouched.
-int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *new_rows, int64_t n_new,
+int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const void *new_rows, int64_t n_new,
              const std::vector<int64_t> &new_ids, const std::vector<int64_t> &new_dst, int64_t total,
              const std::vector<int64_t> &new_off, hipStream_t st) {
     const int64_t n_old = ivf->size;
@@ -115,8 +243,8 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *ne
     std::vector<int64_t> ids_h((size_t)total), seq_h((size_t)total);
     if (n_old) {
         MIRX_HIP(hipMemcpyAsync(ivf->pos.p, old_dst.data(), (size_t)n_old * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        if (ivf->sq8())
-            MIRX_HIP(launch_ivf_place_codes(ivf->rows.as<uint8_t>(), n_old, ivf->dimp, ivf->pos.as<int64_t>(), rows2.as<uint8_t>(), st));
+        if (ivf->sq8() || ivf->pq())
+            MIRX_HIP(launch_ivf_place_codes(ivf->rows.as<uint8_t>(), n_old, ivf->code_ld(), ivf->pos.as<int64_t>(), rows2.as<uint8_t>(), st));
         else
             MIRX_HIP(launch_ivf_place(ivf->rows.as<float>(), n_old, ivf->dimp, ivf->dimp, nullptr, ivf->pos.as<int64_t>(),
                                       rows2.as<float>(), ivf->dimp, st));
@@ -131,12 +259,15 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const float *ne
     if (n_new) {
         MIRX_HIP(hipMemcpyAsync(ivf->pos.p, new_dst.data(), (size_t)n_new * sizeof(int64_t), hipMemcpyHostToDevice, st));
         MIRX_HIP(hipMemcpyAsync(ivf->newids.p, new_ids.data(), (size_t)n_new * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        if (ivf->sq8())
-            MIRX_HIP(launch_sq8_encode_place(new_rows, n_new, ivf->dim, ivf->vmin(), ivf->scale(), ivf->pos.as<int64_t>(),
-                                             rows2.as<uint8_t>(), ivf->dimp, st));
+        if (ivf->pq())                                           // new_rows are the new rows' codes [n_new, m] (mirx_ivf_add)
+            MIRX_HIP(launch_ivf_place_codes(static_cast<const uint8_t *>(new_rows), n_new, ivf->pq_m, ivf->pos.as<int64_t>(),
+                                            rows2.as<uint8_t>(), st));
+        else if (ivf->sq8())
+            MIRX_HIP(launch_sq8_encode_place(static_cast<const float *>(new_rows), n_new, ivf->dim, ivf->vmin(), ivf->scale(),
+                                             ivf->pos.as<int64_t>(), rows2.as<uint8_t>(), ivf->dimp, st));
         else
-            MIRX_HIP(launch_ivf_place(new_rows, n_new, ivf->dim, ivf->dim, nullptr, ivf->pos.as<int64_t>(), rows2.as<float>(),
-                                      ivf->dimp, st));
+            MIRX_HIP(launch_ivf_place(static_cast<const float *>(new_rows), n_new, ivf->dim, ivf->dim, nullptr,
+                                      ivf->pos.as<int64_t>(), rows2.as<float>(), ivf->dimp, st));
         MIRX_HIP(launch_ivf_place_ids(ivf->newids.as<int64_t>(), n_new, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
         for (int64_t j = 0; j < n_new; ++j) {
             ids_h[(size_t)new_dst[(size_t)j]] = new_ids[(size_t)j];
@@ -188,9 +319,65 @@ int fix_centroids(mirx_ivf *ivf, hipStream_t st) {
     return reassign_resident(ivf, st);
 }
 
+// mirx_ivf_search on a PQ handle, behind its argument checks: np = the clamped nprobe, ld = the longest compact row.  Per internal
+// batch: the probes, every query's tables, the items of the scan, the scan, the top-k.  A query costs its compact row of doubles
+// and its m x 2 KiB table out of the one workspace budget.
+int pq_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int np, int64_t ld, int64_t budget, const int64_t *exclude,
+              float *out_values, double *out_f64, int64_t *out_ids, int32_t *out_probes, hipStream_t st) {
+    const int nlist = ivf->nlist, m = ivf->pq_m;
+    const int64_t table_bytes = (int64_t)m * 256 * sizeof(double), items_per_row = (ld + PQ_ITEM_ROWS - 1) / PQ_ITEM_ROWS;
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8 + table_bytes)));
+    per = std::min(per, std::max<int64_t>(1, MAX_BATCH_PAIRS / np));
+    per = std::min(per, std::max<int64_t>(1, 0x7FFFFFFFll / items_per_row));       // work items fit an int
+    hipError_t e;
+    if ((e = ivf->scores.ensure((size_t)per * ld * sizeof(double))) != hipSuccess ||
+        (e = ivf->tables.ensure((size_t)per * table_bytes)) != hipSuccess ||
+        (e = ivf->pids.ensure((size_t)per * np * sizeof(int64_t))) != hipSuccess ||
+        (e = ivf->fval.ensure((size_t)per * np * sizeof(float))) != hipSuccess ||
+        (e = ivf->probes.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->qoff.ensure((size_t)per * (np + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->cntcur.ensure((size_t)nlist * sizeof(int))) != hipSuccess ||
+        (e = ivf->itemoff.ensure((size_t)(per + 1) * sizeof(int32_t))) != hipSuccess)
+        return fail(MIRX_ENOMEM, std::string("ivf_search: workspace: ") + hipGetErrorString(e));
+    for (int64_t q0 = 0; q0 < nq; q0 += per) {
+        const int nb = (int)std::min(per, nq - q0);
+        const float *qb = q + q0 * ivf->dim;
+        int rc = np <= MAX_K ? mirx_index_search(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), ivf->pids.as<int64_t>(), st)
+                             : mirx_index_rank_top(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), nullptr,
+                                                   ivf->pids.as<int64_t>(), st);
+        if (rc) return rc;
+        MIRX_HIP(launch_ivf_probes(ivf->pids.as<int64_t>(), nb, np, ivf->offsets.as<int64_t>(), nlist, ivf->probes.as<int32_t>(),
+                                   out_probes ? out_probes + q0 * np : nullptr, ivf->qoff.as<int32_t>(), ivf->cntcur.as<int>(), st));
+        MIRX_HIP(launch_pq_tables(qb, nb, ivf->dim, m, ivf->metric, ivf->codebooks.as<float>(), ivf->tables.as<double>(), st));
+        MIRX_HIP(launch_pq_items(ivf->qoff.as<int32_t>(), nb, np, ivf->cntcur.as<int>(), nlist, ivf->itemoff.as<int32_t>(),
+                                 ivf->stats_dev, st));
+        PqScanArgs sa{};
+        sa.tables = ivf->tables.as<double>();
+        sa.codes = ivf->rows.as<uint8_t>();
+        sa.m = m;
+        sa.nq = nb;
+        sa.nprobe = np;
+        sa.probes = ivf->probes.as<int32_t>();
+        sa.qoff = ivf->qoff.as<int32_t>();
+        sa.offsets = ivf->offsets.as<int64_t>();
+        sa.itemoff = ivf->itemoff.as<int32_t>();
+        sa.out = ivf->scores.as<double>();
+        sa.ld = ld;
+        MIRX_HIP(launch_pq_scan(sa, ivf->metric, st));
+        MIRX_HIP(launch_ivf_topk(ivf->scores.as<double>(), ld, ivf->probes.as<int32_t>(), ivf->qoff.as<int32_t>(), nb, np,
+                                 ivf->offsets.as<int64_t>(), ivf->ids.as<int64_t>(), exclude ? exclude + q0 : nullptr, k, ivf->metric,
+                                 out_f64 ? out_f64 + q0 * k : nullptr, out_ids + q0 * k, out_values ? out_values + q0 * k : nullptr,
+                                 st));
+        ++ivf->last_batches;
+    }
+    return MIRX_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+static int create_ivf(int dim, int metric, int nlist, int kind, int m, int device, mirx_ivf **out);   // behind every create call
 
 int mirx_ivf_query_tile(int dim) {
     if (dim < 1 || dim > MIRX_IVF_MAX_DIM) return -1;
@@ -205,7 +392,24 @@ int mirx_ivf_create(int dim, int metric, int nlist, int device, mirx_ivf **out) 
 int mirx_ivf_create_typed(int dim, int metric, int nlist, int kind, int device, mirx_ivf **out) {
     MIRX_CHECK(out, "ivf_create: out is null");
     *out = nullptr;
-    MIRX_CHECK(kind == MIRX_IVF_FLAT || kind == MIRX_IVF_SQ8, "ivf_create: unknown kind (MIRX_IVF_FLAT, MIRX_IVF_SQ8)");
+    MIRX_CHECK(kind == MIRX_IVF_FLAT || kind == MIRX_IVF_SQ8,
+               "ivf_create: unknown kind (MIRX_IVF_FLAT, MIRX_IVF_SQ8; MIRX_IVF_PQ needs m: mirx_ivf_create_pq)");
+    return create_ivf(dim, metric, nlist, kind, 0, device, out);
+}
+
+int mirx_ivf_create_pq(int dim, int metric, int nlist, int m, int nbits, int device, mirx_ivf **out) {
+    MIRX_CHECK(out, "ivf_create_pq: out is null");
+    *out = nullptr;
+    MIRX_CHECK(nbits == 8, "ivf_create_pq: nbits must be 8 (256 codewords per sub-quantiser)");
+    MIRX_CHECK(m >= 4 && m <= PQ_MAX_M && m % 4 == 0, "ivf_create_pq: m must be a multiple of 4 in 4 .. 64");
+    MIRX_CHECK(dim >= 1 && dim % (4 * m) == 0, "ivf_create_pq: dim must be a multiple of 4 m");
+    return create_ivf(dim, metric, nlist, MIRX_IVF_PQ, m, device, out);
+}
+
+int mirx_ivf_pq_m(const mirx_ivf *ivf) { return ivf && ivf->pq() ? ivf->pq_m : -1; }
+int mirx_ivf_pq_item_rows(void) { return PQ_ITEM_ROWS; }
+
+static int create_ivf(int dim, int metric, int nlist, int kind, int m, int device, mirx_ivf **out) {
     MIRX_CHECK(dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "ivf_create: dim out of range (1 .. 2048)");
     MIRX_CHECK(metric == MIRX_METRIC_IP || metric == MIRX_METRIC_NEG_L2, "ivf_create: unknown metric");
     MIRX_CHECK(nlist >= 1 && nlist <= MIRX_IVF_MAX_NLIST, "ivf_create: nlist out of range (1 .. 65536)");
@@ -222,12 +426,14 @@ int mirx_ivf_create_typed(int dim, int metric, int nlist, int kind, int device, 
     ivf->nlist = nlist;
     ivf->device = device;
     ivf->kind = kind;
+    ivf->pq_m = m;
     ivf->off_h.assign((size_t)nlist + 1, 0);
     hipError_t e;
     if ((e = ivf->centroids.ensure((size_t)nlist * dim * sizeof(float))) != hipSuccess ||
         (e = ivf->offsets.ensure((size_t)(nlist + 1) * sizeof(int64_t))) != hipSuccess ||
         (e = hipMemset(ivf->offsets.p, 0, (size_t)(nlist + 1) * sizeof(int64_t))) != hipSuccess ||
         (kind == MIRX_IVF_SQ8 && (e = ivf->range.ensure((size_t)2 * ivf->dimp * sizeof(float))) != hipSuccess) ||
+        (kind == MIRX_IVF_PQ && (e = ivf->codebooks.ensure((size_t)256 * dim * sizeof(float))) != hipSuccess) ||
         (e = hipMalloc(&ivf->stats_dev, 3 * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipMemset(ivf->stats_dev, 0, 3 * sizeof(unsigned long long))) != hipSuccess) {
         mirx_ivf_destroy(ivf);
@@ -264,30 +470,12 @@ int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *i
     const float *drows = nullptr;
     DevBuf trows;                                      // a host caller's rows for the length of the call (the stage serves the re-assignment)
     if (int rc = device_rows(ivf, rows, n, trows, &drows)) return rc;
-    MIRX_HIP(ivf->pos.ensure((size_t)nlist * sizeof(int64_t)));
-    MIRX_HIP(ivf->upd.ensure((size_t)nlist * dim * sizeof(float)));
-    MIRX_HIP(ivf->a_order.ensure((size_t)n * sizeof(int32_t)));
-    MIRX_HIP(ivf->a_loff.ensure((size_t)(nlist + 1) * sizeof(int64_t)));
-    MIRX_HIP(hipMemcpyAsync(ivf->pos.p, start.data(), (size_t)nlist * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    MIRX_HIP(launch_ivf_place(drows, nlist, dim, dim, ivf->pos.as<int64_t>(), nullptr, ivf->centroids.as<float>(), dim, st));
-    MIRX_HIP(hipStreamSynchronize(st));
-    std::vector<int64_t> cur, prev, loff((size_t)nlist + 1);
-    std::vector<int32_t> order((size_t)n);
-    for (int it = 0; it < iters; ++it) {
-        if (int rc = rebuild_centroid_index(ivf)) return rc;
-        if (int rc = assign_to_host(ivf, drows, n, cur, st)) return rc;
-        if (it > 0 && cur == prev) break;
-        std::fill(loff.begin(), loff.end(), 0);
-        for (int64_t v : cur) ++loff[(size_t)v + 1];
-        for (int l = 0; l < nlist; ++l) loff[(size_t)l + 1] += loff[(size_t)l];
-        std::vector<int64_t> at(loff.begin(), loff.end() - 1);
-        for (int64_t r = 0; r < n; ++r) order[(size_t)at[(size_t)cur[(size_t)r]]++] = (int32_t)r;
-        MIRX_HIP(hipMemcpyAsync(ivf->a_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        MIRX_HIP(hipMemcpyAsync(ivf->a_loff.p, loff.data(), (size_t)(nlist + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        MIRX_HIP(launch_ivf_update(drows, dim, ivf->a_order.as<int32_t>(), ivf->a_loff.as<int64_t>(), nlist,
-                                   ivf->centroids.as<float>(), ivf->upd.as<float>(), ivf->metric == MIRX_METRIC_IP, st));
-        MIRX_HIP(hipStreamSynchronize(st));
-        prev.swap(cur);
+    if (int rc = lloyd(ivf, drows, n, dim, ivf->metric, nlist, start, iters, ivf->centroids.as<float>(), st)) {
+        // the centroid array is partly trained: as before the loop moved into lloyd(), the index over the centroids follows it
+        // (the resident rows keep their lists; the next train / set_centroids re-assigns them)
+        (void)hipStreamSynchronize(st);
+        (void)rebuild_centroid_index(ivf);
+        return rc;
     }
     return fix_centroids(ivf, st);
 }
@@ -313,6 +501,8 @@ int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids
     if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_add: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
     if (ivf->sq8() && !ivf->range_fixed)
         return fail(MIRX_ESTATE, "ivf_add: the range is not fixed yet (mirx_ivf_sq8_train / _sq8_set_range)");
+    if (ivf->pq() && !ivf->cb_fixed)
+        return fail(MIRX_ESTATE, "ivf_add: the codebooks are not fixed yet (mirx_ivf_pq_train / _pq_set_codebooks)");
     MIRX_CHECK(ivf->size + n <= 0x7FFFFF00ll, "ivf_add: more than 2^31 rows per index");
     MIRX_IVF_ENTER(ivf, "ivf_add");
     if (n == 0) return MIRX_OK;
@@ -338,7 +528,15 @@ int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids
         at[(size_t)l] = ivf->off_h[(size_t)l + 1] + add[(size_t)l];                // behind the list's resident rows
     }
     for (int64_t j = 0; j < n; ++j) new_dst[(size_t)j] = at[(size_t)lists[(size_t)j]]++;
-    return relayout(ivf, old_dst, drows, n, new_ids, new_dst, ivf->size + n, off, nullptr);
+    const void *placed = drows;
+    if (ivf->pq()) {                                             // the list came from the original row; now the row becomes its codes
+        if (ivf->pq_codes.ensure((size_t)n * ivf->pq_m) != hipSuccess) return fail(MIRX_ENOMEM, "ivf_add: no memory for the new codes");
+        if (int rc = pq_encode_rows(ivf->device, ivf->dim, ivf->pq_m, ivf->codebooks.as<float>(), drows, n,
+                                    ivf->pq_codes.as<uint8_t>(), ivf->pq_sub, ivf->pq_found, ivf->fval, nullptr))
+            return rc;
+        placed = ivf->pq_codes.p;
+    }
+    return relayout(ivf, old_dst, placed, n, new_ids, new_dst, ivf->size + n, off, nullptr);
 }
 
 int mirx_ivf_remove_ids(mirx_ivf *ivf, const int64_t *ids, int64_t n, int64_t *out_removed_or_null, void *stream) {
@@ -422,20 +620,23 @@ static int resident_ids_lists(const mirx_ivf *ivf, int64_t *out_ids, int64_t *ou
 
 int mirx_ivf_get_codes(const mirx_ivf *ivf, uint8_t *out_codes, int64_t *out_ids_or_null, int64_t *out_lists_or_null) {
     MIRX_CHECK(ivf && (out_codes || ivf->size == 0), "ivf_get_codes: null argument");
-    MIRX_IVF_SQ8_ONLY(ivf, "ivf_get_codes");
+    MIRX_IVF_CODED_ONLY(ivf, "ivf_get_codes");
     MIRX_IVF_ENTER(ivf, "ivf_get_codes");
     if (ivf->size == 0) return MIRX_OK;
-    MIRX_HIP(hipMemcpy2D(out_codes, (size_t)ivf->dim, ivf->rows.p, (size_t)ivf->dimp, (size_t)ivf->dim, (size_t)ivf->size,
-                         hipMemcpyDeviceToDevice));
+    const size_t width = ivf->pq() ? (size_t)ivf->pq_m : (size_t)ivf->dim;         // the codes of a row, without SQ8's padding
+    MIRX_HIP(hipMemcpy2D(out_codes, width, ivf->rows.p, (size_t)ivf->code_ld(), width, (size_t)ivf->size, hipMemcpyDeviceToDevice));
     return resident_ids_lists(ivf, out_ids_or_null, out_lists_or_null);
 }
 
 int mirx_ivf_reconstruct(const mirx_ivf *ivf, float *out_rows, int64_t *out_ids_or_null) {
     MIRX_CHECK(ivf && (out_rows || ivf->size == 0), "ivf_reconstruct: null argument");
-    MIRX_IVF_SQ8_ONLY(ivf, "ivf_reconstruct");
+    MIRX_IVF_CODED_ONLY(ivf, "ivf_reconstruct");
     MIRX_IVF_ENTER(ivf, "ivf_reconstruct");
     if (ivf->size == 0) return MIRX_OK;
-    MIRX_HIP(launch_sq8_decode(ivf->rows.as<uint8_t>(), ivf->size, ivf->dimp, ivf->dim, ivf->vmin(), ivf->scale(), out_rows, nullptr));
+    if (ivf->pq())
+        MIRX_HIP(launch_pq_decode(ivf->rows.as<uint8_t>(), ivf->size, ivf->dim, ivf->pq_m, ivf->codebooks.as<float>(), out_rows, nullptr));
+    else
+        MIRX_HIP(launch_sq8_decode(ivf->rows.as<uint8_t>(), ivf->size, ivf->dimp, ivf->dim, ivf->vmin(), ivf->scale(), out_rows, nullptr));
     MIRX_HIP(hipStreamSynchronize(nullptr));
     return resident_ids_lists(ivf, out_ids_or_null, nullptr);
 }
@@ -458,6 +659,79 @@ int mirx_sq8_decode(const uint8_t *codes, int64_t n, int dim, const float *vmin,
     MIRX_CHECK(n >= 0 && dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "sq8_decode: n or dim out of range");
     MIRX_CHECK((codes && out_rows && vmin && scale) || n == 0, "sq8_decode: null argument");
     MIRX_HIP(launch_sq8_decode(codes, n, dim, dim, vmin, scale, out_rows, (hipStream_t)stream));
+    return MIRX_OK;
+}
+
+int mirx_ivf_pq_train(mirx_ivf *ivf, const float *rows, int64_t n, int iters, void *stream) {
+    MIRX_CHECK(ivf && rows, "ivf_pq_train: null argument");
+    MIRX_IVF_PQ_ONLY(ivf, "ivf_pq_train");
+    MIRX_CHECK(n >= 256, "ivf_pq_train: fewer rows than codewords (256)");
+    MIRX_CHECK(n <= 0x7FFFFF00ll, "ivf_pq_train: more than 2^31 rows");
+    MIRX_CHECK(iters >= 0, "ivf_pq_train: iters must not be negative");
+    if (int rc = sq8_resident(ivf, "ivf_pq_train")) return rc;
+    MIRX_IVF_ENTER(ivf, "ivf_pq_train");
+    hipStream_t st = (hipStream_t)stream;
+    const float *drows = nullptr;
+    DevBuf trows;
+    if (int rc = device_rows(ivf, rows, n, trows, &drows)) return rc;
+    const int m = ivf->pq_m, dsub = ivf->dim / m;
+    std::vector<int64_t> start(256);
+    for (int c = 0; c < 256; ++c) start[(size_t)c] = (int64_t)c * n / 256;
+    MIRX_HIP(ivf->pq_sub.ensure((size_t)n * dsub * sizeof(float)));
+    ivf->cb_fixed = false;                                   // not fixed while they are trained
+    for (int j = 0; j < m; ++j) {                            // mirx_ivf_train's loop on the columns of sub-space j, 256 lists, always L2
+        MIRX_HIP(launch_ivf_place(drows + (int64_t)j * dsub, n, ivf->dim, dsub, nullptr, nullptr, ivf->pq_sub.as<float>(), dsub, st));
+        if (int rc = lloyd(ivf, ivf->pq_sub.as<float>(), n, dsub, MIRX_METRIC_NEG_L2, 256, start, iters,
+                           ivf->codebooks.as<float>() + (size_t)j * 256 * dsub, st))
+            return rc;
+    }
+    ivf->cb_fixed = true;
+    return MIRX_OK;
+}
+
+int mirx_ivf_pq_set_codebooks(mirx_ivf *ivf, const float *codebooks) {
+    MIRX_CHECK(ivf && codebooks, "ivf_pq_set_codebooks: null argument");
+    MIRX_IVF_PQ_ONLY(ivf, "ivf_pq_set_codebooks");
+    if (int rc = sq8_resident(ivf, "ivf_pq_set_codebooks")) return rc;
+    MIRX_IVF_ENTER(ivf, "ivf_pq_set_codebooks");
+    MIRX_HIP(hipMemcpy(ivf->codebooks.p, codebooks, (size_t)256 * ivf->dim * sizeof(float), hipMemcpyDefault));
+    ivf->cb_fixed = true;
+    return MIRX_OK;
+}
+
+int mirx_ivf_pq_get_codebooks(const mirx_ivf *ivf, float *out_codebooks) {
+    MIRX_CHECK(ivf && out_codebooks, "ivf_pq_get_codebooks: null argument");
+    MIRX_IVF_PQ_ONLY(ivf, "ivf_pq_get_codebooks");
+    if (!ivf->cb_fixed)
+        return fail(MIRX_ESTATE, "ivf_pq_get_codebooks: the codebooks are not fixed yet (mirx_ivf_pq_train / _pq_set_codebooks)");
+    MIRX_IVF_ENTER(ivf, "ivf_pq_get_codebooks");
+    MIRX_HIP(hipMemcpy(out_codebooks, ivf->codebooks.p, (size_t)256 * ivf->dim * sizeof(float), hipMemcpyDefault));
+    return MIRX_OK;
+}
+
+int mirx_pq_encode(const float *rows, int64_t n, int dim, int m, const float *codebooks, uint8_t *out_codes, void *stream) {
+    MIRX_CHECK(n >= 0 && pq_shape_ok(dim, m), "pq_encode: n, dim or m out of range (m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0)");
+    MIRX_CHECK((rows && out_codes && codebooks) || n == 0, "pq_encode: null argument");
+    if (n == 0) return MIRX_OK;
+    int device = 0;
+    MIRX_HIP(hipGetDevice(&device));
+    DevBuf sub, found, fval;
+    return pq_encode_rows(device, dim, m, codebooks, rows, n, out_codes, sub, found, fval, (hipStream_t)stream);
+}
+
+int mirx_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, const float *codebooks, float *out_rows, void *stream) {
+    MIRX_CHECK(n >= 0 && pq_shape_ok(dim, m), "pq_decode: n, dim or m out of range (m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0)");
+    MIRX_CHECK((codes && out_rows && codebooks) || n == 0, "pq_decode: null argument");
+    MIRX_HIP(launch_pq_decode(codes, n, dim, m, codebooks, out_rows, (hipStream_t)stream));
+    return MIRX_OK;
+}
+
+int mirx_pq_tables(const float *q, int64_t nq, int dim, int m, int metric, const float *codebooks, double *out_tables_f64,
+                   void *stream) {
+    MIRX_CHECK(nq >= 0 && pq_shape_ok(dim, m), "pq_tables: nq, dim or m out of range (m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0)");
+    MIRX_CHECK(metric == MIRX_METRIC_IP || metric == MIRX_METRIC_NEG_L2, "pq_tables: unknown metric");
+    MIRX_CHECK((q && out_tables_f64 && codebooks) || nq == 0, "pq_tables: null argument");
+    MIRX_HIP(launch_pq_tables(q, nq, dim, m, metric, codebooks, out_tables_f64, (hipStream_t)stream));
     return MIRX_OK;
 }
 
@@ -508,6 +782,8 @@ int mirx_ivf_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int nprobe
     std::partial_sort(sizes.begin(), sizes.begin() + np, sizes.end(), std::greater<int64_t>());
     const int64_t ld = std::max<int64_t>(1, std::accumulate(sizes.begin(), sizes.begin() + np, (int64_t)0));
     const int64_t budget = ivf->score_bytes > 0 ? ivf->score_bytes : (int64_t)SCORE_WS_BYTES;
+    if (ivf->pq()) return pq_search(ivf, q, nq, k, np, ld, budget, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
+                                    out_probes_or_null, st);
     int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8)));
     per = std::min(per, std::max<int64_t>(1, MAX_BATCH_PAIRS / np));
     while (per > 1 && (per / qt + 1) * std::max<int64_t>(blocks, 1) > 0x7FFFFFFFll) per /= 2;   // work items fit an int

@@ -559,6 +559,36 @@ hipError_t launch_ivf_scores(const IvfScoreArgs &a, int metric, hipStream_t st);
 hipError_t launch_ivf_topk(const double *scores, int64_t ld, const int32_t *probes, const int32_t *qoff, int nq, int nprobe,
                            const int64_t *offsets, const int64_t *ids, const int64_t *exclude, int k, int metric, double *out_f64,
                            int64_t *out_ids, float *out_val, hipStream_t st);
+// launch_ivf_invert's first step alone: probes, out_probes and qoff as there, cnt[nlist] = how many of the nq queries probe each list
+hipError_t launch_ivf_probes(const int64_t *pids, int nq, int nprobe, const int64_t *offsets, int nlist, int32_t *probes,
+                             int32_t *out_probes, int32_t *qoff, int *cnt, hipStream_t st);
+
+// ---- k_ivf_pq.hip: IVF_PQ (mirx_ivf_create_pq): a query's ADC tables, the scan of the probed lists' code rows, code moves ------
+constexpr int PQ_MAX_M = 64;                     // sub-quantisers: a query's table is m x 256 doubles, 128 KiB of LDS at 64
+constexpr int PQ_MAX_DSUB = 512;                 // columns of a sub-space: MIRX_IVF_MAX_DIM / 4
+constexpr int PQ_ITEM_ROWS = 1024;               // entries of a compact score row per work item of the scan: one per thread
+constexpr int PQ_CU_LDS_BYTES = 160 * 1024;
+// out[q][j][c] (fp64) = the score of q's sub-vector j against codeword c of cb [m][256][dim / m]: one sequential accumulator over
+// the columns, IP: + q * c (exact product); L2: d = q - c, + (d * d) with the product rounded before the addition
+hipError_t launch_pq_tables(const float *q, int64_t nq, int dim, int m, int metric, const float *cb, double *out, hipStream_t st);
+// itemoff[nq + 1] = exclusive scan of ceil(qoff[q][nprobe] / PQ_ITEM_ROWS); stats[0..2] += entries, sum of cnt[nlist], items
+hipError_t launch_pq_items(const int32_t *qoff, int nq, int nprobe, const int *cnt, int nlist, int32_t *itemoff,
+                           unsigned long long *stats, hipStream_t st);
+struct PqScanArgs {
+    const double *tables;        // [nq, m, 256] launch_pq_tables'
+    const uint8_t *codes;        // [size, m] list-major code rows
+    int m, nq, nprobe;
+    const int32_t *probes, *qoff;   // launch_ivf_probes'
+    const int64_t *offsets;      // [nlist + 1]
+    const int32_t *itemoff;      // launch_pq_items'
+    double *out;                 // [nq, ld] compact score rows: entry e of query q = sum over j ascending of T[q][j][code[j]], negated for L2
+    int64_t ld;
+};
+hipError_t launch_pq_scan(const PqScanArgs &a, int metric, hipStream_t st);
+// codes[i * m + j] = (uint8)found[i]: the codeword search of sub-space j written into the code rows
+hipError_t launch_pq_pack(const int64_t *found, int64_t n, int m, int j, uint8_t *codes, hipStream_t st);
+// dst [n, dim] = each row's m codewords, concatenated
+hipError_t launch_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, const float *cb, float *dst, hipStream_t st);
 
 // ---- k_fuse.hip: hybrid search's rank / score fusion (mirx_fuse_ranked) ------------------------------------------------------
 struct FuseArgs {

@@ -736,9 +736,12 @@ class IvfFlatIndex:
         self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         self.dim, self.nlist = int(dim), int(nlist)
         h = ctypes.c_void_p()
+        self._create(h)
+        self._h = h
+
+    def _create(self, h):
         _lib.check(self._lib.mirx_ivf_create_typed(self.dim, self.metric, self.nlist, self.KIND, self.device.index,
                                                    ctypes.byref(h)), "mirx_ivf_create_typed")
-        self._h = h
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -929,6 +932,157 @@ class IvfSq8Index(IvfFlatIndex):
         ids = torch.empty((n,), dtype=torch.int64, device=self.device)
         self._call("mirx_ivf_reconstruct", _ptr_or_null(rows), _ptr_or_null(ids))
         return rows, ids
+
+
+PQ_TRAIN_ROWS = 65536                      # IvfPqIndex.train trains the codebooks on at most this many rows
+
+
+def pq_bounds(dim, m):
+    """m of an IVF_PQ index as an int, ValueError outside mirx_ivf_create_pq's contract (m % 4 == 0, 4 <= m <= 64,
+    dim % (4 m) == 0)"""
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+        raise ValueError(f"m must be an integer, got {m!r}")
+    m = int(m)
+    if m % 4 or not 4 <= m <= _lib.PQ_MAX_M:
+        raise ValueError(f"m must be a multiple of 4 in [4, {_lib.PQ_MAX_M}], got {m}")
+    if int(dim) % (4 * m):
+        raise ValueError(f"m = {m} needs a dim that is a multiple of 4 m = {4 * m}, got dim {dim}")
+    return m
+
+
+class IvfPqIndex(IvfFlatIndex):
+    """IVF_PQ (mirx_ivf_create_pq, include/mirx.h): IvfFlatIndex with every row kept as `m` codeword numbers (m bytes).  Sub-space
+    j (columns [j dim/m, (j+1) dim/m)) has a codebook of 256 codewords, k-means under L2 whatever the index metric; a row's code
+    is its nearest codeword per sub-space (FlatIndex's own ranking, ties to the lowest code).  A row's list comes from its
+    original values; then the row is encoded and the original is gone.  search() returns THE EXACT TOP-K OF THE ADC SCORE over
+    the rows of the probed lists: per query a float64 table T[j][c] (one sequential sum over the sub-space's columns), a row's
+    score the sequential sum over j of T[j][code[j]] -- defined to the bit in include/mirx.h, restated in tests/_pq_ref.py.  It is
+    not a search over reconstruct()'s rows (the sums associate differently).  An index that holds rows keeps its centroids and
+    codebooks (MirxError from train / set_centroids / train_codebooks / set_codebooks): remove the rows first."""
+
+    KIND = _lib.IVF_PQ
+
+    def __init__(self, dim, metric="COSINE", nlist=1024, m=None, device=None):
+        if m is None:
+            raise ValueError("IvfPqIndex needs m, the number of sub-quantisers")
+        self.m = pq_bounds(dim, m)
+        super().__init__(dim, metric, nlist, device)
+
+    def _create(self, h):
+        _lib.check(self._lib.mirx_ivf_create_pq(self.dim, self.metric, self.nlist, self.m, 8, self.device.index, ctypes.byref(h)),
+                   "mirx_ivf_create_pq")
+
+    def train(self, rows, iters=10, init_positions=None, max_rows=None, codebook_iters=10):
+        """IvfFlatIndex.train for the centroids, and the codebooks (train_codebooks) from at most 65 536 rows of the same data at
+        an even stride"""
+        IvfFlatIndex.train(self, rows, iters, init_positions, max_rows)
+        self.train_codebooks(rows, codebook_iters)
+
+    def train_codebooks(self, rows, iters=10, max_rows=PQ_TRAIN_ROWS):
+        """Fix the codebooks: per sub-space Lloyd's k-means with 256 codewords under L2 (mirx_ivf_pq_train: mirx_ivf_train's
+        loop, start at the rows floor(c n / 256)), on at most max_rows rows taken at an even stride.  Needs 256 rows."""
+        rows = self._rows(rows, "train_codebooks")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
+            raise ValueError(f"train_codebooks: iters must be a non-negative integer, got {iters!r}")
+        limit, n = int(max_rows), rows.shape[0]
+        if min(limit, n) < 256:
+            raise ValueError(f"train_codebooks: {min(limit, n)} rows cannot seed 256 codewords")
+        if n > limit:
+            pick = (torch.arange(limit, dtype=torch.int64) * n) // limit
+            rows = rows[pick.to(rows.device)].contiguous()
+            if rows.is_cuda:
+                torch.cuda.current_stream(self.device).synchronize()
+        self._call("mirx_ivf_pq_train", _ptr(rows), rows.shape[0], int(iters), _stream_ptr(self.device))
+
+    def set_codebooks(self, codebooks):
+        """Fix the codebooks to a caller's [m, 256, dim / m] array."""
+        cb = torch.as_tensor(codebooks).detach().to(torch.float32).contiguous()
+        if tuple(cb.shape) != (self.m, 256, self.dim // self.m):
+            raise ValueError(f"set_codebooks: expected [{self.m}, 256, {self.dim // self.m}], got {tuple(cb.shape)}")
+        if cb.is_cuda:
+            cb = cb.to(self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+        self._call("mirx_ivf_pq_set_codebooks", _ptr(cb))
+
+    @property
+    def codebooks(self):
+        """[m, 256, dim / m] fp32 on the index device"""
+        out = torch.empty((self.m, 256, self.dim // self.m), dtype=torch.float32, device=self.device)
+        self._call("mirx_ivf_pq_get_codebooks", _ptr(out))
+        return out
+
+    def codes(self):
+        """-> (codes uint8 [n, m], ids int64 [n], lists int64 [n]) on the index device, in list-major order"""
+        n = len(self)
+        codes = torch.empty((n, self.m), dtype=torch.uint8, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        lists = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_get_codes", _ptr_or_null(codes), _ptr_or_null(ids), _ptr_or_null(lists))
+        return codes, ids, lists
+
+    def reconstruct(self):
+        """-> (each row's codewords concatenated, fp32 [n, dim], ids int64 [n]) on the index device, in list-major order"""
+        n = len(self)
+        rows = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_reconstruct", _ptr_or_null(rows), _ptr_or_null(ids))
+        return rows, ids
+
+    def tables(self, q):
+        """-> float64 [nq, m, 256] on the index device: the ADC tables search() builds for q under the index metric"""
+        return pq_tables(self._rows(q, "tables").to(self.device), self.codebooks, self.metric)
+
+
+def _pq_args(first, codebooks, who, dtype):
+    first = torch.as_tensor(first).to(dtype).contiguous()
+    cb = torch.as_tensor(codebooks).to(torch.float32).contiguous()
+    if not first.is_cuda or first.dim() != 2 or cb.dim() != 3 or cb.shape[1] != 256:
+        raise ValueError(f"{who} expects a CUDA [n, .] array and codebooks [m, 256, dsub]")
+    m, dim = int(cb.shape[0]), int(cb.shape[0] * cb.shape[2])
+    pq_bounds(dim, m)
+    return first, cb.to(first.device), m, dim
+
+
+def pq_encode(rows, codebooks):
+    """mirx_pq_encode: CUDA fp32 rows [n, dim] -> uint8 codes [n, m] under codebooks [m, 256, dim / m]"""
+    rows, cb, m, dim = _pq_args(rows, codebooks, "pq_encode", torch.float32)
+    if rows.shape[1] != dim:
+        raise ValueError(f"pq_encode: rows of {rows.shape[1]} columns under codebooks of {dim}")
+    out = torch.empty((rows.shape[0], m), dtype=torch.uint8, device=rows.device)
+    with torch.cuda.device(rows.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_pq_encode(_ptr_or_null(rows), rows.shape[0], dim, m, _ptr(cb), _ptr_or_null(out),
+                                              _stream_ptr(rows.device)), "mirx_pq_encode")
+    return out
+
+
+def pq_decode(codes, codebooks):
+    """mirx_pq_decode: CUDA uint8 codes [n, m] -> fp32 rows [n, dim], each row's codewords concatenated"""
+    if torch.as_tensor(codes).dtype != torch.uint8:
+        raise ValueError("pq_decode expects uint8 codes")
+    codes, cb, m, dim = _pq_args(codes, codebooks, "pq_decode", torch.uint8)
+    if codes.shape[1] != m:
+        raise ValueError(f"pq_decode: codes of {codes.shape[1]} columns under {m} codebooks")
+    out = torch.empty((codes.shape[0], dim), dtype=torch.float32, device=codes.device)
+    with torch.cuda.device(codes.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_pq_decode(_ptr_or_null(codes), codes.shape[0], dim, m, _ptr(cb), _ptr_or_null(out),
+                                              _stream_ptr(codes.device)), "mirx_pq_decode")
+    return out
+
+
+def pq_tables(q, codebooks, metric="COSINE"):
+    """mirx_pq_tables: CUDA fp32 queries [nq, dim] -> float64 [nq, m, 256], T[q][j][c] = the metric's score of q's sub-vector j
+    against codeword c as one sequential float64 sum over the sub-space's columns (include/mirx.h)"""
+    q, cb, m, dim = _pq_args(q, codebooks, "pq_tables", torch.float32)
+    if q.shape[1] != dim:
+        raise ValueError(f"pq_tables: queries of {q.shape[1]} columns under codebooks of {dim}")
+    out = torch.empty((q.shape[0], m, 256), dtype=torch.float64, device=q.device)
+    with torch.cuda.device(q.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_pq_tables(_ptr_or_null(q), q.shape[0], dim, m, metric_code(metric), _ptr(cb), _ptr_or_null(out),
+                                              _stream_ptr(q.device)), "mirx_pq_tables")
+    return out
 
 
 def sq8_encode(rows, vmin, scale):

@@ -158,7 +158,7 @@ def _nih_index_params(metric_type, index_type, nlist):
 def create_nih_collection(collection_name, drop_old=False, metric_type="COSINE", index_type="IVF_FLAT", nlist=1024,
                           device=None, store=None, approximate=False):
     """Schema id / image_path / image_name / label_text / label_vector_json / embedding[256]; index_type and nlist are
-    accepted for compatibility (the search is exhaustive) unless approximate=True turns the reference's IVF_FLAT index (or index_type="IVF_SQ8") on
+    accepted for compatibility (the search is exhaustive) unless approximate=True turns the reference's IVF_FLAT index (or index_type="IVF_SQ8"; "IVF_PQ" raises Collection.create_index's "needs params['m']": this signature carries none) on
     (Collection.create_index(..., approximate=True): process state, searches that carry nprobe probe that many lists).  store: a mirx.store.Store or a directory -- the collection
     persists there (flush() commits; another process finds it with get_nih_collection(name, store=...)); None keeps it in
     this process."""

@@ -13,7 +13,8 @@ The "server" is a device-resident FlatIndex (libmirx); searches are EXACT (the r
 IVF_FLAT nlist=1024 / nprobe=10 index is approximate, milvus_setup.py:191-213) and
 `search_params` / `nprobe` are accepted and ignored, except `radius` / `range_filter` (a range search) and, on a collection
 whose index was created with `create_index(..., approximate=True)`, `nprobe`: the opt-in IVF_FLAT index (mirx.index.IvfFlatIndex,
-DESIGN 41) that reproduces the reference's own search, or IVF_SQ8 (mirx.index.IvfSq8Index), the same over 8-bit codes.  Metadata (image_path, label) stays on
+DESIGN 41) that reproduces the reference's own search, or IVF_SQ8 (mirx.index.IvfSq8Index), the same over 8-bit codes, or IVF_PQ (mirx.index.IvfPqIndex), the ADC
+ranking over product-quantised codes.  Metadata (image_path, label) stays on
 the host, keyed by the int64 ids the index returns.
 
 Errors follow the reference: unknown model type -> ValueError; connect() swallows failures
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex, IvfFlatIndex, IvfSq8Index, group_bounds, range_bounds, tier1_max_k
+from .index import FlatIndex, IvfFlatIndex, IvfPqIndex, IvfSq8Index, group_bounds, pq_bounds, range_bounds, tier1_max_k
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -148,10 +149,12 @@ class Collection:
         self._resident = stored is None                     # whether _index mirrors the live rows
         # the opt-in approximate index (create_index(..., approximate=True)): process state, never stored
         self._approx_nlist = None                           # nlist while the approximate index is on
-        self._approx_type = None                            # "IVF_FLAT" or "IVF_SQ8" while it is on
-        self._ivf = None                                    # the IvfFlatIndex / IvfSq8Index over the live rows; None = to be (re)built
+        self._approx_type = None                            # "IVF_FLAT", "IVF_SQ8" or "IVF_PQ" while it is on
+        self._approx_m = None                               # IVF_PQ: its number of sub-quantisers
+        self._ivf = None                                    # the IvfFlatIndex / IvfSq8Index / IvfPqIndex over the live rows; None = to be (re)built
         self._ivf_centroids = None                          # its centroids, trained once and kept across rebuilds
         self._ivf_range = None                              # IVF_SQ8: its (vmin, scale), trained once and kept likewise
+        self._ivf_codebooks = None                          # IVF_PQ: its codebooks, trained once and kept likewise
 
     @classmethod
     def from_stored(cls, stored, device=None):
@@ -279,19 +282,26 @@ class Collection:
 
     def create_index(self, field_name="embedding", index_params=None, approximate=False):
         """pymilvus' create_index.  Without `approximate` only the metric is kept: index_type and nlist are accepted and
-        ignored, every search is exact.  approximate=True with index_params["index_type"] "IVF_FLAT" or "IVF_SQ8" (any other
-        type: ValueError) turns the collection's approximate index on: an IvfFlatIndex / IvfSq8Index of
+        ignored, every search is exact.  approximate=True with index_params["index_type"] "IVF_FLAT", "IVF_SQ8" or "IVF_PQ" (any
+        other type: ValueError) turns the collection's approximate index on: an IvfFlatIndex / IvfSq8Index / IvfPqIndex of
         index_params["params"]["nlist"] lists (default 1024) beside the flat index, built from the resident rows at load() or at
         the first approximate search and trained once; after insert / delete / compact the lists are rebuilt lazily with the
-        kept centroids (IVF_SQ8: and the kept range, so rows inserted later clamp to the trained range).  It is process state: a
+        kept centroids (IVF_SQ8: and the kept range, so rows inserted later clamp to the trained range; IVF_PQ: and the kept
+        codebooks).  IVF_PQ needs index_params["params"]["m"], as Milvus does (ValueError without it or with an m that
+        mirx.index.pq_bounds refuses), and stays exact below max(nlist, 256) rows.  It is process state: a
         stored collection opened again is exact until this call is made again.  See search() for the calls it serves."""
         params = index_params or {}
-        nlist, kind = None, None
+        nlist, kind, m = None, None, None
         if approximate:
             kind = params.get("index_type")
-            if kind not in ("IVF_FLAT", "IVF_SQ8"):
-                raise ValueError(f"approximate=True needs index_type 'IVF_FLAT' or 'IVF_SQ8', got {kind!r}")
+            if kind not in ("IVF_FLAT", "IVF_SQ8", "IVF_PQ"):
+                raise ValueError(f"approximate=True needs index_type 'IVF_FLAT', 'IVF_SQ8' or 'IVF_PQ', got {kind!r}")
             inner = params.get("params") if isinstance(params.get("params"), dict) else {}
+            if kind == "IVF_PQ":
+                if "m" not in inner:
+                    raise ValueError("index_type 'IVF_PQ' needs params['m'], the number of sub-quantisers; "
+                                     "'IVF_FLAT' and 'IVF_SQ8' take nlist alone")
+                m = pq_bounds(self.dim, inner["m"])
             nlist = inner.get("nlist", 1024)
             if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= 65536:
                 raise ValueError(f"nlist must be an integer in [1, 65536], got {nlist!r}")
@@ -302,30 +312,39 @@ class Collection:
         self.metric_type = metric
         if self._stored is not None:
             self._stored.set_metric(metric)
-        if (nlist, kind) != (self._approx_nlist, self._approx_type):
-            self._approx_nlist, self._approx_type = nlist, kind
-            self._ivf, self._ivf_centroids, self._ivf_range = None, None, None
+        if (nlist, kind, m) != (self._approx_nlist, self._approx_type, self._approx_m):
+            self._approx_nlist, self._approx_type, self._approx_m = nlist, kind, m
+            self._ivf, self._ivf_centroids, self._ivf_range, self._ivf_codebooks = None, None, None, None
         return True
 
     def _ensure_ivf(self):
         """The approximate index over the live rows, or None while there are fewer rows than lists (nothing to train on: the
         exact routes answer).  A build copies the flat index's rows on the device (both indexes stay resident), trains on the
         first build and re-uses those centroids afterwards."""
-        if self._approx_nlist is None or self.num_entities < self._approx_nlist:
+        if self._approx_nlist is None:
+            return None
+        pq = self._approx_type == "IVF_PQ"
+        if self.num_entities < (max(self._approx_nlist, 256) if pq else self._approx_nlist):    # PQ: 256 codewords to seed
             return None
         if self._ivf is None:
             index = self._ensure()
             rows, ids = index.rows()
             sq8 = self._approx_type == "IVF_SQ8"
-            ivf = (IvfSq8Index if sq8 else IvfFlatIndex)(self.dim, self.metric_type, self._approx_nlist, index.device)
+            if pq:
+                ivf = IvfPqIndex(self.dim, self.metric_type, self._approx_nlist, self._approx_m, index.device)
+            else:
+                ivf = (IvfSq8Index if sq8 else IvfFlatIndex)(self.dim, self.metric_type, self._approx_nlist, index.device)
             if self._ivf_centroids is None:
                 ivf.train(rows)
                 self._ivf_centroids = ivf.centroids
                 self._ivf_range = ivf.range if sq8 else None
+                self._ivf_codebooks = ivf.codebooks if pq else None
             else:
                 ivf.set_centroids(self._ivf_centroids)
                 if sq8:
                     ivf.set_range(*self._ivf_range)
+                if pq:
+                    ivf.set_codebooks(self._ivf_codebooks)
             ivf.add(rows, ids)
             self._ivf = ivf
         return self._ivf
@@ -603,11 +622,13 @@ class Collection:
         hits when fewer rows are eligible; the mask of the last expression is reused until the collection changes.
         param: {"params": {"radius": r, "range_filter": f}} (or the two keys at the top level) makes it pymilvus' range search:
         the first `limit` hits of range_search(data, r, f, ...).  Every other key of param (nprobe, ef, metric_type) is ignored,
-        with one exception: on a collection whose index was created with approximate=True (IVF_FLAT or IVF_SQ8), a plain top-k call --
+        with one exception: on a collection whose index was created with approximate=True (IVF_FLAT, IVF_SQ8 or IVF_PQ), a plain top-k call --
         no expr, no grouping, no leave-out, no radius, limit <= 1024; exclude_ids allowed -- whose param carries an integer
         nprobe >= 1 (under "params" or at the top level) is answered by that index: the exact top `limit` of the rows
-        in the nprobe lists nearest to the query (IvfFlatIndex.search; IVF_SQ8: of their decoded rows, IvfSq8Index.search).  Every other call stays on the exact routes below, and
-        so do hybrid_search's lists and self_metrics; so does every call while the collection holds fewer rows than nlist.
+        in the nprobe lists nearest to the query (IvfFlatIndex.search; IVF_SQ8: of their decoded rows, IvfSq8Index.search; IVF_PQ: by the ADC score of their codes,
+        IvfPqIndex.search).  Every other call stays on the exact routes below, and
+        so do hybrid_search's lists and self_metrics; so does every call while the collection holds fewer rows than nlist (IVF_PQ:
+        than max(nlist, 256)).
         group_by_field (a scalar field of the schema) makes it pymilvus' grouping search: `limit` counts GROUPS (at most 1024),
         the result per query is one flat list of Hit, group after group, best group first and rank order inside a group, each
         group holding its best min(group_size, its eligible rows) rows (group_size <= 64, limit * group_size <= 16384); a
@@ -1025,7 +1046,8 @@ class MilvusManager:
         if model_type not in self.collections:
             raise ValueError(f"Collection for {model_type} not loaded")
         # index_type / nlist are accepted for compatibility: the search is exhaustive unless approximate=True asks for the
-        # reference's IVF_FLAT (Collection.create_index)
+        # reference's IVF_FLAT (Collection.create_index).  "IVF_PQ" is handed through and raises there: this signature, the
+        # reference's, carries no m, and Milvus refuses the type without one too
         self.collections[model_type].create_index(
             "embedding", {"metric_type": metric_type, "index_type": index_type, "params": {"nlist": nlist}}, approximate=approximate)
         return True

@@ -1660,6 +1660,58 @@ int mirx_ivf_reconstruct(const mirx_ivf *ivf, float *out_rows, int64_t *out_ids_
 int mirx_sq8_encode(const float *rows, int64_t n, int dim, const float *vmin, const float *scale, uint8_t *out_codes, void *stream);
 int mirx_sq8_decode(const uint8_t *codes, int64_t n, int dim, const float *vmin, const float *scale, float *out_rows, void *stream);
 
+/*
+ * IVF_PQ: the same lists and probes with the master kept as m codeword numbers per row (m bytes; the third IVF type of the
+ * reference's create_index, milvus/milvus_setup.py:191-213).  The rule is bent in one declared place: AN IVF_PQ ANSWER IS THE
+ * EXACT TOP-K, UNDER (score desc, id asc), OF THE ASYMMETRIC-DISTANCE (ADC) SCORE DEFINED BELOW, OVER THE ROWS OF THE PROBED LISTS.
+ * It is not a search over mirx_ivf_reconstruct's rows: the ADC sum associates differently from the lane tree, so the two differ
+ * in bits.  Every step is defined to the bit.
+ *
+ * Parameters: m sub-quantisers of 256 codewords (nbits = 8), dsub = dim / m; m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0.  Codes
+ *   encode the raw row (not a residual, not per list).
+ * Codebooks cb[m][256][dsub] fp32.
+ *     train    sub-space j's codebook is mirx_ivf_train's loop on columns [j dsub, (j+1) dsub) with 256 lists and ALWAYS the L2
+ *              metric (no normalisation): start rows[floor(c n / 256)], one fp64 accumulator per codeword and column in ascending
+ *              row order, an unused codeword keeps its bits, at most `iters` updates, stop when nothing moves.  n >= 256.
+ *     encode   code[j] = the nearest codeword of sub-vector j under the L2 ranking score, ties to the lowest code:
+ *              mirx_index_search(k = 1) over the 256 codewords with ids 0 .. 255 -- list assignment's own rule, not restated.
+ *     decode   the row's m codewords concatenated: exact fp32 copies.
+ *   A row's list is chosen from its ORIGINAL fp32 values, then the row is encoded; the originals are not kept.
+ * Tables, per query, fp64: T[j][c], j < m, c < 256 = ONE sequential accumulator from 0.0 over e = 0 .. dsub-1 ascending;
+ *     IP   acc = acc + (double)q[j dsub + e] * (double)cb[j][c][e]                (the product is exact in double)
+ *     L2   d = (double)q[..] - (double)cb[..]; acc = acc + d * d, the product ROUNDED to double before the addition (no fma)
+ * Score of a row: s = 0.0; for j ascending: s = s + T[j][code[j]].  The ranking score is s (IP) or -s (L2); reported fp32 values,
+ *   the excluded id, (-1, -inf) past the eligible rows and the order of the results are mirx_ivf_search's.  nprobe >= nlist ranks
+ *   every row by the same scores.
+ *
+ * mirx_ivf_create_pq   the only way to a MIRX_IVF_PQ handle (mirx_ivf_kind: 2); mirx_ivf_create's limits and the ones above,
+ *   nbits == 8: MIRX_EINVAL before any device call.  mirx_ivf_create_typed(kind = MIRX_IVF_PQ) stays MIRX_EINVAL: it has no m.
+ * mirx_ivf_pq_train (rows [n, dim], n >= 256, host or device) / _pq_set_codebooks / _pq_get_codebooks ([m][256][dsub] fp32, host
+ *   or device) fix or read the codebooks.  mirx_ivf_pq_m: m, -1 for another kind.  mirx_ivf_get_codes returns m bytes per row,
+ *   mirx_ivf_reconstruct the decoded rows.  The PQ calls on a FLAT or SQ8 handle, the SQ8 calls on a PQ handle: MIRX_EINVAL.
+ * State (MIRX_ESTATE, nothing changed): mirx_ivf_add before both the centroids and the codebooks are fixed; mirx_ivf_train,
+ *   _set_centroids, _pq_train and _pq_set_codebooks while rows are resident.
+ * mirx_ivf_search on a PQ handle, per internal batch: the probes; k_pq_tables writes every query's table into the workspace (a
+ *   query costs its compact row of doubles plus m x 2 KiB of the budget); ONE scan launch whose work item is (a query,
+ *   mirx_ivf_pq_item_rows() consecutive entries of its compact row) -- the workgroup holds the query's table in LDS, a thread owns
+ *   an entry, loads the row's m code bytes as words and adds the m table entries; then mirx_ivf_search's top-k.  In
+ *   mirx_ivf_stats work_items counts these items: the sum over the queries of ceil(entries / item_rows).  No floating atomics.
+ * mirx_pq_encode / _pq_decode / _pq_tables   the quantiser and the tables over device arrays (rows [n, dim] fp32, codes [n, m]
+ *   uint8, codebooks [m][256][dsub], out_tables_f64 [nq, m, 256]), without an index; encode waits for its work (m searches per
+ *   call: it is not a hot path), the other two are enqueued on `stream`.
+ */
+#define MIRX_IVF_PQ 2
+int mirx_ivf_create_pq(int dim, int metric, int nlist, int m, int nbits, int device, mirx_ivf **out);
+int mirx_ivf_pq_train(mirx_ivf *ivf, const float *rows, int64_t n, int iters, void *stream);
+int mirx_ivf_pq_set_codebooks(mirx_ivf *ivf, const float *codebooks);
+int mirx_ivf_pq_get_codebooks(const mirx_ivf *ivf, float *out_codebooks);
+int mirx_ivf_pq_m(const mirx_ivf *ivf);
+int mirx_ivf_pq_item_rows(void);
+int mirx_pq_encode(const float *rows, int64_t n, int dim, int m, const float *codebooks, uint8_t *out_codes, void *stream);
+int mirx_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, const float *codebooks, float *out_rows, void *stream);
+int mirx_pq_tables(const float *q, int64_t nq, int dim, int m, int metric, const float *codebooks, double *out_tables_f64,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,11 @@ ids against the flat index's exact ids, and the train and add times of the IVF i
 
 --index-type IVF_SQ8 adds an IvfSq8Index with the IVF_FLAT index's centroids and a range trained on the same strided
 sample as a third alternating arm, its recall against the exact ids and against IVF_FLAT's at equal nprobe, and for both index
-types the device memory held after the build and the peak during add (torch.cuda.mem_get_info, polled from a thread)."""
+types the device memory held after the build and the peak during add (torch.cuda.mem_get_info, polled from a thread).
+
+--index-type IVF_PQ --m M[,M2] keeps the IVF_SQ8 arm and adds one IvfPqIndex per m on the same centroids, its
+codebooks trained on at most 65 536 strided rows: further alternating arms, with the codebook-training and add times, the memory
+figures, and recall against the exact ids and against IVF_FLAT's at equal nprobe."""
 import argparse
 import json
 import os
@@ -20,7 +24,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, IvfFlatIndex, IvfSq8Index  # noqa: E402
+from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, IvfFlatIndex, IvfPqIndex, IvfSq8Index  # noqa: E402
 
 
 def clustered(n, d, centres, spread, dev, seed):
@@ -92,7 +96,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--heavy-repeats", type=int, default=3, help="repeats of a call that scores more than 2^33 (query, row) pairs")
     ap.add_argument("--train-iters", type=int, default=10)
-    ap.add_argument("--index-type", default="IVF_FLAT", choices=["IVF_FLAT", "IVF_SQ8"])
+    ap.add_argument("--index-type", default="IVF_FLAT", choices=["IVF_FLAT", "IVF_SQ8", "IVF_PQ"])
+    ap.add_argument("--m", default="", help="IVF_PQ: the sub-quantiser counts, one arm each (e.g. 64,32)")
+    ap.add_argument("--codebook-iters", type=int, default=10)
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -111,8 +117,10 @@ def main():
            "flat_add_ms": t_flat_add, "list_sizes": {"min": int(sizes.min()), "median": float(statistics.median(sizes.tolist())),
                                                       "max": int(sizes.max()), "empty": int((sizes == 0).sum())},
            "index_type": a.index_type, "ivf_held_bytes": held, "ivf_add_peak_bytes": peak_add, "cases": []}
-    sq8 = None
-    if a.index_type == "IVF_SQ8":                                            # the same centroids, the range from train()'s sample
+    if a.index_type == "IVF_PQ" and not a.m:
+        ap.error("--index-type IVF_PQ needs --m")
+    sq8, pqs = None, {}
+    if a.index_type in ("IVF_SQ8", "IVF_PQ"):                                          # the same centroids, the range from train()'s sample
         held0 = free_bytes(True)
         sq8 = IvfSq8Index(a.d, "COSINE", a.nlist, 0)
         sq8.set_centroids(ivf.centroids)
@@ -123,6 +131,16 @@ def main():
         t_add8, peak_add8 = peak_during(lambda: sq8.add(rows))
         out.update({"sq8_train_range_ms": t_range, "sq8_add_ms": t_add8, "sq8_held_bytes": held0 - free_bytes(True),
                     "sq8_add_peak_bytes": peak_add8, "rows_bytes_fp32": a.n * a.d * 4})
+    for m in [int(v) for v in a.m.split(",") if v] if a.index_type == "IVF_PQ" else []:
+        held0 = free_bytes(True)
+        pq = IvfPqIndex(a.d, "COSINE", a.nlist, m, 0)
+        pq.set_centroids(ivf.centroids)
+        t_cb, _ = timed(lambda: pq.train_codebooks(rows, a.codebook_iters))
+        t_addp, peak_addp = peak_during(lambda: pq.add(rows))
+        out[f"pq{m}"] = {"m": m, "train_codebooks_ms": t_cb, "codebook_rows": min(a.n, 65536), "codebook_iters": a.codebook_iters,
+                         "add_ms": t_addp, "held_bytes": held0 - free_bytes(True), "add_peak_bytes": peak_addp,
+                         "code_bytes": a.n * m}
+        pqs[f"pq{m}"] = pq
     print({k: v for k, v in out.items() if k != "cases"}, flush=True)
     g = torch.Generator(device=dev).manual_seed(4321)
     for nq in [int(v) for v in a.queries.split(",")]:
@@ -134,17 +152,26 @@ def main():
             st = ivf.last_stats()
             hit = recall(ids, exact)
             ids8 = None if sq8 is None else sq8.search(q, a.k, nprobe)[1]   # warm-up of the third arm
+            idsp, stp = {}, {}
+            for name, pq in pqs.items():                                     # warm-up of the PQ arms
+                idsp[name] = pq.search(q, a.k, nprobe)[1]
+                stp[name] = pq.last_stats()
             reps = a.heavy_repeats if st["rows_scored"] > 1 << 33 else a.repeats
-            t_ivf, t_flat, t_sq8 = [], [], []
+            t_ivf, t_flat, t_sq8, t_pq = [], [], [], {name: [] for name in pqs}
             for _ in range(reps):                                            # alternating arms
                 t_ivf.append(timed(lambda: ivf.search(q, a.k, nprobe))[0])
                 if sq8 is not None:
                     t_sq8.append(timed(lambda: sq8.search(q, a.k, nprobe))[0])
+                for name, pq in pqs.items():
+                    t_pq[name].append(timed(lambda: pq.search(q, a.k, nprobe))[0])
                 t_flat.append(timed(lambda: flat.search(q, a.k))[0])
             case = {"queries": nq, "nprobe": nprobe, "recall_at_k": hit, "ivf": stat(t_ivf), "flat": stat(t_flat),
                     "rows_scored_per_query": st["rows_scored"] / nq, "work_items": st["work_items"], "batches": st["batches"]}
             if sq8 is not None:
                 case.update({"sq8": stat(t_sq8), "sq8_recall_at_k": recall(ids8, exact), "sq8_recall_vs_ivf_flat": recall(ids8, ids)})
+            for name in pqs:
+                case[name] = dict(stat(t_pq[name]), recall_at_k=recall(idsp[name], exact), recall_vs_ivf_flat=recall(idsp[name], ids),
+                                  work_items=stp[name]["work_items"], batches=stp[name]["batches"])
             out["cases"].append(case)
             print(case, flush=True)
     if a.json:
