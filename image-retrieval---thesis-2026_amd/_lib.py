@@ -279,6 +279,11 @@ SYMBOLS = {
     "mirx_pq_encode": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "mirx_pq_decode": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp]),
     "mirx_pq_tables": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp]),
+    "mirx_ivf_create_pq_ex": (_int, [_int, _int, _int, _int, _int, _int, _int, ctypes.POINTER(_vp)]),
+    "mirx_ivf_pq_by_residual": (_int, [_vp]),
+    "mirx_ivf_get_norms": (_int, [_vp, _vp]),
+    "mirx_pq_residuals": (_int, [_vp, _i64, _int, _vp, _vp, _int, _vp, _vp]),
+    "mirx_pq_bases": (_int, [_vp, _i64, _int, _int, _vp, _int, _vp, _int, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,6 +1,8 @@
 // k_ivf_pq.hip -- the kernels of IVF_PQ (mirx_ivf.hip, include/mirx.h): a query's asymmetric-distance tables, the scan of the
 // probed lists' code rows against them, and the small moves around the code master (codes packed from the codeword search,
-// codes decoded to their codewords).  The lists, probes, compact score rows and their top-k are k_ivf.hip's, unchanged.
+// codes decoded to their codewords), and the kernels of residual coding (mirx_ivf_create_pq_ex): residuals, the per-(query, list)
+// bases, the row norms of L2 and the residual instantiations of the scan.  The lists, probes, compact score rows and their top-k are
+// k_ivf.hip's, unchanged.
 //
 // A score is defined by its order of additions (include/mirx.h): a table entry is ONE sequential fp64 accumulator over the
 // sub-space's columns, a row's score ONE sequential accumulator over the sub-quantisers, so the numpy restatement
@@ -105,12 +107,17 @@ __global__ __launch_bounds__(256) void k_pq_items(const int32_t *__restrict__ qo
 // LDS layout: T[j][c] as the tables kernel left it, no padding and no stagger.  Every lane of a wave is at the same j at the same
 // time, so lanes with EQUAL codes read one address (a broadcast) and lanes with different codes of one j spread over that j's 256
 // entries = 32 bank pairs of a ds_read_b64 half-wave; staggering T[j] by j would move all lanes alike and change nothing.
-template <int METRIC, bool V16>
+// RES (residual coding, include/mirx.h): T is the IP table of the residual codebooks whatever the metric, and an entry's sum starts
+// from the base of ITS OWN (query, probed list) -- base[qi * nprobe + lo], lo the slot the entry bisected -- so lanes of one wave
+// start from different bases wherever a list boundary falls inside the wave.  L2 then reads the row's N2 beside its code row and
+// ranks by -((QQ + N2) - 2 ip).  Without RES the three pointers are never read and the code is the raw form's.
+template <int METRIC, bool V16, bool RES>
 __global__ __launch_bounds__(PQ_ITEM_ROWS) void k_pq_scan(const double *__restrict__ tables, const uint8_t *__restrict__ codes, int m,
                                                            const int32_t *__restrict__ probes, const int32_t *__restrict__ qoff,
                                                            int nq, int nprobe, const int64_t *__restrict__ offsets,
                                                            const int32_t *__restrict__ itemoff, double *__restrict__ out,
-                                                           int64_t ld) {
+                                                           int64_t ld, const double *__restrict__ base,
+                                                           const double *__restrict__ qq, const double *__restrict__ n2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *T = reinterpret_cast<double *>(smem);                                  // [m][256]
     const int total = itemoff[nq];
@@ -161,7 +168,7 @@ __global__ __launch_bounds__(PQ_ITEM_ROWS) void k_pq_scan(const double *__restri
 #pragma unroll
             for (int i = 0; i < 16; ++i) w[i] = i < nw ? reinterpret_cast<const uint32_t *>(row)[i] : 0u;
         }
-        double s = 0.0;
+        double s = RES ? base[(int64_t)qi * nprobe + lo] : 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             if (i < nw) {
@@ -172,7 +179,10 @@ __global__ __launch_bounds__(PQ_ITEM_ROWS) void k_pq_scan(const double *__restri
                 s = s + Tj[768 + (w[i] >> 24)];
             }
         }
-        out[(int64_t)qi * ld + e] = METRIC == 0 ? s : -s;
+        if (RES && METRIC != 0)                                                    // 2.0 * ip is exact; every step rounds once
+            out[(int64_t)qi * ld + e] = -__dsub_rn(__dadd_rn(qq[qi], n2[pos]), __dmul_rn(2.0, s));
+        else
+            out[(int64_t)qi * ld + e] = METRIC == 0 ? s : -s;
     }
 }
 
@@ -195,16 +205,148 @@ __global__ __launch_bounds__(256) void k_pq_decode(const uint8_t *__restrict__ c
         }
 }
 
-template <int METRIC, bool V16>
+// ---- residual coding (include/mirx.h, mirx_ivf_create_pq_ex) ----------------------------------------------------------------------
+// dst[i][e] = rows[i][col0 + e] - cent[lists[i]][col0 + e], e < cols: one fp32 subtraction.  The column window lets the trainer
+// write sub-space j's residuals straight into its [n, dsub] buffer and the encoder a chunk of whole rows.
+__global__ __launch_bounds__(256) void k_pq_residual(const float *__restrict__ rows, int64_t n, int dim, int col0, int cols,
+                                                     const int64_t *__restrict__ lists, const float *__restrict__ cent, int nlist,
+                                                     float *__restrict__ dst, int dst_ld) {
+    const int64_t total = n * cols;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t i = idx / cols;
+        const int e = (int)(idx - i * cols);
+        const int64_t l = lists[i];
+        float r = NAN;                                                             // no such list: nothing is read
+        if (l >= 0 && l < nlist) r = __fsub_rn(rows[i * dim + col0 + e], cent[l * dim + col0 + e]);
+        dst[i * dst_ld + e] = r;
+    }
+}
+
+// One workgroup per query, the query in LDS.  A round takes 256 / m probe slots: thread (slot, j) streams sub-space j of the
+// slot's centroid as float4s into P_j, ONE sequential accumulator; behind a barrier thread `slot` adds the m P_j, j ascending.
+// The order of additions is the definition's; only who computes which P_j is free.  METRIC 1 adds QQ[q], the same sum of q * q.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_pq_base(const float *__restrict__ q, int64_t nq, int dim, int m,
+                                                 const int32_t *__restrict__ lists, int nprobe, const float *__restrict__ cent,
+                                                 int nlist, double *__restrict__ base, double *__restrict__ qq) {
+    __shared__ float qs[MIRX_IVF_MAX_DIM];
+    __shared__ double part[256];
+    const int dsub = dim / m, t = threadIdx.x;
+    const int per = 256 / m;                                                       // slots of a round, >= 4
+    const int sl = t / m, j = t - sl * m;
+    for (int64_t qi = blockIdx.x; qi < nq; qi += gridDim.x) {
+        __syncthreads();                                                           // the previous query's reads of qs
+        for (int e = t; e < dim; e += 256) qs[e] = q[qi * dim + e];
+        __syncthreads();
+        for (int s0 = 0; s0 < nprobe; s0 += per) {
+            const int s = s0 + sl;
+            double acc = 0.0;
+            if (sl < per && s < nprobe) {
+                const int l = lists[qi * nprobe + s];
+                if (l >= 0 && l < nlist) {
+                    const float4 *row = reinterpret_cast<const float4 *>(cent + (int64_t)l * dim + (int64_t)j * dsub);
+                    const float *qj = qs + j * dsub;
+                    for (int e4 = 0; e4 < (dsub >> 2); ++e4) {
+                        const float4 v = row[e4];
+                        const float cv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            acc = __dadd_rn(acc, __dmul_rn((double)qj[4 * e4 + e], (double)cv[e]));   // the product is exact
+                    }
+                }
+            }
+            part[t] = acc;
+            __syncthreads();
+            if (t < per && s0 + t < nprobe) {
+                double b = 0.0;
+                for (int jj = 0; jj < m; ++jj) b = __dadd_rn(b, part[t * m + jj]);
+                base[qi * nprobe + s0 + t] = b;
+            }
+            __syncthreads();                                                       // part is rewritten by the next round
+        }
+        if (METRIC != 0) {
+            double acc = 0.0;
+            if (t < m)
+                for (int e = 0; e < dsub; ++e) acc = __dadd_rn(acc, __dmul_rn((double)qs[t * dsub + e], (double)qs[t * dsub + e]));
+            part[t] = acc;
+            __syncthreads();
+            if (t == 0) {
+                double b = 0.0;
+                for (int jj = 0; jj < m; ++jj) b = __dadd_rn(b, part[jj]);
+                qq[qi] = b;
+            }
+        }
+    }
+}
+
+// N2 of coded rows: thread (row, j) of a round of 256 / m rows walks sub-space j of xh = centroid + codeword, the square rounded
+// before it is added; thread `row` then adds the m partial sums, j ascending.
+__global__ __launch_bounds__(256) void k_pq_norms(const uint8_t *__restrict__ codes, int64_t n, int dim, int m,
+                                                  const int64_t *__restrict__ lists, const float *__restrict__ cent, int nlist,
+                                                  const float *__restrict__ cb, double *__restrict__ n2) {
+    __shared__ double part[256];
+    const int dsub = dim / m, t = threadIdx.x;
+    const int per = 256 / m;
+    const int rl = t / m, j = t - rl * m;
+    const int64_t rounds = (n + per - 1) / per;
+    for (int64_t r = blockIdx.x; r < rounds; r += gridDim.x) {
+        const int64_t i = r * per + rl;
+        double acc = 0.0;
+        if (rl < per && i < n) {
+            const int64_t l = lists[i];
+            if (l >= 0 && l < nlist) {
+                const float4 *c4 = reinterpret_cast<const float4 *>(cent + l * dim + (int64_t)j * dsub);
+                const float4 *w4 = reinterpret_cast<const float4 *>(cb + ((int64_t)j * 256 + codes[i * m + j]) * dsub);
+                for (int e4 = 0; e4 < (dsub >> 2); ++e4) {
+                    const float4 c = c4[e4], w = w4[e4];
+                    const float cv[4] = {c.x, c.y, c.z, c.w}, wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const double xh = __dadd_rn((double)cv[e], (double)wv[e]);
+                        acc = __dadd_rn(acc, __dmul_rn(xh, xh));                   // rounded, then added
+                    }
+                }
+            } else {
+                acc = NAN;
+            }
+        }
+        part[t] = acc;
+        __syncthreads();
+        if (t < per && r * per + t < n) {
+            double b = 0.0;
+            for (int jj = 0; jj < m; ++jj) b = __dadd_rn(b, part[t * m + jj]);
+            n2[r * per + t] = b;
+        }
+        __syncthreads();
+    }
+}
+
+// rows[i] = (float)(centroid of the row's list + its codewords): one fp32 addition per column
+__global__ __launch_bounds__(256) void k_pq_decode_residual(const uint8_t *__restrict__ codes, int64_t n, int dim, int m,
+                                                            const float *__restrict__ cb, const int64_t *__restrict__ lists,
+                                                            const float *__restrict__ cent, int nlist, float *__restrict__ dst) {
+    const int dsub = dim / m;
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int64_t l = lists[i];
+        for (int c = threadIdx.x; c < dim; c += 256) {
+            const int j = c / dsub, e = c - j * dsub;
+            float v = NAN;
+            if (l >= 0 && l < nlist) v = __fadd_rn(cent[l * dim + c], cb[((int64_t)j * 256 + codes[i * m + j]) * dsub + e]);
+            dst[i * dim + c] = v;
+        }
+    }
+}
+
+template <int METRIC, bool V16, bool RES>
 hipError_t launch_pq_scan_t(const PqScanArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.m * 256 * sizeof(double);
     static std::atomic<unsigned long long> once{0};
-    hipError_t e = set_dynamic_lds(k_pq_scan<METRIC, V16>, (size_t)PQ_MAX_M * 256 * sizeof(double), &once);
+    hipError_t e = set_dynamic_lds(k_pq_scan<METRIC, V16, RES>, (size_t)PQ_MAX_M * 256 * sizeof(double), &once);
     if (e != hipSuccess) return e;
     const int per_cu = lds * 2 <= PQ_CU_LDS_BYTES ? 2 : 1;                         // 1024 threads each: two workgroups fill a CU
     const unsigned grid = (unsigned)(current_device_cus() * per_cu);
-    hipLaunchKernelGGL((k_pq_scan<METRIC, V16>), dim3(grid), dim3(PQ_ITEM_ROWS), lds, st, a.tables, a.codes, a.m, a.probes, a.qoff,
-                       a.nq, a.nprobe, a.offsets, a.itemoff, a.out, a.ld);
+    hipLaunchKernelGGL((k_pq_scan<METRIC, V16, RES>), dim3(grid), dim3(PQ_ITEM_ROWS), lds, st, a.tables, a.codes, a.m, a.probes,
+                       a.qoff, a.nq, a.nprobe, a.offsets, a.itemoff, a.out, a.ld, a.base, a.qq, a.n2);
     return hipGetLastError();
 }
 
@@ -228,8 +370,15 @@ hipError_t launch_pq_items(const int32_t *qoff, int nq, int nprobe, const int *c
 }
 
 hipError_t launch_pq_scan(const PqScanArgs &a, int metric, hipStream_t st) {
-    if (a.m % 16 == 0) return metric == MIRX_METRIC_IP ? launch_pq_scan_t<0, true>(a, st) : launch_pq_scan_t<1, true>(a, st);
-    return metric == MIRX_METRIC_IP ? launch_pq_scan_t<0, false>(a, st) : launch_pq_scan_t<1, false>(a, st);
+    if (a.base) {                                                                  // residual coding
+        if (metric != MIRX_METRIC_IP && (!a.qq || !a.n2)) return hipErrorInvalidValue;
+        if (a.m % 16 == 0)
+            return metric == MIRX_METRIC_IP ? launch_pq_scan_t<0, true, true>(a, st) : launch_pq_scan_t<1, true, true>(a, st);
+        return metric == MIRX_METRIC_IP ? launch_pq_scan_t<0, false, true>(a, st) : launch_pq_scan_t<1, false, true>(a, st);
+    }
+    if (a.m % 16 == 0)
+        return metric == MIRX_METRIC_IP ? launch_pq_scan_t<0, true, false>(a, st) : launch_pq_scan_t<1, true, false>(a, st);
+    return metric == MIRX_METRIC_IP ? launch_pq_scan_t<0, false, false>(a, st) : launch_pq_scan_t<1, false, false>(a, st);
 }
 
 hipError_t launch_pq_pack(const int64_t *found, int64_t n, int m, int j, uint8_t *codes, hipStream_t st) {
@@ -243,6 +392,43 @@ hipError_t launch_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, con
     if (n <= 0) return hipSuccess;
     const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
     hipLaunchKernelGGL(k_pq_decode, dim3(grid), dim3(256), 0, st, codes, n, dim, m, cb, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_pq_residual(const float *rows, int64_t n, int dim, int col0, int cols, const int64_t *lists, const float *cent,
+                              int nlist, float *dst, int dst_ld, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const int64_t blocks = (n * cols + 255) / 256;
+    const unsigned grid = (unsigned)(blocks < 65536 ? blocks : 65536);
+    hipLaunchKernelGGL(k_pq_residual, dim3(grid), dim3(256), 0, st, rows, n, dim, col0, cols, lists, cent, nlist, dst, dst_ld);
+    return hipGetLastError();
+}
+
+hipError_t launch_pq_base(const float *q, int64_t nq, int dim, int m, const int32_t *lists, int nprobe, const float *cent, int nlist,
+                          double *base, double *qq_or_null, hipStream_t st) {
+    if (nq <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(nq < (1 << 20) ? nq : (1 << 20));
+    if (qq_or_null)
+        hipLaunchKernelGGL(k_pq_base<1>, dim3(grid), dim3(256), 0, st, q, nq, dim, m, lists, nprobe, cent, nlist, base, qq_or_null);
+    else
+        hipLaunchKernelGGL(k_pq_base<0>, dim3(grid), dim3(256), 0, st, q, nq, dim, m, lists, nprobe, cent, nlist, base, qq_or_null);
+    return hipGetLastError();
+}
+
+hipError_t launch_pq_norms(const uint8_t *codes, int64_t n, int dim, int m, const int64_t *lists, const float *cent, int nlist,
+                           const float *cb, double *n2, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const int64_t rounds = (n + 256 / m - 1) / (256 / m);
+    const unsigned grid = (unsigned)(rounds < 65536 ? rounds : 65536);
+    hipLaunchKernelGGL(k_pq_norms, dim3(grid), dim3(256), 0, st, codes, n, dim, m, lists, cent, nlist, cb, n2);
+    return hipGetLastError();
+}
+
+hipError_t launch_pq_decode_residual(const uint8_t *codes, int64_t n, int dim, int m, const float *cb, const int64_t *lists,
+                                     const float *cent, int nlist, float *dst, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)(n < 65536 ? n : 65536);
+    hipLaunchKernelGGL(k_pq_decode_residual, dim3(grid), dim3(256), 0, st, codes, n, dim, m, cb, lists, cent, nlist, dst);
     return hipGetLastError();
 }
 

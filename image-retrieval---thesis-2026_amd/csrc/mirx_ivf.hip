@@ -28,17 +28,20 @@ struct mirx_ivf {
     int pq_m = 0;                         // PQ: sub-quantisers; a code row is pq_m bytes
     DevBuf codebooks;                     // PQ: [pq_m][256][dim / pq_m] fp32
     bool cb_fixed = false;
+    bool pq_res = false;                  // PQ: residual coding (mirx_ivf_create_pq_ex): codes of row - centroid of its list
+    DevBuf norms;                         // residual PQ under L2: N2 [size] fp64, list-major beside ids
     std::vector<int64_t> off_h, ids_h, seq_h;   // host mirrors of offsets / ids, and each row's insertion number (list-major)
     int64_t next_seq = 0, next_auto = 0;
     int64_t score_bytes = 0;              // MIRX_IVF_OPT_SCORE_BYTES; 0 = SCORE_WS_BYTES
     // scratch
     DevBuf stage, lists, fval, a_order, a_loff, upd, pos, newids, q32p, pids, probes, qoff, cntcur, pairoff, itemoff, pair_q,
-        pair_off, scores, tables, pq_sub, pq_found, pq_codes;
+        pair_off, scores, tables, pq_sub, pq_found, pq_codes, pq_lists, pq_resid, pq_n2, pq_base, pq_qq;
     unsigned long long *stats_dev = nullptr;   // [3] rows scored, pairs, work items
     int64_t last_nq = 0, last_batches = 0;
 
     bool sq8() const { return kind == MIRX_IVF_SQ8; }
     bool pq() const { return kind == MIRX_IVF_PQ; }
+    bool res_l2() const { return pq() && pq_res && metric != MIRX_METRIC_IP; }     // the handles that keep N2
     int code_ld() const { return pq() ? pq_m : dimp; }                             // bytes of a code row (SQ8, PQ)
     size_t row_bytes() const { return pq() ? (size_t)pq_m : (size_t)dimp * (sq8() ? 1 : sizeof(float)); }
     const float *vmin() const { return range.as<float>(); }
@@ -212,14 +215,33 @@ int pq_encode_chunks(const std::vector<mirx_index *> &cbidx, int dim, int m, con
 // codes [n, m] (device) of rows [n, dim] (device) under cb (device [m][256][dim / m]): sub-vector j of every row searched in a flat
 // index over sub-space j's codewords.  The m indexes live for the call only -- their search workspaces (tens of MB each) would
 // outweigh the codes if the handle kept them.  Waits for its work, on failure too: the indexes are freed behind it.
+// With dlists (device, [n]) the rows are coded by residual: chunk by chunk rows - cent[dlists] goes into `resid` (one chunk of
+// whole rows, so the scratch stays bounded) and the chunk's residuals are encoded.
+int pq_encode_residual_chunks(const std::vector<mirx_index *> &cbidx, int dim, int m, const float *drows, int64_t n, uint8_t *codes,
+                              DevBuf &sub, DevBuf &found, DevBuf &fval, const int64_t *dlists, const float *cent, int nlist,
+                              DevBuf &resid, hipStream_t st) {
+    const int64_t chunk = std::min<int64_t>(n, PQ_ENCODE_CHUNK);
+    if (resid.ensure((size_t)chunk * dim * sizeof(float)) != hipSuccess)
+        return fail(MIRX_ENOMEM, "pq_encode: no memory for the residuals");
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t nc = std::min(chunk, n - c0);
+        MIRX_HIP(launch_pq_residual(drows + c0 * dim, nc, dim, 0, dim, dlists + c0, cent, nlist, resid.as<float>(), dim, st));
+        if (int rc = pq_encode_chunks(cbidx, dim, m, resid.as<float>(), nc, codes + c0 * m, sub, found, fval, st)) return rc;
+    }
+    return MIRX_OK;
+}
+
 int pq_encode_rows(int device, int dim, int m, const float *cb, const float *drows, int64_t n, uint8_t *codes, DevBuf &sub,
-                   DevBuf &found, DevBuf &fval, hipStream_t st) {
+                   DevBuf &found, DevBuf &fval, hipStream_t st, const int64_t *dlists = nullptr, const float *cent = nullptr,
+                   int nlist = 0, DevBuf *resid = nullptr) {
     if (n == 0) return MIRX_OK;
     std::vector<mirx_index *> cbidx;
     if (int rc = build_codeword_indexes(dim, m, device, cb, cbidx)) return rc;
-    const int rc = pq_encode_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, st);
+    const int rc = dlists ? pq_encode_residual_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, dlists, cent, nlist, *resid, st)
+                          : pq_encode_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, st);
     const hipError_t e = hipStreamSynchronize(st);
     free_codeword_indexes(cbidx);
+    if (resid) resid->release();                             // a chunk of whole fp32 rows (256 MiB at dim 1024): not worth holding
     if (rc) return rc;
     MIRX_HIP(e);
     return MIRX_OK;
@@ -230,12 +252,14 @@ int pq_encode_rows(int device, int dim, int m, const float *cb, const float *dro
 // mirrors follow.  Everything is allocated before a row moves: MIRX_ENOMEM leaves the ivf untouched.
 int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const void *new_rows, int64_t n_new,
              const std::vector<int64_t> &new_ids, const std::vector<int64_t> &new_dst, int64_t total,
-             const std::vector<int64_t> &new_off, hipStream_t st) {
+             const std::vector<int64_t> &new_off, hipStream_t st, const double *new_norms = nullptr) {
     const int64_t n_old = ivf->size;
-    DevBuf rows2, ids2;
+    DevBuf rows2, ids2, norms2;                                  // norms2: N2 travels with the ids (residual PQ under L2), 8 bytes a row
+    const bool nrm = ivf->res_l2();
     const size_t pos_bytes = (size_t)std::max<int64_t>(n_old, n_new) * sizeof(int64_t);
     if (rows2.ensure((size_t)std::max<int64_t>(total, 1) * ivf->row_bytes()) != hipSuccess ||
         ids2.ensure((size_t)std::max<int64_t>(total, 1) * sizeof(int64_t)) != hipSuccess ||
+        (nrm && norms2.ensure((size_t)std::max<int64_t>(total, 1) * sizeof(double)) != hipSuccess) ||
         ivf->pos.ensure(std::max<size_t>(pos_bytes, 8)) != hipSuccess ||
         ivf->newids.ensure((size_t)std::max<int64_t>(n_new, 1) * sizeof(int64_t)) != hipSuccess ||
         ivf->offsets.ensure((size_t)(ivf->nlist + 1) * sizeof(int64_t)) != hipSuccess)
@@ -249,6 +273,7 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const void *new
             MIRX_HIP(launch_ivf_place(ivf->rows.as<float>(), n_old, ivf->dimp, ivf->dimp, nullptr, ivf->pos.as<int64_t>(),
                                       rows2.as<float>(), ivf->dimp, st));
         MIRX_HIP(launch_ivf_place_ids(ivf->ids.as<int64_t>(), n_old, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
+        if (nrm) MIRX_HIP(launch_ivf_place_ids(ivf->norms.as<int64_t>(), n_old, ivf->pos.as<int64_t>(), norms2.as<int64_t>(), st));
         MIRX_HIP(hipStreamSynchronize(st));                     // pos is reused below
         for (int64_t p = 0; p < n_old; ++p)
             if (old_dst[(size_t)p] >= 0) {
@@ -269,6 +294,9 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const void *new
             MIRX_HIP(launch_ivf_place(static_cast<const float *>(new_rows), n_new, ivf->dim, ivf->dim, nullptr,
                                       ivf->pos.as<int64_t>(), rows2.as<float>(), ivf->dimp, st));
         MIRX_HIP(launch_ivf_place_ids(ivf->newids.as<int64_t>(), n_new, ivf->pos.as<int64_t>(), ids2.as<int64_t>(), st));
+        if (nrm)
+            MIRX_HIP(launch_ivf_place_ids(reinterpret_cast<const int64_t *>(new_norms), n_new, ivf->pos.as<int64_t>(),
+                                          norms2.as<int64_t>(), st));
         for (int64_t j = 0; j < n_new; ++j) {
             ids_h[(size_t)new_dst[(size_t)j]] = new_ids[(size_t)j];
             seq_h[(size_t)new_dst[(size_t)j]] = ivf->next_seq + j;
@@ -281,6 +309,10 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const void *new
     std::swap(ivf->rows.bytes, rows2.bytes);
     std::swap(ivf->ids.p, ids2.p);
     std::swap(ivf->ids.bytes, ids2.bytes);
+    if (nrm) {
+        std::swap(ivf->norms.p, norms2.p);
+        std::swap(ivf->norms.bytes, norms2.bytes);
+    }
     ivf->ids_h.swap(ids_h);
     ivf->seq_h.swap(seq_h);
     ivf->off_h = new_off;
@@ -326,10 +358,15 @@ int pq_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int np, int64_t 
               float *out_values, double *out_f64, int64_t *out_ids, int32_t *out_probes, hipStream_t st) {
     const int nlist = ivf->nlist, m = ivf->pq_m;
     const int64_t table_bytes = (int64_t)m * 256 * sizeof(double), items_per_row = (ld + PQ_ITEM_ROWS - 1) / PQ_ITEM_ROWS;
-    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8 + table_bytes)));
+    const bool res = ivf->pq_res, res_l2 = ivf->res_l2();
+    const int64_t base_bytes = res ? (int64_t)8 * np + 8 : 0;                      // residual: a base per probed list, and QQ
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8 + table_bytes + base_bytes)));
     per = std::min(per, std::max<int64_t>(1, MAX_BATCH_PAIRS / np));
     per = std::min(per, std::max<int64_t>(1, 0x7FFFFFFFll / items_per_row));       // work items fit an int
     hipError_t e;
+    if (res && ((e = ivf->pq_base.ensure((size_t)per * np * sizeof(double))) != hipSuccess ||
+                (e = ivf->pq_qq.ensure((size_t)per * sizeof(double))) != hipSuccess))
+        return fail(MIRX_ENOMEM, std::string("ivf_search: workspace: ") + hipGetErrorString(e));
     if ((e = ivf->scores.ensure((size_t)per * ld * sizeof(double))) != hipSuccess ||
         (e = ivf->tables.ensure((size_t)per * table_bytes)) != hipSuccess ||
         (e = ivf->pids.ensure((size_t)per * np * sizeof(int64_t))) != hipSuccess ||
@@ -348,7 +385,11 @@ int pq_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int np, int64_t 
         if (rc) return rc;
         MIRX_HIP(launch_ivf_probes(ivf->pids.as<int64_t>(), nb, np, ivf->offsets.as<int64_t>(), nlist, ivf->probes.as<int32_t>(),
                                    out_probes ? out_probes + q0 * np : nullptr, ivf->qoff.as<int32_t>(), ivf->cntcur.as<int>(), st));
-        MIRX_HIP(launch_pq_tables(qb, nb, ivf->dim, m, ivf->metric, ivf->codebooks.as<float>(), ivf->tables.as<double>(), st));
+        MIRX_HIP(launch_pq_tables(qb, nb, ivf->dim, m, res ? MIRX_METRIC_IP : ivf->metric, ivf->codebooks.as<float>(),
+                                  ivf->tables.as<double>(), st));
+        if (res)
+            MIRX_HIP(launch_pq_base(qb, nb, ivf->dim, m, ivf->probes.as<int32_t>(), np, ivf->centroids.as<float>(), nlist,
+                                    ivf->pq_base.as<double>(), res_l2 ? ivf->pq_qq.as<double>() : nullptr, st));
         MIRX_HIP(launch_pq_items(ivf->qoff.as<int32_t>(), nb, np, ivf->cntcur.as<int>(), nlist, ivf->itemoff.as<int32_t>(),
                                  ivf->stats_dev, st));
         PqScanArgs sa{};
@@ -363,6 +404,9 @@ int pq_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int np, int64_t 
         sa.itemoff = ivf->itemoff.as<int32_t>();
         sa.out = ivf->scores.as<double>();
         sa.ld = ld;
+        sa.base = res ? ivf->pq_base.as<double>() : nullptr;
+        sa.qq = res_l2 ? ivf->pq_qq.as<double>() : nullptr;
+        sa.n2 = res_l2 ? ivf->norms.as<double>() : nullptr;
         MIRX_HIP(launch_pq_scan(sa, ivf->metric, st));
         MIRX_HIP(launch_ivf_topk(ivf->scores.as<double>(), ld, ivf->probes.as<int32_t>(), ivf->qoff.as<int32_t>(), nb, np,
                                  ivf->offsets.as<int64_t>(), ivf->ids.as<int64_t>(), exclude ? exclude + q0 : nullptr, k, ivf->metric,
@@ -406,7 +450,17 @@ int mirx_ivf_create_pq(int dim, int metric, int nlist, int m, int nbits, int dev
     return create_ivf(dim, metric, nlist, MIRX_IVF_PQ, m, device, out);
 }
 
+int mirx_ivf_create_pq_ex(int dim, int metric, int nlist, int m, int nbits, int by_residual, int device, mirx_ivf **out) {
+    MIRX_CHECK(out, "ivf_create_pq_ex: out is null");
+    *out = nullptr;
+    MIRX_CHECK(by_residual == 0 || by_residual == 1, "ivf_create_pq_ex: by_residual must be 0 or 1");
+    if (int rc = mirx_ivf_create_pq(dim, metric, nlist, m, nbits, device, out)) return rc;
+    (*out)->pq_res = by_residual == 1;
+    return MIRX_OK;
+}
+
 int mirx_ivf_pq_m(const mirx_ivf *ivf) { return ivf && ivf->pq() ? ivf->pq_m : -1; }
+int mirx_ivf_pq_by_residual(const mirx_ivf *ivf) { return ivf && ivf->pq() ? (ivf->pq_res ? 1 : 0) : -1; }
 int mirx_ivf_pq_item_rows(void) { return PQ_ITEM_ROWS; }
 
 static int create_ivf(int dim, int metric, int nlist, int kind, int m, int device, mirx_ivf **out) {
@@ -531,12 +585,25 @@ int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids
     const void *placed = drows;
     if (ivf->pq()) {                                             // the list came from the original row; now the row becomes its codes
         if (ivf->pq_codes.ensure((size_t)n * ivf->pq_m) != hipSuccess) return fail(MIRX_ENOMEM, "ivf_add: no memory for the new codes");
+        const int64_t *dlists = nullptr;
+        if (ivf->pq_res) {                                       // the new rows' lists on the device: their centroids are subtracted
+            if (ivf->pq_lists.ensure((size_t)n * sizeof(int64_t)) != hipSuccess ||
+                (ivf->res_l2() && ivf->pq_n2.ensure((size_t)n * sizeof(double)) != hipSuccess))
+                return fail(MIRX_ENOMEM, "ivf_add: no memory for the new rows' lists and norms");
+            MIRX_HIP(hipMemcpy(ivf->pq_lists.p, lists.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+            dlists = ivf->pq_lists.as<int64_t>();
+        }
         if (int rc = pq_encode_rows(ivf->device, ivf->dim, ivf->pq_m, ivf->codebooks.as<float>(), drows, n,
-                                    ivf->pq_codes.as<uint8_t>(), ivf->pq_sub, ivf->pq_found, ivf->fval, nullptr))
+                                    ivf->pq_codes.as<uint8_t>(), ivf->pq_sub, ivf->pq_found, ivf->fval, nullptr, dlists,
+                                    ivf->centroids.as<float>(), nlist, &ivf->pq_resid))
             return rc;
+        if (ivf->res_l2())
+            MIRX_HIP(launch_pq_norms(ivf->pq_codes.as<uint8_t>(), n, ivf->dim, ivf->pq_m, dlists, ivf->centroids.as<float>(), nlist,
+                                     ivf->codebooks.as<float>(), ivf->pq_n2.as<double>(), nullptr));
         placed = ivf->pq_codes.p;
     }
-    return relayout(ivf, old_dst, placed, n, new_ids, new_dst, ivf->size + n, off, nullptr);
+    return relayout(ivf, old_dst, placed, n, new_ids, new_dst, ivf->size + n, off, nullptr,
+                    ivf->res_l2() ? ivf->pq_n2.as<double>() : nullptr);
 }
 
 int mirx_ivf_remove_ids(mirx_ivf *ivf, const int64_t *ids, int64_t n, int64_t *out_removed_or_null, void *stream) {
@@ -633,7 +700,13 @@ int mirx_ivf_reconstruct(const mirx_ivf *ivf, float *out_rows, int64_t *out_ids_
     MIRX_IVF_CODED_ONLY(ivf, "ivf_reconstruct");
     MIRX_IVF_ENTER(ivf, "ivf_reconstruct");
     if (ivf->size == 0) return MIRX_OK;
-    if (ivf->pq())
+    DevBuf dlists;                                           // residual PQ: every row's list, for its centroid
+    if (ivf->pq() && ivf->pq_res) {
+        if (dlists.ensure((size_t)ivf->size * sizeof(int64_t)) != hipSuccess) return fail(MIRX_ENOMEM, "ivf_reconstruct: no memory for the lists");
+        if (int rc = resident_ids_lists(ivf, nullptr, dlists.as<int64_t>())) return rc;
+        MIRX_HIP(launch_pq_decode_residual(ivf->rows.as<uint8_t>(), ivf->size, ivf->dim, ivf->pq_m, ivf->codebooks.as<float>(),
+                                           dlists.as<int64_t>(), ivf->centroids.as<float>(), ivf->nlist, out_rows, nullptr));
+    } else if (ivf->pq())
         MIRX_HIP(launch_pq_decode(ivf->rows.as<uint8_t>(), ivf->size, ivf->dim, ivf->pq_m, ivf->codebooks.as<float>(), out_rows, nullptr));
     else
         MIRX_HIP(launch_sq8_decode(ivf->rows.as<uint8_t>(), ivf->size, ivf->dimp, ivf->dim, ivf->vmin(), ivf->scale(), out_rows, nullptr));
@@ -669,18 +742,31 @@ int mirx_ivf_pq_train(mirx_ivf *ivf, const float *rows, int64_t n, int iters, vo
     MIRX_CHECK(n <= 0x7FFFFF00ll, "ivf_pq_train: more than 2^31 rows");
     MIRX_CHECK(iters >= 0, "ivf_pq_train: iters must not be negative");
     if (int rc = sq8_resident(ivf, "ivf_pq_train")) return rc;
+    if (ivf->pq_res && !ivf->cent)
+        return fail(MIRX_ESTATE, "ivf_pq_train: residual coding trains on rows minus their centroids, and the centroids are not "
+                                 "fixed yet (mirx_ivf_train / _set_centroids)");
     MIRX_IVF_ENTER(ivf, "ivf_pq_train");
     hipStream_t st = (hipStream_t)stream;
     const float *drows = nullptr;
     DevBuf trows;
     if (int rc = device_rows(ivf, rows, n, trows, &drows)) return rc;
     const int m = ivf->pq_m, dsub = ivf->dim / m;
+    if (ivf->pq_res) {                                       // the training rows' lists; lloyd() below reuses ivf->lists
+        std::vector<int64_t> lists;
+        if (int rc = assign_to_host(ivf, drows, n, lists, st)) return rc;
+        MIRX_HIP(ivf->pq_lists.ensure((size_t)n * sizeof(int64_t)));
+        MIRX_HIP(hipMemcpyAsync(ivf->pq_lists.p, ivf->lists.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+    }
     std::vector<int64_t> start(256);
     for (int c = 0; c < 256; ++c) start[(size_t)c] = (int64_t)c * n / 256;
     MIRX_HIP(ivf->pq_sub.ensure((size_t)n * dsub * sizeof(float)));
     ivf->cb_fixed = false;                                   // not fixed while they are trained
     for (int j = 0; j < m; ++j) {                            // mirx_ivf_train's loop on the columns of sub-space j, 256 lists, always L2
-        MIRX_HIP(launch_ivf_place(drows + (int64_t)j * dsub, n, ivf->dim, dsub, nullptr, nullptr, ivf->pq_sub.as<float>(), dsub, st));
+        if (ivf->pq_res)                                     // sub-space j of row - centroid, straight into the trainer's buffer
+            MIRX_HIP(launch_pq_residual(drows, n, ivf->dim, j * dsub, dsub, ivf->pq_lists.as<int64_t>(), ivf->centroids.as<float>(),
+                                        ivf->nlist, ivf->pq_sub.as<float>(), dsub, st));
+        else
+            MIRX_HIP(launch_ivf_place(drows + (int64_t)j * dsub, n, ivf->dim, dsub, nullptr, nullptr, ivf->pq_sub.as<float>(), dsub, st));
         if (int rc = lloyd(ivf, ivf->pq_sub.as<float>(), n, dsub, MIRX_METRIC_NEG_L2, 256, start, iters,
                            ivf->codebooks.as<float>() + (size_t)j * 256 * dsub, st))
             return rc;
@@ -732,6 +818,34 @@ int mirx_pq_tables(const float *q, int64_t nq, int dim, int m, int metric, const
     MIRX_CHECK(metric == MIRX_METRIC_IP || metric == MIRX_METRIC_NEG_L2, "pq_tables: unknown metric");
     MIRX_CHECK((q && out_tables_f64 && codebooks) || nq == 0, "pq_tables: null argument");
     MIRX_HIP(launch_pq_tables(q, nq, dim, m, metric, codebooks, out_tables_f64, (hipStream_t)stream));
+    return MIRX_OK;
+}
+
+int mirx_ivf_get_norms(const mirx_ivf *ivf, double *out_norms_f64) {
+    MIRX_CHECK(ivf && (out_norms_f64 || ivf->size == 0), "ivf_get_norms: null argument");
+    MIRX_CHECK(ivf->res_l2(), "ivf_get_norms: only a residual IVF_PQ handle under L2 keeps norms");
+    MIRX_IVF_ENTER(ivf, "ivf_get_norms");
+    if (ivf->size == 0) return MIRX_OK;
+    MIRX_HIP(hipMemcpy(out_norms_f64, ivf->norms.p, (size_t)ivf->size * sizeof(double), hipMemcpyDefault));
+    return MIRX_OK;
+}
+
+int mirx_pq_residuals(const float *rows, int64_t n, int dim, const int64_t *lists, const float *centroids, int nlist,
+                      float *out_rows, void *stream) {
+    MIRX_CHECK(n >= 0 && dim >= 1 && dim <= MIRX_IVF_MAX_DIM && nlist >= 1 && nlist <= MIRX_IVF_MAX_NLIST,
+               "pq_residuals: n, dim or nlist out of range");
+    MIRX_CHECK((rows && lists && centroids && out_rows) || n == 0, "pq_residuals: null argument");
+    MIRX_HIP(launch_pq_residual(rows, n, dim, 0, dim, lists, centroids, nlist, out_rows, dim, (hipStream_t)stream));
+    return MIRX_OK;
+}
+
+int mirx_pq_bases(const float *q, int64_t nq, int dim, int m, const int32_t *lists, int nprobe, const float *centroids, int nlist,
+                  double *out_base_f64, double *out_qq_f64_or_null, void *stream) {
+    MIRX_CHECK(nq >= 0 && pq_shape_ok(dim, m), "pq_bases: nq, dim or m out of range (m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0)");
+    MIRX_CHECK(nprobe >= 1 && nlist >= 1 && nlist <= MIRX_IVF_MAX_NLIST, "pq_bases: nprobe or nlist out of range");
+    MIRX_CHECK((q && lists && centroids && out_base_f64) || nq == 0, "pq_bases: null argument");
+    MIRX_CHECK(((uintptr_t)centroids & 15) == 0, "pq_bases: centroids must be 16-byte aligned");
+    MIRX_HIP(launch_pq_base(q, nq, dim, m, lists, nprobe, centroids, nlist, out_base_f64, out_qq_f64_or_null, (hipStream_t)stream));
     return MIRX_OK;
 }
 

@@ -583,12 +583,32 @@ struct PqScanArgs {
     const int32_t *itemoff;      // launch_pq_items'
     double *out;                 // [nq, ld] compact score rows: entry e of query q = sum over j ascending of T[q][j][code[j]], negated for L2
     int64_t ld;
+    // residual coding (mirx_ivf_create_pq_ex, by_residual = 1), all null otherwise: tables are then the IP tables of the residual
+    // codebooks for BOTH metrics, an entry's sum starts from base[q * nprobe + slot], and L2 ranks by -((qq[q] + n2[pos]) - 2 ip)
+    const double *base;          // [nq, nprobe] launch_pq_base's
+    const double *qq;            // [nq] launch_pq_base's (L2)
+    const double *n2;            // [size] list-major, launch_pq_norms' (L2)
 };
 hipError_t launch_pq_scan(const PqScanArgs &a, int metric, hipStream_t st);
 // codes[i * m + j] = (uint8)found[i]: the codeword search of sub-space j written into the code rows
 hipError_t launch_pq_pack(const int64_t *found, int64_t n, int m, int j, uint8_t *codes, hipStream_t st);
 // dst [n, dim] = each row's m codewords, concatenated
 hipError_t launch_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, const float *cb, float *dst, hipStream_t st);
+// residual coding.  residual: dst[i * dst_ld + e] = rows[i * dim + col0 + e] - cent[lists[i] * dim + col0 + e], e < cols, one fp32
+// rounding; a list outside 0 .. nlist-1 gives NaN and reads nothing
+hipError_t launch_pq_residual(const float *rows, int64_t n, int dim, int col0, int cols, const int64_t *lists, const float *cent,
+                              int nlist, float *dst, int dst_ld, hipStream_t st);
+// base[q][s] = sum over j ascending of P_j, P_j one sequential fp64 accumulator of (double)q_e * (double)c_e over sub-space j's
+// columns of centroid lists[q][s] (a list outside 0 .. nlist-1: 0.0); qq_or_null[q] = the same two-level sum of q_e * q_e
+hipError_t launch_pq_base(const float *q, int64_t nq, int dim, int m, const int32_t *lists, int nprobe, const float *cent, int nlist,
+                          double *base, double *qq_or_null, hipStream_t st);
+// n2[i] = the two-level sum of xh_e * xh_e (product rounded, then added), xh_e = (double)cent[lists[i]][e] + (double)codeword_e
+hipError_t launch_pq_norms(const uint8_t *codes, int64_t n, int dim, int m, const int64_t *lists, const float *cent, int nlist,
+                           const float *cb, double *n2, hipStream_t st);
+// dst [n, dim] = (float)(centroid of the row's list + its codewords), one fp32 rounding per column; lists [n] as
+// launch_pq_residual's (outside 0 .. nlist-1: NaN)
+hipError_t launch_pq_decode_residual(const uint8_t *codes, int64_t n, int dim, int m, const float *cb, const int64_t *lists,
+                                     const float *cent, int nlist, float *dst, hipStream_t st);
 
 // ---- k_fuse.hip: hybrid search's rank / score fusion (mirx_fuse_ranked) ------------------------------------------------------
 struct FuseArgs {

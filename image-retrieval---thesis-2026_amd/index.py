@@ -961,6 +961,7 @@ class IvfPqIndex(IvfFlatIndex):
     codebooks (MirxError from train / set_centroids / train_codebooks / set_codebooks): remove the rows first."""
 
     KIND = _lib.IVF_PQ
+    by_residual = False                        # IvfResidualPqIndex turns it on
 
     def __init__(self, dim, metric="COSINE", nlist=1024, m=None, device=None):
         if m is None:
@@ -1029,8 +1030,45 @@ class IvfPqIndex(IvfFlatIndex):
         return rows, ids
 
     def tables(self, q):
-        """-> float64 [nq, m, 256] on the index device: the ADC tables search() builds for q under the index metric"""
-        return pq_tables(self._rows(q, "tables").to(self.device), self.codebooks, self.metric)
+        """-> float64 [nq, m, 256] on the index device: the ADC tables search() builds for q under the index metric (with
+        residual coding: the inner-product tables of the residual codebooks, whatever the metric)"""
+        return pq_tables(self._rows(q, "tables").to(self.device), self.codebooks, "IP" if self.by_residual else self.metric)
+
+
+def residual_flag(value, key="by_residual"):
+    """by_residual as a bool, ValueError naming the key for anything else"""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{key} must be True or False, got {value!r}")
+    return bool(value)
+
+
+class IvfResidualPqIndex(IvfPqIndex):
+    """IVF_PQ with residual coding (mirx_ivf_create_pq_ex, include/mirx.h; restated in tests/_rpq_ref.py): a row is encoded as
+    row - centroid of its list, so the codewords describe the spread inside a list.  Per query there is still ONE table -- the
+    inner-product table of the residual codebooks, for both metrics; an entry's sum starts from the base of its (query, probed
+    list), <q, centroid>, and L2 ranks by -((|q|^2 + |centroid + codewords|^2) - 2 ip) with the row's squared norm N2 kept from
+    add() on (8 bytes a row).  train() fixes the centroids first and trains the codebooks on the residuals; train_codebooks needs
+    fixed centroids.  reconstruct() returns centroid + codewords.  by_residual=False gives IvfPqIndex's raw form through the same
+    create call.  IvfPqIndex keeps its own signature and behaviour."""
+
+    def __init__(self, dim, metric="COSINE", nlist=1024, m=None, device=None, by_residual=True):
+        self.by_residual = residual_flag(by_residual)
+        super().__init__(dim, metric, nlist, m, device)
+
+    def _create(self, h):
+        _lib.check(self._lib.mirx_ivf_create_pq_ex(self.dim, self.metric, self.nlist, self.m, 8, int(self.by_residual),
+                                                   self.device.index, ctypes.byref(h)), "mirx_ivf_create_pq_ex")
+
+    def norms(self):
+        """-> float64 [n] on the index device, in list-major order: N2 of the resident rows (L2 with residual coding only)"""
+        out = torch.empty((len(self),), dtype=torch.float64, device=self.device)
+        self._call("mirx_ivf_get_norms", _ptr_or_null(out))
+        return out
+
+    def bases(self, q, lists):
+        """-> (B float64 [nq, nprobe], QQ float64 [nq]) for queries q and list numbers lists [nq, nprobe] under the index's
+        centroids: what search() starts every entry's sum from, and L2's |q|^2"""
+        return pq_bases(self._rows(q, "bases").to(self.device), lists, self.centroids, self.m)
 
 
 def _pq_args(first, codebooks, who, dtype):
@@ -1069,6 +1107,48 @@ def pq_decode(codes, codebooks):
         _lib.check(_lib.load().mirx_pq_decode(_ptr_or_null(codes), codes.shape[0], dim, m, _ptr(cb), _ptr_or_null(out),
                                               _stream_ptr(codes.device)), "mirx_pq_decode")
     return out
+
+
+def pq_residuals(rows, lists, centroids):
+    """mirx_pq_residuals: CUDA fp32 rows [n, dim], int64 lists [n], centroids [nlist, dim] -> fp32 [n, dim], row - centroid of its
+    list with one rounding per column (a list number outside 0 .. nlist-1: a NaN row)"""
+    rows = torch.as_tensor(rows).to(torch.float32).contiguous()
+    cent = torch.as_tensor(centroids).to(torch.float32).contiguous()
+    if not rows.is_cuda or rows.dim() != 2 or cent.dim() != 2 or cent.shape[1] != rows.shape[1] or cent.shape[0] < 1:
+        raise ValueError("pq_residuals expects CUDA rows [n, dim] and centroids [nlist, dim]")
+    lists = torch.as_tensor(lists).to(torch.int64).reshape(-1).contiguous().to(rows.device)
+    if lists.numel() != rows.shape[0]:
+        raise ValueError("pq_residuals: lists and rows disagree in length")
+    cent = cent.to(rows.device)
+    out = torch.empty_like(rows)
+    with torch.cuda.device(rows.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_pq_residuals(_ptr_or_null(rows), rows.shape[0], rows.shape[1], _ptr_or_null(lists), _ptr(cent),
+                                                 cent.shape[0], _ptr_or_null(out), _stream_ptr(rows.device)), "mirx_pq_residuals")
+    return out
+
+
+def pq_bases(q, lists, centroids, m):
+    """mirx_pq_bases: CUDA fp32 queries [nq, dim], int32 list numbers [nq, nprobe], centroids [nlist, dim] -> (B float64
+    [nq, nprobe], QQ float64 [nq]): B[q][s] = <q, centroid lists[q][s]> and QQ[q] = <q, q> as two-level sequential float64 sums
+    (per sub-space of dim / m columns, then over the sub-spaces; include/mirx.h)"""
+    q = torch.as_tensor(q).to(torch.float32).contiguous()
+    cent = torch.as_tensor(centroids).to(torch.float32).contiguous()
+    if not q.is_cuda or q.dim() != 2 or cent.dim() != 2 or cent.shape[1] != q.shape[1] or cent.shape[0] < 1:
+        raise ValueError("pq_bases expects CUDA queries [nq, dim] and centroids [nlist, dim]")
+    m = pq_bounds(q.shape[1], m)
+    lists = torch.as_tensor(lists).to(torch.int32).contiguous().to(q.device)
+    if lists.dim() != 2 or lists.shape[0] != q.shape[0] or lists.shape[1] < 1:
+        raise ValueError("pq_bases: lists must be [nq, nprobe] with nprobe >= 1")
+    cent = cent.to(q.device)
+    base = torch.empty(tuple(lists.shape), dtype=torch.float64, device=q.device)
+    qq = torch.empty((q.shape[0],), dtype=torch.float64, device=q.device)
+    with torch.cuda.device(q.device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.load().mirx_pq_bases(_ptr_or_null(q), q.shape[0], q.shape[1], m, _ptr_or_null(lists), lists.shape[1],
+                                             _ptr(cent), cent.shape[0], _ptr_or_null(base), _ptr_or_null(qq), _stream_ptr(q.device)),
+                   "mirx_pq_bases")
+    return base, qq
 
 
 def pq_tables(q, codebooks, metric="COSINE"):

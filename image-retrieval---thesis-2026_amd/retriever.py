@@ -27,7 +27,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import FlatIndex, IvfFlatIndex, IvfPqIndex, IvfSq8Index, group_bounds, pq_bounds, range_bounds, tier1_max_k
+from .index import (FlatIndex, IvfFlatIndex, IvfPqIndex, IvfResidualPqIndex, IvfSq8Index, group_bounds, pq_bounds, range_bounds,
+                    residual_flag, tier1_max_k)
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -151,6 +152,7 @@ class Collection:
         self._approx_nlist = None                           # nlist while the approximate index is on
         self._approx_type = None                            # "IVF_FLAT", "IVF_SQ8" or "IVF_PQ" while it is on
         self._approx_m = None                               # IVF_PQ: its number of sub-quantisers
+        self._approx_residual = False                       # IVF_PQ: params["by_residual"], residual coding (IvfResidualPqIndex)
         self._ivf = None                                    # the IvfFlatIndex / IvfSq8Index / IvfPqIndex over the live rows; None = to be (re)built
         self._ivf_centroids = None                          # its centroids, trained once and kept across rebuilds
         self._ivf_range = None                              # IVF_SQ8: its (vmin, scale), trained once and kept likewise
@@ -288,10 +290,12 @@ class Collection:
         the first approximate search and trained once; after insert / delete / compact the lists are rebuilt lazily with the
         kept centroids (IVF_SQ8: and the kept range, so rows inserted later clamp to the trained range; IVF_PQ: and the kept
         codebooks).  IVF_PQ needs index_params["params"]["m"], as Milvus does (ValueError without it or with an m that
-        mirx.index.pq_bounds refuses), and stays exact below max(nlist, 256) rows.  It is process state: a
+        mirx.index.pq_bounds refuses), and stays exact below max(nlist, 256) rows; index_params["params"]["by_residual"] (default
+        False; anything but a bool: ValueError) = True encodes every row minus the centroid of its list, Milvus' own IVF_PQ form
+        (IvfResidualPqIndex).  It is process state: a
         stored collection opened again is exact until this call is made again.  See search() for the calls it serves."""
         params = index_params or {}
-        nlist, kind, m = None, None, None
+        nlist, kind, m, residual = None, None, None, False
         if approximate:
             kind = params.get("index_type")
             if kind not in ("IVF_FLAT", "IVF_SQ8", "IVF_PQ"):
@@ -302,6 +306,7 @@ class Collection:
                     raise ValueError("index_type 'IVF_PQ' needs params['m'], the number of sub-quantisers; "
                                      "'IVF_FLAT' and 'IVF_SQ8' take nlist alone")
                 m = pq_bounds(self.dim, inner["m"])
+                residual = residual_flag(inner.get("by_residual", False), "params['by_residual']")
             nlist = inner.get("nlist", 1024)
             if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= 65536:
                 raise ValueError(f"nlist must be an integer in [1, 65536], got {nlist!r}")
@@ -312,8 +317,8 @@ class Collection:
         self.metric_type = metric
         if self._stored is not None:
             self._stored.set_metric(metric)
-        if (nlist, kind, m) != (self._approx_nlist, self._approx_type, self._approx_m):
-            self._approx_nlist, self._approx_type, self._approx_m = nlist, kind, m
+        if (nlist, kind, m, residual) != (self._approx_nlist, self._approx_type, self._approx_m, self._approx_residual):
+            self._approx_nlist, self._approx_type, self._approx_m, self._approx_residual = nlist, kind, m, residual
             self._ivf, self._ivf_centroids, self._ivf_range, self._ivf_codebooks = None, None, None, None
         return True
 
@@ -330,7 +335,9 @@ class Collection:
             index = self._ensure()
             rows, ids = index.rows()
             sq8 = self._approx_type == "IVF_SQ8"
-            if pq:
+            if pq and self._approx_residual:
+                ivf = IvfResidualPqIndex(self.dim, self.metric_type, self._approx_nlist, self._approx_m, index.device)
+            elif pq:
                 ivf = IvfPqIndex(self.dim, self.metric_type, self._approx_nlist, self._approx_m, index.device)
             else:
                 ivf = (IvfSq8Index if sq8 else IvfFlatIndex)(self.dim, self.metric_type, self._approx_nlist, index.device)

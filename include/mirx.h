@@ -1668,7 +1668,7 @@ int mirx_sq8_decode(const uint8_t *codes, int64_t n, int dim, const float *vmin,
  * in bits.  Every step is defined to the bit.
  *
  * Parameters: m sub-quantisers of 256 codewords (nbits = 8), dsub = dim / m; m % 4 == 0, 4 <= m <= 64, dim % (4 m) == 0.  Codes
- *   encode the raw row (not a residual, not per list).
+ *   encode the raw row (not a residual, not per list); mirx_ivf_create_pq_ex below adds the residual form.
  * Codebooks cb[m][256][dsub] fp32.
  *     train    sub-space j's codebook is mirx_ivf_train's loop on columns [j dsub, (j+1) dsub) with 256 lists and ALWAYS the L2
  *              metric (no normalisation): start rows[floor(c n / 256)], one fp64 accumulator per codeword and column in ascending
@@ -1711,6 +1711,44 @@ int mirx_pq_encode(const float *rows, int64_t n, int dim, int m, const float *co
 int mirx_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, const float *codebooks, float *out_rows, void *stream);
 int mirx_pq_tables(const float *q, int64_t nq, int dim, int m, int metric, const float *codebooks, double *out_tables_f64,
                    void *stream);
+
+/*
+ * IVF_PQ with residual coding (opt-in: mirx_ivf_create_pq_ex(by_residual = 1); a handle from mirx_ivf_create_pq, or with
+ * by_residual = 0, is the raw form above in every bit).  The codes encode the row minus the centroid of its list, so the 256
+ * codewords of a sub-space describe the spread inside a list instead of telling the lists apart.  c_l = the centroid of list l.
+ *     residual   r_e = x_e - c_{l,e} in fp32, one rounding; l = the row's list from its ORIGINAL values, as mirx_ivf_add assigns it.
+ *     codebooks  `train` above on the residual sub-vectors of the training rows (always L2); codes = `encode` above of the residuals.
+ *     base       of a (query, probed list): B[q][l] = sum over j ascending of P_j, P_j ONE sequential fp64 accumulator from 0.0 over
+ *                the columns of sub-space j ascending, each step + (double)q_e * (double)c_{l,e} (the product is exact).
+ *     tables     the IP tables T[j][c] above of the residual codebooks, one table per query, for BOTH metrics.
+ *     ip         of an entry: ip = B[q][l]; for j ascending: ip = ip + T[j][code[j]].
+ *     IP         ranking score = ip.
+ *     L2         QQ[q] = the two-level sum (as B) of (double)q_e * (double)q_e.  N2[row] = the two-level sum of xh_e * xh_e with
+ *                xh_e = (double)c_{l,e} + (double)cb[j][code_j][e], each product rounded to double and then added; computed once,
+ *                when the row is added, and kept beside its id (8 bytes a row, L2 handles only).
+ *                ranking score = -((QQ + N2) - 2.0 * ip), each operation rounded in that order (2.0 * ip is exact).  The expanded
+ *                distance may come out slightly negative; the reported value clamps it as mirx_ivf_search's does.
+ *   Selection, the excluded id, the padding and the reported values are mirx_ivf_search's.  mirx_ivf_reconstruct returns
+ *   (float)(c_{l,e} + codeword_e), one fp32 rounding per column; mirx_ivf_get_codes is unchanged.
+ * mirx_ivf_create_pq_ex   mirx_ivf_create_pq with the flag; by_residual other than 0 / 1: MIRX_EINVAL.  mirx_ivf_pq_by_residual:
+ *   the flag, -1 for another kind.
+ * State: on a residual handle mirx_ivf_pq_train needs fixed centroids (MIRX_ESTATE otherwise): it assigns its rows, forms their
+ *   residuals and trains on them.  The other state rules are the raw form's.
+ * mirx_ivf_get_norms   N2 of the resident rows in list-major order (the order of mirx_ivf_get_codes), to a device array; MIRX_EINVAL
+ *   unless the handle is residual and L2.
+ * mirx_pq_residuals / mirx_pq_bases   the kernels over device arrays, without an index, enqueued on `stream`: out [n, dim] fp32
+ *   residuals of rows under lists [n] (int64) and centroids [nlist, dim]; out_base_f64 [nq, nprobe] and out_qq_f64_or_null [nq] for
+ *   queries, list numbers lists [nq, nprobe] (int32) and centroids.  A list number outside 0 .. nlist-1 reads nothing: its
+ *   residual row is NaN, its base 0.0.
+ * mirx_ivf_search's workspace budget counts 8 nprobe + 8 more bytes per query on a residual handle.
+ */
+int mirx_ivf_create_pq_ex(int dim, int metric, int nlist, int m, int nbits, int by_residual, int device, mirx_ivf **out);
+int mirx_ivf_pq_by_residual(const mirx_ivf *ivf);
+int mirx_ivf_get_norms(const mirx_ivf *ivf, double *out_norms_f64);
+int mirx_pq_residuals(const float *rows, int64_t n, int dim, const int64_t *lists, const float *centroids, int nlist,
+                      float *out_rows, void *stream);
+int mirx_pq_bases(const float *q, int64_t nq, int dim, int m, const int32_t *lists, int nprobe, const float *centroids, int nlist,
+                  double *out_base_f64, double *out_qq_f64_or_null, void *stream);
 
 #ifdef __cplusplus
 }

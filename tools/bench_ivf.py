@@ -12,7 +12,10 @@ types the device memory held after the build and the peak during add (torch.cuda
 
 --index-type IVF_PQ --m M[,M2] keeps the IVF_SQ8 arm and adds one IvfPqIndex per m on the same centroids, its
 codebooks trained on at most 65 536 strided rows: further alternating arms, with the codebook-training and add times, the memory
-figures, and recall against the exact ids and against IVF_FLAT's at equal nprobe."""
+figures, and recall against the exact ids and against IVF_FLAT's at equal nprobe.
+
+--by-residual adds, beside every raw PQ arm, an IvfResidualPqIndex of the same m on the same centroids in the same
+process (its codebooks trained on the residuals of the same strided rows): arm "rpq<m>" next to "pq<m>", the same figures."""
 import argparse
 import json
 import os
@@ -24,7 +27,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, IvfFlatIndex, IvfPqIndex, IvfSq8Index  # noqa: E402
+from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, IvfFlatIndex, IvfPqIndex, IvfResidualPqIndex, IvfSq8Index  # noqa: E402
 
 
 def clustered(n, d, centres, spread, dev, seed):
@@ -99,6 +102,7 @@ def main():
     ap.add_argument("--index-type", default="IVF_FLAT", choices=["IVF_FLAT", "IVF_SQ8", "IVF_PQ"])
     ap.add_argument("--m", default="", help="IVF_PQ: the sub-quantiser counts, one arm each (e.g. 64,32)")
     ap.add_argument("--codebook-iters", type=int, default=10)
+    ap.add_argument("--by-residual", action="store_true", help="IVF_PQ: a residual-coded arm rpq<m> beside every raw arm pq<m>")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -131,16 +135,19 @@ def main():
         t_add8, peak_add8 = peak_during(lambda: sq8.add(rows))
         out.update({"sq8_train_range_ms": t_range, "sq8_add_ms": t_add8, "sq8_held_bytes": held0 - free_bytes(True),
                     "sq8_add_peak_bytes": peak_add8, "rows_bytes_fp32": a.n * a.d * 4})
-    for m in [int(v) for v in a.m.split(",") if v] if a.index_type == "IVF_PQ" else []:
+    arms = [(f"pq{int(v)}", int(v), False) for v in a.m.split(",") if v] if a.index_type == "IVF_PQ" else []
+    if a.by_residual:
+        arms = [arm for name, m, _ in arms for arm in ((name, m, False), (f"r{name}", m, True))]
+    for name, m, residual in arms:
         held0 = free_bytes(True)
-        pq = IvfPqIndex(a.d, "COSINE", a.nlist, m, 0)
+        pq = IvfResidualPqIndex(a.d, "COSINE", a.nlist, m, 0) if residual else IvfPqIndex(a.d, "COSINE", a.nlist, m, 0)
         pq.set_centroids(ivf.centroids)
         t_cb, _ = timed(lambda: pq.train_codebooks(rows, a.codebook_iters))
         t_addp, peak_addp = peak_during(lambda: pq.add(rows))
-        out[f"pq{m}"] = {"m": m, "train_codebooks_ms": t_cb, "codebook_rows": min(a.n, 65536), "codebook_iters": a.codebook_iters,
-                         "add_ms": t_addp, "held_bytes": held0 - free_bytes(True), "add_peak_bytes": peak_addp,
-                         "code_bytes": a.n * m}
-        pqs[f"pq{m}"] = pq
+        out[name] = {"m": m, "by_residual": residual, "train_codebooks_ms": t_cb, "codebook_rows": min(a.n, 65536),
+                     "codebook_iters": a.codebook_iters, "add_ms": t_addp, "held_bytes": held0 - free_bytes(True),
+                     "add_peak_bytes": peak_addp, "code_bytes": a.n * m}
+        pqs[name] = pq
     print({k: v for k, v in out.items() if k != "cases"}, flush=True)
     g = torch.Generator(device=dev).manual_seed(4321)
     for nq in [int(v) for v in a.queries.split(",")]:
