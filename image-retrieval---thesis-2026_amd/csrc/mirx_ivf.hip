@@ -23,21 +23,29 @@ struct mirx_ivf {
     DevBuf centroids;                     // [nlist, dim] fp32
     int64_t size = 0;
     DevBuf rows, ids, offsets;            // [size, dimp] list-major (fp32, or uint8 codes for SQ8), [size], [nlist + 1] int64
-    DevBuf range;                         // SQ8: vmin [dimp] then scale [dimp] fp32, zero in the padding
-    bool range_fixed = false;
-    int pq_m = 0;                         // PQ: sub-quantisers; a code row is pq_m bytes
-    DevBuf codebooks;                     // PQ: [pq_m][256][dim / pq_m] fp32
-    bool cb_fixed = false;
-    bool pq_res = false;                  // PQ: residual coding (mirx_ivf_create_pq_ex): codes of row - centroid of its list
-    DevBuf norms;                         // residual PQ under L2: N2 [size] fp64, list-major beside ids
     std::vector<int64_t> off_h, ids_h, seq_h;   // host mirrors of offsets / ids, and each row's insertion number (list-major)
     int64_t next_seq = 0, next_auto = 0;
     int64_t score_bytes = 0;              // MIRX_IVF_OPT_SCORE_BYTES; 0 = SCORE_WS_BYTES
-    // scratch
-    DevBuf stage, lists, fval, a_order, a_loff, upd, pos, newids, q32p, pids, probes, qoff, cntcur, pairoff, itemoff, pair_q,
-        pair_off, scores, tables, pq_sub, pq_found, pq_codes, pq_lists, pq_resid, pq_n2, pq_base, pq_qq;
     unsigned long long *stats_dev = nullptr;   // [3] rows scored, pairs, work items
     int64_t last_nq = 0, last_batches = 0;
+    // scratch of every kind: train / add / remove, then the search loop's common workspace
+    DevBuf stage, lists, fval, a_order, a_loff, upd, pos, newids, pids, probes, qoff, cntcur, itemoff, scores;
+    // scratch of the row scan (FLAT, SQ8): a PQ handle never touches these
+    DevBuf q32p, pairoff, pair_q, pair_off;
+
+    // ---- SQ8 only ----
+    DevBuf range;                         // vmin [dimp] then scale [dimp] fp32, zero in the padding
+    bool range_fixed = false;
+
+    // ---- PQ only: a FLAT or SQ8 handle never touches anything below ----
+    int pq_m = 0;                         // sub-quantisers; a code row is pq_m bytes
+    DevBuf codebooks;                     // [pq_m][256][dim / pq_m] fp32
+    bool cb_fixed = false;
+    bool pq_res = false;                  // residual coding (mirx_ivf_create_pq_ex): codes of row - centroid of its list
+    DevBuf norms;                         // residual PQ under L2: N2 [size] fp64, list-major beside ids
+    // PQ's scratch: the search's tables, bases and |q|^2; the encoder's sub-vectors, found codewords and residual chunk; add's
+    // new codes, lists and norms
+    DevBuf tables, pq_base, pq_qq, pq_sub, pq_found, pq_resid, pq_codes, pq_lists, pq_n2;
 
     bool sq8() const { return kind == MIRX_IVF_SQ8; }
     bool pq() const { return kind == MIRX_IVF_PQ; }
@@ -62,8 +70,22 @@ constexpr int64_t MAX_BATCH_PAIRS = (int64_t)1 << 26;   // (query, probe) pairs 
 #define MIRX_IVF_PQ_ONLY(ivf, who) MIRX_CHECK((ivf)->pq(), std::string(who) + ": the ivf is not MIRX_IVF_PQ")
 #define MIRX_IVF_CODED_ONLY(ivf, who) MIRX_CHECK((ivf)->sq8() || (ivf)->pq(), std::string(who) + ": the ivf is not MIRX_IVF_SQ8 or MIRX_IVF_PQ")
 
+// the trained parts a call needs fixed (trained_parts_fixed): the centroids of every kind, SQ8's range, PQ's codebooks
+enum : unsigned { CENTROIDS = 1, RANGE = 2, CODEBOOKS = 4, ALL_PARTS = CENTROIDS | RANGE | CODEBOOKS };
+
+// MIRX_ESTATE naming the first of `need` that this handle's kind has and that is not fixed yet
+int trained_parts_fixed(const mirx_ivf *ivf, const char *who, unsigned need) {
+    if ((need & CENTROIDS) && !ivf->cent)
+        return fail(MIRX_ESTATE, std::string(who) + ": the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    if ((need & RANGE) && ivf->sq8() && !ivf->range_fixed)
+        return fail(MIRX_ESTATE, std::string(who) + ": the range is not fixed yet (mirx_ivf_sq8_train / _sq8_set_range)");
+    if ((need & CODEBOOKS) && ivf->pq() && !ivf->cb_fixed)
+        return fail(MIRX_ESTATE, std::string(who) + ": the codebooks are not fixed yet (mirx_ivf_pq_train / _pq_set_codebooks)");
+    return MIRX_OK;
+}
+
 // SQ8 and PQ keep no originals: what would re-assign or re-encode the resident rows is refused
-int sq8_resident(const mirx_ivf *ivf, const char *who) {
+int coded_rows_keep_trained_parts(const mirx_ivf *ivf, const char *who) {
     if (ivf->sq8() && ivf->size > 0)
         return fail(MIRX_ESTATE, std::string(who) + ": an IVF_SQ8 index that holds rows keeps its centroids and range (the original rows are gone)");
     if (ivf->pq() && ivf->size > 0)
@@ -192,18 +214,34 @@ int build_codeword_indexes(int dim, int m, int device, const float *cb, std::vec
 
 constexpr int64_t PQ_ENCODE_CHUNK = (int64_t)1 << 16;   // rows per pass of the encoder: bounds its scratch and the m indexes' workspaces
 
-// the encoder's passes over rows [n, dim] with the m codeword indexes given; enqueued on st
+// residual coding for the encoder: row i is coded as rows[i] - cent[lists[i]] (lists: device, [n]); buf holds one chunk of residuals
+struct PqResidual {
+    const int64_t *lists;
+    const float *cent;
+    int nlist;
+    DevBuf *buf;
+};
+
+// the encoder's passes over rows [n, dim] with the m codeword indexes given; enqueued on st.  With res, chunk by chunk
+// rows - cent[lists] goes into res->buf (one chunk of whole rows, so the scratch stays bounded) and the chunk's residuals are encoded.
 int pq_encode_chunks(const std::vector<mirx_index *> &cbidx, int dim, int m, const float *drows, int64_t n, uint8_t *codes,
-                     DevBuf &sub, DevBuf &found, DevBuf &fval, hipStream_t st) {
+                     DevBuf &sub, DevBuf &found, DevBuf &fval, const PqResidual *res, hipStream_t st) {
     const int dsub = dim / m;
     const int64_t chunk = std::min<int64_t>(n, PQ_ENCODE_CHUNK);
+    if (res && res->buf->ensure((size_t)chunk * dim * sizeof(float)) != hipSuccess)
+        return fail(MIRX_ENOMEM, "pq_encode: no memory for the residuals");
     if (sub.ensure((size_t)chunk * dsub * sizeof(float)) != hipSuccess || found.ensure((size_t)chunk * sizeof(int64_t)) != hipSuccess ||
         fval.ensure((size_t)chunk * sizeof(float)) != hipSuccess)
         return fail(MIRX_ENOMEM, "pq_encode: no memory for the encoder's scratch");
     for (int64_t c0 = 0; c0 < n; c0 += chunk) {
         const int64_t nc = std::min(chunk, n - c0);
+        const float *src = drows + c0 * dim;
+        if (res) {
+            MIRX_HIP(launch_pq_residual(src, nc, dim, 0, dim, res->lists + c0, res->cent, res->nlist, res->buf->as<float>(), dim, st));
+            src = res->buf->as<float>();
+        }
         for (int j = 0; j < m; ++j) {
-            MIRX_HIP(launch_ivf_place(drows + c0 * dim + (int64_t)j * dsub, nc, dim, dsub, nullptr, nullptr, sub.as<float>(), dsub, st));
+            MIRX_HIP(launch_ivf_place(src + (int64_t)j * dsub, nc, dim, dsub, nullptr, nullptr, sub.as<float>(), dsub, st));
             if (int rc = mirx_index_search(cbidx[(size_t)j], sub.as<float>(), nc, 1, nullptr, fval.as<float>(), found.as<int64_t>(), st))
                 return rc;
             MIRX_HIP(launch_pq_pack(found.as<int64_t>(), nc, m, j, codes + c0 * m, st));
@@ -215,33 +253,16 @@ int pq_encode_chunks(const std::vector<mirx_index *> &cbidx, int dim, int m, con
 // codes [n, m] (device) of rows [n, dim] (device) under cb (device [m][256][dim / m]): sub-vector j of every row searched in a flat
 // index over sub-space j's codewords.  The m indexes live for the call only -- their search workspaces (tens of MB each) would
 // outweigh the codes if the handle kept them.  Waits for its work, on failure too: the indexes are freed behind it.
-// With dlists (device, [n]) the rows are coded by residual: chunk by chunk rows - cent[dlists] goes into `resid` (one chunk of
-// whole rows, so the scratch stays bounded) and the chunk's residuals are encoded.
-int pq_encode_residual_chunks(const std::vector<mirx_index *> &cbidx, int dim, int m, const float *drows, int64_t n, uint8_t *codes,
-                              DevBuf &sub, DevBuf &found, DevBuf &fval, const int64_t *dlists, const float *cent, int nlist,
-                              DevBuf &resid, hipStream_t st) {
-    const int64_t chunk = std::min<int64_t>(n, PQ_ENCODE_CHUNK);
-    if (resid.ensure((size_t)chunk * dim * sizeof(float)) != hipSuccess)
-        return fail(MIRX_ENOMEM, "pq_encode: no memory for the residuals");
-    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
-        const int64_t nc = std::min(chunk, n - c0);
-        MIRX_HIP(launch_pq_residual(drows + c0 * dim, nc, dim, 0, dim, dlists + c0, cent, nlist, resid.as<float>(), dim, st));
-        if (int rc = pq_encode_chunks(cbidx, dim, m, resid.as<float>(), nc, codes + c0 * m, sub, found, fval, st)) return rc;
-    }
-    return MIRX_OK;
-}
-
+// res (or null): the rows are coded by residual.
 int pq_encode_rows(int device, int dim, int m, const float *cb, const float *drows, int64_t n, uint8_t *codes, DevBuf &sub,
-                   DevBuf &found, DevBuf &fval, hipStream_t st, const int64_t *dlists = nullptr, const float *cent = nullptr,
-                   int nlist = 0, DevBuf *resid = nullptr) {
+                   DevBuf &found, DevBuf &fval, const PqResidual *res, hipStream_t st) {
     if (n == 0) return MIRX_OK;
     std::vector<mirx_index *> cbidx;
     if (int rc = build_codeword_indexes(dim, m, device, cb, cbidx)) return rc;
-    const int rc = dlists ? pq_encode_residual_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, dlists, cent, nlist, *resid, st)
-                          : pq_encode_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, st);
+    const int rc = pq_encode_chunks(cbidx, dim, m, drows, n, codes, sub, found, fval, res, st);
     const hipError_t e = hipStreamSynchronize(st);
     free_codeword_indexes(cbidx);
-    if (resid) resid->release();                             // a chunk of whole fp32 rows (256 MiB at dim 1024): not worth holding
+    if (res) res->buf->release();                            // a chunk of whole fp32 rows (256 MiB at dim 1024): not worth holding
     if (rc) return rc;
     MIRX_HIP(e);
     return MIRX_OK;
@@ -320,7 +341,7 @@ int relayout(mirx_ivf *ivf, const std::vector<int64_t> &old_dst, const void *new
     return MIRX_OK;
 }
 
-// the resident rows to the lists of the current centroids, insertion order kept inside each list (fp32 rows only: sq8_resident)
+// the resident rows to the lists of the current centroids, insertion order kept inside each list (fp32 rows only: coded_rows_keep_trained_parts)
 int reassign_resident(mirx_ivf *ivf, hipStream_t st) {
     const int64_t n = ivf->size;
     if (n == 0) return MIRX_OK;
@@ -351,69 +372,98 @@ int fix_centroids(mirx_ivf *ivf, hipStream_t st) {
     return reassign_resident(ivf, st);
 }
 
-// mirx_ivf_search on a PQ handle, behind its argument checks: np = the clamped nprobe, ld = the longest compact row.  Per internal
-// batch: the probes, every query's tables, the items of the scan, the scan, the top-k.  A query costs its compact row of doubles
-// and its m x 2 KiB table out of the one workspace budget.
-int pq_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int np, int64_t ld, int64_t budget, const int64_t *exclude,
-              float *out_values, double *out_f64, int64_t *out_ids, int32_t *out_probes, hipStream_t st) {
-    const int nlist = ivf->nlist, m = ivf->pq_m;
-    const int64_t table_bytes = (int64_t)m * 256 * sizeof(double), items_per_row = (ld + PQ_ITEM_ROWS - 1) / PQ_ITEM_ROWS;
-    const bool res = ivf->pq_res, res_l2 = ivf->res_l2();
-    const int64_t base_bytes = res ? (int64_t)8 * np + 8 : 0;                      // residual: a base per probed list, and QQ
-    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8 + table_bytes + base_bytes)));
-    per = std::min(per, std::max<int64_t>(1, MAX_BATCH_PAIRS / np));
-    per = std::min(per, std::max<int64_t>(1, 0x7FFFFFFFll / items_per_row));       // work items fit an int
+// ---- mirx_ivf_search's per-kind step: one internal batch's scores into ivf->scores, compact rows of ld doubles ------------------
+// nb queries qb with their np nearest lists in ivf->pids (nearest first); out_probes (or null) receives the batch's probes
+struct SearchBatch {
+    const float *qb;
+    int nb, np;
+    int64_t ld;
+    int32_t *out_probes;
+};
+
+// what one PQ query costs beside its compact row: its m x 2 KiB table, and with residual coding a base per probed list and QQ
+int64_t pq_query_bytes(const mirx_ivf *ivf, int np) {
+    return (int64_t)ivf->pq_m * 256 * sizeof(double) + (ivf->pq_res ? (int64_t)8 * np + 8 : 0);
+}
+
+hipError_t scan_workspace(mirx_ivf *ivf, int64_t per, int np) {
+    const int nlist = ivf->nlist;
     hipError_t e;
-    if (res && ((e = ivf->pq_base.ensure((size_t)per * np * sizeof(double))) != hipSuccess ||
-                (e = ivf->pq_qq.ensure((size_t)per * sizeof(double))) != hipSuccess))
-        return fail(MIRX_ENOMEM, std::string("ivf_search: workspace: ") + hipGetErrorString(e));
-    if ((e = ivf->scores.ensure((size_t)per * ld * sizeof(double))) != hipSuccess ||
-        (e = ivf->tables.ensure((size_t)per * table_bytes)) != hipSuccess ||
-        (e = ivf->pids.ensure((size_t)per * np * sizeof(int64_t))) != hipSuccess ||
-        (e = ivf->fval.ensure((size_t)per * np * sizeof(float))) != hipSuccess ||
-        (e = ivf->probes.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess ||
-        (e = ivf->qoff.ensure((size_t)per * (np + 1) * sizeof(int32_t))) != hipSuccess ||
-        (e = ivf->cntcur.ensure((size_t)nlist * sizeof(int))) != hipSuccess ||
-        (e = ivf->itemoff.ensure((size_t)(per + 1) * sizeof(int32_t))) != hipSuccess)
-        return fail(MIRX_ENOMEM, std::string("ivf_search: workspace: ") + hipGetErrorString(e));
-    for (int64_t q0 = 0; q0 < nq; q0 += per) {
-        const int nb = (int)std::min(per, nq - q0);
-        const float *qb = q + q0 * ivf->dim;
-        int rc = np <= MAX_K ? mirx_index_search(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), ivf->pids.as<int64_t>(), st)
-                             : mirx_index_rank_top(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), nullptr,
-                                                   ivf->pids.as<int64_t>(), st);
-        if (rc) return rc;
-        MIRX_HIP(launch_ivf_probes(ivf->pids.as<int64_t>(), nb, np, ivf->offsets.as<int64_t>(), nlist, ivf->probes.as<int32_t>(),
-                                   out_probes ? out_probes + q0 * np : nullptr, ivf->qoff.as<int32_t>(), ivf->cntcur.as<int>(), st));
-        MIRX_HIP(launch_pq_tables(qb, nb, ivf->dim, m, res ? MIRX_METRIC_IP : ivf->metric, ivf->codebooks.as<float>(),
-                                  ivf->tables.as<double>(), st));
-        if (res)
-            MIRX_HIP(launch_pq_base(qb, nb, ivf->dim, m, ivf->probes.as<int32_t>(), np, ivf->centroids.as<float>(), nlist,
-                                    ivf->pq_base.as<double>(), res_l2 ? ivf->pq_qq.as<double>() : nullptr, st));
-        MIRX_HIP(launch_pq_items(ivf->qoff.as<int32_t>(), nb, np, ivf->cntcur.as<int>(), nlist, ivf->itemoff.as<int32_t>(),
-                                 ivf->stats_dev, st));
-        PqScanArgs sa{};
-        sa.tables = ivf->tables.as<double>();
-        sa.codes = ivf->rows.as<uint8_t>();
-        sa.m = m;
-        sa.nq = nb;
-        sa.nprobe = np;
-        sa.probes = ivf->probes.as<int32_t>();
-        sa.qoff = ivf->qoff.as<int32_t>();
-        sa.offsets = ivf->offsets.as<int64_t>();
-        sa.itemoff = ivf->itemoff.as<int32_t>();
-        sa.out = ivf->scores.as<double>();
-        sa.ld = ld;
-        sa.base = res ? ivf->pq_base.as<double>() : nullptr;
-        sa.qq = res_l2 ? ivf->pq_qq.as<double>() : nullptr;
-        sa.n2 = res_l2 ? ivf->norms.as<double>() : nullptr;
-        MIRX_HIP(launch_pq_scan(sa, ivf->metric, st));
-        MIRX_HIP(launch_ivf_topk(ivf->scores.as<double>(), ld, ivf->probes.as<int32_t>(), ivf->qoff.as<int32_t>(), nb, np,
-                                 ivf->offsets.as<int64_t>(), ivf->ids.as<int64_t>(), exclude ? exclude + q0 : nullptr, k, ivf->metric,
-                                 out_f64 ? out_f64 + q0 * k : nullptr, out_ids + q0 * k, out_values ? out_values + q0 * k : nullptr,
-                                 st));
-        ++ivf->last_batches;
-    }
+    if ((e = ivf->q32p.ensure((size_t)per * ivf->dimp * sizeof(float))) != hipSuccess ||
+        (e = ivf->cntcur.ensure((size_t)2 * nlist * sizeof(int))) != hipSuccess ||
+        (e = ivf->pairoff.ensure((size_t)(nlist + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->itemoff.ensure((size_t)(nlist + 1) * sizeof(int32_t))) != hipSuccess ||
+        (e = ivf->pair_q.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess)
+        return e;
+    return ivf->pair_off.ensure((size_t)per * np * sizeof(int32_t));
+}
+
+hipError_t pq_workspace(mirx_ivf *ivf, int64_t per, int np) {
+    hipError_t e;
+    if (ivf->pq_res && ((e = ivf->pq_base.ensure((size_t)per * np * sizeof(double))) != hipSuccess ||
+                        (e = ivf->pq_qq.ensure((size_t)per * sizeof(double))) != hipSuccess))
+        return e;
+    if ((e = ivf->tables.ensure((size_t)per * ivf->pq_m * 256 * sizeof(double))) != hipSuccess ||
+        (e = ivf->cntcur.ensure((size_t)ivf->nlist * sizeof(int))) != hipSuccess)
+        return e;
+    return ivf->itemoff.ensure((size_t)(per + 1) * sizeof(int32_t));
+}
+
+// FLAT and SQ8: the padded queries, the probes inverted into per-list (query, offset) pairs, the rows of every probed list scored
+int scan_scores(mirx_ivf *ivf, const SearchBatch &b, hipStream_t st) {
+    const int nlist = ivf->nlist, dimp = ivf->dimp, qt = ivf_query_tile(dimp);
+    MIRX_HIP(launch_ivf_place(b.qb, b.nb, ivf->dim, ivf->dim, nullptr, nullptr, ivf->q32p.as<float>(), dimp, st));
+    MIRX_HIP(launch_ivf_invert(ivf->pids.as<int64_t>(), b.nb, b.np, ivf->offsets.as<int64_t>(), nlist, qt, ivf->probes.as<int32_t>(),
+                               b.out_probes, ivf->qoff.as<int32_t>(), ivf->cntcur.as<int>(), ivf->pairoff.as<int32_t>(),
+                               ivf->itemoff.as<int32_t>(), ivf->pair_q.as<int32_t>(), ivf->pair_off.as<int32_t>(), ivf->stats_dev, st));
+    IvfScoreArgs sa{};
+    sa.q32p = ivf->q32p.as<float>();
+    sa.rows = ivf->rows.p;
+    sa.vmin = ivf->sq8() ? ivf->vmin() : nullptr;
+    sa.scale = ivf->sq8() ? ivf->scale() : nullptr;
+    sa.dimp = dimp;
+    sa.nlist = nlist;
+    sa.qt = qt;
+    sa.offsets = ivf->offsets.as<int64_t>();
+    sa.pairoff = ivf->pairoff.as<int32_t>();
+    sa.itemoff = ivf->itemoff.as<int32_t>();
+    sa.pair_q = ivf->pair_q.as<int32_t>();
+    sa.pair_off = ivf->pair_off.as<int32_t>();
+    sa.out = ivf->scores.as<double>();
+    sa.ld = b.ld;
+    MIRX_HIP(launch_ivf_scores(sa, ivf->metric, st));
+    return MIRX_OK;
+}
+
+// PQ: the probes, every query's tables (residual: and its bases), the items of the scan, the ADC scan
+int pq_scores(mirx_ivf *ivf, const SearchBatch &b, hipStream_t st) {
+    const int nlist = ivf->nlist, m = ivf->pq_m;
+    const bool res = ivf->pq_res, res_l2 = ivf->res_l2();
+    MIRX_HIP(launch_ivf_probes(ivf->pids.as<int64_t>(), b.nb, b.np, ivf->offsets.as<int64_t>(), nlist, ivf->probes.as<int32_t>(),
+                               b.out_probes, ivf->qoff.as<int32_t>(), ivf->cntcur.as<int>(), st));
+    MIRX_HIP(launch_pq_tables(b.qb, b.nb, ivf->dim, m, res ? MIRX_METRIC_IP : ivf->metric, ivf->codebooks.as<float>(),
+                              ivf->tables.as<double>(), st));
+    if (res)
+        MIRX_HIP(launch_pq_base(b.qb, b.nb, ivf->dim, m, ivf->probes.as<int32_t>(), b.np, ivf->centroids.as<float>(), nlist,
+                                ivf->pq_base.as<double>(), res_l2 ? ivf->pq_qq.as<double>() : nullptr, st));
+    MIRX_HIP(launch_pq_items(ivf->qoff.as<int32_t>(), b.nb, b.np, ivf->cntcur.as<int>(), nlist, ivf->itemoff.as<int32_t>(),
+                             ivf->stats_dev, st));
+    PqScanArgs sa{};
+    sa.tables = ivf->tables.as<double>();
+    sa.codes = ivf->rows.as<uint8_t>();
+    sa.m = m;
+    sa.nq = b.nb;
+    sa.nprobe = b.np;
+    sa.probes = ivf->probes.as<int32_t>();
+    sa.qoff = ivf->qoff.as<int32_t>();
+    sa.offsets = ivf->offsets.as<int64_t>();
+    sa.itemoff = ivf->itemoff.as<int32_t>();
+    sa.out = ivf->scores.as<double>();
+    sa.ld = b.ld;
+    sa.base = res ? ivf->pq_base.as<double>() : nullptr;
+    sa.qq = res_l2 ? ivf->pq_qq.as<double>() : nullptr;
+    sa.n2 = res_l2 ? ivf->norms.as<double>() : nullptr;
+    MIRX_HIP(launch_pq_scan(sa, ivf->metric, st));
     return MIRX_OK;
 }
 
@@ -421,7 +471,7 @@ int pq_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int np, int64_t 
 
 extern "C" {
 
-static int create_ivf(int dim, int metric, int nlist, int kind, int m, int device, mirx_ivf **out);   // behind every create call
+static int create_ivf(int dim, int metric, int nlist, int kind, int m, bool by_residual, int device, mirx_ivf **out);   // behind every create call
 
 int mirx_ivf_query_tile(int dim) {
     if (dim < 1 || dim > MIRX_IVF_MAX_DIM) return -1;
@@ -438,32 +488,29 @@ int mirx_ivf_create_typed(int dim, int metric, int nlist, int kind, int device, 
     *out = nullptr;
     MIRX_CHECK(kind == MIRX_IVF_FLAT || kind == MIRX_IVF_SQ8,
                "ivf_create: unknown kind (MIRX_IVF_FLAT, MIRX_IVF_SQ8; MIRX_IVF_PQ needs m: mirx_ivf_create_pq)");
-    return create_ivf(dim, metric, nlist, kind, 0, device, out);
+    return create_ivf(dim, metric, nlist, kind, 0, false, device, out);
 }
 
 int mirx_ivf_create_pq(int dim, int metric, int nlist, int m, int nbits, int device, mirx_ivf **out) {
     MIRX_CHECK(out, "ivf_create_pq: out is null");
-    *out = nullptr;
-    MIRX_CHECK(nbits == 8, "ivf_create_pq: nbits must be 8 (256 codewords per sub-quantiser)");
-    MIRX_CHECK(m >= 4 && m <= PQ_MAX_M && m % 4 == 0, "ivf_create_pq: m must be a multiple of 4 in 4 .. 64");
-    MIRX_CHECK(dim >= 1 && dim % (4 * m) == 0, "ivf_create_pq: dim must be a multiple of 4 m");
-    return create_ivf(dim, metric, nlist, MIRX_IVF_PQ, m, device, out);
+    return mirx_ivf_create_pq_ex(dim, metric, nlist, m, nbits, 0, device, out);
 }
 
 int mirx_ivf_create_pq_ex(int dim, int metric, int nlist, int m, int nbits, int by_residual, int device, mirx_ivf **out) {
     MIRX_CHECK(out, "ivf_create_pq_ex: out is null");
     *out = nullptr;
     MIRX_CHECK(by_residual == 0 || by_residual == 1, "ivf_create_pq_ex: by_residual must be 0 or 1");
-    if (int rc = mirx_ivf_create_pq(dim, metric, nlist, m, nbits, device, out)) return rc;
-    (*out)->pq_res = by_residual == 1;
-    return MIRX_OK;
+    MIRX_CHECK(nbits == 8, "ivf_create_pq: nbits must be 8 (256 codewords per sub-quantiser)");
+    MIRX_CHECK(m >= 4 && m <= PQ_MAX_M && m % 4 == 0, "ivf_create_pq: m must be a multiple of 4 in 4 .. 64");
+    MIRX_CHECK(dim >= 1 && dim % (4 * m) == 0, "ivf_create_pq: dim must be a multiple of 4 m");
+    return create_ivf(dim, metric, nlist, MIRX_IVF_PQ, m, by_residual == 1, device, out);
 }
 
 int mirx_ivf_pq_m(const mirx_ivf *ivf) { return ivf && ivf->pq() ? ivf->pq_m : -1; }
 int mirx_ivf_pq_by_residual(const mirx_ivf *ivf) { return ivf && ivf->pq() ? (ivf->pq_res ? 1 : 0) : -1; }
 int mirx_ivf_pq_item_rows(void) { return PQ_ITEM_ROWS; }
 
-static int create_ivf(int dim, int metric, int nlist, int kind, int m, int device, mirx_ivf **out) {
+static int create_ivf(int dim, int metric, int nlist, int kind, int m, bool by_residual, int device, mirx_ivf **out) {
     MIRX_CHECK(dim >= 1 && dim <= MIRX_IVF_MAX_DIM, "ivf_create: dim out of range (1 .. 2048)");
     MIRX_CHECK(metric == MIRX_METRIC_IP || metric == MIRX_METRIC_NEG_L2, "ivf_create: unknown metric");
     MIRX_CHECK(nlist >= 1 && nlist <= MIRX_IVF_MAX_NLIST, "ivf_create: nlist out of range (1 .. 65536)");
@@ -481,6 +528,7 @@ static int create_ivf(int dim, int metric, int nlist, int kind, int m, int devic
     ivf->device = device;
     ivf->kind = kind;
     ivf->pq_m = m;
+    ivf->pq_res = by_residual;
     ivf->off_h.assign((size_t)nlist + 1, 0);
     hipError_t e;
     if ((e = ivf->centroids.ensure((size_t)nlist * dim * sizeof(float))) != hipSuccess ||
@@ -512,7 +560,7 @@ int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *i
     MIRX_CHECK(n >= ivf->nlist, "ivf_train: fewer rows than lists");
     MIRX_CHECK(n <= 0x7FFFFF00ll, "ivf_train: more than 2^31 rows");
     MIRX_CHECK(iters >= 0, "ivf_train: iters must not be negative");
-    if (int rc = sq8_resident(ivf, "ivf_train")) return rc;
+    if (int rc = coded_rows_keep_trained_parts(ivf, "ivf_train")) return rc;
     const int nlist = ivf->nlist, dim = ivf->dim;
     std::vector<int64_t> start((size_t)nlist);
     for (int j = 0; j < nlist; ++j) {
@@ -536,7 +584,7 @@ int mirx_ivf_train(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *i
 
 int mirx_ivf_set_centroids(mirx_ivf *ivf, const float *centroids) {
     MIRX_CHECK(ivf && centroids, "ivf_set_centroids: null argument");
-    if (int rc = sq8_resident(ivf, "ivf_set_centroids")) return rc;
+    if (int rc = coded_rows_keep_trained_parts(ivf, "ivf_set_centroids")) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_set_centroids");
     MIRX_HIP(hipMemcpy(ivf->centroids.p, centroids, (size_t)ivf->nlist * ivf->dim * sizeof(float), hipMemcpyDefault));
     return fix_centroids(ivf, nullptr);
@@ -544,7 +592,7 @@ int mirx_ivf_set_centroids(mirx_ivf *ivf, const float *centroids) {
 
 int mirx_ivf_get_centroids(const mirx_ivf *ivf, float *out_centroids) {
     MIRX_CHECK(ivf && out_centroids, "ivf_get_centroids: null argument");
-    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_get_centroids: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    if (int rc = trained_parts_fixed(ivf, "ivf_get_centroids", CENTROIDS)) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_get_centroids");
     MIRX_HIP(hipMemcpy(out_centroids, ivf->centroids.p, (size_t)ivf->nlist * ivf->dim * sizeof(float), hipMemcpyDefault));
     return MIRX_OK;
@@ -552,11 +600,7 @@ int mirx_ivf_get_centroids(const mirx_ivf *ivf, float *out_centroids) {
 
 int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids_or_null) {
     MIRX_CHECK(ivf && n >= 0 && (rows || n == 0), "ivf_add: bad argument");
-    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_add: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
-    if (ivf->sq8() && !ivf->range_fixed)
-        return fail(MIRX_ESTATE, "ivf_add: the range is not fixed yet (mirx_ivf_sq8_train / _sq8_set_range)");
-    if (ivf->pq() && !ivf->cb_fixed)
-        return fail(MIRX_ESTATE, "ivf_add: the codebooks are not fixed yet (mirx_ivf_pq_train / _pq_set_codebooks)");
+    if (int rc = trained_parts_fixed(ivf, "ivf_add", ALL_PARTS)) return rc;
     MIRX_CHECK(ivf->size + n <= 0x7FFFFF00ll, "ivf_add: more than 2^31 rows per index");
     MIRX_IVF_ENTER(ivf, "ivf_add");
     if (n == 0) return MIRX_OK;
@@ -585,20 +629,19 @@ int mirx_ivf_add(mirx_ivf *ivf, const float *rows, int64_t n, const int64_t *ids
     const void *placed = drows;
     if (ivf->pq()) {                                             // the list came from the original row; now the row becomes its codes
         if (ivf->pq_codes.ensure((size_t)n * ivf->pq_m) != hipSuccess) return fail(MIRX_ENOMEM, "ivf_add: no memory for the new codes");
-        const int64_t *dlists = nullptr;
         if (ivf->pq_res) {                                       // the new rows' lists on the device: their centroids are subtracted
             if (ivf->pq_lists.ensure((size_t)n * sizeof(int64_t)) != hipSuccess ||
                 (ivf->res_l2() && ivf->pq_n2.ensure((size_t)n * sizeof(double)) != hipSuccess))
                 return fail(MIRX_ENOMEM, "ivf_add: no memory for the new rows' lists and norms");
             MIRX_HIP(hipMemcpy(ivf->pq_lists.p, lists.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-            dlists = ivf->pq_lists.as<int64_t>();
         }
+        const PqResidual res{ivf->pq_lists.as<int64_t>(), ivf->centroids.as<float>(), nlist, &ivf->pq_resid};
         if (int rc = pq_encode_rows(ivf->device, ivf->dim, ivf->pq_m, ivf->codebooks.as<float>(), drows, n,
-                                    ivf->pq_codes.as<uint8_t>(), ivf->pq_sub, ivf->pq_found, ivf->fval, nullptr, dlists,
-                                    ivf->centroids.as<float>(), nlist, &ivf->pq_resid))
+                                    ivf->pq_codes.as<uint8_t>(), ivf->pq_sub, ivf->pq_found, ivf->fval, ivf->pq_res ? &res : nullptr,
+                                    nullptr))
             return rc;
         if (ivf->res_l2())
-            MIRX_HIP(launch_pq_norms(ivf->pq_codes.as<uint8_t>(), n, ivf->dim, ivf->pq_m, dlists, ivf->centroids.as<float>(), nlist,
+            MIRX_HIP(launch_pq_norms(ivf->pq_codes.as<uint8_t>(), n, ivf->dim, ivf->pq_m, res.lists, ivf->centroids.as<float>(), nlist,
                                      ivf->codebooks.as<float>(), ivf->pq_n2.as<double>(), nullptr));
         placed = ivf->pq_codes.p;
     }
@@ -637,7 +680,7 @@ int mirx_ivf_sq8_train(mirx_ivf *ivf, const float *rows, int64_t n, void *stream
     MIRX_CHECK(ivf && rows, "ivf_sq8_train: null argument");
     MIRX_IVF_SQ8_ONLY(ivf, "ivf_sq8_train");
     MIRX_CHECK(n >= 1, "ivf_sq8_train: no rows");
-    if (int rc = sq8_resident(ivf, "ivf_sq8_train")) return rc;
+    if (int rc = coded_rows_keep_trained_parts(ivf, "ivf_sq8_train")) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_sq8_train");
     hipStream_t st = (hipStream_t)stream;
     const float *drows = nullptr;
@@ -654,7 +697,7 @@ int mirx_ivf_sq8_train(mirx_ivf *ivf, const float *rows, int64_t n, void *stream
 int mirx_ivf_sq8_set_range(mirx_ivf *ivf, const float *vmin, const float *scale) {
     MIRX_CHECK(ivf && vmin && scale, "ivf_sq8_set_range: null argument");
     MIRX_IVF_SQ8_ONLY(ivf, "ivf_sq8_set_range");
-    if (int rc = sq8_resident(ivf, "ivf_sq8_set_range")) return rc;
+    if (int rc = coded_rows_keep_trained_parts(ivf, "ivf_sq8_set_range")) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_sq8_set_range");
     MIRX_HIP(hipMemset(ivf->range.p, 0, (size_t)2 * ivf->dimp * sizeof(float)));
     MIRX_HIP(hipMemcpy(ivf->range.p, vmin, (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
@@ -666,7 +709,7 @@ int mirx_ivf_sq8_set_range(mirx_ivf *ivf, const float *vmin, const float *scale)
 int mirx_ivf_sq8_get_range(const mirx_ivf *ivf, float *out_vmin, float *out_scale) {
     MIRX_CHECK(ivf && out_vmin && out_scale, "ivf_sq8_get_range: null argument");
     MIRX_IVF_SQ8_ONLY(ivf, "ivf_sq8_get_range");
-    if (!ivf->range_fixed) return fail(MIRX_ESTATE, "ivf_sq8_get_range: the range is not fixed yet (mirx_ivf_sq8_train / _sq8_set_range)");
+    if (int rc = trained_parts_fixed(ivf, "ivf_sq8_get_range", RANGE)) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_sq8_get_range");
     MIRX_HIP(hipMemcpy(out_vmin, ivf->vmin(), (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
     MIRX_HIP(hipMemcpy(out_scale, ivf->scale(), (size_t)ivf->dim * sizeof(float), hipMemcpyDefault));
@@ -741,7 +784,7 @@ int mirx_ivf_pq_train(mirx_ivf *ivf, const float *rows, int64_t n, int iters, vo
     MIRX_CHECK(n >= 256, "ivf_pq_train: fewer rows than codewords (256)");
     MIRX_CHECK(n <= 0x7FFFFF00ll, "ivf_pq_train: more than 2^31 rows");
     MIRX_CHECK(iters >= 0, "ivf_pq_train: iters must not be negative");
-    if (int rc = sq8_resident(ivf, "ivf_pq_train")) return rc;
+    if (int rc = coded_rows_keep_trained_parts(ivf, "ivf_pq_train")) return rc;
     if (ivf->pq_res && !ivf->cent)
         return fail(MIRX_ESTATE, "ivf_pq_train: residual coding trains on rows minus their centroids, and the centroids are not "
                                  "fixed yet (mirx_ivf_train / _set_centroids)");
@@ -778,7 +821,7 @@ int mirx_ivf_pq_train(mirx_ivf *ivf, const float *rows, int64_t n, int iters, vo
 int mirx_ivf_pq_set_codebooks(mirx_ivf *ivf, const float *codebooks) {
     MIRX_CHECK(ivf && codebooks, "ivf_pq_set_codebooks: null argument");
     MIRX_IVF_PQ_ONLY(ivf, "ivf_pq_set_codebooks");
-    if (int rc = sq8_resident(ivf, "ivf_pq_set_codebooks")) return rc;
+    if (int rc = coded_rows_keep_trained_parts(ivf, "ivf_pq_set_codebooks")) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_pq_set_codebooks");
     MIRX_HIP(hipMemcpy(ivf->codebooks.p, codebooks, (size_t)256 * ivf->dim * sizeof(float), hipMemcpyDefault));
     ivf->cb_fixed = true;
@@ -788,8 +831,7 @@ int mirx_ivf_pq_set_codebooks(mirx_ivf *ivf, const float *codebooks) {
 int mirx_ivf_pq_get_codebooks(const mirx_ivf *ivf, float *out_codebooks) {
     MIRX_CHECK(ivf && out_codebooks, "ivf_pq_get_codebooks: null argument");
     MIRX_IVF_PQ_ONLY(ivf, "ivf_pq_get_codebooks");
-    if (!ivf->cb_fixed)
-        return fail(MIRX_ESTATE, "ivf_pq_get_codebooks: the codebooks are not fixed yet (mirx_ivf_pq_train / _pq_set_codebooks)");
+    if (int rc = trained_parts_fixed(ivf, "ivf_pq_get_codebooks", CODEBOOKS)) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_pq_get_codebooks");
     MIRX_HIP(hipMemcpy(out_codebooks, ivf->codebooks.p, (size_t)256 * ivf->dim * sizeof(float), hipMemcpyDefault));
     return MIRX_OK;
@@ -802,7 +844,7 @@ int mirx_pq_encode(const float *rows, int64_t n, int dim, int m, const float *co
     int device = 0;
     MIRX_HIP(hipGetDevice(&device));
     DevBuf sub, found, fval;
-    return pq_encode_rows(device, dim, m, codebooks, rows, n, out_codes, sub, found, fval, (hipStream_t)stream);
+    return pq_encode_rows(device, dim, m, codebooks, rows, n, out_codes, sub, found, fval, nullptr, (hipStream_t)stream);
 }
 
 int mirx_pq_decode(const uint8_t *codes, int64_t n, int dim, int m, const float *codebooks, float *out_rows, void *stream) {
@@ -857,7 +899,7 @@ int mirx_ivf_list_sizes(const mirx_ivf *ivf, int64_t *out_sizes) {
 
 int mirx_ivf_assign(mirx_ivf *ivf, const float *rows, int64_t n, int64_t *out_lists, void *stream) {
     MIRX_CHECK(ivf && n >= 0 && ((rows && out_lists) || n == 0), "ivf_assign: bad argument");
-    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_assign: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    if (int rc = trained_parts_fixed(ivf, "ivf_assign", CENTROIDS)) return rc;
     MIRX_IVF_ENTER(ivf, "ivf_assign");
     return assign_rows(ivf, rows, n, out_lists, (hipStream_t)stream);
 }
@@ -877,11 +919,11 @@ int mirx_ivf_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int nprobe
     MIRX_CHECK(out_values_or_null || out_f64_or_null || nq == 0, "ivf_search: both score outputs are null");
     MIRX_CHECK(k >= 1 && k <= MAX_K, "ivf_search: k out of range (1 .. 1024)");
     MIRX_CHECK(nprobe >= 1, "ivf_search: nprobe must be at least 1");
-    if (!ivf->cent) return fail(MIRX_ESTATE, "ivf_search: the centroids are not fixed yet (mirx_ivf_train / _set_centroids)");
+    if (int rc = trained_parts_fixed(ivf, "ivf_search", CENTROIDS)) return rc;   // rows imply the range / codebooks (mirx_ivf_add)
     MIRX_IVF_ENTER(ivf, "ivf_search");
     hipStream_t st = (hipStream_t)stream;
-    const int nlist = ivf->nlist, np = std::min(nprobe, nlist), dimp = ivf->dimp;
-    const int qt = ivf_query_tile(dimp);
+    const int nlist = ivf->nlist, np = std::min(nprobe, nlist);
+    const bool pq = ivf->pq();
     ivf->last_nq = nq;
     ivf->last_batches = 0;
     MIRX_HIP(hipMemsetAsync(ivf->stats_dev, 0, 3 * sizeof(unsigned long long), st));
@@ -895,56 +937,35 @@ int mirx_ivf_search(mirx_ivf *ivf, const float *q, int64_t nq, int k, int nprobe
     }
     std::partial_sort(sizes.begin(), sizes.begin() + np, sizes.end(), std::greater<int64_t>());
     const int64_t ld = std::max<int64_t>(1, std::accumulate(sizes.begin(), sizes.begin() + np, (int64_t)0));
+    // the queries of one internal batch: a query's compact row of doubles (PQ: and its tables and bases) out of the one workspace
+    // budget, the (query, probe) pairs bounded, the kind's work items within an int
     const int64_t budget = ivf->score_bytes > 0 ? ivf->score_bytes : (int64_t)SCORE_WS_BYTES;
-    if (ivf->pq()) return pq_search(ivf, q, nq, k, np, ld, budget, exclude_ids_or_null, out_values_or_null, out_f64_or_null, out_ids,
-                                    out_probes_or_null, st);
-    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8)));
+    int64_t per = std::max<int64_t>(1, std::min<int64_t>(nq, budget / (ld * 8 + (pq ? pq_query_bytes(ivf, np) : 0))));
     per = std::min(per, std::max<int64_t>(1, MAX_BATCH_PAIRS / np));
-    while (per > 1 && (per / qt + 1) * std::max<int64_t>(blocks, 1) > 0x7FFFFFFFll) per /= 2;   // work items fit an int
-    MIRX_CHECK((per / qt + 1) * std::max<int64_t>(blocks, 1) <= 0x7FFFFFFFll, "ivf_search: too many row blocks for one query");
+    if (pq) {
+        per = std::min(per, std::max<int64_t>(1, 0x7FFFFFFFll / ((ld + PQ_ITEM_ROWS - 1) / PQ_ITEM_ROWS)));
+    } else {
+        const int qt = ivf_query_tile(ivf->dimp);
+        while (per > 1 && (per / qt + 1) * std::max<int64_t>(blocks, 1) > 0x7FFFFFFFll) per /= 2;
+        MIRX_CHECK((per / qt + 1) * std::max<int64_t>(blocks, 1) <= 0x7FFFFFFFll, "ivf_search: too many row blocks for one query");
+    }
     hipError_t e;
     if ((e = ivf->scores.ensure((size_t)per * ld * sizeof(double))) != hipSuccess ||
-        (e = ivf->q32p.ensure((size_t)per * dimp * sizeof(float))) != hipSuccess ||
         (e = ivf->pids.ensure((size_t)per * np * sizeof(int64_t))) != hipSuccess ||
         (e = ivf->fval.ensure((size_t)per * np * sizeof(float))) != hipSuccess ||
         (e = ivf->probes.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess ||
         (e = ivf->qoff.ensure((size_t)per * (np + 1) * sizeof(int32_t))) != hipSuccess ||
-        (e = ivf->cntcur.ensure((size_t)2 * nlist * sizeof(int))) != hipSuccess ||
-        (e = ivf->pairoff.ensure((size_t)(nlist + 1) * sizeof(int32_t))) != hipSuccess ||
-        (e = ivf->itemoff.ensure((size_t)(nlist + 1) * sizeof(int32_t))) != hipSuccess ||
-        (e = ivf->pair_q.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess ||
-        (e = ivf->pair_off.ensure((size_t)per * np * sizeof(int32_t))) != hipSuccess)
+        (e = pq ? pq_workspace(ivf, per, np) : scan_workspace(ivf, per, np)) != hipSuccess)
         return fail(MIRX_ENOMEM, std::string("ivf_search: workspace: ") + hipGetErrorString(e));
     for (int64_t q0 = 0; q0 < nq; q0 += per) {
-        const int nb = (int)std::min(per, nq - q0);
-        const float *qb = q + q0 * ivf->dim;
+        const SearchBatch b{q + q0 * ivf->dim, (int)std::min(per, nq - q0), np, ld, out_probes_or_null ? out_probes_or_null + q0 * np : nullptr};
         // the probes: the centroid index's own top-np (past mirx_index_search's k limit, its radix ranking: the same ranking)
-        int rc = np <= MAX_K ? mirx_index_search(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), ivf->pids.as<int64_t>(), st)
-                             : mirx_index_rank_top(ivf->cent, qb, nb, np, nullptr, ivf->fval.as<float>(), nullptr,
+        int rc = np <= MAX_K ? mirx_index_search(ivf->cent, b.qb, b.nb, np, nullptr, ivf->fval.as<float>(), ivf->pids.as<int64_t>(), st)
+                             : mirx_index_rank_top(ivf->cent, b.qb, b.nb, np, nullptr, ivf->fval.as<float>(), nullptr,
                                                    ivf->pids.as<int64_t>(), st);
         if (rc) return rc;
-        MIRX_HIP(launch_ivf_place(qb, nb, ivf->dim, ivf->dim, nullptr, nullptr, ivf->q32p.as<float>(), dimp, st));
-        MIRX_HIP(launch_ivf_invert(ivf->pids.as<int64_t>(), nb, np, ivf->offsets.as<int64_t>(), nlist, qt, ivf->probes.as<int32_t>(),
-                                   out_probes_or_null ? out_probes_or_null + q0 * np : nullptr, ivf->qoff.as<int32_t>(),
-                                   ivf->cntcur.as<int>(), ivf->pairoff.as<int32_t>(), ivf->itemoff.as<int32_t>(),
-                                   ivf->pair_q.as<int32_t>(), ivf->pair_off.as<int32_t>(), ivf->stats_dev, st));
-        IvfScoreArgs sa{};
-        sa.q32p = ivf->q32p.as<float>();
-        sa.rows = ivf->rows.p;
-        sa.vmin = ivf->sq8() ? ivf->vmin() : nullptr;
-        sa.scale = ivf->sq8() ? ivf->scale() : nullptr;
-        sa.dimp = dimp;
-        sa.nlist = nlist;
-        sa.qt = qt;
-        sa.offsets = ivf->offsets.as<int64_t>();
-        sa.pairoff = ivf->pairoff.as<int32_t>();
-        sa.itemoff = ivf->itemoff.as<int32_t>();
-        sa.pair_q = ivf->pair_q.as<int32_t>();
-        sa.pair_off = ivf->pair_off.as<int32_t>();
-        sa.out = ivf->scores.as<double>();
-        sa.ld = ld;
-        MIRX_HIP(launch_ivf_scores(sa, ivf->metric, st));
-        MIRX_HIP(launch_ivf_topk(ivf->scores.as<double>(), ld, ivf->probes.as<int32_t>(), ivf->qoff.as<int32_t>(), nb, np,
+        if ((rc = pq ? pq_scores(ivf, b, st) : scan_scores(ivf, b, st))) return rc;
+        MIRX_HIP(launch_ivf_topk(ivf->scores.as<double>(), ld, ivf->probes.as<int32_t>(), ivf->qoff.as<int32_t>(), b.nb, np,
                                  ivf->offsets.as<int64_t>(), ivf->ids.as<int64_t>(),
                                  exclude_ids_or_null ? exclude_ids_or_null + q0 : nullptr, k, ivf->metric,
                                  out_f64_or_null ? out_f64_or_null + q0 * k : nullptr, out_ids + q0 * k,

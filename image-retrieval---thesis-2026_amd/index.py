@@ -698,6 +698,19 @@ class FlatIndex:
 IVF_TRAIN_ROWS_PER_LIST = 256              # IvfFlatIndex.train(max_rows=None) trains on at most this many rows per list
 
 
+def strided_sample(rows, limit):
+    """The training sample of the IVF family: all of rows [n, .] when n <= limit, else the `limit` rows floor(i n / limit), as a
+    contiguous copy that is complete when this returns."""
+    n = rows.shape[0]
+    if n <= limit:
+        return rows
+    pick = (torch.arange(limit, dtype=torch.int64) * n) // limit
+    rows = rows[pick.to(rows.device)].contiguous()
+    if rows.is_cuda:
+        torch.cuda.current_stream(rows.device).synchronize()
+    return rows
+
+
 def ivf_search_bounds(k, nprobe):
     """k / nprobe of an IVF search as ints, ValueError outside mirx_ivf_search's contract"""
     for name, v in (("k", k), ("nprobe", nprobe)):
@@ -721,6 +734,7 @@ class IvfFlatIndex:
     is FlatIndex.search's answer.  "Nearest" is FlatIndex's own ranking over the centroids (ties to the lowest list)."""
 
     KIND = _lib.IVF_FLAT
+    STATE_KEYS = ("centroids",)                # the trained parts, as state() names them; the subclasses append theirs
 
     def __init__(self, dim, metric="COSINE", nlist=1024, device=None):
         if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= _lib.IVF_MAX_NLIST:
@@ -767,8 +781,25 @@ class IvfFlatIndex:
         with torch.cuda.device(self.device):
             _lib.check(getattr(self._lib, name)(self._h, *args), name)
 
-    def _train_sample(self, rows, iters, init_positions, max_rows):
-        """train()'s argument checks -> (the rows to train on: at most max_rows at an even stride, init positions or None)"""
+    @classmethod
+    def min_train_rows(cls, nlist):
+        """the fewest rows train() accepts for an index of nlist lists"""
+        return nlist
+
+    def state(self):
+        """-> the trained parts as a dict of device tensors, keys STATE_KEYS: what set_state() of an index built with the same
+        arguments takes"""
+        return {"centroids": self.centroids}
+
+    def set_state(self, state):
+        """Fix the trained parts to another index's state().  A missing key: ValueError before anything is set."""
+        for key in self.STATE_KEYS:
+            if key not in state:
+                raise ValueError(f"set_state: the state of {type(self).__name__} needs {key!r}")
+        self.set_centroids(state["centroids"])
+
+    def _train(self, rows, iters, init_positions, max_rows):
+        """train(): the argument checks and mirx_ivf_train -> the rows it trained on (at most max_rows at an even stride)"""
         rows = self._rows(rows, "train")
         limit = IVF_TRAIN_ROWS_PER_LIST * self.nlist if max_rows is None else int(max_rows)
         if limit < self.nlist:
@@ -777,27 +808,22 @@ class IvfFlatIndex:
             raise ValueError(f"train: {rows.shape[0]} rows cannot seed {self.nlist} lists")
         if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 0:
             raise ValueError(f"train: iters must be a non-negative integer, got {iters!r}")
-        n = rows.shape[0]
-        if n > limit:
-            pick = (torch.arange(limit, dtype=torch.int64) * n) // limit
-            rows = rows[pick.to(rows.device)].contiguous()
-            if rows.is_cuda:
-                torch.cuda.current_stream(self.device).synchronize()
+        rows = strided_sample(rows, limit)
         pos = None
         if init_positions is not None:
             pos = np.ascontiguousarray(np.asarray(init_positions).reshape(-1), dtype=np.int64)
             if pos.size != self.nlist or (pos < 0).any() or (pos >= rows.shape[0]).any():
                 raise ValueError(f"train: init_positions needs {self.nlist} row numbers in [0, {rows.shape[0]})")
-        return rows, pos
+        self._call("mirx_ivf_train", _ptr(rows), rows.shape[0], None if pos is None else ctypes.c_void_p(pos.ctypes.data),
+                   int(iters), _stream_ptr(self.device))
+        return rows
 
     def train(self, rows, iters=10, init_positions=None, max_rows=None):
         """Lloyd's k-means (mirx_ivf_train) and fix the centroids: start from rows[init_positions] (default: the rows at
         floor(j n / nlist)), `iters` updates at most, stop early when no row changes its list.  It trains on at most max_rows
         rows taken at an even stride (row floor(i n / max_rows)); max_rows=None means 256 * nlist.  Deterministic: two calls
         give equal bits."""
-        rows, pos = self._train_sample(rows, iters, init_positions, max_rows)
-        self._call("mirx_ivf_train", _ptr(rows), rows.shape[0], None if pos is None else ctypes.c_void_p(pos.ctypes.data),
-                   int(iters), _stream_ptr(self.device))
+        self._train(rows, iters, init_positions, max_rows)
 
     def set_centroids(self, centroids):
         """Fix the centroids to a caller's [nlist, dim] array; rows already added are re-assigned."""
@@ -873,7 +899,30 @@ class IvfFlatIndex:
         return s.as_dict()
 
 
-class IvfSq8Index(IvfFlatIndex):
+class _CodedIvfIndex(IvfFlatIndex):
+    """What IVF_SQ8 and IVF_PQ share: the rows are kept as uint8 codes of `code_width` bytes, and the originals are gone"""
+
+    def codes(self):
+        """-> (codes uint8 [n, code_width], ids int64 [n], lists int64 [n]) on the index device, in list-major order; a code row
+        is dim bytes for IVF_SQ8 and m bytes for IVF_PQ"""
+        n = len(self)
+        codes = torch.empty((n, self.code_width), dtype=torch.uint8, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        lists = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_get_codes", _ptr_or_null(codes), _ptr_or_null(ids), _ptr_or_null(lists))
+        return codes, ids, lists
+
+    def reconstruct(self):
+        """-> (decoded rows fp32 [n, dim], ids int64 [n]) on the index device, in list-major order.  IVF_SQ8: the rows search()
+        scores.  IVF_PQ: each row's codewords concatenated (with residual coding: plus the centroid of its list)"""
+        n = len(self)
+        rows = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
+        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
+        self._call("mirx_ivf_reconstruct", _ptr_or_null(rows), _ptr_or_null(ids))
+        return rows, ids
+
+
+class IvfSq8Index(_CodedIvfIndex):
     """IVF_SQ8 (mirx_ivf_create_typed(MIRX_IVF_SQ8), include/mirx.h): IvfFlatIndex with the rows kept as 8-bit codes, a quarter
     of the fp32 master.  The quantiser is per column and global: code = round((x - vmin[d]) / scale[d]) clamped to 0 .. 255, the
     decoded value (float)(vmin[d] + code * scale[d]) in double arithmetic.  A row's list comes from its original values; then the
@@ -882,13 +931,20 @@ class IvfSq8Index(IvfFlatIndex):
     keeps its centroids and its range (MirxError from train / set_centroids / train_range / set_range): remove the rows first."""
 
     KIND = _lib.IVF_SQ8
+    STATE_KEYS = IvfFlatIndex.STATE_KEYS + ("vmin", "scale")
+    code_width = property(lambda self: self.dim)
 
     def train(self, rows, iters=10, init_positions=None, max_rows=None):
         """IvfFlatIndex.train, and the range (train_range) from the same strided sample"""
-        rows, pos = self._train_sample(rows, iters, init_positions, max_rows)
-        self._call("mirx_ivf_train", _ptr(rows), rows.shape[0], None if pos is None else ctypes.c_void_p(pos.ctypes.data),
-                   int(iters), _stream_ptr(self.device))
-        self._call("mirx_ivf_sq8_train", _ptr(rows), rows.shape[0], _stream_ptr(self.device))
+        self.train_range(self._train(rows, iters, init_positions, max_rows))
+
+    def state(self):
+        vmin, scale = self.range
+        return dict(super().state(), vmin=vmin, scale=scale)
+
+    def set_state(self, state):
+        super().set_state(state)
+        self.set_range(state["vmin"], state["scale"])
 
     def train_range(self, rows):
         """Fix the range to the rows' per-column minimum and (maximum - minimum) / 255 (NaN ignored); every row is read."""
@@ -916,23 +972,6 @@ class IvfSq8Index(IvfFlatIndex):
         self._call("mirx_ivf_sq8_get_range", _ptr(vmin), _ptr(scale))
         return vmin, scale
 
-    def codes(self):
-        """-> (codes uint8 [n, dim], ids int64 [n], lists int64 [n]) on the index device, in list-major order"""
-        n = len(self)
-        codes = torch.empty((n, self.dim), dtype=torch.uint8, device=self.device)
-        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
-        lists = torch.empty((n,), dtype=torch.int64, device=self.device)
-        self._call("mirx_ivf_get_codes", _ptr_or_null(codes), _ptr_or_null(ids), _ptr_or_null(lists))
-        return codes, ids, lists
-
-    def reconstruct(self):
-        """-> (decoded rows fp32 [n, dim], ids int64 [n]) on the index device, in list-major order: the rows search() scores"""
-        n = len(self)
-        rows = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
-        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
-        self._call("mirx_ivf_reconstruct", _ptr_or_null(rows), _ptr_or_null(ids))
-        return rows, ids
-
 
 PQ_TRAIN_ROWS = 65536                      # IvfPqIndex.train trains the codebooks on at most this many rows
 
@@ -950,7 +989,7 @@ def pq_bounds(dim, m):
     return m
 
 
-class IvfPqIndex(IvfFlatIndex):
+class IvfPqIndex(_CodedIvfIndex):
     """IVF_PQ (mirx_ivf_create_pq, include/mirx.h): IvfFlatIndex with every row kept as `m` codeword numbers (m bytes).  Sub-space
     j (columns [j dim/m, (j+1) dim/m)) has a codebook of 256 codewords, k-means under L2 whatever the index metric; a row's code
     is its nearest codeword per sub-space (FlatIndex's own ranking, ties to the lowest code).  A row's list comes from its
@@ -961,6 +1000,8 @@ class IvfPqIndex(IvfFlatIndex):
     codebooks (MirxError from train / set_centroids / train_codebooks / set_codebooks): remove the rows first."""
 
     KIND = _lib.IVF_PQ
+    STATE_KEYS = IvfFlatIndex.STATE_KEYS + ("codebooks",)
+    code_width = property(lambda self: self.m)
     by_residual = False                        # IvfResidualPqIndex turns it on
 
     def __init__(self, dim, metric="COSINE", nlist=1024, m=None, device=None):
@@ -972,6 +1013,17 @@ class IvfPqIndex(IvfFlatIndex):
     def _create(self, h):
         _lib.check(self._lib.mirx_ivf_create_pq(self.dim, self.metric, self.nlist, self.m, 8, self.device.index, ctypes.byref(h)),
                    "mirx_ivf_create_pq")
+
+    @classmethod
+    def min_train_rows(cls, nlist):
+        return max(nlist, 256)                 # 256 codewords to seed
+
+    def state(self):
+        return dict(super().state(), codebooks=self.codebooks)
+
+    def set_state(self, state):
+        super().set_state(state)
+        self.set_codebooks(state["codebooks"])
 
     def train(self, rows, iters=10, init_positions=None, max_rows=None, codebook_iters=10):
         """IvfFlatIndex.train for the centroids, and the codebooks (train_codebooks) from at most 65 536 rows of the same data at
@@ -988,11 +1040,7 @@ class IvfPqIndex(IvfFlatIndex):
         limit, n = int(max_rows), rows.shape[0]
         if min(limit, n) < 256:
             raise ValueError(f"train_codebooks: {min(limit, n)} rows cannot seed 256 codewords")
-        if n > limit:
-            pick = (torch.arange(limit, dtype=torch.int64) * n) // limit
-            rows = rows[pick.to(rows.device)].contiguous()
-            if rows.is_cuda:
-                torch.cuda.current_stream(self.device).synchronize()
+        rows = strided_sample(rows, limit)
         self._call("mirx_ivf_pq_train", _ptr(rows), rows.shape[0], int(iters), _stream_ptr(self.device))
 
     def set_codebooks(self, codebooks):
@@ -1011,23 +1059,6 @@ class IvfPqIndex(IvfFlatIndex):
         out = torch.empty((self.m, 256, self.dim // self.m), dtype=torch.float32, device=self.device)
         self._call("mirx_ivf_pq_get_codebooks", _ptr(out))
         return out
-
-    def codes(self):
-        """-> (codes uint8 [n, m], ids int64 [n], lists int64 [n]) on the index device, in list-major order"""
-        n = len(self)
-        codes = torch.empty((n, self.m), dtype=torch.uint8, device=self.device)
-        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
-        lists = torch.empty((n,), dtype=torch.int64, device=self.device)
-        self._call("mirx_ivf_get_codes", _ptr_or_null(codes), _ptr_or_null(ids), _ptr_or_null(lists))
-        return codes, ids, lists
-
-    def reconstruct(self):
-        """-> (each row's codewords concatenated, fp32 [n, dim], ids int64 [n]) on the index device, in list-major order"""
-        n = len(self)
-        rows = torch.empty((n, self.dim), dtype=torch.float32, device=self.device)
-        ids = torch.empty((n,), dtype=torch.int64, device=self.device)
-        self._call("mirx_ivf_reconstruct", _ptr_or_null(rows), _ptr_or_null(ids))
-        return rows, ids
 
     def tables(self, q):
         """-> float64 [nq, m, 256] on the index device: the ADC tables search() builds for q under the index metric (with
@@ -1071,6 +1102,39 @@ class IvfResidualPqIndex(IvfPqIndex):
         return pq_bases(self._rows(q, "bases").to(self.device), lists, self.centroids, self.m)
 
 
+IVF_INDEX_TYPES = {"IVF_FLAT": IvfFlatIndex, "IVF_SQ8": IvfSq8Index, "IVF_PQ": IvfPqIndex}    # by_residual: IvfResidualPqIndex
+
+
+def ivf_index_spec(dim, index_type, params):
+    """(dim, a Milvus index_type, its inner params dict) -> (the index class, its constructor keywords beside dim, metric and
+    device): the one place that knows which parameters a member of the IVF family takes.  ValueError for an unknown type, an m
+    that pq_bounds refuses, a by_residual that is no bool, an nlist outside [1, 65536].  Needs no GPU."""
+    if not isinstance(index_type, str) or index_type not in IVF_INDEX_TYPES:
+        raise ValueError(f"approximate=True needs index_type 'IVF_FLAT', 'IVF_SQ8' or 'IVF_PQ', got {index_type!r}")
+    params = params if isinstance(params, dict) else {}
+    cls, kwargs = IVF_INDEX_TYPES[index_type], {}
+    if cls is IvfPqIndex:
+        if "m" not in params:
+            raise ValueError("index_type 'IVF_PQ' needs params['m'], the number of sub-quantisers; "
+                             "'IVF_FLAT' and 'IVF_SQ8' take nlist alone")
+        kwargs["m"] = pq_bounds(dim, params["m"])
+        if residual_flag(params.get("by_residual", False), "params['by_residual']"):
+            cls = IvfResidualPqIndex
+    nlist = params.get("nlist", 1024)
+    if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= _lib.IVF_MAX_NLIST:
+        raise ValueError(f"nlist must be an integer in [1, {_lib.IVF_MAX_NLIST}], got {nlist!r}")
+    kwargs["nlist"] = int(nlist)
+    return cls, kwargs
+
+
+def _device_call(name, device, *args):
+    """A stand-alone libmirx call on tensors of `device`: the device selected, its current stream's pending work done, the call
+    made on that stream and its return code checked"""
+    with torch.cuda.device(device):
+        torch.cuda.current_stream().synchronize()
+        _lib.check(getattr(_lib.load(), name)(*args, _stream_ptr(device)), name)
+
+
 def _pq_args(first, codebooks, who, dtype):
     first = torch.as_tensor(first).to(dtype).contiguous()
     cb = torch.as_tensor(codebooks).to(torch.float32).contiguous()
@@ -1087,10 +1151,7 @@ def pq_encode(rows, codebooks):
     if rows.shape[1] != dim:
         raise ValueError(f"pq_encode: rows of {rows.shape[1]} columns under codebooks of {dim}")
     out = torch.empty((rows.shape[0], m), dtype=torch.uint8, device=rows.device)
-    with torch.cuda.device(rows.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_pq_encode(_ptr_or_null(rows), rows.shape[0], dim, m, _ptr(cb), _ptr_or_null(out),
-                                              _stream_ptr(rows.device)), "mirx_pq_encode")
+    _device_call("mirx_pq_encode", rows.device, _ptr_or_null(rows), rows.shape[0], dim, m, _ptr(cb), _ptr_or_null(out))
     return out
 
 
@@ -1102,10 +1163,7 @@ def pq_decode(codes, codebooks):
     if codes.shape[1] != m:
         raise ValueError(f"pq_decode: codes of {codes.shape[1]} columns under {m} codebooks")
     out = torch.empty((codes.shape[0], dim), dtype=torch.float32, device=codes.device)
-    with torch.cuda.device(codes.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_pq_decode(_ptr_or_null(codes), codes.shape[0], dim, m, _ptr(cb), _ptr_or_null(out),
-                                              _stream_ptr(codes.device)), "mirx_pq_decode")
+    _device_call("mirx_pq_decode", codes.device, _ptr_or_null(codes), codes.shape[0], dim, m, _ptr(cb), _ptr_or_null(out))
     return out
 
 
@@ -1121,10 +1179,8 @@ def pq_residuals(rows, lists, centroids):
         raise ValueError("pq_residuals: lists and rows disagree in length")
     cent = cent.to(rows.device)
     out = torch.empty_like(rows)
-    with torch.cuda.device(rows.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_pq_residuals(_ptr_or_null(rows), rows.shape[0], rows.shape[1], _ptr_or_null(lists), _ptr(cent),
-                                                 cent.shape[0], _ptr_or_null(out), _stream_ptr(rows.device)), "mirx_pq_residuals")
+    _device_call("mirx_pq_residuals", rows.device, _ptr_or_null(rows), rows.shape[0], rows.shape[1], _ptr_or_null(lists),
+                 _ptr(cent), cent.shape[0], _ptr_or_null(out))
     return out
 
 
@@ -1143,11 +1199,8 @@ def pq_bases(q, lists, centroids, m):
     cent = cent.to(q.device)
     base = torch.empty(tuple(lists.shape), dtype=torch.float64, device=q.device)
     qq = torch.empty((q.shape[0],), dtype=torch.float64, device=q.device)
-    with torch.cuda.device(q.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_pq_bases(_ptr_or_null(q), q.shape[0], q.shape[1], m, _ptr_or_null(lists), lists.shape[1],
-                                             _ptr(cent), cent.shape[0], _ptr_or_null(base), _ptr_or_null(qq), _stream_ptr(q.device)),
-                   "mirx_pq_bases")
+    _device_call("mirx_pq_bases", q.device, _ptr_or_null(q), q.shape[0], q.shape[1], m, _ptr_or_null(lists), lists.shape[1],
+                 _ptr(cent), cent.shape[0], _ptr_or_null(base), _ptr_or_null(qq))
     return base, qq
 
 
@@ -1158,10 +1211,7 @@ def pq_tables(q, codebooks, metric="COSINE"):
     if q.shape[1] != dim:
         raise ValueError(f"pq_tables: queries of {q.shape[1]} columns under codebooks of {dim}")
     out = torch.empty((q.shape[0], m, 256), dtype=torch.float64, device=q.device)
-    with torch.cuda.device(q.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_pq_tables(_ptr_or_null(q), q.shape[0], dim, m, metric_code(metric), _ptr(cb), _ptr_or_null(out),
-                                              _stream_ptr(q.device)), "mirx_pq_tables")
+    _device_call("mirx_pq_tables", q.device, _ptr_or_null(q), q.shape[0], dim, m, metric_code(metric), _ptr(cb), _ptr_or_null(out))
     return out
 
 
@@ -1172,10 +1222,8 @@ def sq8_encode(rows, vmin, scale):
         raise ValueError("sq8_encode expects CUDA rows [n, dim] and vmin / scale [dim]")
     vmin, scale = vmin.to(rows.device), scale.to(rows.device)
     out = torch.empty(rows.shape, dtype=torch.uint8, device=rows.device)
-    with torch.cuda.device(rows.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_sq8_encode(_ptr_or_null(rows), rows.shape[0], rows.shape[1], _ptr(vmin), _ptr(scale),
-                                               _ptr_or_null(out), _stream_ptr(rows.device)), "mirx_sq8_encode")
+    _device_call("mirx_sq8_encode", rows.device, _ptr_or_null(rows), rows.shape[0], rows.shape[1], _ptr(vmin), _ptr(scale),
+                 _ptr_or_null(out))
     return out
 
 
@@ -1188,10 +1236,8 @@ def sq8_decode(codes, vmin, scale):
         raise ValueError("sq8_decode expects CUDA uint8 codes [n, dim] and vmin / scale [dim]")
     vmin, scale = vmin.to(codes.device), scale.to(codes.device)
     out = torch.empty(codes.shape, dtype=torch.float32, device=codes.device)
-    with torch.cuda.device(codes.device):
-        torch.cuda.current_stream().synchronize()
-        _lib.check(_lib.load().mirx_sq8_decode(_ptr_or_null(codes), codes.shape[0], codes.shape[1], _ptr(vmin), _ptr(scale),
-                                               _ptr_or_null(out), _stream_ptr(codes.device)), "mirx_sq8_decode")
+    _device_call("mirx_sq8_decode", codes.device, _ptr_or_null(codes), codes.shape[0], codes.shape[1], _ptr(vmin), _ptr(scale),
+                 _ptr_or_null(out))
     return out
 
 

@@ -27,8 +27,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .index import (FlatIndex, IvfFlatIndex, IvfPqIndex, IvfResidualPqIndex, IvfSq8Index, group_bounds, pq_bounds, range_bounds,
-                    residual_flag, tier1_max_k)
+from .index import FlatIndex, IvfResidualPqIndex, group_bounds, ivf_index_spec, range_bounds, tier1_max_k
 
 MODEL_CONFIGS = {
     "densenet121": {"embedding_dim": 1024, "description": "DenseNet121 image embeddings"},
@@ -153,10 +152,9 @@ class Collection:
         self._approx_type = None                            # "IVF_FLAT", "IVF_SQ8" or "IVF_PQ" while it is on
         self._approx_m = None                               # IVF_PQ: its number of sub-quantisers
         self._approx_residual = False                       # IVF_PQ: params["by_residual"], residual coding (IvfResidualPqIndex)
-        self._ivf = None                                    # the IvfFlatIndex / IvfSq8Index / IvfPqIndex over the live rows; None = to be (re)built
-        self._ivf_centroids = None                          # its centroids, trained once and kept across rebuilds
-        self._ivf_range = None                              # IVF_SQ8: its (vmin, scale), trained once and kept likewise
-        self._ivf_codebooks = None                          # IVF_PQ: its codebooks, trained once and kept likewise
+        self._approx_spec = None                            # (class, constructor keywords) of it: mirx.index.ivf_index_spec
+        self._ivf = None                                    # the index of that class over the live rows; None = to be (re)built
+        self._ivf_state = None                              # its state(): trained once, set_state() across rebuilds
 
     @classmethod
     def from_stored(cls, stored, device=None):
@@ -292,25 +290,15 @@ class Collection:
         codebooks).  IVF_PQ needs index_params["params"]["m"], as Milvus does (ValueError without it or with an m that
         mirx.index.pq_bounds refuses), and stays exact below max(nlist, 256) rows; index_params["params"]["by_residual"] (default
         False; anything but a bool: ValueError) = True encodes every row minus the centroid of its list, Milvus' own IVF_PQ form
-        (IvfResidualPqIndex).  It is process state: a
+        (IvfResidualPqIndex).  The type and its parameters are checked by mirx.index.ivf_index_spec, which also names
+        the class.  It is process state: a
         stored collection opened again is exact until this call is made again.  See search() for the calls it serves."""
         params = index_params or {}
-        nlist, kind, m, residual = None, None, None, False
+        nlist, kind, m, residual, spec = None, None, None, False, None
         if approximate:
             kind = params.get("index_type")
-            if kind not in ("IVF_FLAT", "IVF_SQ8", "IVF_PQ"):
-                raise ValueError(f"approximate=True needs index_type 'IVF_FLAT', 'IVF_SQ8' or 'IVF_PQ', got {kind!r}")
-            inner = params.get("params") if isinstance(params.get("params"), dict) else {}
-            if kind == "IVF_PQ":
-                if "m" not in inner:
-                    raise ValueError("index_type 'IVF_PQ' needs params['m'], the number of sub-quantisers; "
-                                     "'IVF_FLAT' and 'IVF_SQ8' take nlist alone")
-                m = pq_bounds(self.dim, inner["m"])
-                residual = residual_flag(inner.get("by_residual", False), "params['by_residual']")
-            nlist = inner.get("nlist", 1024)
-            if isinstance(nlist, bool) or not isinstance(nlist, (int, np.integer)) or not 1 <= int(nlist) <= 65536:
-                raise ValueError(f"nlist must be an integer in [1, 65536], got {nlist!r}")
-            nlist = int(nlist)
+            spec = ivf_index_spec(self.dim, kind, params.get("params"))
+            nlist, m, residual = spec[1]["nlist"], spec[1].get("m"), spec[0] is IvfResidualPqIndex
         metric = params.get("metric_type", self.metric_type)
         if self._ids and metric != self.metric_type:
             raise ValueError("metric_type cannot change after rows were inserted")
@@ -319,39 +307,28 @@ class Collection:
             self._stored.set_metric(metric)
         if (nlist, kind, m, residual) != (self._approx_nlist, self._approx_type, self._approx_m, self._approx_residual):
             self._approx_nlist, self._approx_type, self._approx_m, self._approx_residual = nlist, kind, m, residual
-            self._ivf, self._ivf_centroids, self._ivf_range, self._ivf_codebooks = None, None, None, None
+            self._approx_spec, self._ivf, self._ivf_state = spec, None, None
         return True
 
     def _ensure_ivf(self):
         """The approximate index over the live rows, or None while there are fewer rows than lists (nothing to train on: the
-        exact routes answer).  A build copies the flat index's rows on the device (both indexes stay resident), trains on the
-        first build and re-uses those centroids afterwards."""
+        exact routes answer; IVF_PQ: than max(nlist, 256) -- the class's min_train_rows).  A build copies the flat index's rows
+        on the device (both indexes stay resident), trains on the first build and keeps the index's state(); later builds
+        set_state() it: the same centroids, range and codebooks."""
         if self._approx_nlist is None:
             return None
-        pq = self._approx_type == "IVF_PQ"
-        if self.num_entities < (max(self._approx_nlist, 256) if pq else self._approx_nlist):    # PQ: 256 codewords to seed
+        cls, kwargs = self._approx_spec
+        if self.num_entities < cls.min_train_rows(self._approx_nlist):
             return None
         if self._ivf is None:
             index = self._ensure()
             rows, ids = index.rows()
-            sq8 = self._approx_type == "IVF_SQ8"
-            if pq and self._approx_residual:
-                ivf = IvfResidualPqIndex(self.dim, self.metric_type, self._approx_nlist, self._approx_m, index.device)
-            elif pq:
-                ivf = IvfPqIndex(self.dim, self.metric_type, self._approx_nlist, self._approx_m, index.device)
-            else:
-                ivf = (IvfSq8Index if sq8 else IvfFlatIndex)(self.dim, self.metric_type, self._approx_nlist, index.device)
-            if self._ivf_centroids is None:
+            ivf = cls(self.dim, self.metric_type, device=index.device, **kwargs)
+            if self._ivf_state is None:
                 ivf.train(rows)
-                self._ivf_centroids = ivf.centroids
-                self._ivf_range = ivf.range if sq8 else None
-                self._ivf_codebooks = ivf.codebooks if pq else None
+                self._ivf_state = ivf.state()
             else:
-                ivf.set_centroids(self._ivf_centroids)
-                if sq8:
-                    ivf.set_range(*self._ivf_range)
-                if pq:
-                    ivf.set_codebooks(self._ivf_codebooks)
+                ivf.set_state(self._ivf_state)
             ivf.add(rows, ids)
             self._ivf = ivf
         return self._ivf

@@ -13,24 +13,9 @@ import pytest
 import torch
 
 import _ivf_ref as R
-from oracle import search as OS
+from _ivf_cases import SIZES, _lib, _np, _unit, forced
 
 pytestmark = pytest.mark.gpu
-
-SIZES = [257, 0, 1, 63, 64, 65, 120]          # list 1 is empty: its centroid duplicates list 0's and the tie goes to list 0
-
-
-def _lib():
-    import mirx._lib as L
-    return L
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _unit(x):
-    return OS.l2_normalize(np.ascontiguousarray(x, dtype=np.float32))
 
 
 def _flat(rows, ids, metric):
@@ -75,27 +60,6 @@ def _check(ivf, flat, cflat, lists, q, k, nprobe, ex=None):
     return ids, probes
 
 
-def _forced(dim, metric, seed):
-    """rows around 7 centroids so that the lists hold SIZES rows, user ids descending, two duplicated rows in list 0"""
-    rng = np.random.default_rng(seed)
-    base = _unit(rng.standard_normal((len(SIZES), dim)))
-    cent = base.copy()
-    cent[1] = cent[0]
-    rows, want = [], []
-    for l, m in enumerate(SIZES):
-        r = base[l] + 0.02 * rng.standard_normal((m, dim)).astype(np.float32)
-        rows.append(_unit(r) if metric == "COSINE" else r.astype(np.float32))
-        want += [l] * m
-    rows = np.concatenate(rows)
-    perm = rng.permutation(rows.shape[0])
-    rows, want = np.ascontiguousarray(rows[perm]), np.asarray(want)[perm]
-    first = np.flatnonzero(want == 0)
-    rows[first[1]] = rows[first[0]]                      # equal scores: only the ids tell them apart
-    rows[first[3]] = rows[first[2]]
-    ids = (10 ** 6 - 3 * np.arange(rows.shape[0], dtype=np.int64))
-    return rows, ids, cent, base
-
-
 @pytest.mark.parametrize("metric", ["COSINE", "L2"])
 @pytest.mark.parametrize("dim", [20, 64, 100, 256, 300, 1024, 1100])
 def test_forced_lists_every_block_edge(dim, metric):
@@ -103,7 +67,7 @@ def test_forced_lists_every_block_edge(dim, metric):
     lib = L.load()
     qt, rb = lib.mirx_ivf_query_tile(dim), lib.mirx_ivf_row_block()
     assert rb + 1 in SIZES and qt == min(16, 65536 // (8 * ((dim + 127) // 128 * 128)))
-    rows, ids, cent, base = _forced(dim, metric, dim)
+    rows, ids, cent, base = forced(SIZES, dim, metric, dim, 0.02)
     flat, cflat = _flat(rows, ids, metric), _flat(cent, None, metric)
     ivf = _ivf(rows, ids, cent, metric)
     lists = _np(cflat.search(torch.from_numpy(rows), 1)[1])[:, 0]
@@ -138,7 +102,7 @@ def test_forced_lists_every_block_edge(dim, metric):
 @pytest.mark.parametrize("metric", ["COSINE", "L2"])
 @pytest.mark.parametrize("k", [1, 10, 65, 300, 1024])
 def test_k_edges_and_padding(k, metric):
-    rows, ids, cent, base = _forced(64, metric, 5)
+    rows, ids, cent, base = forced(SIZES, 64, metric, 5, 0.02)
     flat, cflat = _flat(rows, ids, metric), _flat(cent, None, metric)
     ivf = _ivf(rows, ids, cent, metric)
     lists = _np(cflat.search(torch.from_numpy(rows), 1)[1])[:, 0]
@@ -232,7 +196,7 @@ def test_one_update_step_with_an_empty_list(metric):
 
 @pytest.mark.parametrize("metric", ["COSINE", "L2"])
 def test_add_in_batches_remove_and_new_centroids(metric):
-    rows, ids, cent, base = _forced(100, metric, 21)
+    rows, ids, cent, base = forced(SIZES, 100, metric, 21, 0.02)
     n = rows.shape[0]
     q = np.concatenate([(base[l] + np.float32(0.01)).astype(np.float32)[None] for l in (0, 3, 5, 6)])
     from mirx.index import IvfFlatIndex

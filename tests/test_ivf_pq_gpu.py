@@ -19,53 +19,11 @@ import torch
 
 import _ivf_ref as R
 import _pq_ref as P
-from oracle import search as OS
+from _ivf_cases import SIZES, _bits, _lib, _np, _unit, forced
 
 pytestmark = pytest.mark.gpu
 
-F4, F8 = np.float32, np.float64
-SIZES = [257, 0, 1, 63, 64, 65, 120]          # list 1 is empty: its centroid duplicates list 0's and the tie goes to list 0
-
-
-def _lib():
-    import mirx._lib as L
-    return L
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _unit(x):
-    return OS.l2_normalize(np.ascontiguousarray(x, dtype=F4))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == F8 else np.uint32)
-
-
-def _forced(sizes, dim, metric, seed):
-    """rows around len(sizes) centroids so that the lists hold `sizes` rows (an empty list's centroid duplicates list 0's), user
-    ids descending, two pairs of equal rows in list 0: equal codes and scores, only the ids tell them apart"""
-    rng = np.random.default_rng(seed)
-    base = _unit(rng.standard_normal((len(sizes), dim)))
-    cent = base.copy()
-    rows, want = [], []
-    for l, n in enumerate(sizes):
-        if n == 0:
-            cent[l] = cent[0]
-        r = base[l] + 0.02 * rng.standard_normal((n, dim)).astype(F4)
-        rows.append(_unit(r) if metric == "COSINE" else r.astype(F4))
-        want += [l] * n
-    rows = np.concatenate(rows)
-    perm = rng.permutation(rows.shape[0])
-    rows, want = np.ascontiguousarray(rows[perm]), np.asarray(want)[perm]
-    first = np.flatnonzero(want == 0)
-    rows[first[1]] = rows[first[0]]
-    rows[first[3]] = rows[first[2]]
-    ids = (10 ** 6 - 3 * np.arange(rows.shape[0], dtype=np.int64))
-    assert np.bincount(R.assign(rows, cent, metric), minlength=len(sizes)).tolist() == list(sizes)
-    return rows, ids, cent, base
+F4 = np.float32
 
 
 def _codebooks(rows, m, seed):
@@ -184,7 +142,7 @@ def test_forced_lists_every_list_edge(m, metric):
     lib = L.load()
     ir = lib.mirx_ivf_pq_item_rows()
     dim = 4 * m
-    rows, ids, cent, base = _forced(SIZES, dim, metric, 100 + m)
+    rows, ids, cent, base = forced(SIZES, dim, metric, 100 + m, 0.02)
     cb = _codebooks(rows, m, m)
     ivf = _pq(rows, ids, cent, cb, metric)
     assert lib.mirx_ivf_kind(ivf._h) == L.IVF_PQ == 2 and lib.mirx_ivf_pq_m(ivf._h) == m
@@ -234,7 +192,7 @@ def test_compact_rows_on_the_item_edges(m, metric):
     assert 2 * ir + 1 <= 3000
     sizes = [ir - 1, 1, 1, ir]
     dim = 64
-    rows, ids, cent, base = _forced(sizes, dim, metric, 77)
+    rows, ids, cent, base = forced(sizes, dim, metric, 77, 0.02)
     cb = _codebooks(rows, m, 3)
     ivf = _pq(rows, ids, cent, cb, metric)
     assert ivf.list_sizes().tolist() == sizes
@@ -264,7 +222,7 @@ def test_a_workgroup_walks_many_items_and_queries(m, metric):
     ir = lib.mirx_ivf_pq_item_rows()
     dim = 4 * m
     sizes = [ir - 1, 1, 1, ir]
-    rows, ids, cent, base = _forced(sizes, dim, metric, 300 + m)
+    rows, ids, cent, base = forced(sizes, dim, metric, 300 + m, 0.02)
     rng = np.random.default_rng(m)
     far = _unit(rng.standard_normal((1, dim)))                            # four empty lists, their centroids side by side
     cent = np.ascontiguousarray(np.concatenate([cent, (3 * far + 0.001 * rng.standard_normal((4, dim))).astype(F4)]), dtype=F4)
@@ -297,7 +255,7 @@ def test_add_in_two_calls_remove_state_errors_and_determinism(metric):
     from mirx.index import IvfPqIndex, IvfFlatIndex, IvfSq8Index
     L = _lib()
     dim, m = 32, 8
-    rows, ids, cent, base = _forced(SIZES, dim, metric, 21)
+    rows, ids, cent, base = forced(SIZES, dim, metric, 21, 0.02)
     n = rows.shape[0]
     cb = _codebooks(rows, m, 2)
     q = np.concatenate([(base[l] + F4(0.01)).astype(F4)[None] for l in (0, 3, 5, 6)])

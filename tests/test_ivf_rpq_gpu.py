@@ -17,54 +17,11 @@ import torch
 import _ivf_ref as R
 import _pq_ref as P
 import _rpq_ref as RP
-from oracle import search as OS
+from _ivf_cases import SIZES, _bits, _lib, _np, _unit, forced
 
 pytestmark = pytest.mark.gpu
 
 F4, F8 = np.float32, np.float64
-SIZES = [257, 0, 1, 63, 64, 65, 120]          # list 1 is empty: its centroid duplicates list 0's and the tie goes to list 0
-
-
-def _lib():
-    import mirx._lib as L
-    return L
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _unit(x):
-    return OS.l2_normalize(np.ascontiguousarray(x, dtype=F4))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == F8 else np.uint32)
-
-
-def _forced(sizes, dim, metric, seed, spread=0.05):
-    """rows around len(sizes) centroids so that the lists hold `sizes` rows (an empty list's centroid duplicates list 0's), user
-    ids descending, two pairs of equal rows in list 0: equal codes, norms and scores, only the ids tell them apart"""
-    rng = np.random.default_rng(seed)
-    base = _unit(rng.standard_normal((len(sizes), dim)))
-    cent = base.copy()
-    rows, want = [], []
-    for l, n in enumerate(sizes):
-        if n == 0:
-            cent[l] = cent[0]
-        r = base[l] + spread / dim ** 0.5 * rng.standard_normal((n, dim)).astype(F4)
-        rows.append(_unit(r) if metric == "COSINE" else r.astype(F4))
-        want += [l] * n
-    rows = np.concatenate(rows)
-    perm = rng.permutation(rows.shape[0])
-    rows, want = np.ascontiguousarray(rows[perm]), np.asarray(want)[perm]
-    first = np.flatnonzero(want == 0)
-    rows[first[1]] = rows[first[0]]
-    rows[first[3]] = rows[first[2]]
-    ids = (10 ** 6 - 3 * np.arange(rows.shape[0], dtype=np.int64))
-    assert np.bincount(R.assign(rows, cent, metric), minlength=len(sizes)).tolist() == list(sizes)
-    return rows, ids, cent, base
 
 
 def _codebooks(rows, cent, metric, m, seed):
@@ -170,7 +127,7 @@ def test_forced_lists_every_list_edge(m, metric):
     L = _lib()
     lib = L.load()
     dim = 4 * m
-    rows, ids, cent, base = _forced(SIZES, dim, metric, 100 + m)
+    rows, ids, cent, base = forced(SIZES, dim, metric, 100 + m, 0.05 / dim ** 0.5)
     cb = _codebooks(rows, cent, metric, m, m)
     ivf = _rpq(rows, ids, cent, cb, metric)
     assert lib.mirx_ivf_kind(ivf._h) == L.IVF_PQ and lib.mirx_ivf_pq_m(ivf._h) == m and lib.mirx_ivf_pq_by_residual(ivf._h) == 1
@@ -228,7 +185,7 @@ def test_compact_rows_on_the_item_edges(m, metric):
     assert 2 * ir + 1 <= 3000
     sizes = [ir - 1, 1, 1, ir]
     dim = 64
-    rows, ids, cent, base = _forced(sizes, dim, metric, 77)
+    rows, ids, cent, base = forced(sizes, dim, metric, 77, 0.05 / dim ** 0.5)
     cb = _codebooks(rows, cent, metric, m, 3)
     ivf = _rpq(rows, ids, cent, cb, metric)
     assert ivf.list_sizes().tolist() == sizes
@@ -257,7 +214,7 @@ def test_a_workgroup_walks_many_items_and_queries(m, metric):
     ir = lib.mirx_ivf_pq_item_rows()
     dim = 4 * m
     sizes = [ir - 1, 1, 1, ir]
-    rows, ids, cent, base = _forced(sizes, dim, metric, 300 + m)
+    rows, ids, cent, base = forced(sizes, dim, metric, 300 + m, 0.05 / dim ** 0.5)
     rng = np.random.default_rng(m)
     far = -_unit(base.sum(axis=0, keepdims=True))                         # four empty lists side by side, behind every other list
     cent = np.ascontiguousarray(np.concatenate([cent, (3 * far + 0.001 * rng.standard_normal((4, dim))).astype(F4)]), dtype=F4)
@@ -316,7 +273,7 @@ def test_add_in_two_calls_remove_and_state_errors(metric):
     from mirx.index import IvfResidualPqIndex
     L = _lib()
     dim, m = 32, 8
-    rows, ids, cent, base = _forced(SIZES, dim, metric, 21)
+    rows, ids, cent, base = forced(SIZES, dim, metric, 21, 0.05 / dim ** 0.5)
     n = rows.shape[0]
     cb = _codebooks(rows, cent, metric, m, 2)
     q = np.concatenate([(base[l] + F4(0.01)).astype(F4)[None] for l in (0, 3, 5, 6)])
@@ -375,7 +332,7 @@ def test_add_in_two_calls_remove_and_state_errors(metric):
 def test_flag_off_through_the_new_call_is_the_raw_form(metric):
     from mirx.index import IvfPqIndex
     dim, m = 64, 16
-    rows, ids, cent, base = _forced(SIZES, dim, metric, 5)
+    rows, ids, cent, base = forced(SIZES, dim, metric, 5, 0.05 / dim ** 0.5)
     cb = _codebooks(rows, np.zeros_like(cent), metric, m, 4)              # zero centroids: slices of the raw rows
     q = np.concatenate([(base[l] + F4(0.01)).astype(F4)[None] for l in (0, 2, 3, 6)])
     a, b = _rpq(rows, ids, cent, cb, metric, by_residual=False), _rpq(rows, ids, cent, cb, metric, by_residual=False)

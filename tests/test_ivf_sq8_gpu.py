@@ -16,12 +16,11 @@ import torch
 import _ivf_ref as R
 import _sq8_ref as Q
 import test_ivf_gpu as T
+from _ivf_cases import SIZES, _lib, _np, _unit, forced
 
 pytestmark = pytest.mark.gpu
 
 F4 = np.float32
-SIZES = T.SIZES
-_np = T._np
 
 
 def _sq8(rows, ids, cent, metric, vmin=None, scale=None):
@@ -106,7 +105,7 @@ def test_train_range_equals_the_restatement(n, dim):
     rows[:, 6] = np.nan                                                   # a column without a number
     rows[n // 3, 7] = np.nan                                              # NaN is ignored
     a, b = IvfSq8Index(dim, "L2", nlist=4), IvfSq8Index(dim, "L2", nlist=4)
-    with pytest.raises(T._lib().MirxError, match=r"\(-4\).*range is not fixed"):
+    with pytest.raises(_lib().MirxError, match=r"\(-4\).*range is not fixed"):
         a.range
     a.train_range(torch.from_numpy(rows))
     b.train_range(torch.from_numpy(rows).cuda())                          # host and device rows, two calls: equal bits
@@ -129,11 +128,11 @@ def test_train_range_equals_the_restatement(n, dim):
 @pytest.mark.parametrize("metric", ["COSINE", "L2"])
 @pytest.mark.parametrize("dim", [20, 64, 100, 256, 300, 1024, 1100])
 def test_forced_lists_every_block_edge(dim, metric):
-    L = T._lib()
+    L = _lib()
     lib = L.load()
     qt, rb = lib.mirx_ivf_query_tile(dim), lib.mirx_ivf_row_block()
     assert rb + 1 in SIZES
-    rows, ids, cent, base = T._forced(dim, metric, dim)
+    rows, ids, cent, base = forced(SIZES, dim, metric, dim, 0.02)
     ivf = _sq8(rows, ids, cent, metric)
     assert lib.mirx_ivf_kind(ivf._h) == L.IVF_SQ8
     flat, cflat, lists = _oracle(ivf, rows, ids, cent, metric)
@@ -179,7 +178,7 @@ def test_forced_lists_every_block_edge(dim, metric):
 @pytest.mark.parametrize("metric", ["COSINE", "L2"])
 @pytest.mark.parametrize("k", [1, 10, 300])
 def test_k_edges_and_padding(k, metric):
-    rows, ids, cent, base = T._forced(64, metric, 5)
+    rows, ids, cent, base = forced(SIZES, 64, metric, 5, 0.02)
     ivf = _sq8(rows, ids, cent, metric)
     flat, cflat, lists = _oracle(ivf, rows, ids, cent, metric)
     rng = np.random.default_rng(6)
@@ -196,9 +195,9 @@ def test_recipe_is_the_restatement_and_not_ivf_flat(metric):
     """tests/test_ivf_cpu.py's recipe, trained on the device: centroids, range, lists and answers are the restatement's; the
     answer is neither IVF_FLAT's nor the one an index that assigned from the decoded rows would give"""
     from mirx.index import IvfSq8Index, IvfFlatIndex
-    rows = T._unit(np.random.default_rng(0).standard_normal((3000, 32)))
+    rows = _unit(np.random.default_rng(0).standard_normal((3000, 32)))
     rng = np.random.default_rng(1)
-    q = T._unit(rows[rng.choice(3000, 64, replace=False)] + 0.3 * rng.standard_normal((64, 32)).astype(F4))
+    q = _unit(rows[rng.choice(3000, 64, replace=False)] + 0.3 * rng.standard_normal((64, 32)).astype(F4))
     ivf = IvfSq8Index(32, metric, nlist=24)
     ivf.train(torch.from_numpy(rows), iters=10)           # centroids and range from the same sample (here: every row)
     ivf.add(torch.from_numpy(rows))
@@ -235,8 +234,8 @@ def test_recipe_is_the_restatement_and_not_ivf_flat(metric):
 @pytest.mark.parametrize("metric", ["COSINE", "L2"])
 def test_add_in_two_calls_remove_state_errors_and_determinism(metric):
     from mirx.index import IvfSq8Index, IvfFlatIndex
-    L = T._lib()
-    rows, ids, cent, base = T._forced(100, metric, 21)
+    L = _lib()
+    rows, ids, cent, base = forced(SIZES, 100, metric, 21, 0.02)
     n = rows.shape[0]
     vmin, scale = Q.train_range(rows)
     q = torch.from_numpy(np.concatenate([(base[l] + F4(0.01)).astype(F4)[None] for l in (0, 3, 5, 6)]))
@@ -294,9 +293,9 @@ def test_collection_route():
     from mirx.retriever import Collection
     from mirx.index import IvfSq8Index
     from mirx.nih import create_nih_collection
-    rows = T._unit(np.random.default_rng(0).standard_normal((1200, 32)))
+    rows = _unit(np.random.default_rng(0).standard_normal((1200, 32)))
     rng = np.random.default_rng(1)
-    q = T._unit(rows[rng.choice(1200, 12, replace=False)] + 0.3 * rng.standard_normal((12, 32)).astype(F4))
+    q = _unit(rows[rng.choice(1200, 12, replace=False)] + 0.3 * rng.standard_normal((12, 32)).astype(F4))
     labels = [f"c{i % 3}" for i in range(1200)]
     paths = [f"p{i}.png" for i in range(1200)]
     params = {"metric_type": "COSINE", "index_type": "IVF_SQ8", "params": {"nlist": 12}}

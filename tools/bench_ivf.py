@@ -27,7 +27,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, IvfFlatIndex, IvfPqIndex, IvfResidualPqIndex, IvfSq8Index  # noqa: E402
+from mirx.index import IVF_TRAIN_ROWS_PER_LIST, FlatIndex, ivf_index_spec, strided_sample  # noqa: E402
 
 
 def clustered(n, d, centres, spread, dev, seed):
@@ -107,10 +107,15 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = clustered(a.n, a.d, a.centres, a.spread, dev, 1234)
+
+    def build(index_type, **params):                                                  # an index of the family from the one table
+        cls, kwargs = ivf_index_spec(a.d, index_type, dict(params, nlist=a.nlist))
+        return cls(a.d, "COSINE", device=0, **kwargs)
+
     flat = FlatIndex(a.d, "COSINE", 0)
     flat.reserve(a.n)
     t_flat_add, _ = timed(lambda: flat.add(rows))
-    ivf = IvfFlatIndex(a.d, "COSINE", a.nlist, 0)
+    ivf = build("IVF_FLAT")
     held0 = free_bytes(True)
     t_train, _ = timed(lambda: ivf.train(rows, iters=a.train_iters))
     t_add, peak_add = peak_during(lambda: ivf.add(rows))
@@ -126,10 +131,9 @@ def main():
     sq8, pqs = None, {}
     if a.index_type in ("IVF_SQ8", "IVF_PQ"):                                          # the same centroids, the range from train()'s sample
         held0 = free_bytes(True)
-        sq8 = IvfSq8Index(a.d, "COSINE", a.nlist, 0)
+        sq8 = build("IVF_SQ8")
         sq8.set_centroids(ivf.centroids)
-        limit = IVF_TRAIN_ROWS_PER_LIST * a.nlist
-        sample = rows if a.n <= limit else rows[(torch.arange(limit, dtype=torch.int64, device=dev) * a.n) // limit].contiguous()
+        sample = strided_sample(rows, IVF_TRAIN_ROWS_PER_LIST * a.nlist)
         t_range, _ = timed(lambda: sq8.train_range(sample))
         del sample
         t_add8, peak_add8 = peak_during(lambda: sq8.add(rows))
@@ -140,7 +144,7 @@ def main():
         arms = [arm for name, m, _ in arms for arm in ((name, m, False), (f"r{name}", m, True))]
     for name, m, residual in arms:
         held0 = free_bytes(True)
-        pq = IvfResidualPqIndex(a.d, "COSINE", a.nlist, m, 0) if residual else IvfPqIndex(a.d, "COSINE", a.nlist, m, 0)
+        pq = build("IVF_PQ", m=m, by_residual=residual)
         pq.set_centroids(ivf.centroids)
         t_cb, _ = timed(lambda: pq.train_codebooks(rows, a.codebook_iters))
         t_addp, peak_addp = peak_during(lambda: pq.add(rows))
